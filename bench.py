@@ -1,6 +1,6 @@
 """bench.py -- OSSID hot-path benchmark on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one frame of Zephyr hypothesis scoring, BASELINE.json configs[1]: 1000 pose hypotheses x 2048 model
@@ -58,7 +58,22 @@ def parse():
     p.add_argument("--dtoid-images", type=int, default=32, help="images per batch of the configs[2] leg")
     p.add_argument("--dtoid-timeout", type=int, default=420, help="watchdog (s) for the secondary DTOID leg")
     p.add_argument("--dtoid-batch", type=int, default=8, help="finetune batch per GPU (cfg-4: 64 over 8 GPUs)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (the frame's scores and its top-1 "
+                        "index) as DIR/<name>.npy; inputs are seeded, so two builds can be compared output for output")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+def dump_outputs(out_dir, scores, top, rank, world):
+    """The last timed step's results as float32 / float64 .npy files (a few kB). With more than one rank every rank
+    writes its own frame's results under a _rank<r> suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(out_dir, "scores%s.npy" % sfx), scores.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "top1%s.npy" % sfx), np.array([int(top.item())], dtype=np.float64))
 
 
 class Args:
@@ -487,6 +502,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, scores, top, rank, world)
 
     # The roofline leg: the same K frames once more, ONE frame in flight, HIP events recorded on the launch stream around
     # every stage (ossid_pn2_score's stage_events_host) and around the featurize kernel -- each kernel alone on the chip,

@@ -113,3 +113,19 @@ def test_reported_world_is_the_launched_world_never_the_gpus_flag():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "a.gpus *" not in src and '"n_gpus": a.gpus' not in src           # numbers come from `world`
     assert "os._exit(0)" not in src                                           # the watchdog leaves non-zero
+
+
+def test_dump_outputs_writes_the_last_steps_results_as_float_npy(tmp_path):
+    """--dump-outputs DIR: the timed path's results (scores, top-1 index) as float32 / float64 .npy files, one set per rank."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    scores = torch.linspace(-1.0, 1.0, 1000)
+    bench.dump_outputs(str(tmp_path / "one"), scores, scores.argmax(), 0, 1)
+    s, t = np.load(tmp_path / "one" / "scores.npy"), np.load(tmp_path / "one" / "top1.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, scores.numpy())
+    assert t.dtype == np.float64 and t.tolist() == [999.0]
+    bench.dump_outputs(str(tmp_path / "two"), scores, scores.argmax(), 1, 2)
+    assert sorted(os.listdir(tmp_path / "two")) == ["scores_rank1.npy", "top1_rank1.npy"]
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--dump-outputs"' in src
