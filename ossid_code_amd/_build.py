@@ -52,7 +52,7 @@ def build_lib(force=False, verbose=False):
     LAST_BUILD.update(compiled=0, linked=False)
     if not force and not is_stale():
         return LIB_PATH
-    extra = os.environ.get("OSSID_HIPCC_EXTRA", "").split()       # A/B builds of ablation switches (-DOSSID_...)
+    extra = os.environ.get("OSSID_HIPCC_EXTRA", "").split()       # the all-exact and diagnostic builds (-DOSSID_...)
     tag = ("_" + "".join(c if c.isalnum() else "_" for c in " ".join(extra))) if extra else ""
     obj_dir = OBJ_DIR + tag
     os.makedirs(obj_dir, exist_ok=True)

@@ -257,7 +257,7 @@ _QUERIES = frozenset((
     "ossid_dw_add_stats_partials", "ossid_stem_pool_bwd_partials", "ossid_dense_dgrad1_acc_partials", "ossid_dense_fwd1_stats_partials", "ossid_dense_dgrad3_mask_partials", "ossid_conv_split_bf16"))
 
 
-SEQ_C = os.environ.get("OSSID_SEQ_C", "1") != "0"      # replay through ossid_seq_replay (0: the Python loop, for A/B runs)
+SEQ_C = True      # replay through ossid_seq_replay (False: the Python loop)
 _U32 = C.c_uint32
 
 
@@ -274,7 +274,7 @@ class Seq:
 
     def run(self, streams):
         """streams: torch.cuda.Stream per slot (slot 0 first). Enqueues every recorded launch: through the C-side loop
-        (ossid_seq_replay, csrc/seq.hip) unless bench's flop counter is listening or OSSID_SEQ_C=0."""
+        (ossid_seq_replay, csrc/seq.hip) unless bench's flop counter is listening or SEQ_C is False."""
         raw = [st.cuda_stream for st in streams]
         cnt = _MFMA_COUNT
         if cnt is None and SEQ_C:

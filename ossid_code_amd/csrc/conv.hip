@@ -66,21 +66,15 @@ __device__ __forceinline__ v16f mfma3(const float4& whi, const float4& wlo, cons
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
 }
 
-#ifndef OSSID_WPF
-#define OSSID_WPF 1
-#endif
 // One float4 of padding per patch position: a wave's ds_read_b128 takes the same 16 bytes of 32 consecutive positions, a
 // lane stride of KCH*4 bytes -- 64 / 128 / 256 / 512 bytes, i.e. every lane of a 16-lane group on the same banks. On the f32
 // instruction this cost nothing measurable (round 2: the MFMAs hid it); on the split forms SQ_LDS_BANK_CONFLICT was 72-91 %
 // of all LDS cycles (tools/pmc_lds_conflicts.py, profiles/r03_lds_conflicts.txt) and the padding is worth 20-40 % of a layer.
-// Likewise OSSID_WPF (weight prefetch distance in groups): 1, 2 and 3 time the same; the main loop's MFMA pipe is
+// Likewise WPF (weight prefetch distance in groups): 1, 2 and 3 time the same; the main loop's MFMA pipe is
 // 74-89 % busy at the clock the part actually holds under this load (1.95-2.03 GHz, tools/conv_timeline.py).
-#ifndef OSSID_LDS_PAD
-#define OSSID_LDS_PAD 1
-#endif
-#ifndef OSSID_MEDIUM_WGS
-#define OSSID_MEDIUM_WGS 600
-#endif
+constexpr int LDS_PAD = 1;
+constexpr int WPF = 1;
+constexpr long MEDIUM_WGS = 600;    // plain-workgroup count under which narrow images take the medium variants (ossid_conv3x3)
 
 struct ConvArgs {
     const float* x;
@@ -114,7 +108,7 @@ __device__ __forceinline__ void conv_nhwc_body(const ConvArgs& A) {
     constexpr int BPX = WN * NT * 32;
     constexpr int F4 = KCH / 4;                 // float4 STAGED per patch position (f32 from global memory)
     constexpr int WPQ = FORM + 1;               // pieces: float4 per weight unit and lane, 16-byte slots per (unit, lane half) in LDS
-    constexpr int F4P = (FORM == 2 ? KCH / 16 * 6 : F4) + OSSID_LDS_PAD;     // float4 per patch position in LDS
+    constexpr int F4P = (FORM == 2 ? KCH / 16 * 6 : F4) + LDS_PAD;     // float4 per patch position in LDS
     constexpr int UNIT = SB ? 16 : 8;           // reduction channels per weight unit
     constexpr int NKB = KCH / UNIT / WK;        // units of a chunk handled by one wave
     constexpr int KY = TAPS == 9 ? 3 : (TAPS == 4 ? 2 : 1);   // prefetch groups per channel block (one kernel row each)
@@ -370,7 +364,7 @@ __device__ __forceinline__ void conv_nhwc_body(const ConvArgs& A) {
     // (split form: a group's MFMAs take 96 cycles per unit and pixel tile instead of 512, so the ring is deeper where a
     // group is short -- the distance has to cover an L2 round trip either way)
     constexpr int GROUP_CYCLES = GQ * NT * (FORM == 2 ? 192 : (SB ? 96 : 512));
-    constexpr int PF = !SB ? OSSID_WPF : (GROUP_CYCLES >= 768 ? 1 : (GROUP_CYCLES >= 384 ? 2 : 3));
+    constexpr int PF = !SB ? WPF : (GROUP_CYCLES >= 768 ? 1 : (GROUP_CYCLES >= 384 ? 2 : 3));
     float4 wq[PF + 1][GQ][WPQ];
 #pragma unroll
     for (int d = 0; d < PF; ++d)
@@ -555,7 +549,7 @@ int launch_conv_form(ConvArgs a, int B, hipStream_t s) {
     }
     a.buf_pos = rows * PW;
     if (a.buf_pos * F4 > NLD * 256) return OSSID_EINVAL;
-    size_t lds = (size_t)2 * a.buf_pos * ((FORM == 2 ? KCH / 16 * 6 : F4) + OSSID_LDS_PAD) * 16;
+    size_t lds = (size_t)2 * a.buf_pos * ((FORM == 2 ? KCH / 16 * 6 : F4) + LDS_PAD) * 16;
     const size_t red = WK > 1 ? (size_t)WK * (WM * WN) * NT * 16 * 64 * 4 : 0;
     if (red > lds) lds = red;
     auto kern0 = [] {        // (if constexpr: only the wrapper a tiling uses is instantiated)
@@ -684,7 +678,6 @@ int ossid_conv_nhwc_fwd(const ossid_conv_desc* d, void* stream) {
             }
         }
         (void)per128;
-#ifndef OSSID_PHASE_SPLIT      // (-DOSSID_PHASE_SPLIT: one phase per workgroup everywhere, the A/B build)
         // the decoder's few-channel layers on wide images (128 -> 64 at 116 x 156, 64 -> 32 at 232 x 312): all four phases
         // per workgroup off ONE staged patch
         if (a.split == 1) {
@@ -693,7 +686,6 @@ int ossid_conv_nhwc_fwd(const ossid_conv_desc* d, void* stream) {
             // (... and a tie with one tile per wave: 3.611 vs 3.608)
             // (the narrow layers -- 128 -> 64 at 58 x 78, 256 -> 128 at 29 x 39 -- measured slower in this form: graph 3.656 vs 3.596 ms)
         }
-#endif
         if (tiles >= 2) return wide ? launch_conv<2, 1, 2, 2, 8, 4, 16>(a, B, s) : launch_conv<2, 1, 2, 0, 8, 4, 16>(a, B, s);
         return wide ? launch_conv<1, 1, 2, 2, 8, 4, 16>(a, B, s) : launch_conv<1, 1, 1, 0, 8, 4, 16>(a, B, s);
     }
@@ -713,7 +705,7 @@ int ossid_conv_nhwc_fwd(const ossid_conv_desc* d, void* stream) {
     // two waves per SIMD and a ragged tail): one channel tile x 32 flat pixels per workgroup, reduction split over the
     // four waves in 32-channel chunks -> 8x as many, 4x shorter work items
     const int rows32 = (32 + W - 2) / W + 3;                          // patch rows of a 32-pixel flat run
-    if (plain_wgs < OSSID_MEDIUM_WGS && (Cin % 32) == 0 && (rows32 < H + 2 ? rows32 : H + 2) * (W + 2) * 8 <= 6 * 256) {
+    if (plain_wgs < MEDIUM_WGS && (Cin % 32) == 0 && (rows32 < H + 2 ? rows32 : H + 2) * (W + 2) * 8 <= 6 * 256) {
         // two channel tiles x 32 pixels, the reduction split over two waves: measured 5-8 % faster than one tile split
         // over four on the batch-8 head layers (256..640 -> 256/512 at 29x39), fewer partial tiles through LDS
         if (tiles >= 2) return launch_conv<2, 2, 1, false, 6, 9, 32>(a, B, s);

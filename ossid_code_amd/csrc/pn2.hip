@@ -587,11 +587,7 @@ __global__ __launch_bounds__(256, 2) void sa1_kernel(const float* __restrict__ p
         float4 x[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-#ifdef OSSID_ABL_NOGATHER
-            float4 r = make_float4(lane * 1e-3f + t, 0.1f * cw, 0.2f, 0.3f);
-#else
             float4 r = r_n[t];
-#endif
             if (h == 0) {
                 r.x = r.x - cn[0];
                 r.y = r.y - cn[1];
@@ -626,13 +622,8 @@ __global__ __launch_bounds__(256, 2) void sa1_kernel(const float* __restrict__ p
         __builtin_amdgcn_sched_barrier(0);
         stream_last_layer<2, 2, 4>((const float4*)(w + SA1_W3) + lane, w + SA1_B3, Y2, c, 4,
                                    [&](int mt, v16f(&acc)[2]) {
-#ifdef OSSID_ABL_NOEPI
-                                       asm volatile("" ::"v"(acc[0]), "v"(acc[1]));
-                                       if (mt == 77) out[0] = acc[0][0];
-#else
                                        const float r = pool_swapped(max16(acc[0], acc[1]));
                                        if (h == 0) out[mt * 32] = r;
-#endif
                                    });
     }
 }

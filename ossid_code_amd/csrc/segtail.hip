@@ -58,11 +58,7 @@ __device__ __forceinline__ int src_index(int dst, float scale, int n_src) {
 __device__ __forceinline__ void seg_tail_second_conv(const SegTailArgs& A, const float* mid, const float* w2s, const int y0,
                                                      const int x0, const int b) {
     const int tid = threadIdx.x, H = A.H, W = A.W;
-#ifdef ST_ABL_NOCONV2
-    for (int p = tid; p < 1; p += 256) {
-#else
     for (int p = tid; p < ST_TH * ST_TW; p += 256) {
-#endif
         const int oy = p / ST_TW, ox = p - oy * ST_TW;
         const int y = y0 + oy, x = x0 + ox;
         if (y >= H || x >= W) continue;
@@ -145,11 +141,7 @@ __global__ __launch_bounds__(256, 2) void seg_tail_kernel(const SegTailArgs A, c
     // MFMA's weight operand is shared by its 16 pixels.) Rows touching the frame border keep the full 3 x 3 form.
     const bool can_merge = 2.0f * A.scale_h <= 1.0f;
 #pragma unroll 1
-#ifdef ST_ABL_NOMFMA
-    for (int t0 = 2 * wave_u; t0 < 0; t0 += 8) {
-#else
     for (int t0 = 2 * wave_u; t0 < ST_MH * 2; t0 += 8) {    // the pair (t0, t0+1) = the two halves of ONE mid row
-#endif
         const int my = t0 >> 1;
         const int Y = y0 - 1 + my;                           // up-sampled row of this pair's mid pixels (wave-uniform)
         int rofs[3];

@@ -1669,25 +1669,19 @@ int ossid_conv_pack_weights_dgrad(const float* w, int Cout, int Cin, int taps, f
     return ossid_conv_pack_weights_form(w, Cout, Cin, taps, 1, 0, wpk, stream);
 }
 
-#ifndef OSSID_WGRAD_FEWCH
-#define OSSID_WGRAD_FEWCH 1      // the decoder's few-channel 3x3 layers on csrc/wgrad_fc.hip (0: the general kernel, for A/B runs)
-#endif
-#ifndef OSSID_WGRAD_T9
-#define OSSID_WGRAD_T9 1         // the dense blocks' 3x3 layers (128 -> 32) on csrc/wgrad_t9.hip (0: this file's grouped kernel)
-#endif
-#ifndef OSSID_WGRAD_T9_SINGLE
-#define OSSID_WGRAD_T9_SINGLE 1  // ... and every other plain 3x3 layer with input channels in 128s (the head) through ossid_conv_wgrad
-#endif
+// Weight gradients go to csrc/wgrad_fc.hip (the decoder's few-channel 3x3 layers) and csrc/wgrad_t9.hip (the dense blocks'
+// 3x3 layers, 128 -> 32, and every other plain 3x3 layer with input channels in 128s, such as the head's) where those take
+// the shape; this file's kernels take the rest.
 
 size_t ossid_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int taps) {
     WgradPlan p;
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !wgrad_plan(B, H, W, Cin, Cout, taps, p)) return 0;
     size_t n = (size_t)p.nsplit * p.wk * taps * Cout * Cin * sizeof(float);
-    if (OSSID_WGRAD_FEWCH && ossid_wgrad_fewch_takes(Cin, Cout, taps, Cin, Cout)) {
+    if (ossid_wgrad_fewch_takes(Cin, Cout, taps, Cin, Cout)) {
         const size_t m = ossid_wgrad_fewch_workspace_bytes(B, H, W, Cin, Cout);
         if (m > n) n = m;
     }
-    if (OSSID_WGRAD_T9 && OSSID_WGRAD_T9_SINGLE) {          // (a shape-only probe: pointers and strides are checked at the call)
+    {                                                        // (a shape-only probe: pointers and strides are checked at the call)
         ossid_wgrad_desc d = {};
         d.batch = B, d.height = H, d.width = W, d.cin = Cin, d.cout = Cout, d.taps = taps;
         if (Cin <= 256 && ossid_wgrad_t9_takes(&d)) {
@@ -1706,15 +1700,15 @@ int ossid_conv_wgrad(const ossid_wgrad_desc* d, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % 4) || (Cout % 4)) return OSSID_EINVAL;
     if (!d->x || !d->dy || !d->dw || !d->workspace || (d->pre_scale && !d->pre_shift)) return OSSID_EINVAL;
     if (d->dy_add) return OSSID_EINVAL;                        // (only csrc/wgrad_t9.hip's 1x1 jobs, reached through the group entry)
-    if (OSSID_WGRAD_FEWCH && ossid_wgrad_fewch_takes(Cin, Cout, taps, d->in_channel_stride > 0 ? d->in_channel_stride : Cin,
-                                                     d->dy_channel_stride > 0 ? d->dy_channel_stride : Cout) &&
+    if (ossid_wgrad_fewch_takes(Cin, Cout, taps, d->in_channel_stride > 0 ? d->in_channel_stride : Cin,
+                                d->dy_channel_stride > 0 ? d->dy_channel_stride : Cout) &&
         d->workspace_bytes >= ossid_wgrad_fewch_workspace_bytes(B, H, W, Cin, Cout) && !((uintptr_t)d->x & 15) &&
         !((uintptr_t)d->dy & 15) && !((uintptr_t)d->workspace & 15))
         return ossid_wgrad_fewch(d, stream);                 // 2-D pixel tiles, every tap from one staged patch (csrc/wgrad_fc.hip)
     // (measured per layer at batch 8, 29 x 39, tools/train_layers_bench.py: 256 -> 256 / 96 / 48 take 0.091 / 0.054 / 0.034 ms there
     // against 0.104 / 0.081 / 0.054 here; 512 -> 256, 640 -> 256, 768 -> 512 are no faster there -- 0.152 / 0.196 / 0.409 against
     // 0.143 / 0.162 / 0.421: this file's 128 x 128 tiles re-use a staged element four times -- so only up to 256 input channels)
-    if (OSSID_WGRAD_T9 && OSSID_WGRAD_T9_SINGLE && Cin <= 256 && ossid_wgrad_t9_takes(d) && !((uintptr_t)d->workspace & 15) &&
+    if (Cin <= 256 && ossid_wgrad_t9_takes(d) && !((uintptr_t)d->workspace & 15) &&
         d->workspace_bytes >= ossid_wgrad_t9_workspace_bytes(d, 1))
         return ossid_wgrad_t9_group(d, 1, d->workspace, d->workspace_bytes, stream);      // the same, split-bf16 (csrc/wgrad_t9.hip)
     WgradPlan p;
@@ -1776,11 +1770,11 @@ static int fill_wgrad_args(const ossid_wgrad_desc* d, const WgradPlan& p, WgradA
 // per CU over the whole group (ONE round of resident workgroups: 640 measured 1 ms slower per step than 500, the second
 // round runs a quarter full), shared out in proportion to each problem's work (chunks x tiles).
 static void group_splits(WgradPlan* plans, int n) {
+    const double target = 500.0;
     double total = 0.0;
     for (int i = 0; i < n; ++i) total += (double)plans[i].n_chunks * plans[i].ntiles;
     for (int i = 0; i < n; ++i) {
         const double share = (double)plans[i].n_chunks * plans[i].ntiles / total;
-        static const double target = getenv("OSSID_WGRAD_GROUP_BLOCKS") ? atof(getenv("OSSID_WGRAD_GROUP_BLOCKS")) : 500.0;
         long sp = (long)(target * share / plans[i].ntiles + 0.5);
         if (sp < 1) sp = 1;
         if (sp > plans[i].n_chunks) sp = (long)plans[i].n_chunks;
@@ -1800,10 +1794,10 @@ static void split_tiled(const ossid_wgrad_desc* descs, int n, WgradSplit& S) {
     for (int i = 0; i < n; ++i) {
         const ossid_wgrad_desc& d = descs[i];
         auto same = [&](const ossid_wgrad_desc& o) { return d.batch == o.batch && d.height == o.height && d.width == o.width; };
-        if (OSSID_WGRAD_T9 && ossid_wgrad_t9_takes(&d) &&
+        if (ossid_wgrad_t9_takes(&d) &&
             (S.n9 == 0 || (same(S.t9[0]) && ossid_wgrad_t9_class(&d) == ossid_wgrad_t9_class(&S.t9[0]))))
             S.t9[S.n9++] = d;
-        else if (OSSID_WGRAD_T9 && ossid_wgrad_t1_takes(&d) && (S.n1 == 0 || same(S.t1[0]))) S.t1[S.n1++] = d;
+        else if (ossid_wgrad_t1_takes(&d) && (S.n1 == 0 || same(S.t1[0]))) S.t1[S.n1++] = d;
         else S.rest[S.nr++] = d;
     }
 }

@@ -276,16 +276,6 @@ __device__ __forceinline__ void wino_conv_body(const WinoArgs& A, const int bloc
             o[(size_t)(i * 4 + 3) * 32 * F4] = sub(R[1], R[3]);
         };
 #endif
-#ifdef OSSID_WINO_ABL_RAWTF      // ablation (wrong results, timing only): the staged patch stored as it is -- the loads and their
-        {                        // waits stay, the transform's vector-ALU work goes: what does the LATENCY of the patch cost?
-            for (int k = 0; k < 8; ++k) {
-                const v4f v = st[k % 3][k & 3];
-                *(uint2*)(ob + (size_t)((2 * ih) * 4 + k) * 32 * F4 * 16) = make_uint2(__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1]));
-                *(uint2*)(ob + (size_t)((2 * ih) * 4 + k) * 32 * F4 * 16 + lo_delta) = make_uint2(__builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3]));
-            }
-            return;
-        }
-#endif
         v4f Ra[4], Rb[4];
         if (ih == 0) {            // (two code paths, not selects: ih is wave-uniform)
             asm volatile("" ::: "memory");
@@ -321,7 +311,7 @@ __device__ __forceinline__ void wino_conv_body(const WinoArgs& A, const int bloc
     // and multiplies at once. With waves 0-3 transforming behind everybody's MFMAs, the matrix pipe stood still for that
     // phase: 47 % of the kernel (profiles/r03_wino_ct4.txt). CT = 2: four waves, all of them stage (two workgroups per CU run
     // out of phase by themselves).
-#if !defined(OSSID_WINO_F32) && !defined(OSSID_WINO_NO_TURNS)      // (-DOSSID_WINO_NO_TURNS: the A/B switch, round 3's schedule)
+#ifndef OSSID_WINO_F32
     constexpr bool TURNS = CT == 4;
 #else
     constexpr bool TURNS = false;
@@ -366,9 +356,7 @@ __device__ __forceinline__ void wino_conv_body(const WinoArgs& A, const int bloc
         if (TURNS) {
             if (grp == ((ch + 1) & 1)) {
                 if (ch + 1 < ch1) transform_write((ch + 1) & 1, (ch + 1) * KCH);    // beside the other group's MFMAs of this chunk
-#ifndef OSSID_WINO_LATE_STAGE
                 if (ch + 3 < ch1) stage_load((ch + 3) * KCH);                   // this group's next chunk: two iterations of cover
-#endif
             }
         } else if (stager && ch + 1 < ch1) {
             stage_load((ch + 1) * KCH);   // in flight under this chunk's MFMAs
@@ -385,19 +373,12 @@ __device__ __forceinline__ void wino_conv_body(const WinoArgs& A, const int bloc
             acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo, vh, acc[e], 0, 0, 0);
             acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, vl, acc[e], 0, 0, 0);
             acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, vh, acc[e], 0, 0, 0);
-#ifndef OSSID_WINO_ABL_NOW          // (ablations, wrong results, timing only: what the loop costs without its weight stream ...
             wq[e & 1][0] = W4[(size_t)unit_of(p0 + e + 2, 0) * 64 + lane];
             wq[e & 1][1] = W4[(size_t)unit_of(p0 + e + 2, 1) * 64 + lane];
-#endif
             __builtin_amdgcn_sched_barrier(0);      // keep this order: the compiler would sink the loads to their use
         }
         p0 += 8;
-#ifndef OSSID_WINO_ABL_NOTF         // ... and without the input transform of the next chunk)
         if (!TURNS && stager && ch + 1 < ch1) transform_write((ch + 1) & 1, (ch + 1) * KCH);
-#endif
-#ifdef OSSID_WINO_LATE_STAGE     // (A/B: the patch requested BEHIND the chunk's MFMAs -- loads return in order, and a wait for a weight quad
-        if (TURNS && grp == ((ch + 1) & 1) && ch + 3 < ch1) stage_load((ch + 3) * KCH);     // issued behind the patch waits for the patch too)
-#endif
         __syncthreads();
     }
 #else
@@ -643,13 +624,11 @@ static int wino_args(const ossid_conv_desc* d, WinoArgs& a, long& nwg) {
     const long long T = (long long)B * a.TH * a.TW;
     if (T > 0x7fffffffLL) return OSSID_EINVAL;
     a.T = (int)T;
-    // 128 output channels per workgroup where the layer has them (the transform of a tile group is then done half as often);
-    // OSSID_WINO_CT=2 / 4 forces one form (A/B runs)
-    static const int ct_env = getenv("OSSID_WINO_CT") ? atoi(getenv("OSSID_WINO_CT")) : 0;
+    // 128 output channels per workgroup where the layer has them (the transform of a tile group is then done half as often)
     // (measured, profiles/r03_wino_ct4.txt: 8-13 % on the 256 / 512-channel layers at 21 templates; at the finetune batch --
     // 75 tile groups -- the 512-thread workgroups leave the side streams' kernels less room and the step loses 0.4 ms)
     a.gx = (int)((T + 31) / 32);
-    a.ct = ct_env == 2 || ct_env == 4 ? ct_env : ((a.n_cotiles >= 4 && a.gx >= 128) ? 4 : 2);
+    a.ct = (a.n_cotiles >= 4 && a.gx >= 128) ? 4 : 2;
     a.gy = (a.n_cotiles + a.ct - 1) / a.ct;
     const long P = a.gx;
     if (a.gy <= 8 && 8 % a.gy == 0)

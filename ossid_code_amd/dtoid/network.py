@@ -294,13 +294,7 @@ class _PadOne:
 # 42.3 ms in a fresh process but 48.4 ms once a test-time graph had been captured in it (other streams created first, another
 # mapping); with the encoders REUSING the two branch slots -- they are never busy at the same time as the branches -- it is
 # 41.9 ms either way. (GPU_MAX_HW_QUEUES=8 made it 79 ms; left alone.)
-ENC_G_STREAM = int(os.environ.get("OSSID_ENC_G_STREAM", "0"))
-ENC_L_STREAM = int(os.environ.get("OSSID_ENC_L_STREAM", "1"))
-# The global template encoder's node created BEFORE the stem convolution's (1) or behind it (0). Autograd runs ready nodes in
-# reverse order of creation: created first, the encoder's backward -- a chain of ~110 small launches on its side stream that
-# needs the stem's kernel gradient and ends the step -- is enqueued AFTER the stem convolution's weight gradient instead of in
-# front of it (where that launch and its host work became a tail of their own behind the chain).
-ENC_G_FIRST = os.environ.get("OSSID_ENC_G_FIRST", "1") != "0"
+# The global template encoder runs on branch slot 0, the local one on slot 1.
 
 
 class _CatConv:
@@ -367,7 +361,7 @@ class CorrelationModel(nn.Module):
 
 
 # bumped by every writer that changes parameters behind the modules' back (finetune.FusedAMSGrad.step): see
-# Network.optimistic_checks
+# Network._graphed_dense_impl
 PARAM_EPOCH = [0]
 
 
@@ -405,7 +399,7 @@ class FusedHead:
     # from this many templates on the channel-contraction-last form of `dot` wins: G costs 0.30 ms per frame (0.74 GB) and
     # the GEMM ~0.010 ms per template, against 0.0174 ms per template for the Winograd convolution it replaces since that
     # kernel's tail split (round 3: 0.37 ms at 21 templates) -- the crossover moved from 16 to ~40 templates
-    DOT_GEMM_MIN_TEMPLATES = int(os.environ.get("OSSID_DOT_GEMM_MIN", "40"))
+    DOT_GEMM_MIN_TEMPLATES = 40
 
     def _fill_derived(self):
         """Weight re-layouts the linearity tricks need, (re)written IN PLACE (a captured graph reads `_dot_wcto`):
@@ -597,18 +591,18 @@ class FusedHead:
 class FusedBackbone:
     """Test-time execution plan of the DenseNet-121 part of ImageFeatExtract on csrc/conv.hip. Each dense layer is two
     launches -- 1x1 conv with norm1+ReLU folded into its input staging, 3x3 conv with norm2+ReLU folded likewise -- and
-    writes its 32 channels straight into the block's resident channels-last buffer; transitions are one fused 1x1 conv
-    plus the average pool; norm5 -> c1 (1x1) -> ELU -> n1 is ONE launch. The stem: csrc/stem.hip's 7x7 stride-2 kernel,
-    then template modulation + norm0 + ReLU in one pass and the max-pool. Rebuilt whenever the parameters change."""
+    writes its 32 channels straight into the block's resident channels-last buffer; transitions are the average pool
+    (with norm + ReLU) followed by the 1x1 conv; norm5 -> c1 (1x1) -> ELU -> n1 is ONE launch. The stem: csrc/stem.hip's
+    7x7 stride-2 kernel, then template modulation + norm0 + ReLU + the max-pool in one pass. Rebuilt whenever the
+    parameters change."""
 
     def __init__(self, ife):
         P = ops.PackedConv
         self.ife = ife
         seq = list(ife.backdense_1) + list(ife.backdense_2)      # norm0 relu0 pool0 block1 | trans1 block2 ... norm5
-        self.stem = seq[:3]
         # stem on this repo's kernels: implicit-im2col 7x7 / 2 MFMA convolution (+ normalizeImageRange; reads the parameter
-        # itself: nothing to pack) -> template modulation + norm0 + ReLU in one pass -> max-pool, channels-last throughout
-        self.norm0 = self.stem[0]
+        # itself: nothing to pack) -> template modulation + norm0 + ReLU + max-pool in one pass, channels-last throughout
+        self.norm0 = seq[0]
         self.norm0_affine = [t.clone() for t in ops._bn_affine(self.norm0)]
         self.stages = []
         for m in seq[3:]:
@@ -630,12 +624,8 @@ class FusedBackbone:
         for dst, src in zip(self.norm0_affine, ops._bn_affine(self.norm0)):
             dst.copy_(src)
 
-    use_fused_stem = os.environ.get("OSSID_FUSED_STEM", "1") != "0"
-    # stem_tail + pool0 in one pass, transitions with the pool in front of the 1x1 convolution, both written straight into the
-    # next dense block's buffer
-    use_pooled_transitions = os.environ.get("OSSID_POOLED_TRANSITIONS", "1") != "0"
     # a dense block of at most this many pixels (batch x height x width) takes the one-launch-per-layer form
-    DENSE_FUSED_MAX_PIXELS = int(os.environ.get("OSSID_DENSE_FUSED_MAX_PIXELS", "20000"))
+    DENSE_FUSED_MAX_PIXELS = 20000
 
     def __call__(self, image, template_feat, raw_image=False):
         """raw_image: `image` is in [0, 1] and normalizeImageRange is applied inside the stem's gather (D1)."""
@@ -648,26 +638,14 @@ class FusedBackbone:
             mod = self.stages[si][1]
             return torch.empty((B, C + mod.nlayers * mod.growth, H, W), dtype=torch.float32, device=image.device,
                                memory_format=torch.channels_last)
-        pending = None                      # the next block's buffer, already holding its input
-        if self.use_fused_stem:
-            x0 = ops.stem_conv(image, ife.backdense_0[0], normalize=raw_image)
-            B, C, H0, W0 = x0.shape
-            pending = block_buffer(0, B, C, (H0 - 1) // 2 + 1, (W0 - 1) // 2 + 1) if self.use_pooled_transitions else None
-            x = ops.stem_tail_pool(x0, template_feat, *self.norm0_affine, out=pending) if self.use_pooled_transitions else \
-                ops.maxpool_nhwc(ops.stem_tail(x0, template_feat, *self.norm0_affine), 3, 2, 1)
-            if pending is not None:
-                x = pending[:, :C]
-        else:
-            if raw_image:
-                from .model import normalizeImageRange
-                image = normalizeImageRange(image)
-            x0 = ife.backdense_0(image)
-            if template_feat.shape[0] == 1 and x0.shape[0] > 1:    # a batch of images of ONE object (batched test time)
-                template_feat = template_feat.expand(x0.shape[0], -1, -1, -1)
-            x = x0 + ops.dw_xcorr(x0, template_feat)
-            for m in self.stem:
-                x = m(x)
-            x = x.contiguous(memory_format=torch.channels_last)
+        # stem_tail + pool0 in one pass and transitions with the pool in front of the 1x1 convolution, both written straight
+        # into the next dense block's buffer (`pending`, already holding that block's input)
+        x0 = ops.stem_conv(image, ife.backdense_0[0], normalize=raw_image)
+        B, C, H0, W0 = x0.shape
+        pending = block_buffer(0, B, C, (H0 - 1) // 2 + 1, (W0 - 1) // 2 + 1)
+        x = ops.stem_tail_pool(x0, template_feat, *self.norm0_affine, out=pending)
+        if pending is not None:
+            x = pending[:, :C]
         for si, (kind, mod, packed) in enumerate(self.stages):
             B, C, H, W = x.shape
             if kind == "block":
@@ -694,7 +672,7 @@ class FusedBackbone:
                 x = buf
             else:
                 st = mod.pool.stride if isinstance(mod.pool.stride, int) else mod.pool.stride[0]
-                if self.use_pooled_transitions and mod.conv.bias is None and st in (1, 2) and H >= 2 and W >= 2:
+                if mod.conv.bias is None and st in (1, 2) and H >= 2 and W >= 2:
                     # norm -> relu -> conv 1x1 -> avg-pool with the pool moved in front of the (bias-free, linear, pixelwise)
                     # convolution: one pass that normalises, rectifies and averages, then the convolution on the pooled
                     # pixels (a quarter of them at stride 2), written straight into the next block's buffer
@@ -777,7 +755,7 @@ class Network(nn.Module):
             if isinstance(layer, nn.BatchNorm2d):
                 layer.eval()
 
-    use_fused_templates = os.environ.get("OSSID_FUSED_TEMPLATES", "1") != "0"
+    use_fused_templates = True    # test-time template encoders on csrc/conv.hip; False = the nn.Module encoders
 
     def _fused_template_encoder(self, mod, slot):
         key = FusedHead.version_key(mod)
@@ -805,8 +783,8 @@ class Network(nn.Module):
     use_hip_training = os.environ.get("OSSID_TRAIN_IMPL", "hip") != "miopen"
     # The two SqueezeNet template encoders train on this repo's kernels as one autograd node each, replaying recorded launch
     # sequences (dtoid/train_encoders.py; round 3 -- round 2's form, ~25 autograd nodes per encoder, was 0.3-1.1 ms slower
-    # than torch / MIOpen because of its host cost). OSSID_TRAIN_TEMPLATES=0: the nn.Module path (MIOpen).
-    use_hip_template_training = os.environ.get("OSSID_TRAIN_TEMPLATES", "1") != "0"
+    # than torch / MIOpen because of its host cost). False: the nn.Module path (MIOpen).
+    use_hip_template_training = True
     # The 7x7 stem + template modulation + norm0 + pool0 on this repo's kernels (csrc/stem.hip: implicit-im2col MFMA
     # convolution and weight gradient, fused statistics / pooling passes; train_ops.StemConv / StemTail). False = the
     # nn.Module path (MIOpen) for these layers: what the tests compare against.
@@ -818,7 +796,7 @@ class Network(nn.Module):
     # 60-75 % of the chip's workgroup slots; two or three of them in flight fill the rest. autograd runs every node's
     # backward on the stream of its forward, so the backward pass is concurrent in the same way. Tensors that cross
     # streams are record_stream()ed for the caching allocator.
-    use_train_streams = os.environ.get("OSSID_TRAIN_STREAMS", "1") != "0"
+    use_train_streams = True
 
     def _branches_on(self, device):
         return (self.use_train_streams and device.type == "cuda" and not torch.cuda.is_current_stream_capturing())
@@ -876,12 +854,14 @@ class Network(nn.Module):
         seq = list(ife.backdense_1) + list(ife.backdense_2)      # norm0 relu0 pool0 block1 | trans1 block2 ... norm5
         if self.use_hip_stem_training:
             # stem on this repo's kernels, channels-last from the first one
-            if lazy_g is not None and ENC_G_FIRST:
+            # The global template encoder's node is created BEFORE the stem convolution's. Autograd runs ready nodes in reverse
+            # order of creation: the encoder's backward -- a chain of ~110 small launches on its side stream that needs the
+            # stem's kernel gradient and ends the step -- is then enqueued AFTER the stem convolution's weight gradient instead
+            # of in front of it (where that launch and its host work became a tail of their own behind the chain).
+            if lazy_g is not None:
                 g, s_g = lazy_g()
             x0 = T.stem_conv(image, ife.backdense_0[0])           # implicit-im2col 7x7 / 2 kernel, exact f32 (csrc/stem.hip)
             if lazy_g is not None:
-                if not ENC_G_FIRST:
-                    g, s_g = lazy_g()
                 self._join(s_g, [g])
             self.__dict__["_pack_event"] = pack_event            # (later forks -- the local encoder -- wait for the first big part)
             x = T.stem_tail(x0, g, seq[0])                        # modulation + norm0 + ReLU + pool0: three passes
@@ -1108,8 +1088,8 @@ class Network(nn.Module):
             # that does not need it; the local one in the middle of the backbone, so that its backward is enqueued in the
             # middle of the backbone's backward, while the host is ahead of the device, instead of as a tail behind
             # everything else
-            lazy_g = lambda: self._fork(ENC_G_STREAM, [global_template, global_template_mask], enc_g)       # noqa: E731
-            lazy_l = lambda: self._fork(ENC_L_STREAM, [template, template_mask], enc_l)                     # noqa: E731
+            lazy_g = lambda: self._fork(0, [global_template, global_template_mask], enc_g)       # noqa: E731
+            lazy_l = lambda: self._fork(1, [template, template_mask], enc_l)                     # noqa: E731
             return self._forward_train_hip(image, None, None, lazy_g=lazy_g, lazy_local=lazy_l)
         g, local = enc_g(), enc_l()
         if hip_train:
@@ -1172,21 +1152,20 @@ class Network(nn.Module):
         with torch.no_grad():
             return self._graphed_dense_impl(*args, **kwargs)
 
-    # The parameter checks of a frame (FusedHead.version_key over ~1 000 tensors: 0.15-0.2 ms of host time) AFTER its launch
-    # instead of in front of it: the frame is launched on the plans of the previous call, the checks run while the GPU works,
-    # and only if they find a change are the plans refreshed and the frame launched again (its first results are never
-    # read). Known writers (FusedAMSGrad.step) bump PARAM_EPOCH, and the first call behind a bump checks first.
-    optimistic_checks = os.environ.get("OSSID_OPTIMISTIC_CHECKS", "1") != "0"
-
     def _graphed_dense_impl(self, image, template_features, template_global, head_only=False, raw_image=False, post_hw=None,
                             _checked=False):
         """The dense part replayed from a captured hipGraph (the B=1 backbone alone is ~500 launches and otherwise
         host-bound). One graph per (input shape, chunk sizes, packed-head identity); inputs are copied into the
         graph's static buffers, outputs are read from them. head_only: `image` is already the feature map [1,640,h,w]
-        (the batched test-time path runs the backbone once for the whole batch and replays this graph per image)."""
+        (the batched test-time path runs the backbone once for the whole batch and replays this graph per image).
+
+        The parameter checks of a frame (FusedHead.version_key over ~1 000 tensors: 0.15-0.2 ms of host time) run AFTER its
+        launch instead of in front of it: the frame is launched on the plans of the previous call, the checks run while the
+        GPU works, and only if they find a change are the plans refreshed and the frame launched again (its first results are
+        never read). Known writers (FusedAMSGrad.step) bump PARAM_EPOCH, and the first call behind a bump checks first."""
         want_bb = self.use_fused_backbone and not head_only
         fc, bc = self.__dict__.get("_fused_cache"), self.__dict__.get("_fused_bb_cache")
-        optimistic = (self.optimistic_checks and not _checked and self.use_fused_head and fc is not None and
+        optimistic = (not _checked and self.use_fused_head and fc is not None and
                       (not want_bb or bc is not None) and self.__dict__.get("_checked_epoch") == PARAM_EPOCH[0])
         if optimistic:
             fused, fused_bb = fc[1], (bc[1] if want_bb else None)
@@ -1313,7 +1292,7 @@ class Network(nn.Module):
             return self.postprocess(cls_all, reg_all, seg_all, heat_all, fmap, (image.shape[2], image.shape[3]), topk,
                                     seg_sigmoid)
 
-    use_fused_post = os.environ.get("OSSID_FUSED_POST", "1") != "0"
+    use_fused_post = True    # False: post-processing step by step outside the graph (what the tests compare against)
 
     def post_dense(self, cls_all, reg_all, fmap, img_hw, state=None):
         """The part of postprocess that needs no host decision (decode + clip of the candidates, top-1000 object scores over

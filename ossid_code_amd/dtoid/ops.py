@@ -1,7 +1,6 @@
 """Torch-facing wrappers of the DTOID device ops in libossid_hip.so (include/ossid_hip.h, "DTOID ops").
 Tensors only cross as raw pointers; autograd sees DwXcorr as one differentiable node."""
 import ctypes
-import os
 
 import torch
 
@@ -429,11 +428,8 @@ def _bn_affine(bn):
     return scale, (bn.bias.detach().float() - bn.running_mean.detach().float() * scale).contiguous()
 
 
-USE_PHASE_CONV = os.environ.get("OSSID_PHASE_CONV", "1") != "0"
-
-
-USE_WINO = os.environ.get("OSSID_WINO", "1") != "0"
-WINO_MIN_WGS = int(os.environ.get("OSSID_WINO_MIN_WGS", "256"))
+USE_WINO = True
+WINO_MIN_WGS = 256
 
 
 _WINO_WS = {}
@@ -597,7 +593,7 @@ class PackedConv:
         x = x.float().contiguous(memory_format=torch.channels_last)
         out = torch.empty((B, self.cout, H, W), dtype=torch.float32, device=x.device,
                           memory_format=torch.channels_last)
-        if self.wpk4 is not None and USE_PHASE_CONV and (H, W) == (2 * Hs, 2 * Ws) and self.pre_scale is None:
+        if self.wpk4 is not None and (H, W) == (2 * Hs, 2 * Ws) and self.pre_scale is None:
             if self.run_phases(x, B, Hs, Ws, out):
                 return out
         return self.run(x, B, H, W, out, src_hw=(Hs, Ws) if size is not None else (0, 0))

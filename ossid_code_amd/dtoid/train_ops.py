@@ -18,7 +18,6 @@ autograd sees a handful of coarse Functions (FusedConv, BNFold, ColStats, AvgPoo
 logical NCHW in torch.channels_last memory format, so torch ops (losses, the few layers left on MIOpen) interoperate.
 """
 import ctypes
-import os
 
 import torch
 
@@ -192,16 +191,14 @@ _ACTIVE_PLAN = None  # weakref to the PackPlan that packed last. Its `fresh` dic
 _KIND_FORM = {"fwd": 0, "dgrad": 0, "fwd_exact": 1, "dgrad_exact": 1, "fwd_x6": 2}
 # The forward layout of layers whose output a ReLU / max-pool decides on: f32-level accuracy is needed (a pre-activation on the
 # other side of zero changes the gradient's path) -- the three-way split delivers it at 2x the split form's
-# matrix-pipe time instead of 5x. OSSID_TRAIN_FWD=fwd_exact puts these layers on the exact-f32 instruction. Data gradients and
-# the ELU head run split-bf16.
-FWD_DECIDING = os.environ.get("OSSID_TRAIN_FWD", "fwd_x6")
-assert FWD_DECIDING in ("fwd_x6", "fwd_exact")
+# matrix-pipe time instead of 5x ("fwd_exact" would put these layers on the exact-f32 instruction). Data gradients and the ELU
+# head run split-bf16.
+FWD_DECIDING = "fwd_x6"
 # The two SqueezeNet template encoders keep the exact-f32 instruction: their convolutions are small (0.3 ms of the step), and
 # with ~2 M ReLU / max-pool decisions per pass ANY f32-level path lands one of them differently from torch's in some passes
 # (2e-3 .. 1e-2 on the gradients in front of it instead of 2e-5: measured in round 3, one pass in six with the exact
 # instruction, three in six with the three-way split) -- the tests' bound is calibrated on the exact one.
-FWD_ENCODER = os.environ.get("OSSID_TRAIN_FWD_ENCODER", "fwd_exact")
-assert FWD_ENCODER in ("fwd_x6", "fwd_exact")
+FWD_ENCODER = "fwd_exact"
 
 
 def _pack(w, kind):
@@ -335,9 +332,6 @@ def conv_raw(x, wpk, B, H, W, cin, cout, taps, out, bias=None, pre=None, pre_rel
         d.post_scale, d.post_shift = post[0].data_ptr(), post[1].data_ptr()
     name = "ossid_conv3x3_wino_fwd" if wino else "ossid_conv_nhwc_fwd"       # wino: wpk is the Winograd layout
     with _lib.on_device(out.device):
-        if wino and d.scratch is None and WINO_TAIL_SPLIT:
-            from .ops import wino_workspace
-            wino_workspace((d,), out.device)                                  # scratch for the launch's tail split
         _lib.check(_lib.fn(name)(_byref(d), _lib.stream()), name)
     return out
 
@@ -539,7 +533,7 @@ def bn_fold(sums, n, bn):
 # ends (an autograd engine callback, so a bare loss.backward() is as safe as finetune_step) and wherever gradients are
 # read earlier (GradSync's per-bucket hooks). Tensors the side stream reads are record_stream()ed: the caching allocator
 # then keeps their memory until that work has run.
-WGRAD_SIDE = os.environ.get("OSSID_WGRAD_STREAM", "1") != "0"
+WGRAD_SIDE = True
 _wg_streams, _wg_dirty = {}, set()
 
 from ..streams import N_STREAM_CANDIDATES, _side_pools, side_streams  # noqa: E402,F401  (the probe lives in ossid_code_amd/streams.py)
@@ -550,13 +544,6 @@ def join_wgrad_stream():
     for idx in list(_wg_dirty):
         torch.cuda.current_stream(idx).wait_stream(_wg_streams[idx])
     _wg_dirty.clear()
-
-
-_SKIP_WGRAD = os.environ.get("OSSID_ABL_SKIP_WGRAD", "0") != "0"       # timing ablation only: results are then wrong
-if _SKIP_WGRAD:
-    import warnings
-    warnings.warn("OSSID_ABL_SKIP_WGRAD is set: convolution weight gradients are NOT computed (timing ablation; every "
-                  "training result of this process is wrong)")
 
 
 def _wgrad_side_ok(device, weights=()):
@@ -583,8 +570,6 @@ def _wgrad_async(tensors, fn, device, weights=(), side=None):
     """Run fn() -- weight-gradient launches writing the `dw` tensors a backward() is about to return -- on the side stream
     (side=None: decide here, see _wgrad_side_ok). Inside a recorded launch sequence the launches are stored under stream
     slot 1 behind a wait entry; the replay (_run_seq) does the bookkeeping below."""
-    if _SKIP_WGRAD:
-        return None
     if side is None:
         side = _wgrad_side_ok(device, weights)
     if not side:
@@ -615,13 +600,13 @@ def _wgrad_async(tensors, fn, device, weights=(), side=None):
     _wg_dirty.add(idx)
 
 
-USE_WINO = os.environ.get("OSSID_TRAIN_WINO", "1") != "0"
-# The Winograd launch's tail split (its last, partial round of workgroups cut along the reduction + a finishing launch: fills an
-# otherwise idle chip) in the training step: OFF -- three or four streams keep the chip busy there, and the split's partial sums and
-# finishing launches (27 per step, 0.8 ms of kernel time, most of them on the two detection trunks' streams) are then only work:
-# step 23.55 -> 23.40 ms with it off (same box, two runs each). The test-time head keeps it (one stream: ops.FusedConv).
-WINO_TAIL_SPLIT = os.environ.get("OSSID_TRAIN_WINO_TAIL", "0") != "0"
-WINO_MIN_WGS = int(os.environ.get("OSSID_TRAIN_WINO_MIN_WGS", "128"))
+USE_WINO = True
+# The Winograd launches of the training step run without the tail split (the last, partial round of workgroups cut along the
+# reduction + a finishing launch: fills an otherwise idle chip): three or four streams keep the chip busy there, and the split's
+# partial sums and finishing launches (27 per step, 0.8 ms of kernel time, most of them on the two detection trunks' streams) are
+# then only work: step 23.55 -> 23.40 ms without it (same box, two runs each). The test-time head keeps it (one stream:
+# ops.FusedConv).
+WINO_MIN_WGS = 128
 
 
 def wino_fits(B, H, W, cin, cout, taps, plain=True):
@@ -776,7 +761,7 @@ class AvgPool2(torch.autograd.Function):
 # Recorded launch sequences (_lib.Seq) for the fixed-shape pieces of the step: on (default) the dense blocks -- and the template
 # encoders and the stem, below -- build their launch sequence once per (shape, parameter addresses) into persistent buffers and
 # replay it afterwards; off: every step runs the Python bodies with fresh buffers (what the sequences are recorded from).
-SEQ_REPLAY = os.environ.get("OSSID_SEQ_REPLAY", "1") != "0"
+SEQ_REPLAY = True
 
 
 class _Plan:
@@ -819,12 +804,7 @@ def _run_seq(seq, dev):
 
 
 # The dense layers' 1x1 forward with norm2's batch statistics in its epilogue (csrc/dense_bwd.hip) instead of the convolution +
-# a pass that reads its output again for two sums.
-DENSE_FWD_FUSED = os.environ.get("OSSID_DENSE_FWD_FUSED", "1") != "0"
-# ... and the finalize of a layer's slab statistics inside the next layer's norm1 fold (one launch less per layer)
-DENSE_FOLD_TAIL = os.environ.get("OSSID_DENSE_FOLD_TAIL", "1") != "0"
-
-
+# a pass that reads its output again for two sums (the split-bf16 build only).
 def dense_fwd1_stats(buf, wpk_x6, y1, N, c, Ct, ps, pt):
     """y1 = conv1x1(relu(ps * buf[:, :c] + pt)); returns (rows [P][3][128], counts [P], P) for bn_fold_fwd_rows -- valid until
     the next call on this stream."""
@@ -859,12 +839,11 @@ def _dense_forward(buf, table, block, params, C0):
     N = B * H * W
     growth = block.growth
     batch_stats(flat(buf), N, C0, cs=Ct, sums=table, sums_row_stride=Ct)
-    fused_fwd = (DENSE_FWD_FUSED and FWD_DECIDING == "fwd_x6" and growth == 32 and bool(_lib.fn("ossid_conv_split_bf16")()) and
+    fused_fwd = (FWD_DECIDING == "fwd_x6" and growth == 32 and bool(_lib.fn("ossid_conv_split_bf16")()) and
                  all(int(params[6 * li + 2].shape[0]) == 128 for li in range(len(block))))
     saved = []
     c = C0
     tail = None                     # the previous layer's slab statistics, still partial rows (finalized by this layer's fold)
-    fold_tail = DENSE_FOLD_TAIL and C0 % 32 == 0 and growth == 32
     L = len(block)
     for li, layer in enumerate(block.values()):
         g1, b1, w1, g2, b2, w2 = params[6 * li:6 * li + 6]
@@ -893,7 +872,7 @@ def _dense_forward(buf, table, block, params, C0):
             f2 = bn_fold_fwd(s2, mid, N, g2, b2, layer.norm2.eps, _mom(layer.norm2), layer.norm2.running_mean,
                              layer.norm2.running_var)
         conv_raw(y1, _pack(w2, FWD_DECIDING), B, H, W, mid, growth, 9, buf, pre=(f2[0], f2[1]), pre_relu=True, out_cs=Ct, out_coff=c)
-        if fold_tail and li + 1 < L:
+        if li + 1 < L:
             tail = batch_stats(flat(buf, c), N, growth, cs=Ct, defer=True)       # finished by the next layer's fold
         else:
             batch_stats(flat(buf, c), N, growth, cs=Ct, sums=table.view(-1)[c:], sums_row_stride=Ct)
@@ -904,16 +883,11 @@ def _dense_forward(buf, table, block, params, C0):
 
 # The dense layers' 1x1 data gradient with the masked, scaled accumulation onto the block's gradient buffer and norm1's column
 # sums in ONE launch (csrc/dense_bwd.hip) instead of the convolution + a generic pass over a [N][c] tensor in between.
-DENSE_BWD_FUSED = os.environ.get("OSSID_DENSE_BWD_FUSED", "1") != "0"
-
-
 # ... and the layers' 3x3 data gradient with norm2 / ReLU's backward in its epilogue. (The dense layers' second convolution then
-# needs the DIRECT data-gradient layout, not the Winograd one: Network._train_pack_plan asks this function.)
-DENSE_BWD3_FUSED = os.environ.get("OSSID_DENSE_BWD3_FUSED", "1") != "0"
-
-
+# needs the DIRECT data-gradient layout, not the Winograd one: Network._train_pack_plan asks this function.) Both take the
+# split-bf16 build only: the all-exact build runs the plain convolutions and the generic passes.
 def dense_bwd3_fused():
-    return DENSE_BWD3_FUSED and bool(_lib.fn("ossid_conv_split_bf16")())
+    return bool(_lib.fn("ossid_conv_split_bf16")())
 
 
 def dense_dgrad1_acc(dz, wpk_dgrad, buf, G, N, c, Ct, alpha, ms, mt, add=None):
@@ -947,7 +921,7 @@ def _dense_backward(G, buf, saved, block, params, C0, side, direct=False):
     deferred = []                                                 # the block's 2 L weight gradients: ONE grouped launch below
     side_reads = []                                               # small tensors of this function the grouped launch reads
     da = None
-    fused_bwd = (DENSE_BWD_FUSED and mid == 128 and Ct <= 1024 and N * Ct < (1 << 32) and
+    fused_bwd = (mid == 128 and Ct <= 1024 and N * Ct < (1 << 32) and
                  bool(_lib.fn("ossid_conv_split_bf16")()))
     fused_bwd3 = dense_bwd3_fused() and mid == 128 and growth == 32 and N * mid < (1 << 31)
     c = C0 + L * growth
@@ -1093,7 +1067,7 @@ class DenseBlockTrain(torch.autograd.Function):
         if plan is not None and ctx.gen != plan.gen:
             raise RuntimeError("DenseBlockTrain: this block ran another training forward since the one being differentiated; "
                                "its persistent buffers hold the later pass (run backward before the next forward, or set "
-                               "OSSID_SEQ_REPLAY=0)")
+                               "train_ops.SEQ_REPLAY = False)")
         if plan is not None and torch.cuda.is_current_stream_capturing():
             plan = None                                                    # (forward outside, backward inside a capture)
         if plan is None:

@@ -4,8 +4,6 @@ HIP maps streams onto a few hardware queues in order of creation and two streams
 stream created "now" overlaps with the main stream depends on how many streams the process created before (measured in round
 2: the same finetune step 42.0 or 48.4 ms). The streams are therefore CHOSEN by a probe, once per device.
 """
-import os
-
 import torch
 
 # Which HIP streams actually run beside the main one. HIP maps streams onto a few hardware queues (4 by default) in order of
@@ -15,7 +13,7 @@ import torch
 # queues; each is probed -- a long kernel on the main stream, a short one on the candidate, did the short one finish
 # first? -- and three that run beside the main stream AND beside each other become the weight-gradient stream and the two branch slots.
 _side_pools = {}
-N_STREAM_CANDIDATES = int(os.environ.get("OSSID_STREAM_CANDIDATES", "8"))
+N_STREAM_CANDIDATES = 8
 
 
 def side_streams(device):

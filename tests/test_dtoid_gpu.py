@@ -919,10 +919,9 @@ def test_template_encoders_and_stem_on_own_kernels_match_module_path(hiplib):
             net.use_fused_templates = False
             loc_r, glob_r = net.compute_template_local(tm), net.compute_template_global(tm[:1])
             net.use_fused_templates = True
-            fb = net._fused_backbone()
-            fb.use_fused_stem = False
+            net.use_fused_backbone = False
             feat_r = net._features(img, glob, raw_image=True)
-            fb.use_fused_stem = True
+            net.use_fused_backbone = True
             assert loc.shape == (5, 640, 7, 7) and glob.shape == (1, 64, 3, 3) and feat.shape == (1, 640, 29, 39)
             assert rel(loc, loc_r) < 1e-4 and rel(glob, glob_r) < 1e-4 and rel(feat, feat_r) < 1e-4, trial
     # and the whole test-time call goes through them (raw image in, template cache filled by the fused encoders)

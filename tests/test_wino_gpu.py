@@ -47,8 +47,8 @@ def test_wino_forward_matches_conv2d(T, B, cin, cout, H, W):
                                             (16, 48, 160, 32, 32)])    # five channel tiles: the second group is one tile wide
 def test_wino_128_channel_workgroups_match_conv2d(T, B, cin, cout, H, W):
     """Layers with >= 128 output channels and >= 128 tile groups run four channel tiles per (512-thread) workgroup -- the
-    test-time head at 21 templates; incl. the tail split with its finishing launch, and against the 64-channel form
-    (OSSID_WINO_CT is read once per process, so that comparison is against the direct kernel and float64 only)."""
+    test-time head at 21 templates; incl. the tail split with its finishing launch. (The library picks the channel tiles per
+    workgroup from the shape alone, so the comparison is against the direct kernel and float64, not the 64-channel form.)"""
     g = torch.Generator().manual_seed(B + cin + cout)
     x = torch.randn(B, cin, H, W, generator=g)
     w = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5

@@ -1,5 +1,5 @@
-"""Times ossid_conv_wgrad_group on the 3x3 problems of each dense block at the finetune batch (A/B: OSSID_WGRAD_FEWCH=1 keeps
-them on the general grouped kernel, 3 = default sends them to csrc/wgrad_fc.hip).  python tools/wgrad_group_bench.py"""
+"""Times ossid_conv_wgrad_group on the 3x3 and 1x1 problems of each dense block at the finetune batch.
+python tools/wgrad_group_bench.py"""
 import os
 import sys
 
