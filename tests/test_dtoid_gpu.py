@@ -966,6 +966,8 @@ def test_template_encoder_training_node_matches_module_path(hiplib, which, repla
                 m.bias.normal_(0, 0.1)
     ref = copy.deepcopy(mod)
     ref64 = copy.deepcopy(mod).double().cpu()
+    mod_off = copy.deepcopy(mod)              # this repo's node again, with the weight gradients on the main stream
+    monkeypatch.setattr(train_ops, "WGRAD_SIDE", True)
     B = 3
 
     def l2(a, b):
@@ -974,7 +976,7 @@ def test_template_encoder_training_node_matches_module_path(hiplib, which, repla
     missed64 = []
     for rnd in range(3):
         img = torch.rand(B, 4, 124, 124, device="cuda") * (0.5 + 0.5 * rnd)
-        for m in (mod, ref, ref64):
+        for m in (mod, ref, ref64, mod_off):
             for p in m.parameters():
                 p.grad = None
         y_ref = ref(img)
@@ -984,7 +986,16 @@ def test_template_encoder_training_node_matches_module_path(hiplib, which, repla
         y64.backward(go.double().cpu())
         y = TE.template_encoder_train(mod, img)
         y.backward(go)
+        # WGRAD_SIDE only moves the weight-gradient launches to another stream: the same node with it off must give every bit
+        monkeypatch.setattr(train_ops, "WGRAD_SIDE", False)
+        y_off = TE.template_encoder_train(mod_off, img)
+        y_off.backward(go)
+        monkeypatch.setattr(train_ops, "WGRAD_SIDE", True)
+        train_ops.join_wgrad_stream()
         torch.cuda.synchronize()
+        assert torch.equal(y, y_off), rnd
+        for (n, p), q in zip(mod.named_parameters(), mod_off.parameters()):
+            assert (p.grad is None) == (q.grad is None) and (p.grad is None or torch.equal(p.grad, q.grad)), (rnd, n)
         assert y.shape == y_ref.shape == ((B, 640, 7, 7) if which == "local" else (B, 64, 3, 3))
         assert l2(y, y_ref) < 2e-4, rnd
         assert l2(y, y64) < max(2e-5, 3 * l2(y_ref, y64)), (rnd, l2(y, y64), l2(y_ref, y64))

@@ -242,6 +242,7 @@ def test_dense_block_training_path_matches_module_path(hiplib, L, C0, B, H, W, r
     sequences (train_ops.SEQ_REPLAY) and rounds 1, 2 replay them from the persistent buffers: a launch missing from the
     recording, or a torch kernel inside it, would leave round 1 with round 0's values."""
     monkeypatch.setattr(T, "SEQ_REPLAY", replay)
+    monkeypatch.setattr(T, "WGRAD_SIDE", True)
     torch.manual_seed(2)
     blk = backbones.DenseBlock(L, C0).cuda().train()
     with torch.no_grad():
@@ -252,6 +253,7 @@ def test_dense_block_training_path_matches_module_path(hiplib, L, C0, B, H, W, r
     import copy
     ref = copy.deepcopy(blk)
     ref64 = copy.deepcopy(blk).double().cpu()            # the anchor: the same module in float64 on the CPU
+    blk_off = copy.deepcopy(blk)                         # the same block with its weight gradients on the main stream
 
     def module_path(mod, xx, g):
         xr = xx.clone().requires_grad_(True)
@@ -276,6 +278,19 @@ def test_dense_block_training_path_matches_module_path(hiplib, L, C0, B, H, W, r
         xm = x.clone().requires_grad_(True)
         y = T.dense_block_train(xm, blk)
         y.backward(go)
+        # WGRAD_SIDE only moves the grouped weight-gradient launch to another stream: every bit must match the main-stream run
+        monkeypatch.setattr(T, "WGRAD_SIDE", False)
+        for p in blk_off.parameters():
+            p.grad = None
+        xo = x.clone().requires_grad_(True)
+        yo = T.dense_block_train(xo, blk_off)
+        yo.backward(go)
+        monkeypatch.setattr(T, "WGRAD_SIDE", True)
+        T.join_wgrad_stream()
+        torch.cuda.synchronize()
+        assert torch.equal(y, yo) and torch.equal(xm.grad, xo.grad), rnd
+        for (n, p), q in zip(blk.named_parameters(), blk_off.parameters()):
+            assert torch.equal(p.grad, q.grad), (rnd, n)
         assert rel(y, yr) < 5e-5, rnd
         # against float64: this path (three-way-split forward: f32-level) must be as close as torch's own f32 path is, within 3x
         # (max-norm for the output; the gradients in L2 -- a single ReLU decision flipped between two float32 paths moves single
