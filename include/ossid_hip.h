@@ -735,6 +735,17 @@ int ossid_visib_mask_iou(const float* depth_obs, const float* depth_pred, const 
                          int H, int W, float delta, uint8_t* pred_mask, uint8_t* pred_mask_visib, int32_t* counts4,
                          void* stream);
 
+/* 8f-4  ICP refinement of the chosen pose (scripts/online_learning.py:471-480: zephyr.utils.icp.icpRefinement with
+ * inpaint_depth=False, icp_max_dist=0.01), point-to-point, SPEC.md section 5. One workgroup per pose, all iterations in
+ * the one launch. depth f32 [H][W] (m, 0 = invalid), uv int32 [K][M][2] (x = column, y = row, (-1,-1) = no projection),
+ * poses_in f64 [K][4][4], points f32 [M][3] (1 <= M <= OSSID_ICP_MAX_POINTS) -> poses_out f64 [K][4][4], fitness /
+ * rmse f64 [K] of the returned pose, iterations int32 [K] (updates done). The caller owns all memory; there is no
+ * workspace. Every output is written by the kernel. */
+#define OSSID_ICP_MAX_POINTS 2048
+int ossid_icp_refine(const float* depth, int H, int W, const int32_t* uv, const double* poses_in, const float* points, int K,
+                     int M, float fx, float fy, float cx, float cy, float max_dist, int max_iter, double* poses_out,
+                     double* fitness, double* rmse, int32_t* iterations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

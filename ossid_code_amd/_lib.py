@@ -77,6 +77,7 @@ _PROTOS = {
     "ossid_mask_bbox_heatmap": (_i, [_vp, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     "ossid_render_depth_points": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_visib_mask_iou": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "ossid_icp_refine": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -187,6 +188,8 @@ _PROTOS = {
                              C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_double), _vp]),
 }
 
+
+ICP_MAX_POINTS = 2048   # OSSID_ICP_MAX_POINTS of include/ossid_hip.h
 
 ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
 

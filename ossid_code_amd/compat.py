@@ -12,9 +12,10 @@ install() registers this package's mirrors under the module paths the script imp
     from zephyr.models.pointnet2 import PointNet2SSG
     from zephyr.options import getOptions
     from zephyr.utils import K2meta, meta2K, projectPointsUv
+    from zephyr.utils.icp import icpRefinement
 
-resolve to the MI355X path. Only the hot-path names are provided; everything else the script imports (Halcon PPF,
-ICP, the renderer, BOP tooling, datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
+resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF, the
+renderer, BOP tooling, datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
 `ossid` package is importable, just these attributes are overridden on it, nothing else is shadowed.
 """
 import importlib
@@ -36,13 +37,14 @@ def _module(name):
 
 
 def install():
-    from . import dtoid, hostutil, scoring, zephyr
+    from . import dtoid, hostutil, pipeline, scoring, zephyr
     table = {
         "zephyr.datasets.score_dataset": {"ScoreDataset": zephyr.ScoreDataset},
         "zephyr.models.pointnet2": {"PointNet2SSG": zephyr.PointNet2SSG},
         "zephyr.options": {"getOptions": zephyr.getOptions},
         "zephyr.utils": {"projectPointsUv": zephyr.projectPointsUv, "K2meta": hostutil.K2meta,
                          "meta2K": hostutil.meta2K},
+        "zephyr.utils.icp": {"icpRefinement": pipeline.icpRefinement},
         "ossid.utils.zephyr_utils": {"networkInference": scoring.networkInference,
                                      "filterHypoByMask": scoring.filterHypoByMask},
         "ossid.models.dtoid": {"DtoidNet": dtoid.DtoidNet},

@@ -4,9 +4,11 @@ through host memory between detector, scorer and pseudo-label:
   make_dtoid_sample      datasets/dtoid_bop_dataset.py:256-338 (__getitem__) + utils/data.py:7-83 (processData)
   visibility_and_iou     scripts/online_learning.py:485-500, :557-558 (render depth, estimate_visib_mask_gt, IoUs)
   render_depth_points    depth-only point-splat renderer in place of pyrender (online_learning.py:485)
+  icp_refine             point-to-point ICP of the chosen pose, SPEC.md section 5 (online_learning.py:471-480);
+  icpRefinement          its drop-in for zephyr.utils.icp.icpRefinement (csrc/icp.hip)
   save_results_bop       utils/bop_utils.py:9-52 (BOP csv)
 
-All paths cite /root/reference/python/ossid. Compute goes through libossid_hip.so (csrc/pipeline.hip).
+All paths cite /root/reference/python/ossid. Compute goes through libossid_hip.so (csrc/pipeline.hip, csrc/icp.hip).
 """
 import csv
 import os
@@ -78,6 +80,60 @@ def render_depth_points(pose, model_points, cam_K, hw, radius=1):
                                                   zbuf.data_ptr(), depth.data_ptr(), _lib.stream())
     _lib.check(rc, "ossid_render_depth_points")
     return depth
+
+
+def icp_refine(depth, uv, poses, cam_K, model_points, max_dist=0.01, max_iter=30):
+    """Point-to-point ICP (SPEC.md section 5) of K poses in one launch. depth [H,W] (m, 0 = invalid); uv [M,2] or
+    [K,M,2] integer pixels (x = column, y = row, (-1,-1) = no projection), a device int32 tensor such as a row of
+    networkInference's uv_original, or numpy; poses [4,4] or [K,4,4]; model_points [M,3].
+    -> device tensors poses f64 [K,4,4], fitness f64 [K], rmse f64 [K], iterations int32 [K]."""
+    dev = _dev()
+    T = poses if torch.is_tensor(poses) else torch.from_numpy(np.asarray(poses, dtype=np.float64))
+    if T.dim() not in (2, 3) or tuple(T.shape[-2:]) != (4, 4):
+        raise ValueError("poses must be [4,4] or [K,4,4], got %s" % (tuple(T.shape),))
+    T = T.to(dev, torch.float64).reshape(-1, 4, 4).contiguous()
+    P = _f32(model_points, dev)
+    if P.dim() != 2 or P.shape[1] != 3:
+        raise ValueError("model_points must be [M,3]")
+    M, K = int(P.shape[0]), int(T.shape[0])
+    U = uv if torch.is_tensor(uv) else torch.from_numpy(np.ascontiguousarray(uv))
+    if U.shape[-1] != 2 or U.dim() not in (2, 3) or int(U.shape[-2]) != M:
+        raise ValueError("uv must be [M,2] or [K,M,2] with M = len(model_points) (%d), got %s" % (M, tuple(U.shape)))
+    U = U.to(dev, torch.int32).reshape(-1, M, 2)
+    if int(U.shape[0]) == 1 and K > 1:
+        U = U.expand(K, M, 2)
+    if int(U.shape[0]) != K:
+        raise ValueError("uv has %d rows of hypotheses, poses %d" % (int(U.shape[0]), K))
+    U = U.contiguous()
+    if not float(max_dist) > 0.0:
+        raise ValueError("max_dist must be > 0")
+    if M > _lib.ICP_MAX_POINTS:
+        raise ValueError("ICP takes at most %d model points, got %d" % (_lib.ICP_MAX_POINTS, M))
+    D = _f32(depth, dev)
+    H, W = int(D.shape[0]), int(D.shape[1])
+    Kc = np.asarray(cam_K, dtype=np.float64)
+    out = torch.empty(K, 4, 4, dtype=torch.float64, device=dev)
+    fit = torch.empty(K, dtype=torch.float64, device=dev)
+    rmse = torch.empty(K, dtype=torch.float64, device=dev)
+    its = torch.empty(K, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.fn("ossid_icp_refine")(D.data_ptr(), H, W, U.data_ptr(), T.data_ptr(), P.data_ptr(), K, M,
+                                         float(np.float32(Kc[0, 0])), float(np.float32(Kc[1, 1])),
+                                         float(np.float32(Kc[0, 2])), float(np.float32(Kc[1, 2])), float(max_dist),
+                                         int(max_iter), out.data_ptr(), fit.data_ptr(), rmse.data_ptr(), its.data_ptr(),
+                                         _lib.stream())
+    _lib.check(rc, "ossid_icp_refine")
+    return out, fit, rmse, its
+
+
+def icpRefinement(depth, uv, pose, cam_K, model_points, inpaint_depth=False, icp_max_dist=0.01):
+    """zephyr.utils.icp.icpRefinement as online_learning.py:471-480 calls it -> (pose np.float64 [4,4], info dict
+    {"fitness", "inlier_rmse", "iterations"}). The caller discards the second value; its content is this build's."""
+    if inpaint_depth:
+        raise ValueError("icpRefinement: inpaint_depth=True is not supported (depth inpainting is not part of this "
+                         "build; scripts/online_learning.py:475 passes inpaint_depth=False)")
+    out, fit, rmse, its = icp_refine(depth, uv, pose, cam_K, model_points, max_dist=icp_max_dist)
+    return out[0].cpu().numpy(), {"fitness": float(fit[0]), "inlier_rmse": float(rmse[0]), "iterations": int(its[0])}
 
 
 def visibility_and_iou(depth_obs, depth_pred, gt_mask=None, gt_mask_visib=None, delta=15 / 1000.0):

@@ -4,6 +4,7 @@ scripts/online_learning.py:314-591 (SURVEY.md 8d cfg-5, 8e "full online stream")
     detect (DtoidNet.forwardTestTime)                       :346
     -> pose hypotheses (GIVEN: Halcon PPF / SIFT are out of scope, :416-446)
     -> per-hypothesis ADD/ADI (:452) -> Zephyr score (networkInference, :464) -> argmax (:466-469)
+    -> optional ICP refinement of the chosen pose (icpRefinement, :471-480; OnlineStream(icp_max_dist=...))
     -> predicted depth (point-splat renderer for pyrender, :485) -> visibility mask (:500)
     -> if score > threshold: pseudo-label joins the finetune set (:506-516)
     -> when the set reaches the next multiple of finetune_interval: finetune DTOID (:517-533)
@@ -70,12 +71,19 @@ class SpeculativeWindow:
 
 class OnlineStream:
     """One GPU's worth of the loop. `detector` is a dtoid.DtoidNet (eval), `scorer` a zephyr.PointNet2SSG (eval),
-    `score_dataset` a zephyr.ScoreDataset; `finetune_fn(samples)` is called with the accumulated pseudo-labelled samples."""
+    `score_dataset` a zephyr.ScoreDataset; `finetune_fn(samples)` is called with the accumulated pseudo-labelled samples.
+    icp_max_dist (None = off): refine the argmax pose by point-to-point ICP (pipeline.icp_refine) against the device row
+    uv_original[best] before rendering, timed under times["icp"]; "pred_pose" is then the refined pose and "pred_err" its
+    ADD / ADI, recomputed as online_learning.py:482 does after ICP, and the result carries "icp" (fitness, inlier_rmse,
+    iterations, the unrefined pose and its error)."""
 
-    def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None):
+    def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None,
+                 icp_max_dist=None):
         self.detector, self.scorer, self.dataset = detector, scorer, score_dataset
         self.threshold, self.symmetric, self.finetune_fn = confident_threshold, symmetric, finetune_fn
-        self.times = {k: 0.0 for k in ("detect", "pose_err", "score", "pseudo_label")}
+        self.icp_max_dist = icp_max_dist
+        keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ())
+        self.times = {k: 0.0 for k in keys}
         self.n_processed = 0
 
     def _timed(self, key, fn):
@@ -100,10 +108,23 @@ class OnlineStream:
         data = {k: frame[k] for k in ("img", "depth", "cam_K", "model_points", "model_normals", "model_colors",
                                       "pose_hypos")}
         data["pp_err"] = pp_err
-        poses, scores, errs, _uv = self._timed("score", lambda: networkInference(self.scorer, self.dataset, data))
+        poses, scores, errs, uv = self._timed("score", lambda: networkInference(self.scorer, self.dataset, data))
         best = int(scores.argmax())
         pred_pose, pred_score = poses[best], float(scores.max())
         H, W = frame["depth"].shape
+        pred_err = float(np.asarray(errs)[best])
+        icp = None
+        if self.icp_max_dist is not None:
+            def refine():
+                out, fit, rmse, its = pipeline.icp_refine(frame["depth"], uv[best], pred_pose, frame["cam_K"],
+                                                          frame["model_points"], max_dist=self.icp_max_dist)
+                T = out[0].cpu().numpy()
+                err = pose_errors(T[None], frame["pose_gt"], frame["model_points"], self.symmetric)   # :482
+                return T, float(err[0]), float(fit[0]), float(rmse[0]), int(its[0])
+            refined, refined_err, fit, rmse, its = self._timed("icp", refine)
+            icp = {"fitness": fit, "inlier_rmse": rmse, "iterations": its, "pose_unrefined": pred_pose,
+                   "err_unrefined": pred_err}
+            pred_pose, pred_err = refined, refined_err
 
         def pseudo():
             pred_depth = pipeline.render_depth_points(pred_pose, frame["model_points"], frame["cam_K"], (H, W), radius=1)
@@ -113,9 +134,9 @@ class OnlineStream:
         sample = None
         if confident:
             sample = pipeline.make_dtoid_sample(frame["img"], frame["depth"], pred_mask_visib.float(), frame["cam_K"])
-        return {"pred_pose": pred_pose, "pred_score": pred_score, "pred_err": float(np.asarray(errs)[best]),
+        return {"pred_pose": pred_pose, "pred_score": pred_score, "pred_err": pred_err,
                 "confident": confident, "dtoid_score": det["pred_scores"][:1], "dtoid_bbox": det["pred_bbox"][:1],
-                "pred_mask_visib": pred_mask_visib, "sample": sample}
+                "pred_mask_visib": pred_mask_visib, "sample": sample, **({"icp": icp} if icp is not None else {})}
 
     def run(self, frames, finetune_interval=8):
         """Sequential loop on this GPU (world 1); returns (results, window bookkeeping)."""
