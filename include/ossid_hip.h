@@ -746,6 +746,48 @@ int ossid_icp_refine(const float* depth, int H, int W, const int32_t* uv, const 
                      int M, float fx, float fy, float cx, float cy, float max_dist, int max_iter, double* poses_out,
                      double* fitness, double* rmse, int32_t* iterations, void* stream);
 
+/* 8f-5  Point-pair-feature pose hypotheses (scripts/online_learning.py:295-301 PPFModel(...) and :413-418 / :441-447
+ * find_surface_model: MVTec Halcon in the reference), SPEC.md section 6. Raw device pointers, caller-owned memory; counts
+ * that depend on the data stay on the device (int32 `count`), so one frame is one launch chain with no host round trip.
+ *
+ * ossid_ppf_sample: voxel subsampling (SPEC 6.2) of either an f32 cloud points [N][3] (normals [N][3] for a model: then
+ * a vertex needs a finite non-zero normal, nrm_out receives it normalised; without normals it is a scene point and needs
+ * z > 0), or a depth image f32 [H][W] + mask u8 [H][W] (pixel i valid iff mask && depth > 0, back-projected as SPEC 5.2,
+ * input index = row-major pixel index). Voxel edge h = rel * (diam > 0 ? diam : this cloud's own diameter D). Outputs:
+ * idx_out int32 [max_out] (input indices, ascending), pts_out f32 [max_out][3], count[0] = the number of voxels, which
+ * may exceed max_out (then only max_out rows are written), stats f32 [8] = lo[3], hi[3], D, h. */
+#define OSSID_PPF_MAX_MODEL_POINTS 4096
+#define OSSID_PPF_MAX_SCENE_SAMPLES 8192
+size_t ossid_ppf_sample_workspace_bytes(int n_in);
+int ossid_ppf_sample(const float* points, const float* normals, int N, const float* depth, const uint8_t* mask, int H, int W,
+                     float fx, float fy, float cx, float cy, float rel, float diam, int max_out, void* workspace,
+                     size_t workspace_bytes, int32_t* idx_out, float* pts_out, float* nrm_out, int32_t* count,
+                     float* stats, void* stream);
+/* The model's hash table (SPEC 6.5): Ms <= OSSID_PPF_MAX_MODEL_POINTS sampled points / unit normals, its h and D ->
+ * offsets u32 [words] (words = ossid_ppf_model_table_words(...), 0 = bad arguments; offsets[(key * chunks + chunk)] ..
+ * [.. + 1] delimit the entries of a key whose reference point lies in chunk = m_r / 1024), entries u32 [max_entries >=
+ * Ms (Ms - 1)] = m_r * 32 + rotation bin, in unspecified order within a range. Workspace: 4 * words bytes. */
+int64_t ossid_ppf_model_table_words(int Ms, float h, float D);
+int ossid_ppf_model_table(const float* points, const float* normals, int Ms, float h, float D, uint32_t* offsets,
+                          uint32_t* entries, int64_t max_entries, void* workspace, size_t workspace_bytes, void* stream);
+/* Scene normals (SPEC 6.3) of the first min(count, cap) sampled points f32 [cap][3] (cap <= OSSID_PPF_MAX_SCENE_SAMPLES;
+ * count > cap: nothing is valid): normals f32 [cap][3], ok u8 [cap] (0 = fewer than 3 neighbours within radius). */
+int ossid_ppf_scene_normals(const float* scene, const int32_t* count, int cap, float radius, float* normals, uint8_t* ok,
+                            void* stream);
+/* Voting (SPEC 6.5) for reference points 0, ref_step, 2 ref_step, ... -> peaks int32 [max_ref][3] = (m_r, alpha, votes;
+ * votes 0 = no candidate), cand_poses f64 [max_ref][4][4], max_ref = ceil(cap / ref_step). */
+size_t ossid_ppf_vote_workspace_bytes(int cap, int ref_step, int Ms);
+int ossid_ppf_vote(const float* scene, const float* scene_normals, const uint8_t* scene_ok, const int32_t* count, int cap,
+                   int ref_step, const float* model_points, const float* model_normals, int Ms, float h, float D,
+                   const uint32_t* offsets, const uint32_t* entries, void* workspace, size_t workspace_bytes,
+                   int32_t* peaks, double* cand_poses, void* stream);
+/* Clustering (SPEC 6.6) -> poses_out f64 [num_result][4][4], scores_out f64 [num_result] (rows past info[0] are zero),
+ * info int32 [4] = results, sampled scene points (count[0]; > cap means the scene was not processed), candidates,
+ * clusters. */
+int ossid_ppf_cluster(const int32_t* peaks, const double* cand_poses, const int32_t* count, int cap, int ref_step, int Ms,
+                      float D, float dist_rel, int num_result, double* poses_out, double* scores_out, int32_t* info,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,14 @@ _PROTOS = {
     "ossid_render_depth_points": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_visib_mask_iou": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "ossid_icp_refine": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ossid_ppf_sample_workspace_bytes": (_sz, [_i]),
+    "ossid_ppf_sample": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ossid_ppf_model_table_words": (C.c_int64, [_i, _f, _f]),
+    "ossid_ppf_model_table": (_i, [_vp, _vp, _i, _f, _f, _vp, _vp, C.c_int64, _vp, _sz, _vp]),
+    "ossid_ppf_scene_normals": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "ossid_ppf_vote_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ossid_ppf_vote": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ossid_ppf_cluster": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -190,6 +198,8 @@ _PROTOS = {
 
 
 ICP_MAX_POINTS = 2048   # OSSID_ICP_MAX_POINTS of include/ossid_hip.h
+PPF_MAX_MODEL_POINTS = 4096    # OSSID_PPF_MAX_MODEL_POINTS
+PPF_MAX_SCENE_SAMPLES = 8192   # OSSID_PPF_MAX_SCENE_SAMPLES
 
 ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
 

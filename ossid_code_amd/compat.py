@@ -13,8 +13,9 @@ install() registers this package's mirrors under the module paths the script imp
     from zephyr.options import getOptions
     from zephyr.utils import K2meta, meta2K, projectPointsUv
     from zephyr.utils.icp import icpRefinement
+    from zephyr.utils.halcon_wrapper import PPFModel      (only with install(ppf=True))
 
-resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF, the
+resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF unless install(ppf=True), the
 renderer, BOP tooling, datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
 `ossid` package is importable, just these attributes are overridden on it, nothing else is shadowed.
 """
@@ -36,7 +37,9 @@ def _module(name):
         return mod
 
 
-def install():
+def install(ppf=False):
+    """ppf=True also maps zephyr.utils.halcon_wrapper.PPFModel to this build's device PPF (SPEC.md section 6, which differs
+    from a Halcon run: no dense pose refinement); by default a user with Halcon keeps Halcon."""
     from . import dtoid, hostutil, pipeline, scoring, zephyr
     table = {
         "zephyr.datasets.score_dataset": {"ScoreDataset": zephyr.ScoreDataset},
@@ -49,6 +52,9 @@ def install():
                                      "filterHypoByMask": scoring.filterHypoByMask},
         "ossid.models.dtoid": {"DtoidNet": dtoid.DtoidNet},
     }
+    if ppf:
+        from . import ppf as ppf_mod
+        table["zephyr.utils.halcon_wrapper"] = {"PPFModel": ppf_mod.PPFModel}
     for modname, attrs in table.items():
         mod = _module(modname)
         for k, v in attrs.items():

@@ -2,7 +2,8 @@
 scripts/online_learning.py:314-591 (SURVEY.md 8d cfg-5, 8e "full online stream"):
 
     detect (DtoidNet.forwardTestTime)                       :346
-    -> pose hypotheses (GIVEN: Halcon PPF / SIFT are out of scope, :416-446)
+    -> pose hypotheses (GIVEN per frame, or device PPF with OnlineStream(ppf_models=...), :384-418 / :441-447;
+       SIFT is out of scope)
     -> per-hypothesis ADD/ADI (:452) -> Zephyr score (networkInference, :464) -> argmax (:466-469)
     -> optional ICP refinement of the chosen pose (icpRefinement, :471-480; OnlineStream(icp_max_dist=...))
     -> predicted depth (point-splat renderer for pyrender, :485) -> visibility mask (:500)
@@ -20,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from . import pipeline
+from . import pipeline, ppf
 from .hostutil import K2meta
 from .scoring import networkInference, pose_errors
 
@@ -75,14 +76,19 @@ class OnlineStream:
     icp_max_dist (None = off): refine the argmax pose by point-to-point ICP (pipeline.icp_refine) against the device row
     uv_original[best] before rendering, timed under times["icp"]; "pred_pose" is then the refined pose and "pred_err" its
     ADD / ADI, recomputed as online_learning.py:482 does after ICP, and the result carries "icp" (fitness, inlier_rmse,
-    iterations, the unrefined pose and its error)."""
+    iterations, the unrefined pose and its error).
+    ppf_models (None = off): dict obj_id -> ppf.PPFModel built in metres; hypotheses then come from the frame's depth
+    inside the DTOID boxes (ppf.PPFModel.find_hypotheses, mask as online_learning.py:384-405 builds it), timed under
+    times["ppf"], `frame["pose_hypos"]` is not read, and the result carries "n_hypos" and the hypotheses ("ppf_hypos"). ppf_kwargs go to find_hypotheses."""
 
     def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None,
-                 icp_max_dist=None):
+                 icp_max_dist=None, ppf_models=None, ppf_kwargs=None):
         self.detector, self.scorer, self.dataset = detector, scorer, score_dataset
         self.threshold, self.symmetric, self.finetune_fn = confident_threshold, symmetric, finetune_fn
         self.icp_max_dist = icp_max_dist
-        keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ())
+        self.ppf_models, self.ppf_kwargs = ppf_models, dict(ppf_kwargs or {})
+        keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ()) + \
+            (("ppf",) if ppf_models is not None else ())
         self.times = {k: 0.0 for k in keys}
         self.n_processed = 0
 
@@ -103,11 +109,12 @@ class OnlineStream:
         batch = {"img": img_t, "obj_id": torch.tensor([int(frame["obj_id"])]), "limg": frame["limg"][None].to(dev),
                  "lmask": frame["lmask"][None].to(dev)}
         det = self._timed("detect", lambda: self.detector.forwardTestTime(batch))
-        pp_err = self._timed("pose_err", lambda: pose_errors(frame["pose_hypos"], frame["pose_gt"],
-                                                             frame["model_points"], self.symmetric))
-        data = {k: frame[k] for k in ("img", "depth", "cam_K", "model_points", "model_normals", "model_colors",
-                                      "pose_hypos")}
-        data["pp_err"] = pp_err
+        hypos = frame["pose_hypos"] if self.ppf_models is None else \
+            self._timed("ppf", lambda: self._ppf_hypotheses(frame, det))
+        pp_err = self._timed("pose_err", lambda: pose_errors(hypos, frame["pose_gt"], frame["model_points"],
+                                                             self.symmetric))
+        data = {k: frame[k] for k in ("img", "depth", "cam_K", "model_points", "model_normals", "model_colors")}
+        data["pose_hypos"], data["pp_err"] = hypos, pp_err
         poses, scores, errs, uv = self._timed("score", lambda: networkInference(self.scorer, self.dataset, data))
         best = int(scores.argmax())
         pred_pose, pred_score = poses[best], float(scores.max())
@@ -136,7 +143,27 @@ class OnlineStream:
             sample = pipeline.make_dtoid_sample(frame["img"], frame["depth"], pred_mask_visib.float(), frame["cam_K"])
         return {"pred_pose": pred_pose, "pred_score": pred_score, "pred_err": pred_err,
                 "confident": confident, "dtoid_score": det["pred_scores"][:1], "dtoid_bbox": det["pred_bbox"][:1],
-                "pred_mask_visib": pred_mask_visib, "sample": sample, **({"icp": icp} if icp is not None else {})}
+                "pred_mask_visib": pred_mask_visib, "sample": sample, **({"icp": icp} if icp is not None else {}),
+                **({"n_hypos": len(hypos), "ppf_hypos": hypos} if self.ppf_models is not None else {})}
+
+    def _ppf_hypotheses(self, frame, det):
+        """online_learning.py:384-405 (mask from the expanded DTOID boxes) and :441-447 (PPF on the masked depth)."""
+        depth = np.asarray(frame["depth"], dtype=np.float32)
+        H, W = depth.shape
+        mask = np.zeros((H, W), dtype=np.uint8)
+        boxes = det["final_bbox"][0].detach().cpu().numpy().reshape(-1, 4)
+        scores = det["final_score"][0].detach().cpu().numpy().reshape(-1)
+        for (x1, y1, x2, y2), sc in zip(boxes, scores):
+            if sc < 0.5 and (mask.astype(bool) & (depth > 0)).any():
+                continue
+            x1, y1, x2, y2 = pipeline.expand_box(x1, y1, x2, y2, H, W, 1.2)
+            mask[int(y1):int(y2), int(x1):int(x2)] = 1
+        model = self.ppf_models[int(frame["obj_id"])]
+        poses, _scores, info = model.find_hypotheses(depth, mask, frame["cam_K"], **self.ppf_kwargs)
+        n = ppf.check_info(info, self.ppf_kwargs.get("SceneSamplingDist", 0.05))[0]
+        if n == 0:           # nothing found: one identity hypothesis, as online_learning.py:429-430 does for SIFT
+            return np.eye(4)[None]
+        return poses[:n].cpu().numpy()
 
     def run(self, frames, finetune_interval=8):
         """Sequential loop on this GPU (world 1); returns (results, window bookkeeping)."""

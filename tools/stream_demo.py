@@ -2,6 +2,9 @@
 `--interval` confident frames. Prints one JSON line with frames/s and the per-stage wall time. Random-init networks and
 synthetic frames: this measures the loop, not accuracy.
   python tools/stream_demo.py --frames 24 --hypos 1000 --interval 8
+With --ppf the hypotheses come from each frame's depth (device PPF, ossid_code_amd/ppf.py) instead of perturbations of the
+ground truth, and the object is the asymmetric ellipsoid with a bump of tests/ref_icp.py (on the package's sphere every
+rotation is equally good), placed at a different pose per frame.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--interval", type=int, default=8)
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--ppf", action="store_true", help="PPF hypotheses from the frame (asymmetric test object)")
     a = ap.parse_args()
     t_start = time.perf_counter()
     from ossid_code_amd import parallel
@@ -53,7 +57,25 @@ def main():
     bank = pipeline.TemplateBank(n_local_test=a.templates)
     bank.add(1, limg, lmask)
     frames = []
-    for f in range(a.frames):
+    ppf_models = None
+    if a.ppf:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+        import ref_icp as ri                                            # the asymmetric test object
+        from ossid_code_amd import ppf
+        surf_p, surf_n = ri._surface(40000, np.random.default_rng(7))
+        ppf_models = {1: ppf.PPFModel(surf_p, normals=surf_n)}
+        rng = np.random.default_rng(3)
+        for f in range(a.frames):
+            img, bg = synth.make_frame(100 + f)
+            T = np.eye(4)
+            T[:3, :3] = ri.rot(rng.normal(size=3), rng.uniform(0, 180))
+            T[:3, 3] = [rng.uniform(-0.1, 0.1), rng.uniform(-0.08, 0.08), rng.uniform(0.65, 0.85)]
+            M = ri.model_points(T, a.points, seed=f)
+            frames.append({"img": img, "depth": ri.render_into(bg, T, synth.CAM_K), "cam_K": synth.CAM_K.copy(),
+                           "model_points": M, "model_normals": M / np.linalg.norm(M, axis=1, keepdims=True),
+                           "model_colors": np.full_like(M, 0.5), "limg": limg, "lmask": lmask, "obj_id": 1,
+                           "pose_gt": T})
+    for f in range(0 if a.ppf else a.frames):
         d = synth.make_scoring_inputs(a.hypos, a.points, seed=100 + f)
         d.update(limg=limg, lmask=lmask, obj_id=1, pose_gt=d["pose_hypos"][0].copy())
         frames.append(d)
@@ -113,7 +135,7 @@ def main():
         torch.cuda.synchronize()
         ft_time[0] += time.perf_counter() - t0
 
-    stream = OnlineStream(det, scorer, dataset, confident_threshold=-1e30, finetune_fn=finetune_fn)
+    stream = OnlineStream(det, scorer, dataset, confident_threshold=-1e30, finetune_fn=finetune_fn, ppf_models=ppf_models)
     note("models and %d frames ready" % len(frames))
     r0 = stream.process(frames[0])             # warm-up: graph capture, workspace allocation ...
     note("warm-up frame done")
@@ -158,6 +180,8 @@ def main():
             dist.destroy_process_group()
         return
     per = {k: 1e3 * v / max(1, stream.n_processed) for k, v in stream.times.items()}   # frames THIS rank processed
+    if a.ppf:
+        a.hypos = float(np.mean([r["n_hypos"] for r in results])) if dist is None else "ppf"
     print(json.dumps({"metric": "online stream frames/sec", "value": a.frames / total, "unit": "frames/s", "n_gpus": world,
                       "speculated_frames_discarded": win.discarded,
                       "frames": a.frames, "hypotheses_per_frame": a.hypos, "points": a.points,
@@ -165,7 +189,8 @@ def main():
                       "finetune_steps": ft_steps[0], "finetune_ms_per_step": 1e3 * ft_time[0] / max(1, ft_steps[0]),
                       "ms_per_frame_excl_finetune": 1e3 * (total - ft_time[0]) / a.frames,
                       "frames_processed_by_rank0": stream.n_processed,
-                      "stage_ms_per_frame": per, "hyp_per_sec_in_stream": a.hypos / (per["score"] * 1e-3),
+                      "stage_ms_per_frame": per, "hyp_per_sec_in_stream": (a.hypos / (per["score"] * 1e-3)) if not isinstance(a.hypos, str) else None,
+                      "hypotheses": "ppf" if a.ppf else "perturbed ground truth",
                       "data": "synthetic", "weights": "random-init"}))
     if dist is not None:
         dist.destroy_process_group()
