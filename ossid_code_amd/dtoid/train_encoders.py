@@ -133,6 +133,21 @@ def stem_relayout(src, dst, cout, cin, k, kpad, inverse=False):
                                                          _lib.stream()), "ossid_stem_weight_relayout")
 
 
+def stem_packed(w):
+    """The stem's [64, 4, 3, 3] weights as the 1x1 convolution on ossid_im2col_stem's 48 columns runs them: re-laid to
+    column order, then packed in the encoders' forward form (raw ops only: recordable)."""
+    dev = w.device
+    w_stem = new_buf((64, STEM_KPAD), dev)
+    stem_relayout(w, w_stem, 64, 4, 3, STEM_KPAD)
+    form = T._KIND_FORM[T.FWD_ENCODER]     # every convolution in front of a ReLU / max-pool runs at f32-level accuracy (T.FWD_ENCODER)
+    wpk = new_buf((_lib.fn("ossid_conv_packed_floats_form")(64, STEM_KPAD, 1, form),), dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.fn("ossid_conv_pack_weights_form")(w_stem.data_ptr(), 64, STEM_KPAD, 1, 0, form, wpk.data_ptr(), _lib.stream()),
+                   "ossid_conv_pack_weights_form")
+    wpk._ossid_exact = form
+    return wpk
+
+
 def _bn_train(x_flat, n, C, bn, cs=0):
     """Column sums + fold of a training BatchNorm on a channels-last tensor: [4, C] = scale, shift, mean, rstd."""
     st = batch_stats(x_flat, n, C, cs=cs)
@@ -158,14 +173,7 @@ def _encoder_forward(mod, cols):
     B, _, H, W = cols.shape
     stem = mod.backbone_0[0]
     sv = {"cols": cols, "stages": []}
-    w_stem = new_buf((64, STEM_KPAD), dev)
-    stem_relayout(stem.weight.detach(), w_stem, 64, 4, 3, STEM_KPAD)
-    form = T._KIND_FORM[T.FWD_ENCODER]     # every convolution in front of a ReLU / max-pool runs at f32-level accuracy (T.FWD_ENCODER)
-    wpk = new_buf((_lib.fn("ossid_conv_packed_floats_form")(64, STEM_KPAD, 1, form),), dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.fn("ossid_conv_pack_weights_form")(w_stem.data_ptr(), 64, STEM_KPAD, 1, 0, form, wpk.data_ptr(), _lib.stream()),
-                   "ossid_conv_pack_weights_form")
-    wpk._ossid_exact = form
+    wpk = stem_packed(stem.weight.detach())
     x = new_buf((B, 64, H, W), dev, channels_last=True)
     conv_raw(cols, wpk, B, H, W, STEM_KPAD, 64, 1, x, bias=stem.bias.detach(), act=2)
     sv["x0"] = x

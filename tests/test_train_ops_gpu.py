@@ -26,30 +26,44 @@ def cl(t):
 
 @pytest.mark.parametrize("N,C,Ct,off", [(1000, 32, 96, 32), (4097, 640, 640, 0), (77, 8, 8, 0), (50000, 128, 128, 0),
                                         (3, 256, 512, 128)])
-@pytest.mark.parametrize("mask_mode,sum_mode,acc", [(0, 1, False), (1, 1, True), (2, 2, False), (0, 0, True), (1, 0, False)])
+@pytest.mark.parametrize("mask_mode,sum_mode,acc", [(0, 1, False), (1, 1, True), (2, 2, False), (0, 0, True), (1, 0, False),
+                                                    (3, 2, False), (3, 1, True), (0, 3, False), (0, 3, True)])
 def test_chan_op_all_modes(hiplib, N, C, Ct, off, mask_mode, sum_mode, acc):
+    """Every mask / sum mode of ossid_chan_op on a channel slice. mask_mode 3 (the ReLU derivative read from the ReLU's
+    output: 1 where x > 0, so exact zeros are masked) runs on x = a ReLU output; sum_mode 3 (batch statistics about a
+    per-channel pivot, the tensor's first row, as batch_stats takes them) returns (sum (g - p), sum (g - p)^2, p)."""
     g = torch.Generator().manual_seed(N + C + mask_mode)
     G, X, O = (torch.randn(N, Ct, generator=g) for _ in range(3))
+    if mask_mode == 3:
+        X = X.clamp(min=0)
+    if sum_mode == 3:
+        G = G + 3.0
     al, be, ka, ms, mt = (torch.randn(C, generator=g) for _ in range(5))
     gs, xs = G[:, off:off + C].double(), X[:, off:off + C].double()
     if mask_mode == 0:
         m = torch.ones_like(xs)
     elif mask_mode == 1:
         m = ((ms.float() * X[:, off:off + C] + mt.float()) > 0).double()
-    else:
+    elif mask_mode == 2:
         m = torch.where(xs > 0, torch.ones_like(xs), xs + 1)
+    else:
+        m = (xs > 0).double()
     r = (al.double() * gs + be.double() * xs + ka.double()) * m
     want_out = O.double().clone()
     want_out[:, off:off + C] = (want_out[:, off:off + C] + r) if acc else r
     Gd, Xd, Od = G.cuda(), X.cuda(), O.cuda()
     sums = T.chan_op(Gd.view(-1)[off:], N, C, x=Xd.view(-1)[off:], out=Od.view(-1)[off:], g_cs=Ct, x_cs=Ct, out_cs=Ct,
                      alpha=al.cuda(), beta=be.cuda(), kappa=ka.cuda(), mask_mode=mask_mode, mask_scale=ms.cuda(),
-                     mask_shift=mt.cuda(), accumulate=acc, sum_mode=sum_mode)
+                     mask_shift=mt.cuda(), accumulate=acc, sum_mode=sum_mode, pivot=Gd.view(-1)[off:] if sum_mode == 3 else None)
     assert rel(Od, want_out) < 1e-5
     if sum_mode == 1:
         assert rel(sums[0], (gs * m).sum(0)) < 2e-5 and rel(sums[1], (gs * m * xs).sum(0)) < 2e-5
     elif sum_mode == 2:
         assert rel(sums[0], r.sum(0)) < 2e-5 and rel(sums[1], (r * xs).sum(0)) < 2e-5
+    elif sum_mode == 3:
+        d = gs - gs[0]
+        assert sums.shape == (3, C) and torch.equal(sums[2].cpu(), G[0, off:off + C])
+        assert rel(sums[0], d.sum(0)) < 3e-7 and rel(sums[1], (d * d).sum(0)) < 3e-7     # (measured 9.4e-8)
     else:
         assert sums is None
 
