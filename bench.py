@@ -1,6 +1,6 @@
 """bench.py -- OSSID hot-path benchmark on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one frame of Zephyr hypothesis scoring, BASELINE.json configs[1]: 1000 pose hypotheses x 2048 model
@@ -9,10 +9,14 @@ model table, project + gather + featurize every (hypothesis, point), and score w
 already resident in HBM when the timed region starts, scores stay on the device (one sync after the K steps).
 Frames shard across ranks with no data-path collective ("weak" scaling): every rank scores its own frame.
 
-The JSON line also carries
-  roofline      the dominant kernel's achieved rate (HIP events recorded around it inside the timed steps),
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the outputs
+(--dump-outputs) and print the headline line (headline()). With --full the JSON line also carries
+  roofline      the dominant kernel's achieved rate (HIP events recorded around it in a second pass over the K frames,
+                one frame in flight), with stage_ms and featurize from the same pass,
   cpu_baseline  the CPU oracle (oracle/, a port of the same algorithm: kind "port") timed on the host cores on a
-                bounded sample of the same workload, rank 0 / N=1 only.
+                bounded sample of the same workload, rank 0 / N=1 only; the GPU scores of that sample are checked
+                against it bit for bit,
+  dtoid         the secondary DTOID measurements (test-time forward, batched forward, pairs, finetune step).
 """
 import argparse
 import gc
@@ -46,9 +50,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--cpu-sample", type=int, default=192, help="hypotheses in the CPU-oracle sample")
-    p.add_argument("--no-dtoid", action="store_true", help="skip the secondary DTOID measurements")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline figure does not need: the one-frame-in-flight pass for "
+                        "the roofline / stage_ms / featurize blocks, the CPU oracle (cpu_baseline, and the bit-for-bit check "
+                        "of the GPU scores against it) and the DTOID legs (dtoid). Off: set up, warm up, time the steps, "
+                        "write the outputs and print the headline line")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle")
+    p.add_argument("--cpu-sample", type=int, default=192, help="hypotheses in the CPU-oracle sample (--full)")
+    p.add_argument("--no-dtoid", action="store_true", help="with --full: skip the secondary DTOID measurements")
     p.add_argument("--streams", type=int, default=2,
                    help="frames in flight per GPU in the timed region, on alternating HIP streams (the product form: "
                         "scoring.networkInferenceMany keeps two in flight). The kernels of one frame fill the launch tails of "
@@ -375,11 +384,27 @@ def spawn_ranks(n):
     sys.exit(subprocess.call(cmd))
 
 
+def headline(elapsed, world, steps, warmup, n_streams, top1):
+    """The line of a plain run (pure host logic, tests/test_bench_contract.py): the headline figure and the workload.
+    elapsed: seconds for `steps` frames per rank (max over ranks) with n_streams frames in flight."""
+    return {
+        "metric": "hypotheses scored/sec", "value": world * steps * N_HYP / elapsed, "unit": "hyp/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "zephyr_score: %d hypotheses x %d model points, %dx%d RGB-D frame, "
+                               "HSVD_diff_uv_norm features (D=8) + PointNet2SSG (SA 512/0.2/64 [8,64,64,128], "
+                               "SA 128/0.4/64 [131,128,128,256], SA all [259,256,512,1024], FC 512-256-1); "
+                               "BASELINE.json configs[1]" % (N_HYP, N_PTS, IMG_W, IMG_H),
+                   "frames_per_step_per_gpu": 1, "frames_in_flight_per_gpu": n_streams,
+                   "parallelism": "frames sharded, %d rank(s)" % world, "top1": top1},
+    }
+
+
 def make_line(names, stage_ms, feat_ms, elapsed, world, steps, warmup, n_streams, top1, base, dtoid_out, extra=None):
-    """THE json line (pure host logic: tests/test_bench_contract.py checks its schema and arithmetic on synthetic stage
-    times). names / stage_ms: the scorer's stage names and their mean HIP-event durations (ms) per frame with every kernel
-    alone on the chip (one stream, one launch per stage); feat_ms: the featurize kernel's; elapsed: seconds for `steps`
-    frames per rank (max over ranks) with n_streams frames in flight. extra: reserved."""
+    """THE json line of a --full run: headline() plus what only --full measures (pure host logic:
+    tests/test_bench_contract.py checks its schema and arithmetic on synthetic stage times). names / stage_ms: the
+    scorer's stage names and their mean HIP-event durations (ms) per frame with every kernel alone on the chip (one
+    stream, one launch per stage); feat_ms: the featurize kernel's; elapsed: as in headline(). extra: reserved."""
     traffic = None
     try:   # HBM-side bytes per launch from the committed rocprofv3 PMC passes (tools/pmc_traffic.py)
         pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))["kernels"]
@@ -392,16 +417,8 @@ def make_line(names, stage_ms, feat_ms, elapsed, world, steps, warmup, n_streams
     dom_ms = float(stage_ms[names.index(dom)])
     achieved = STAGE_FLOPS[dom] * N_HYP / (dom_ms * 1e-3) / 1e12
     feat_bytes = N_HYP * N_PTS * (32 + 8) + IMG_H * IMG_W * 16 + N_PTS * 48 + N_HYP * 64
-    return {
-        "metric": "hypotheses scored/sec", "value": world * steps * N_HYP / elapsed, "unit": "hyp/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "zephyr_score: %d hypotheses x %d model points, %dx%d RGB-D frame, "
-                               "HSVD_diff_uv_norm features (D=8) + PointNet2SSG (SA 512/0.2/64 [8,64,64,128], "
-                               "SA 128/0.4/64 [131,128,128,256], SA all [259,256,512,1024], FC 512-256-1); "
-                               "BASELINE.json configs[1]" % (N_HYP, N_PTS, IMG_W, IMG_H),
-                   "frames_per_step_per_gpu": 1, "frames_in_flight_per_gpu": n_streams,
-                   "parallelism": "frames sharded, %d rank(s)" % world, "top1": top1},
+    line = headline(elapsed, world, steps, warmup, n_streams, top1)
+    line.update({
         "roofline": {"bound": "mfma", "kernel": dom + "_kernel", "achieved": achieved,
                      "peak": PEAK_F32_MATRIX_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_F32_MATRIX_TFLOPS,
                      "traffic": traffic, "avg_launch_ms": dom_ms,
@@ -420,7 +437,8 @@ def make_line(names, stage_ms, feat_ms, elapsed, world, steps, warmup, n_streams
                       "measured": "HIP events around the launch in the one-frame-in-flight pass, like the scorer's stages"},
         "cpu_baseline": base,
         "dtoid": dtoid_out,
-    }
+    })
+    return line
 
 
 def main():
@@ -453,7 +471,7 @@ def main():
     model = synth.random_pn2_state(zephyr.PointNet2SSG(8, Args(), num_class=1), 0).eval()
 
     base, base_scores = None, None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         base, base_scores = cpu_baseline(d, model, a.cpu_sample)
 
     model = model.to(dev)
@@ -464,10 +482,9 @@ def main():
                      ("model_points", "model_normals", "model_colors"))
     K = d["cam_K"]
     cam = tuple(float(np.float32(v)) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
-    names = _lib.StageEvents.names()
     # The timed region runs the product form of the loop: `--streams` frames in flight on alternating HIP streams
-    # (scoring.networkInferenceMany). Per-kernel HIP events are taken in a second pass (below), one frame at a time.
-    feat_evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+    # (scoring.networkInferenceMany). With --full, per-kernel HIP events are taken in a second pass (below), one frame at
+    # a time.
 
     def step(events=None, feat_pair=None):
         rgbd = zephyr.stage_frame(img, depth, dev, blur=True)
@@ -504,11 +521,21 @@ def main():
         elapsed = float(t.item())
     if a.dump_outputs:
         dump_outputs(a.dump_outputs, scores, top, rank, world)
+    top1 = int(top.item())
+    if not a.full:
+        # a plain run ends here: the headline line is all it measures
+        if rank == 0:
+            print(json.dumps(headline(elapsed, world, a.steps, a.warmup, len(streams), top1)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # The roofline leg: the same K frames once more, ONE frame in flight, HIP events recorded on the launch stream around
     # every stage (ossid_pn2_score's stage_events_host) and around the featurize kernel -- each kernel alone on the chip,
     # which is what a per-kernel fraction of peak means. (rocprofv3's per-kernel averages over this command mix both
     # passes: launches of the timed region run beside another frame's kernels and take a few per cent longer.)
+    names = _lib.StageEvents.names()
+    feat_evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
     clean = [_lib.StageEvents() for _ in range(a.steps)]
     for i in range(a.steps):
         step(clean[i], feat_evs[i])
@@ -518,7 +545,6 @@ def main():
     for e in clean:
         e.close()
 
-    top1 = int(top.item())
     got_sample = scores[: len(base_scores)].cpu().numpy() if base_scores is not None else None
 
     def emit(dtoid_out):

@@ -55,6 +55,35 @@ def test_make_line_has_every_contract_field_and_consistent_arithmetic():
     assert bench.make_line(STAGES, stage_ms2, 0.035, elapsed, 1, steps, 3, 1, 0, None, None)["roofline"]["kernel"] == "sa2_kernel"
 
 
+def test_plain_line_is_the_headline_and_the_full_line_extends_it():
+    """A plain run prints headline(): the headline figure and the workload, none of what only --full measures; the
+    --full line (make_line) carries the same headline fields with the same values."""
+    bench = _bench_module()
+    steps, world, elapsed = 20, 2, 0.31
+    h = json.loads(json.dumps(bench.headline(elapsed, world, steps, 3, 2, 7)))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in h, key
+    for key in ("roofline", "stage_ms", "stage_ms_sum", "featurize", "cpu_baseline", "dtoid"):
+        assert key not in h, key
+    assert h["metric"] == "hypotheses scored/sec" and h["unit"] == "hyp/s" and h["higher_is_better"] is True
+    assert h["dtype"] == "f32" and h["config"]["top1"] == 7 and h["config"]["frames_in_flight_per_gpu"] == 2
+    assert abs(h["ms_per_step"] - 1e3 * elapsed / steps) < 1e-9
+    assert abs(h["value"] - world * 1000.0 * 1e3 / h["ms_per_step"]) < 1e-6 * h["value"]
+    full = bench.make_line(STAGES, [0.44, 0.43, 6.2, 0.26, 0.07, 0.05, 6.0, 0.8, 0.13], 0.035, elapsed, world, steps, 3,
+                           2, 7, None, None)
+    assert {k: full[k] for k in h} == bench.headline(elapsed, world, steps, 3, 2, 7)
+
+
+def test_full_is_off_by_default(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup) == (5, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full"])
+    assert bench.parse().full is True
+
+
 def test_dtoid_flop_model_is_consistent():
     """nominal = the survey's 39.7 + 45.96 n_t GFLOP; the executed count never exceeds it and the GEMM reassociation only
     switches on from 40 templates."""

@@ -6,9 +6,9 @@ T=${1:-r04}
 O=gpurun_out/$T/ev
 mkdir -p $O
 R=$PWD
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp && cd $R
-rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 > $O/bench_under_profiler.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --full > $O/bench_under_profiler.json 2> $O/stats.err
 cp $O/stats/*/*kernel_stats.csv $O/kernel_stats.csv
 python tools/stats_by_pass.py $O/stats/*/*kernel_trace.csv --steps 20 --warmup 5 > $O/kernel_stats_by_pass.txt
 rocprofv3 --kernel-trace -d $O/ft --output-format csv -- python3 tools/bench_finetune.py --reps 3 --no-graph > $O/ft.log 2>&1

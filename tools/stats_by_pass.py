@@ -1,6 +1,6 @@
-"""Per-kernel durations of the Zephyr scorer's launches in a rocprofv3 --kernel-trace csv of `bench.py`, split by the pass
-they belong to. bench.py launches every scorer kernel W (warm-up) + K (timed region: `--streams` frames in flight, so a
-launch shares the chip with another frame's kernels) + K (roofline pass: one frame in flight, each kernel alone -- what
+"""Per-kernel durations of the Zephyr scorer's launches in a rocprofv3 --kernel-trace csv of `bench.py --full`, split by the
+pass they belong to. bench.py --full launches every scorer kernel W (warm-up) + K (timed region: `--streams` frames in
+flight, so a launch shares the chip with another frame's kernels) + K (roofline pass: one frame in flight, each kernel alone -- what
 `roofline.avg_launch_ms` of the JSON line is measured on) times; rocprofv3's --stats average mixes the three.
   python tools/stats_by_pass.py trace.csv --steps 20 --warmup 5"""
 import argparse
