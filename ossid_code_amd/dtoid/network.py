@@ -241,7 +241,7 @@ class FusedTemplateEncoder:
         for pk in self.final or []:
             pk.refresh()
 
-    def _run(self, plan, x):
+    def _run(self, plan, x, taps=None):
         for kind, item in plan:
             if kind == "pool":
                 k = item.kernel_size if isinstance(item.kernel_size, int) else item.kernel_size[0]
@@ -257,18 +257,26 @@ class FusedTemplateEncoder:
                 e1.run(s, B, H, W, out, out_cs=e1.cout + e3.cout, out_coff=0)
                 e3.run(s, B, H, W, out, out_cs=e1.cout + e3.cout, out_coff=e1.cout)
                 x = out
+            if taps is not None:
+                taps.append(x)
         return x
 
-    def __call__(self, img):
+    def __call__(self, img, taps=None):
+        """taps: a list that receives every stage's output (the stem after its ReLU, each max-pool and Fire module, each
+        final convolution) -- tensors the plan computes anyway, appended as they are; None adds nothing."""
         mod = self.mod
         x = self.stem(ops.im2col_stem(img, 3, 2, 0, 48))
-        x1 = self._run(self.stages[0], x)
-        x2 = self._run(self.stages[1], x1)
+        if taps is not None:
+            taps.append(x)
+        x1 = self._run(self.stages[0], x, taps)
+        x2 = self._run(self.stages[1], x1, taps)
         x1n, x2n = mod.norm_1(x1), mod.norm_2(x2)
         xf = torch.cat([x2n, _bilinear_resize(x1n, x2.size(3))], dim=1)
         if self.final is not None:
             for pk in self.final:                          # valid 3x3: pad-1 convolution, keep the interior
                 xf = pk(xf)[:, :, 1:-1, 1:-1]
+                if taps is not None:
+                    taps.append(xf)
         return xf.contiguous()
 
 
@@ -627,8 +635,10 @@ class FusedBackbone:
     # a dense block of at most this many pixels (batch x height x width) takes the one-launch-per-layer form
     DENSE_FUSED_MAX_PIXELS = 20000
 
-    def __call__(self, image, template_feat, raw_image=False):
-        """raw_image: `image` is in [0, 1] and normalizeImageRange is applied inside the stem's gather (D1)."""
+    def __call__(self, image, template_feat, raw_image=False, taps=None):
+        """raw_image: `image` is in [0, 1] and normalizeImageRange is applied inside the stem's gather (D1).
+        taps: a list that receives every stage's output -- pool0, each dense block's whole buffer, each transition, the
+        final map -- as the views the plan holds anyway (no copy, no launch); None adds nothing."""
         ife = self.ife
         def block_buffer(si, B, C, H, W):
             """The resident buffer of the dense block at stage si (None if that stage is no block): its producer -- the stem's
@@ -646,6 +656,8 @@ class FusedBackbone:
         x = ops.stem_tail_pool(x0, template_feat, *self.norm0_affine, out=pending)
         if pending is not None:
             x = pending[:, :C]
+        if taps is not None:
+            taps.append(x)
         for si, (kind, mod, packed) in enumerate(self.stages):
             B, C, H, W = x.shape
             if kind == "block":
@@ -685,7 +697,12 @@ class FusedBackbone:
                     x = out[:, :packed.cout]
                 else:
                     x = ops.avgpool2_nhwc(packed(x), st)
-        return self.final(x)
+            if taps is not None:
+                taps.append(x)
+        out = self.final(x)
+        if taps is not None:
+            taps.append(out)
+        return out
 
 
 class Network(nn.Module):
