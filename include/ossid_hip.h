@@ -788,6 +788,38 @@ int ossid_ppf_cluster(const int32_t* peaks, const double* cand_poses, const int3
                       float D, float dist_rel, int num_result, double* poses_out, double* scores_out, int32_t* info,
                       void* stream);
 
+/* Dense pose refinement of PPF hypotheses (SPEC 6.9; Halcon's DensePoseRefinement 'true', the default of the LM-O call
+ * :441-447): point-to-plane Gauss-Newton of every hypothesis against a voxel sampling of the scene (ossid_ppf_sample with
+ * rel = RefineSamplingRel and diam = the model's D), correspondences scene -> model. h is the refinement sampling step
+ * h_r = f32(RefineSamplingRel) * D, steps <= 16. Step k accepts pairs within thr_k = f32(max(0.1 * 2^-k * D, 2 h)).
+ *
+ * The model grid, once per model: the Mr <= OSSID_PPF_MAX_REFINE_MODEL_POINTS refinement points f32 [Mr][3] and unit
+ * normals f32 [Mr][3] (ossid_ppf_sample of the model with rel = RefineSamplingRel) -> grid, an opaque buffer of
+ * ossid_ppf_refine_grid_bytes(Mr, steps, D, h) bytes (0 = bad arguments), for refinements of at most `steps` steps.
+ *
+ * ossid_ppf_refine, per frame: scene f32 [cap][3] with count[0] sampled points (cap <= OSSID_PPF_MAX_REFINE_SCENE_POINTS;
+ * count > cap: refinement is skipped), poses_in f64 [num_poses][4][4] of which the first min(num_hyp[0], num_poses) are
+ * refined (num_hyp: info[0] of ossid_ppf_cluster, read on the device) -> sorted by score descending, ties by input rank:
+ * poses_out f64 [num_poses][4][4], scores f64 [num_poses] (pairs / Mr), pairs int32 [num_poses] (scene points within
+ * thr_{steps-1} of the model at the final pose), steps_done int32 [num_poses]; rows past the refined ones are zero.
+ * status int32 [4] = (1 if the scene was over cap else 0, count[0], hypotheses refined, 0). num_poses <= 4096.
+ *
+ * ossid_ppf_refine_match: the correspondence set of step `step` at each of num_poses poses (no update): match int32
+ * [num_poses][cap], entry i = the matched model index of scene point i or -1, for i < count[0]. */
+#define OSSID_PPF_MAX_REFINE_MODEL_POINTS 16384
+#define OSSID_PPF_MAX_REFINE_SCENE_POINTS 65536
+size_t ossid_ppf_refine_grid_bytes(int Mr, int steps, float D, float h);
+int ossid_ppf_refine_model_grid(const float* points, const float* normals, int Mr, int steps, float D, float h, void* grid,
+                                size_t grid_bytes, void* stream);
+size_t ossid_ppf_refine_workspace_bytes(int cap, int num_poses);
+int ossid_ppf_refine(const float* scene, const int32_t* count, int cap, const void* grid, size_t grid_bytes, int Mr,
+                     const double* poses_in, const int32_t* num_hyp, int num_poses, int steps, float D, float h,
+                     void* workspace, size_t workspace_bytes, double* poses_out, double* scores, int32_t* pairs,
+                     int32_t* steps_done, int32_t* status, void* stream);
+int ossid_ppf_refine_match(const float* scene, const int32_t* count, int cap, const void* grid, size_t grid_bytes, int Mr,
+                           const double* poses, int num_poses, int steps, int step, float D, float h, void* workspace,
+                           size_t workspace_bytes, int32_t* match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,11 @@ _PROTOS = {
     "ossid_ppf_vote_workspace_bytes": (_sz, [_i, _i, _i]),
     "ossid_ppf_vote": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ossid_ppf_cluster": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "ossid_ppf_refine_grid_bytes": (_sz, [_i, _i, _f, _f]),
+    "ossid_ppf_refine_model_grid": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp]),
+    "ossid_ppf_refine_workspace_bytes": (_sz, [_i, _i]),
+    "ossid_ppf_refine": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ossid_ppf_refine_match": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _i, _i, _i, _f, _f, _vp, _sz, _vp, _vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -200,6 +205,8 @@ _PROTOS = {
 ICP_MAX_POINTS = 2048   # OSSID_ICP_MAX_POINTS of include/ossid_hip.h
 PPF_MAX_MODEL_POINTS = 4096    # OSSID_PPF_MAX_MODEL_POINTS
 PPF_MAX_SCENE_SAMPLES = 8192   # OSSID_PPF_MAX_SCENE_SAMPLES
+PPF_MAX_REFINE_MODEL_POINTS = 16384   # OSSID_PPF_MAX_REFINE_MODEL_POINTS
+PPF_MAX_REFINE_SCENE_POINTS = 65536   # OSSID_PPF_MAX_REFINE_SCENE_POINTS
 
 ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
 

@@ -13,7 +13,8 @@ install() registers this package's mirrors under the module paths the script imp
     from zephyr.options import getOptions
     from zephyr.utils import K2meta, meta2K, projectPointsUv
     from zephyr.utils.icp import icpRefinement
-    from zephyr.utils.halcon_wrapper import PPFModel      (only with install(ppf=True))
+    from zephyr.utils.halcon_wrapper import PPFModel      (only with install(ppf=True); refining by default with
+                                                          install(ppf=True, ppf_dense_refinement=True))
 
 resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF unless install(ppf=True), the
 renderer, BOP tooling, datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
@@ -37,9 +38,11 @@ def _module(name):
         return mod
 
 
-def install(ppf=False):
-    """ppf=True also maps zephyr.utils.halcon_wrapper.PPFModel to this build's device PPF (SPEC.md section 6, which differs
-    from a Halcon run: no dense pose refinement); by default a user with Halcon keeps Halcon."""
+def install(ppf=False, ppf_dense_refinement=False):
+    """ppf=True also maps zephyr.utils.halcon_wrapper.PPFModel to this build's device PPF (SPEC.md section 6), whose
+    find_surface_model defaults to DensePoseRefinement='false'; with ppf_dense_refinement=True as well it maps
+    ppf.PPFModelDense instead, whose default is Halcon's 'true' (SPEC.md 6.9), so the LM-O call (:446, no keyword) gets
+    refined hypotheses and the YCB-V call (:418, 'false') does not. By default a user with Halcon keeps Halcon."""
     from . import dtoid, hostutil, pipeline, scoring, zephyr
     table = {
         "zephyr.datasets.score_dataset": {"ScoreDataset": zephyr.ScoreDataset},
@@ -54,7 +57,8 @@ def install(ppf=False):
     }
     if ppf:
         from . import ppf as ppf_mod
-        table["zephyr.utils.halcon_wrapper"] = {"PPFModel": ppf_mod.PPFModel}
+        cls = ppf_mod.PPFModelDense if ppf_dense_refinement else ppf_mod.PPFModel
+        table["zephyr.utils.halcon_wrapper"] = {"PPFModel": cls}
     for modname, attrs in table.items():
         mod = _module(modname)
         for k, v in attrs.items():

@@ -5,6 +5,10 @@ matching that scripts/online_learning.py reaches through zephyr.utils.halcon_wra
     poses, scores, seconds = ppf_model.find_surface_model(scene_pc * 1000.0[, DensePoseRefinement='false',
                                                           SceneSamplingDist=0.03, RefPtRate=0.2])  :418 / :446
 
+DensePoseRefinement='true' refines every hypothesis against the scene (csrc/ppf_refine.hip, SPEC.md 6.9); the drop-in's
+default stays 'false', compat.install(ppf=True, ppf_dense_refinement=True) maps PPFModelDense, whose default is Halcon's
+'true'.
+
 find_surface_model is the drop-in (host arrays in, host arrays out, the caller's units); find_hypotheses is the device
 form that OnlineStream uses: depth image + mask in, device tensors out, one launch chain and no host copy.
 """
@@ -17,7 +21,18 @@ import torch
 from . import _lib
 
 NORMAL_RADIUS_REL = 2.0          # SPEC 6.3: scene normal radius in units of the scene sampling step
+REFINE_SAMPLING_REL = 0.02       # SPEC 6.9: refinement sampling step in units of D
+REFINE_STEPS = 5
 ACCEPTED = ("SceneSamplingDist", "RefPtRate", "NumResult", "DensePoseRefinement", "PoseClusterDistRel", "NormalRadiusRel")
+
+
+def dense_flag(v):
+    """DensePoseRefinement: 'true' / 'false' in any letter case or a bool -> bool; anything else raises."""
+    if isinstance(v, (bool, np.bool_)):
+        return bool(v)
+    if isinstance(v, str) and v.lower() in ("true", "false"):
+        return v.lower() == "true"
+    raise ValueError("find_surface_model: DensePoseRefinement=%r is not 'true' or 'false'" % (v,))
 
 
 def _dev():
@@ -156,7 +171,8 @@ class PPFModel:
         self.device = dev
         self.sampling_dist = float(ModelSamplingDist)
         cap = _lib.PPF_MAX_MODEL_POINTS
-        s = _sample(dev, ModelSamplingDist, 0.0, cap, points=_f32(points, dev), normals=_f32(normals, dev))
+        Pd, Nd = _f32(points, dev), _f32(normals, dev)
+        s = _sample(dev, ModelSamplingDist, 0.0, cap, points=Pd, normals=Nd)
         Ms = int(s["count"].item())
         if Ms > cap:
             raise ValueError("PPFModel: ModelSamplingDist=%g keeps %d model points, more than the %d this build takes; "
@@ -177,6 +193,55 @@ class PPFModel:
               self.offsets.data_ptr(), self.entries.data_ptr(), int(self.entries.numel()), ws.data_ptr(), 4 * words,
               _lib.stream())
         self.chunks = (Ms + 1023) // 1024
+        self.refine, self.refine_reason = self._refine_surface(Pd, Nd)
+
+    DENSE_DEFAULT = "false"              # find_surface_model's DensePoseRefinement default (PPFModelDense: 'true')
+
+    def _refine_surface(self, Pd, Nd):
+        """SPEC 6.9's refinement surface and its grid -> (dict, None), or (None, reason) when it cannot be built."""
+        cap = _lib.PPF_MAX_REFINE_MODEL_POINTS
+        s = _sample(self.device, REFINE_SAMPLING_REL, float(self.D), cap, points=Pd, normals=Nd)
+        Mr = int(s["count"].item())
+        if Mr > cap:
+            return None, ("the refinement sampling (%g D) keeps %d model points, more than the %d this build takes"
+                          % (REFINE_SAMPLING_REL, Mr, cap))
+        if Mr < 6:
+            return None, "the refinement sampling keeps %d model point(s)" % Mr
+        h = np.float32(s["stats"][7].item())
+        gb = int(_lib.fn("ossid_ppf_refine_grid_bytes")(Mr, REFINE_STEPS, float(self.D), float(h)))
+        if gb == 0:
+            return None, "no refinement grid for D=%g, h=%g" % (self.D, h)
+        grid = torch.empty(gb, dtype=torch.uint8, device=self.device)
+        pts, nrm = s["pts"][:Mr].contiguous(), s["nrm"][:Mr].contiguous()
+        _call("ossid_ppf_refine_model_grid", pts.data_ptr(), nrm.data_ptr(), Mr, REFINE_STEPS, float(self.D), float(h),
+              grid.data_ptr(), gb, _lib.stream())
+        return {"Mr": Mr, "h": h, "idx": s["idx"][:Mr], "points": pts, "normals": nrm, "grid": grid,
+                "steps": REFINE_STEPS}, None
+
+    def _refine(self, source, r, steps=REFINE_STEPS):
+        """SPEC 6.9 on the hypotheses of one _run (device tensors, no host copy) -> dict of device tensors."""
+        R, dev = self.refine, self.device
+        cap = _lib.PPF_MAX_REFINE_SCENE_POINTS
+        s = _sample(dev, REFINE_SAMPLING_REL, float(self.D), cap, **source)
+        NR = int(r["poses"].shape[0])
+        wsb = int(_lib.fn("ossid_ppf_refine_workspace_bytes")(cap, NR))
+        if wsb == 0:
+            raise ValueError("find_surface_model: NumResult=%d is more than this build refines" % NR)
+        out = {"sample": s, "ws": torch.empty(wsb, dtype=torch.uint8, device=dev),
+               "poses": torch.empty(NR, 4, 4, dtype=torch.float64, device=dev),
+               "scores": torch.empty(NR, dtype=torch.float64, device=dev),
+               "pairs": torch.empty(NR, dtype=torch.int32, device=dev), "steps": torch.empty(NR, dtype=torch.int32, device=dev),
+               "status": torch.empty(4, dtype=torch.int32, device=dev)}
+        _call("ossid_ppf_refine", s["pts"].data_ptr(), s["count"].data_ptr(), cap, R["grid"].data_ptr(), int(R["grid"].numel()),
+              R["Mr"], r["poses"].data_ptr(), r["info"].data_ptr(), NR, int(steps), float(self.D), float(R["h"]),
+              out["ws"].data_ptr(), wsb, out["poses"].data_ptr(), out["scores"].data_ptr(), out["pairs"].data_ptr(),
+              out["steps"].data_ptr(), out["status"].data_ptr(), _lib.stream())
+        return out
+
+    def _need_refine(self):
+        if getattr(self, "refine", None) is None:
+            raise ValueError("find_surface_model: DensePoseRefinement='true' needs the model's refinement surface, which "
+                             "this model does not hold (%s)" % (getattr(self, "refine_reason", None) or "not built"))
 
     # ---- the device form -----------------------------------------------------------------------------------------------
     def _run(self, source, SceneSamplingDist=0.05, RefPtRate=0.2, NumResult=100, PoseClusterDistRel=0.1,
@@ -222,44 +287,63 @@ class PPFModel:
                 "poses": poses, "scores": scores, "info": info, "h": h}
 
     def find_hypotheses(self, depth, mask, cam_K, SceneSamplingDist=0.05, RefPtRate=0.2, NumResult=100,
-                        PoseClusterDistRel=0.1, NormalRadiusRel=NORMAL_RADIUS_REL):
+                        PoseClusterDistRel=0.1, NormalRadiusRel=NORMAL_RADIUS_REL, DensePoseRefinement=False):
         """Device form: depth f32 [H,W] (the model's units, 0 = invalid), mask [H,W] (bool / u8; pixel used iff mask
         && depth > 0), cam_K [3,3] -> device tensors (poses f64 [NumResult,4,4], scores f64 [NumResult], info int32 [4]
         = results, sampled scene points, candidates, clusters). Rows past info[0] are zero. Nothing is copied to the host:
-        a scene over the sample cap shows as info[1] > PPF_MAX_SCENE_SAMPLES (check_info raises on it)."""
+        a scene over the sample cap shows as info[1] > PPF_MAX_SCENE_SAMPLES (check_info raises on it).
+        DensePoseRefinement=True refines the hypotheses against the same pixels (SPEC 6.9): poses and scores are then the
+        refined ones, sorted by refined score, and a fourth tensor, the refinement status int32 [4], follows
+        (check_refine raises when the refinement scene was over its cap)."""
+        dense = dense_flag(DensePoseRefinement)
+        if dense:
+            self._need_refine()
         dev = self.device
         D = _f32(depth, dev)
         M = (mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(mask)))
         if D.dim() != 2 or tuple(M.shape) != tuple(D.shape):
             raise ValueError("find_hypotheses: depth and mask must both be [H,W]")
         M = M.to(dev).to(torch.uint8).contiguous()
-        r = self._run({"depth": D, "mask": M, "cam_K": cam_K}, SceneSamplingDist, RefPtRate, NumResult, PoseClusterDistRel,
-                      NormalRadiusRel)
-        return r["poses"], r["scores"], r["info"]
+        source = {"depth": D, "mask": M, "cam_K": cam_K}
+        r = self._run(source, SceneSamplingDist, RefPtRate, NumResult, PoseClusterDistRel, NormalRadiusRel)
+        if not dense:
+            return r["poses"], r["scores"], r["info"]
+        f = self._refine(source, r)
+        return f["poses"], f["scores"], r["info"], f["status"]
 
     # ---- the drop-in ---------------------------------------------------------------------------------------------------
     def find_surface_model(self, scene_pc, **kwargs):
         """Halcon's find_surface_model as online_learning.py:418 / :446 call it: scene_pc [N,3] in the model's units ->
         (poses np.float64 [n,4,4] in those units, scores np.float64 [n], seconds), n <= NumResult, best first.
-        Keywords: SceneSamplingDist (0.05), RefPtRate (0.2), NumResult (100), DensePoseRefinement ('false' only),
+        Keywords: SceneSamplingDist (0.05), RefPtRate (0.2), NumResult (100), DensePoseRefinement ('false'; 'true' /
+        'false' in any case or a bool; 'true' refines every hypothesis, SPEC 6.9, and `seconds` includes it),
         PoseClusterDistRel (0.1), NormalRadiusRel (2.0); anything else raises."""
         unknown = sorted(set(kwargs) - set(ACCEPTED))
         if unknown:
             raise ValueError("find_surface_model: unknown keyword(s) %s; accepted: %s" % (", ".join(unknown), ", ".join(ACCEPTED)))
-        dense = kwargs.pop("DensePoseRefinement", "false")
-        if str(dense).lower() != "false":
-            raise ValueError("find_surface_model: DensePoseRefinement=%r is not supported (this build has no dense pose "
-                             "refinement, SPEC.md 6.7); pass DensePoseRefinement='false'" % (dense,))
+        dense = dense_flag(kwargs.pop("DensePoseRefinement", self.DENSE_DEFAULT))
+        if dense:
+            self._need_refine()
         P = np.asarray(scene_pc, dtype=np.float64)
         if P.ndim != 2 or P.shape[1] != 3 or len(P) == 0:
             raise ValueError("find_surface_model: scene_pc must be [N,3] with N > 0")
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        r = self._run({"points": _f32(P, self.device)}, **kwargs)
+        source = {"points": _f32(P, self.device)}
+        r = self._run(source, **kwargs)
+        f = self._refine(source, r) if dense else r
         info = check_info(r["info"], kwargs.get("SceneSamplingDist", 0.05))
+        if dense:
+            check_refine(f["status"])
         n = info[0]
-        poses, scores = r["poses"][:n].cpu().numpy(), r["scores"][:n].cpu().numpy()
+        poses, scores = f["poses"][:n].cpu().numpy(), f["scores"][:n].cpu().numpy()
         return poses, scores, time.perf_counter() - t0
+
+
+class PPFModelDense(PPFModel):
+    """PPFModel whose find_surface_model defaults to Halcon's DensePoseRefinement='true' (compat.install(ppf=True,
+    ppf_dense_refinement=True)): the LM-O call :446, which passes no keyword, gets refined hypotheses."""
+    DENSE_DEFAULT = "true"
 
 
 def check_info(info, scene_sampling_dist):
@@ -269,4 +353,14 @@ def check_info(info, scene_sampling_dist):
         raise ValueError("find_surface_model: SceneSamplingDist=%g keeps %d scene points, more than the %d this build "
                          "takes; raise SceneSamplingDist or shrink the mask" % (scene_sampling_dist, v[1],
                                                                                  _lib.PPF_MAX_SCENE_SAMPLES))
+    return v
+
+
+def check_refine(status):
+    """status of a refinement (device int32 [4]) -> host list; raises when the refinement scene was over its cap."""
+    v = [int(x) for x in status.cpu().numpy()]
+    if v[0] != 0:
+        raise ValueError("find_surface_model: DensePoseRefinement: the refinement sampling (%g D) keeps %d scene points, "
+                         "more than the %d this build takes; shrink the mask or pass DensePoseRefinement='false'"
+                         % (REFINE_SAMPLING_REL, v[1], _lib.PPF_MAX_REFINE_SCENE_POINTS))
     return v

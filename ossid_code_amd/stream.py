@@ -79,7 +79,8 @@ class OnlineStream:
     iterations, the unrefined pose and its error).
     ppf_models (None = off): dict obj_id -> ppf.PPFModel built in metres; hypotheses then come from the frame's depth
     inside the DTOID boxes (ppf.PPFModel.find_hypotheses, mask as online_learning.py:384-405 builds it), timed under
-    times["ppf"], `frame["pose_hypos"]` is not read, and the result carries "n_hypos" and the hypotheses ("ppf_hypos"). ppf_kwargs go to find_hypotheses."""
+    times["ppf"], `frame["pose_hypos"]` is not read, and the result carries "n_hypos" and the hypotheses ("ppf_hypos"). ppf_kwargs go to find_hypotheses
+    ({"DensePoseRefinement": True} refines the hypotheses, SPEC.md 6.9)."""
 
     def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None,
                  icp_max_dist=None, ppf_models=None, ppf_kwargs=None):
@@ -159,8 +160,11 @@ class OnlineStream:
             x1, y1, x2, y2 = pipeline.expand_box(x1, y1, x2, y2, H, W, 1.2)
             mask[int(y1):int(y2), int(x1):int(x2)] = 1
         model = self.ppf_models[int(frame["obj_id"])]
-        poses, _scores, info = model.find_hypotheses(depth, mask, frame["cam_K"], **self.ppf_kwargs)
+        out = model.find_hypotheses(depth, mask, frame["cam_K"], **self.ppf_kwargs)
+        poses, info = out[0], out[2]
         n = ppf.check_info(info, self.ppf_kwargs.get("SceneSamplingDist", 0.05))[0]
+        if len(out) > 3:     # DensePoseRefinement: the refined hypotheses, best refined score first
+            ppf.check_refine(out[3])
         if n == 0:           # nothing found: one identity hypothesis, as online_learning.py:429-430 does for SIFT
             return np.eye(4)[None]
         return poses[:n].cpu().numpy()
