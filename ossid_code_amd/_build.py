@@ -18,6 +18,11 @@ LIB_PATH = os.environ.get("OSSID_HIP_LIB") or os.path.join(_HERE, "libossid_hip.
 OBJ_DIR = os.path.join(_HERE, "build")
 SOURCES = ["zephyr.hip", "pn2.hip", "dtoid.hip", "conv.hip", "segtail.hip", "pipeline.hip", "icp.hip", "ppf.hip", "ppf_refine.hip", "train.hip", "wino.hip", "stem.hip", "wgrad_fc.hip", "dense.hip", "wgrad_t9.hip", "dense_bwd.hip", "seq.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
+# Per-source additions. pn2.hip: sa1_kernel runs one wave per SIMD on all 512 registers; for such a kernel the compiler by
+# default selects the MFMA form whose accumulators live in the AGPR half, which vector instructions cannot read, and every
+# ReLU / max then pays a v_accvgpr_read. With the VGPR form the accumulators are vector registers and the AGPR half holds the
+# (pinned) weights, which only MFMAs read. tests/test_pn2_resources.py compiles with the same flags.
+SOURCE_FLAGS = {"pn2.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _hipcc():
@@ -63,7 +68,7 @@ def build_lib(force=False, verbose=False):
         obj = os.path.join(obj_dir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_t):
-            jobs.append([hipcc] + FLAGS + extra + ["-c", src, "-o", obj])
+            jobs.append([hipcc] + FLAGS + SOURCE_FLAGS.get(os.path.basename(src), []) + extra + ["-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:

@@ -39,15 +39,28 @@ __device__ __forceinline__ v16f bias_tile(const float* __restrict__ b, int mt, i
     return acc;
 }
 
+// max of two floats as ONE instruction. fmaxf() on an MFMA result costs two: the compiler cannot prove the value is not a
+// signalling NaN and puts a canonicalising v_max_f32 x, x in front of the real one. v_med3_f32 with +inf as third operand
+// returns the hardware's own MAX(a, b) (and MIN3 = the non-NaN operand when one is a NaN, as v_max_f32 does), so the value
+// is the same in every case, signed zeros and NaNs included. It matters because a vector instruction does not hide beside
+// an f32 MFMA: each one takes about four cycles out of the matrix stream (profiles/r08_sa1_after.txt).
+// (The +inf goes through an empty asm into a scalar register: given the literal, the compiler folds the median back into
+// fmaxf and its canonicalisation. The statement is not volatile, so one copy per kernel survives.)
+__device__ __forceinline__ float max1(float a, float b) {
+    float inf = __builtin_inff();
+    asm("" : "+s"(inf));
+    return __builtin_amdgcn_fmed3f(a, b, inf);
+}
+
 __device__ __forceinline__ v16f relu16(v16f a) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = fmaxf(a[i], 0.0f);
+    for (int i = 0; i < 16; ++i) a[i] = max1(a[i], 0.0f);
     return a;
 }
 
 __device__ __forceinline__ v16f max16(v16f a, v16f b) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = fmaxf(a[i], b[i]);
+    for (int i = 0; i < 16; ++i) a[i] = max1(a[i], b[i]);
     return a;
 }
 
@@ -180,16 +193,16 @@ __device__ __forceinline__ v16f splat16(float v) {
 // max over the 32 samples of a swapped tile (16 registers x 2 lane halves), ReLU folded in (it commutes with max);
 // every lane returns the pooled value of channel lane&31
 __device__ __forceinline__ float pool_swapped(const v16f& a) {
-    float m0 = fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3]));
-    float m1 = fmaxf(fmaxf(a[4], a[5]), fmaxf(a[6], a[7]));
-    float m2 = fmaxf(fmaxf(a[8], a[9]), fmaxf(a[10], a[11]));
-    float m3 = fmaxf(fmaxf(a[12], a[13]), fmaxf(a[14], a[15]));
-    float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+    float m0 = max1(max1(a[0], a[1]), max1(a[2], a[3]));
+    float m1 = max1(max1(a[4], a[5]), max1(a[6], a[7]));
+    float m2 = max1(max1(a[8], a[9]), max1(a[10], a[11]));
+    float m3 = max1(max1(a[12], a[13]), max1(a[14], a[15]));
+    float m = max1(max1(m0, m1), max1(m2, m3));
     // the other lane half's value: v_permlane32_swap (gfx950) is a plain VALU op; __shfl_xor(m, 32) goes through the LDS
     // crossbar (ds_bpermute: address VGPR, lgkmcnt wait) in the middle of an MFMA stream
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-    m = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    return fmaxf(m, 0.0f);
+    m = max1(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    return max1(m, 0.0f);
 }
 
 template <int KT, int NT, int G, class Epi>
@@ -529,40 +542,60 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
 }
 
 // ---- SA1: gather (K=8) -> 64 -> 64 -> 128 -> max over the group's 64 samples -------------------------
-// One wave per centre; both 32-sample column tiles ride together so every weight quad feeds 8 MFMAs.
-constexpr int SA1_CPW = 8;  // centres per wave
-// LDS image of the three layers (floats): W1p 512 | W2p 4096 | W3p 8192 | b1 64 | b2 64 | b3 128  = 52 224 B.
-// The probe in tools/probes/mfma_probe.hip shows why: a chained f32 MFMA stream fed with A operands from L2 tops out
-// at 62 % of the matrix peak at two waves per SIMD (the vector-memory path, not the matrix core, sets the pace),
-// the same stream fed from LDS reaches 90-94 %.
-constexpr int SA1_W1 = 0, SA1_W2 = 512, SA1_W3 = 512 + 4096, SA1_B1 = SA1_W3 + 8192, SA1_B2 = SA1_B1 + 64,
-              SA1_B3 = SA1_B2 + 64, SA1_LDS_FLOATS = SA1_B3 + 128;
+// One wave per centre; both 32-sample column tiles ride together. The kernel is persistent and runs ONE wave per SIMD
+// (512 registers per lane): each wave loads the three packed layers once, straight from the blob, into 50 float4 = 200
+// registers (the packed image is lane-linear: quad q of a layer is the float4 at W4[q * 64 + lane]) and the folded biases of
+// layers 1-2 as four ready-made accumulator tiles (64 registers, the C operand of each chain's first MFMA), then walks a
+// contiguous slice of the centres. All three layers are fully unrolled over their quads (16 + 128 + 256 = 400 MFMAs per
+// centre): no LDS, no barrier, no operand read between MFMAs.
+//
+// What sets this kernel's rate (profiles/r08_sa1_before.txt, r08_sa1_after.txt): it runs at the clock of a bare
+// register-fed MFMA stream, and the time it loses is proportional to the number of vector / LDS instructions per centre --
+// about four to five cycles of matrix time each, wherever they sit in the stream (re-ordering them between the MFMAs of an
+// independent accumulator measured nothing). So the design is about instruction COUNT: no ds_read per weight quad, no bias
+// read, one instruction per ReLU / max (max1), accumulators in vector registers so that ReLU and pool read them in place.
+//
+// Register budget (per lane): weights 200 + bias tiles 64 + last-layer bias 4 + x 8 + Y1 64 + Y2 64 + accumulators 32 + next
+// centre's gather 13 = 449 at the widest point (layer 2). tests/test_pn2_resources.py holds the build to zero scratch.
+//
+// The weights are only ever MFMA operands, which may come from the accumulator (AGPR) half of the register file; ReLU and
+// pool are vector instructions, which may not read it. The file is compiled with the VGPR form of the MFMA (_build.py:
+// accumulators in vector registers), and the weights are pinned to the AGPR half as they arrive: without the pin the
+// allocator keeps them on the vector side's books and copies each one back (v_accvgpr_read) before the MFMA that uses it.
+__device__ __forceinline__ void pin_acc(float4& w) { asm volatile("" : "+a"(w.x), "+a"(w.y), "+a"(w.z), "+a"(w.w)); }
 
-__device__ __forceinline__ void stage_lds(float* dst, const float* __restrict__ src, int nfloats) {
-    for (int i = threadIdx.x * 4; i < nfloats; i += blockDim.x * 4) *(float4*)(dst + i) = *(const float4*)(src + i);
+template <int N>
+__device__ __forceinline__ void load_quads(float4 (&w)[N], const float* __restrict__ Wp, int lane) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) w[q] = ((const float4*)Wp)[q * 64 + lane], pin_acc(w[q]);
 }
 
-__global__ __launch_bounds__(256, 2) void sa1_kernel(const float* __restrict__ point_x, int M,
+__global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ point_x, int M,
                                                      const int* __restrict__ ball, const float* __restrict__ cxyz,
                                                      int np, int total, const float* __restrict__ W1p,
                                                      const float* __restrict__ b1, const float* __restrict__ W2p,
                                                      const float* __restrict__ b2, const float* __restrict__ W3p,
                                                      const float* __restrict__ b3, float* __restrict__ feat) {
-    extern __shared__ __attribute__((aligned(16))) float wl[];
-    stage_lds(wl + SA1_W1, W1p, 512);
-    stage_lds(wl + SA1_W2, W2p, 4096);
-    stage_lds(wl + SA1_W3, W3p, 8192);
-    stage_lds(wl + SA1_B1, b1, 64);
-    stage_lds(wl + SA1_B2, b2, 64);
-    stage_lds(wl + SA1_B3, b3, 128);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, c = lane & 31;
-    const int row = scatter_row(lane);
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    // this wave's contiguous slice of the centres (consecutive centres mostly share a hypothesis, i.e. a gather base); the
+    // wave index is made visibly uniform so that the centre walk lives in scalar registers
+    const int gw = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = gridDim.x * 4;
+    const int per = total / nw, rem = total % nw;
+    const int first = gw * per + min(gw, rem), end = first + per + (gw < rem ? 1 : 0);
+    if (first >= end) return;          // fewer centres than waves: nothing to do, no weights loaded
+    float4 w1[2], w2[16], w3[32];
+    load_quads(w1, W1p, lane);
+    load_quads(w2, W2p, lane);
+    load_quads(w3, W3p, lane);
+    v16f B1[2], B2[2];
+    float b3v[4];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) B1[mt] = bias_tile(b1, mt, h), B2[mt] = bias_tile(b2, mt, h);
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) b3v[mt] = b3[mt * 32 + c];
     // The gather of a centre's 64 samples is two dependent global loads (ball index -> feature row): it is issued one
     // centre AHEAD -- the indices under the current centre's first layers, the rows under its last layer -- so that a
-    // wave never sits on ~2 memory latencies between centres.
-    const int centre0 = (blockIdx.x * 4 + wave) * SA1_CPW;
-    if (centre0 >= total) return;
+    // wave never sits on ~2 memory latencies between centres (there is no partner wave to cover them).
     int i_n[2];
     float4 r_n[2];
     float cn[3];
@@ -573,17 +606,18 @@ __global__ __launch_bounds__(256, 2) void sa1_kernel(const float* __restrict__ p
     };
     auto fetch_rows = [&](int ce) {
         const size_t base = (size_t)(ce / np) * M;
-        r_n[0] = *(const float4*)(point_x + (base + i_n[0]) * 8 + 4 * h);
-        r_n[1] = *(const float4*)(point_x + (base + i_n[1]) * 8 + 4 * h);
+        // the indices are consumed HERE: left alone, the compiler widens them right behind their loads in fetch_index
+        // and waits for them there, a memory latency with nothing in flight
+        int i0 = i_n[0], i1 = i_n[1];
+        asm volatile("" : "+v"(i0), "+v"(i1));
+        r_n[0] = *(const float4*)(point_x + (base + i0) * 8 + 4 * h);
+        r_n[1] = *(const float4*)(point_x + (base + i1) * 8 + 4 * h);
     };
-    fetch_index(centre0);
-    fetch_rows(centre0);
+    fetch_index(first);
+    fetch_rows(first);
 #pragma unroll 1
-    for (int cw = 0; cw < SA1_CPW; ++cw) {
-        const int centre = centre0 + cw;
-        if (centre >= total) break;
-        const int next = min(centre + 1, total - 1);          // (the last centre prefetches itself: harmless)
-        const float* w = wl + opaque_zero();   // per-iteration laundering (see opaque_zero)
+    for (int centre = first; centre < end; ++centre) {
+        const int next = min(centre + 1, end - 1);            // (the last centre prefetches itself: harmless)
         float4 x[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -601,31 +635,50 @@ __global__ __launch_bounds__(256, 2) void sa1_kernel(const float* __restrict__ p
         v16f Y1[2][2], Y2[2][2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            float4 a = ((const float4*)(w + SA1_W1))[mt * 64 + lane];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                v16f acc = bias_tile(w + SA1_B1, mt, h);
-                acc = mfma(a.x, x[t].x, acc);
-                acc = mfma(a.y, x[t].y, acc);
-                acc = mfma(a.z, x[t].z, acc);
-                acc = mfma(a.w, x[t].w, acc);
+                v16f acc = mfma(w1[mt].x, x[t].x, B1[mt]);
+                acc = mfma(w1[mt].y, x[t].y, acc);
+                acc = mfma(w1[mt].z, x[t].z, acc);
+                acc = mfma(w1[mt].w, x[t].w, acc);
                 Y1[t][mt] = relu16(acc);
             }
         }
-        stream_layer<2, 2, 2, 4>((const float4*)(w + SA1_W2) + lane, w + SA1_B2, Y1, h, [&](int mt, v16f(&acc)[2]) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            v16f acc[2] = {B2[mt], B2[mt]};
+#pragma unroll
+            for (int kq = 0; kq < 8; ++kq) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[t] = mfma4(w2[mt * 8 + kq], Y1[t][kq / 4], 4 * (kq % 4), acc[t]);
+            }
             Y2[0][mt] = relu16(acc[0]);
             Y2[1][mt] = relu16(acc[1]);
-        });
-        float* out = feat + (size_t)centre * 128 + c;
+        }
+        float* out = feat + (size_t)centre * 128 + lane;   // lane = 32 h + c: half h stores the m-tile after half 0's
         __builtin_amdgcn_sched_barrier(0);
         fetch_rows(next);
         __builtin_amdgcn_sched_barrier(0);
-        stream_last_layer<2, 2, 4>((const float4*)(w + SA1_W3) + lane, w + SA1_B3, Y2, c, 4,
-                                   [&](int mt, v16f(&acc)[2]) {
-                                       const float r = pool_swapped(max16(acc[0], acc[1]));
-                                       if (h == 0) out[mt * 32] = r;
-                                   });
+        // last layer, operands swapped (see mfma4_swapped). After the pool both lane halves hold the tile's 32 maxima, so one
+        // full-wave store writes TWO m-tiles (half h stores tile 2j + h)
+        float pooled[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            v16f acc[2];
+            acc[0] = acc[1] = splat16(b3v[mt]);
+#pragma unroll
+            for (int kq = 0; kq < 8; ++kq) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[t] = mfma4_swapped(Y2[t][kq / 4], 4 * (kq % 4), w3[mt * 8 + kq], acc[t]);
+            }
+            pooled[mt] = pool_swapped(max16(acc[0], acc[1]));
+            if (mt & 1) out[(mt - 1) * 32] = h ? pooled[mt] : pooled[mt - 1];
+        }
     }
+}
+
+__device__ __forceinline__ void stage_lds(float* dst, const float* __restrict__ src, int nfloats) {
+    for (int i = threadIdx.x * 4; i < nfloats; i += blockDim.x * 4) *(float4*)(dst + i) = *(const float4*)(src + i);
 }
 
 // ---- P2: per-point part of SA2's first layer: p[pt][o] = chain(bias, W[:, :128] . feat1[pt]) ----------
@@ -1081,12 +1134,23 @@ int pn2_ball1(const Pn2Call& c) { return launch_ball(c.point_x, 8, c.B, c.M, c.w
 int pn2_fps2(const Pn2Call& c) { return launch_fps(c.ws.xyz1, 3, c.B, c.np1, c.np2, c.ws.fps2, c.ws.xyz2, c.s); }
 int pn2_ball2(const Pn2Call& c) { return launch_ball(c.ws.xyz1, 3, c.B, c.np1, c.ws.xyz2, c.np2, c.w->radius2, c.ws.ball2, c.s); }
 
+// persistent grid of sa1_kernel: one 4-wave workgroup per CU (one wave per SIMD), cached per device
+int sa1_grid() {
+    static int cache[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cache[dev]) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, dev) != hipSuccess || p.multiProcessorCount <= 0) return 256;
+        cache[dev] = p.multiProcessorCount;
+    }
+    return cache[dev];
+}
+
 int pn2_sa1(const Pn2Call& c) {
     const float* blob = c.w->blob;
     const int total = c.B * c.np1;
-    const int grid = (total + 4 * SA1_CPW - 1) / (4 * SA1_CPW);
-    OSSID_ENSURE_LDS(sa1_kernel, (size_t)SA1_LDS_FLOATS * 4);
-    hipLaunchKernelGGL(sa1_kernel, dim3(grid), dim3(256), SA1_LDS_FLOATS * 4, c.s, c.point_x, c.M, c.ws.ball1, c.ws.xyz1, c.np1, total,
+    hipLaunchKernelGGL(sa1_kernel, dim3(sa1_grid()), dim3(256), 0, c.s, c.point_x, c.M, c.ws.ball1, c.ws.xyz1, c.np1, total,
                        blob + c.w->w_off[0], blob + c.w->b_off[0], blob + c.w->w_off[1], blob + c.w->b_off[1],
                        blob + c.w->w_off[2], blob + c.w->b_off[2], c.ws.feat1);
     return ossid_launch_status();

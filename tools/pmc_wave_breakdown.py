@@ -10,7 +10,7 @@ import sys
 f = (glob.glob(sys.argv[1] + "/*/*counter_collection.csv") + glob.glob(sys.argv[1] + "/*counter_collection.csv"))[0]
 acc = collections.defaultdict(lambda: collections.defaultdict(float))
 for r in csv.DictReader(open(f)):
-    name = r["Kernel_Name"]
+    name = r["Kernel_Name"].replace("(anonymous namespace)::", "")
     short = name.split("(")[0].split("::")[-1][:40] + (" " + name[name.find("<"):name.find(">") + 1][:34] if "<" in name else "")
     acc[short][r["Counter_Name"]] += float(r["Counter_Value"])
 print("%-76s %10s %8s %8s %8s %8s %10s" % ("kernel", "wave Mcyc", "parked", "stalled", "issuing", "lds-iss", "mfma/busy"))

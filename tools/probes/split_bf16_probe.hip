@@ -22,6 +22,16 @@ __global__ __launch_bounds__(256, 2) void rate(float* out, unsigned long long* s
     const float a = 1e-3f * lane, b = 1.0f + 1e-3f * lane;
     v8bf ah, bh;
     for (int i = 0; i < 8; ++i) ah[i] = (__bf16)(a + i), bh[i] = (__bf16)(b - i);
+    // MODE 2: the f32 arm on RANDOM operands (constant operands rank by cycles and can flatter the clock): eight zero-mean
+    // values per lane and operand, register-resident, cycled through the chain; the sums are random walks and stay finite
+    float ra[8], rb[8];
+    unsigned seed = 2654435761u * (blockIdx.x * 256 + threadIdx.x + 1);
+    for (int i = 0; i < 8; ++i) {
+        seed = seed * 1664525u + 1013904223u;
+        ra[i] = ((seed >> 8) & 0xffff) / 32768.0f - 1.0f;
+        seed = seed * 1664525u + 1013904223u;
+        rb[i] = ((seed >> 8) & 0xffff) / 32768.0f - 1.0f;
+    }
     const unsigned long long r0 = rt(), c0 = ct();
     for (int it = 0; it < iters; ++it) {
 #pragma unroll
@@ -29,6 +39,9 @@ __global__ __launch_bounds__(256, 2) void rate(float* out, unsigned long long* s
             if (MODE == 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) acc[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[e], 0, 0, 0);
+            } else if (MODE == 2) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[k], rb[(k + e) & 7], acc[e], 0, 0, 0);
             } else {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[e], 0, 0, 0);
@@ -68,9 +81,10 @@ int main() {
     float* out; unsigned long long* st;
     hipMalloc(&out, blocks * 256 * 4); hipMalloc(&st, blocks * 16);
     std::vector<unsigned long long> h(2 * blocks);
-    for (int mode = 0; mode < 2; ++mode) {
+    for (int mode = 0; mode < 3; ++mode) {
         for (int rep = 0; rep < 2; ++rep) {
             if (mode == 0) hipLaunchKernelGGL(rate<0>, dim3(blocks), dim3(256), 0, 0, out, st, iters);
+            else if (mode == 2) hipLaunchKernelGGL(rate<2>, dim3(blocks), dim3(256), 0, 0, out, st, iters);
             else hipLaunchKernelGGL(rate<1>, dim3(blocks), dim3(256), 0, 0, out, st, iters);
             hipDeviceSynchronize();
         }
@@ -83,7 +97,8 @@ int main() {
         const double flop = (double)iters * 4 * 32768.0 * 4 * blocks;
         const double t = us * 1e-6 * (blocks / 512.0);          // one round of 512 resident workgroups
         printf("%s: %.1f us per workgroup, clock %.3f GHz, %.1f f32-equivalent TFLOP/s\n",
-               mode == 0 ? "f32 MFMA 32x32x2 (8 per 16 channels)  " : "bf16 MFMA 32x32x16 (3 per 16 channels)", us, ghz, flop / t / 1e12);
+               mode == 0 ? "f32 MFMA 32x32x2 (8 per 16 channels)  " : mode == 2 ? "f32 MFMA 32x32x2, random operands     " :
+                                                                        "bf16 MFMA 32x32x16 (3 per 16 channels)", us, ghz, flop / t / 1e12);
     }
     std::vector<float> A(512), B(512), Df(1024), Ds(1024);
     unsigned seed = 12345;
