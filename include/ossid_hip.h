@@ -820,6 +820,26 @@ int ossid_ppf_refine_match(const float* scene, const int32_t* count, int cap, co
                            const double* poses, int num_poses, int steps, int step, float D, float h, void* workspace,
                            size_t workspace_bytes, int32_t* match, void* stream);
 
+/* 8f-3b  the mesh renderer of the per-frame loop (scripts/online_learning.py:485-493: zephyr.utils.renderer.Renderer --
+ * addObject(obj_id, ply_path, pose, mm2m=True), obj_nodes[obj_id].matrix = pred_pose, render(depth_only=True); pyrender's
+ * rasterisation of the triangle mesh), depth only, SPEC.md section 7 (csrc/raster.hip). vertices f32 [V][3] in the units
+ * of the poses' translations, faces int32 [F][3] (indices in [0, V): the caller checks them; a triangle with an index
+ * outside is dropped and counted as unusable), transforms f32 [N][4][4] row-major, pixel_offset in [0, 1] (the sample of
+ * pixel (x, y) is (x + pixel_offset, y + pixel_offset): 0.5 = OpenGL / pyrender, 0 = depth2xyz of this library),
+ * z_near >= 0 -> depth_out f32 [N][H][W]: camera-space Z of the nearest surface, 0 where nothing is drawn. depth_out
+ * doubles as the z-buffer; the workspace (16-byte aligned, ossid_raster_workspace_bytes(V, F, N) bytes, 0 = bad
+ * arguments) holds the projected vertices. stats int32 [N][4] (may be NULL) = per pose: triangles dropped for an
+ * unusable vertex, degenerate triangles, triangles that covered at least one sample, triangles walked by a whole wave
+ * (diagnostic). F = 0 is legal (an all-zero image). Three launches, nothing read back, capturable. */
+#define OSSID_RASTER_MAX_VERTICES 4194304
+#define OSSID_RASTER_MAX_FACES 4194304
+#define OSSID_RASTER_MAX_POSES 256
+#define OSSID_RASTER_MAX_PIXELS 16777216
+size_t ossid_raster_workspace_bytes(int V, int F, int N);
+int ossid_raster_depth(const float* vertices, int V, const int32_t* faces, int F, const float* transforms, int N, float fx,
+                       float fy, float cx, float cy, int H, int W, float pixel_offset, float z_near, void* workspace,
+                       size_t workspace_bytes, float* depth_out, int32_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,8 @@ _PROTOS = {
     "ossid_ppf_refine_workspace_bytes": (_sz, [_i, _i]),
     "ossid_ppf_refine": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ossid_ppf_refine_match": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _i, _i, _i, _f, _f, _vp, _sz, _vp, _vp]),
+    "ossid_raster_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ossid_raster_depth": (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -207,6 +209,10 @@ PPF_MAX_MODEL_POINTS = 4096    # OSSID_PPF_MAX_MODEL_POINTS
 PPF_MAX_SCENE_SAMPLES = 8192   # OSSID_PPF_MAX_SCENE_SAMPLES
 PPF_MAX_REFINE_MODEL_POINTS = 16384   # OSSID_PPF_MAX_REFINE_MODEL_POINTS
 PPF_MAX_REFINE_SCENE_POINTS = 65536   # OSSID_PPF_MAX_REFINE_SCENE_POINTS
+RASTER_MAX_VERTICES = 1 << 22  # OSSID_RASTER_MAX_VERTICES
+RASTER_MAX_FACES = 1 << 22     # OSSID_RASTER_MAX_FACES
+RASTER_MAX_POSES = 256         # OSSID_RASTER_MAX_POSES
+RASTER_MAX_PIXELS = 1 << 24    # OSSID_RASTER_MAX_PIXELS
 
 ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
 

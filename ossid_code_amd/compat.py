@@ -15,9 +15,11 @@ install() registers this package's mirrors under the module paths the script imp
     from zephyr.utils.icp import icpRefinement
     from zephyr.utils.halcon_wrapper import PPFModel      (only with install(ppf=True); refining by default with
                                                           install(ppf=True, ppf_dense_refinement=True))
+    from zephyr.utils.renderer import Renderer, blend      (only with install(renderer=True): render.Renderer, the
+                                                          device rasteriser of SPEC.md section 7, depth only)
 
 resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF unless install(ppf=True), the
-renderer, BOP tooling, datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
+renderer unless install(renderer=True), BOP tooling, datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
 `ossid` package is importable, just these attributes are overridden on it, nothing else is shadowed.
 """
 import importlib
@@ -25,24 +27,31 @@ import sys
 import types
 
 
-def _module(name):
+def _module(name, made=None):
+    """The importable module `name`, or an empty stand-in registered under it (then noted in `made`)."""
     try:
         return importlib.import_module(name)
     except Exception:
+        if made is not None:
+            made.add(name)
         mod = types.ModuleType(name)
         mod.__path__ = []
         sys.modules[name] = mod
         parent, _, child = name.rpartition(".")
         if parent:
-            setattr(_module(parent), child, mod)
+            setattr(_module(parent, made), child, mod)
         return mod
 
 
-def install(ppf=False, ppf_dense_refinement=False):
+def install(ppf=False, ppf_dense_refinement=False, renderer=False):
     """ppf=True also maps zephyr.utils.halcon_wrapper.PPFModel to this build's device PPF (SPEC.md section 6), whose
     find_surface_model defaults to DensePoseRefinement='false'; with ppf_dense_refinement=True as well it maps
     ppf.PPFModelDense instead, whose default is Halcon's 'true' (SPEC.md 6.9), so the LM-O call (:446, no keyword) gets
-    refined hypotheses and the YCB-V call (:418, 'false') does not. By default a user with Halcon keeps Halcon."""
+    refined hypotheses and the YCB-V call (:418, 'false') does not. By default a user with Halcon keeps Halcon.
+    renderer=True maps zephyr.utils.renderer.Renderer to render.Renderer (:485-493). The script's import line also names
+    `blend`, which it never calls: when -- and only when -- no real zephyr.utils.renderer imports and the module had to
+    be synthesised, render.blend (a plain alpha blend, a placeholder of unknown fidelity) is set so that the line
+    imports. By default a user with pyrender keeps pyrender."""
     from . import dtoid, hostutil, pipeline, scoring, zephyr
     table = {
         "zephyr.datasets.score_dataset": {"ScoreDataset": zephyr.ScoreDataset},
@@ -59,8 +68,14 @@ def install(ppf=False, ppf_dense_refinement=False):
         from . import ppf as ppf_mod
         cls = ppf_mod.PPFModelDense if ppf_dense_refinement else ppf_mod.PPFModel
         table["zephyr.utils.halcon_wrapper"] = {"PPFModel": cls}
+    if renderer:
+        from . import render
+        table["zephyr.utils.renderer"] = {"Renderer": render.Renderer}
     for modname, attrs in table.items():
-        mod = _module(modname)
+        made = set()
+        mod = _module(modname, made)
         for k, v in attrs.items():
             setattr(mod, k, v)
+        if modname == "zephyr.utils.renderer" and modname in made:
+            mod.blend = render.blend
     return sorted(table)

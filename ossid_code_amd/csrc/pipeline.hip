@@ -4,7 +4,8 @@
 //       utils/data.py:7-83, utils/__init__.py:241-255 (depth2xyz), :354-367 (heatmapGaussain)
 //   (3) post-score step: visibility mask (bop_toolkit estimate_visib_mask_gt, bop19 mode), mask IoUs, pseudo-label box
 //       scripts/online_learning.py:485-500, :557-558; and a depth-only point-splat renderer standing in for pyrender
-//       (:485 renderer.render(depth_only=True)) so that the predicted depth never leaves the GPU.
+//       (:485 renderer.render(depth_only=True)) so that the predicted depth never leaves the GPU. The mesh itself is
+//       rasterised by csrc/raster.hip (SPEC.md section 7); the splat remains for callers that hold only model points.
 #include "common.h"
 
 namespace {

@@ -1,0 +1,242 @@
+// Depth-only rasteriser of a triangle mesh at a batch of poses (SPEC.md section 7), the renderer of the per-frame loop:
+// scripts/online_learning.py:485-493 (zephyr.utils.renderer.Renderer: addObject, obj_nodes[id].matrix = pose,
+// render(depth_only=True) -- pyrender's OpenGL rasterisation of the mesh).
+//
+// Three launches on the caller's stream, nothing read back:
+//   prepare   one thread per (vertex, pose): transform, project, snap to 1/256 pixel -> a 16-byte record {sx, sy, 1/Z f64}
+//             in the workspace (a vertex is shared by ~6 triangles: done once, not per incident triangle); the same
+//             grid-stride kernel clears depth_out, viewed as uint32, to +inf and zeroes the statistics;
+//   triangles one lane per (triangle, pose): three 16-byte gathers, int64 area, orientation, bounding box clipped to the
+//             frame, exit when the box holds no sample (most triangles of a BOP mesh are sub-pixel). A box of at most
+//             COOP_MIN samples is walked by its lane; a larger one is walked by the whole wave, 8x8 samples per step, one
+//             such triangle after the other (ballot, broadcast by shuffles). Calls with few triangles get fewer
+//             triangles per wave (tpw) so that their large triangles spread over the CUs, and several waves per
+//             workgroup that share each large box by rows of tiles. Depth goes into the z-buffer by
+//             atomicMin on the float's bits (positive floats order like their bit patterns) behind a plain load: values
+//             only fall, so a sample that is already hidden costs no atomic, and a stale load only costs a useless one;
+//   resolve   +inf -> 0.
+// A minimum does not depend on the order of arrival: the image is bit-reproducible whatever the schedule.
+#include <limits.h>
+
+#include <cmath>
+
+#include "common.h"
+
+namespace {
+
+constexpr int COOP_MIN = 64;          // clipped boxes with more samples than one wave covers in a step go to the wave
+constexpr int TARGET_WAVES = 2048;    // 256 CUs x 8: below this many full waves the triangles are spread thinner
+constexpr int MAX_WAVES = 16;         // waves per workgroup that share the large boxes of a call with few triangles
+constexpr int RESIDENT_WAVES = 8192;  // 256 CUs x 32: extra waves per workgroup are added only while all stay resident
+constexpr unsigned ZFAR = 0x7f800000u;
+
+struct __attribute__((aligned(16))) VRec {
+    int sx, sy;      // snapped window coordinates (1/256 pixel); sx == INT_MIN: unusable vertex
+    double rz;       // 1 / (double) Z
+};
+static_assert(sizeof(VRec) == 16, "vertex record");
+
+__global__ __launch_bounds__(256) void raster_prepare_kernel(const float* __restrict__ vertices, int V,
+                                                             const float* __restrict__ transforms, int N, float fx, float fy,
+                                                             float cx, float cy, float z_near, VRec* __restrict__ rec,
+                                                             unsigned* __restrict__ zbuf, size_t npix,
+                                                             int32_t* __restrict__ stats) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nthreads = (size_t)gridDim.x * 256;
+    for (size_t i = tid; i < npix; i += nthreads) zbuf[i] = ZFAR;
+    if (stats && tid < (size_t)4 * N) stats[tid] = 0;
+    const size_t nv = (size_t)N * V;
+    for (size_t i = tid; i < nv; i += nthreads) {
+        const int pose = (int)(i / V), k = (int)(i - (size_t)pose * V);
+        const float* T = transforms + 16 * (size_t)pose;
+        const float x = vertices[3 * (size_t)k], y = vertices[3 * (size_t)k + 1], z = vertices[3 * (size_t)k + 2];
+        const float X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+        const float Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+        const float Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+        const float u = (X / Z) * fx + cx, v = (Y / Z) * fy + cy;
+        const bool ok = (Z > z_near) && isfinite(X) && isfinite(Y) && isfinite(Z) && (fabsf(u) < 1048576.0f) &&
+                        (fabsf(v) < 1048576.0f);      // NaN u, v fail the comparisons
+        VRec r;
+        r.sx = ok ? (int)rintf(u * 256.0f) : INT_MIN;
+        r.sy = ok ? (int)rintf(v * 256.0f) : 0;
+        r.rz = ok ? 1.0 / (double)Z : 0.0;
+        rec[i] = r;
+    }
+}
+
+// One triangle after setup: vertices ordered so that the area A is positive.
+struct Tri {
+    int x0, y0, x1, y1, x2, y2;
+    double r0, r1, r2;
+    int xa, ya, xb, yb;      // clipped box of pixels whose sample can lie inside (inclusive)
+};
+
+// E_ab(p) = dx (py - ay) - dy (px - ax). dx, dy and both offsets fit 31 bits (29-bit coordinates; a sample of the
+// clipped box lies within the triangle's extent), so each product is a 32 x 32 -> 64 multiply and the int64 result exact.
+__device__ __forceinline__ bool edge_in(int ax, int ay, int bx, int by, int px, int py, long long& e) {
+    const int dx = bx - ax, dy = by - ay;
+    e = (long long)dx * (long long)(py - ay) - (long long)dy * (long long)(px - ax);
+    return e > 0 || (e == 0 && (dy > 0 || (dy == 0 && dx < 0)));
+}
+
+// Sample of pixel (x, y): coverage, perspective-correct depth, z-buffer update. Returns whether it was covered.
+__device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, int o, int W, unsigned* __restrict__ zb) {
+    const int px = 256 * x + o, py = 256 * y + o;
+    long long w0, w1, w2;
+    const bool in2 = edge_in(t.x0, t.y0, t.x1, t.y1, px, py, w2);
+    const bool in0 = edge_in(t.x1, t.y1, t.x2, t.y2, px, py, w0);
+    const bool in1 = edge_in(t.x2, t.y2, t.x0, t.y0, px, py, w1);
+    if (!(in0 && in1 && in2)) return false;
+    const double den = ((double)w0 * t.r0 + (double)w1 * t.r1) + (double)w2 * t.r2;
+    const unsigned zbits = __float_as_uint((float)(area / den));
+    unsigned* p = zb + (size_t)y * W + x;
+    if (zbits < *p) atomicMin(p, zbits);
+    return true;
+}
+
+__global__ __launch_bounds__(64 * MAX_WAVES) void raster_tri_kernel(const int32_t* __restrict__ faces, int F, int V,
+                                                        const VRec* __restrict__ rec, int H, int W, int o, int tpw,
+                                                        unsigned* __restrict__ zbuf, int32_t* __restrict__ stats) {
+    // every wave of the workgroup sets up the same tpw triangles; wave 0 walks the small boxes and keeps the statistics,
+    // all waves share the large boxes
+    const int pose = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __shared__ unsigned long long cov_large;
+    if (nw > 1) {
+        if (threadIdx.x == 0) cov_large = 0ull;
+        __syncthreads();
+    }
+    const long long tri = (long long)blockIdx.x * tpw + lane;
+    const VRec* vr = rec + (size_t)pose * V;
+    unsigned* zb = zbuf + (size_t)pose * H * W;
+    Tri t = {};
+    long long A = 0;
+    int n_bad = 0, n_degen = 0, n_cov = 0, n_large = 0;
+    bool large = false;
+    if (lane < tpw && tri < F) {
+        const unsigned i0 = (unsigned)faces[3 * tri], i1 = (unsigned)faces[3 * tri + 1], i2 = (unsigned)faces[3 * tri + 2];
+        bool bad = i0 >= (unsigned)V || i1 >= (unsigned)V || i2 >= (unsigned)V;   // never read outside the records
+        VRec a = {}, b = {}, c = {};
+        if (!bad) {
+            a = vr[i0], b = vr[i1], c = vr[i2];
+            bad = a.sx == INT_MIN || b.sx == INT_MIN || c.sx == INT_MIN;
+        }
+        if (bad) {
+            n_bad = 1;
+        } else {
+            A = (long long)(b.sx - a.sx) * (long long)(c.sy - a.sy) - (long long)(b.sy - a.sy) * (long long)(c.sx - a.sx);
+            if (A == 0) {
+                n_degen = 1;
+            } else {
+                if (A < 0) {
+                    const VRec s = b;
+                    b = c, c = s, A = -A;
+                }
+                t.x0 = a.sx, t.y0 = a.sy, t.x1 = b.sx, t.y1 = b.sy, t.x2 = c.sx, t.y2 = c.sy;
+                t.r0 = a.rz, t.r1 = b.rz, t.r2 = c.rz;
+                // pixels x with min <= 256 x + o <= max: ceil and floor by arithmetic shifts
+                t.xa = max(0, (min(min(t.x0, t.x1), t.x2) - o + 255) >> 8);
+                t.xb = min(W - 1, (max(max(t.x0, t.x1), t.x2) - o) >> 8);
+                t.ya = max(0, (min(min(t.y0, t.y1), t.y2) - o + 255) >> 8);
+                t.yb = min(H - 1, (max(max(t.y0, t.y1), t.y2) - o) >> 8);
+                if (t.xa <= t.xb && t.ya <= t.yb) {
+                    large = (long long)(t.xb - t.xa + 1) * (t.yb - t.ya + 1) > COOP_MIN;
+                    if (large) {
+                        n_large = 1;
+                    } else if (wv == 0) {
+                        bool cov = false;
+                        for (int y = t.ya; y <= t.yb; ++y)
+                            for (int x = t.xa; x <= t.xb; ++x) cov |= shade(t, (double)A, x, y, o, W, zb);
+                        n_cov = cov;
+                    }
+                }
+            }
+        }
+    }
+    // large boxes: the whole wave walks each, 8 x 8 samples per step
+    unsigned long long todo = __ballot(large);
+    const int lx = lane & 7, ly = lane >> 3;
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        Tri s;
+        s.x0 = __shfl(t.x0, src), s.y0 = __shfl(t.y0, src), s.x1 = __shfl(t.x1, src), s.y1 = __shfl(t.y1, src);
+        s.x2 = __shfl(t.x2, src), s.y2 = __shfl(t.y2, src);
+        s.r0 = __shfl(t.r0, src), s.r1 = __shfl(t.r1, src), s.r2 = __shfl(t.r2, src);
+        s.xa = __shfl(t.xa, src), s.ya = __shfl(t.ya, src), s.xb = __shfl(t.xb, src), s.yb = __shfl(t.yb, src);
+        const double area = (double)__shfl(A, src);
+        bool cov = false;
+        for (int y0 = s.ya + 8 * wv; y0 <= s.yb; y0 += 8 * nw)
+            for (int x0 = s.xa; x0 <= s.xb; x0 += 8) {
+                const int x = x0 + lx, y = y0 + ly;
+                if (x <= s.xb && y <= s.yb) cov |= shade(s, area, x, y, o, W, zb);
+            }
+        if (__ballot(cov) != 0ull && lane == src) n_cov = 1;
+    }
+    if (nw > 1) {
+        if (n_cov && large) atomicOr(&cov_large, 1ull << lane);
+        __syncthreads();
+        if (large) n_cov = (int)((cov_large >> lane) & 1ull);
+    }
+    if (stats && wv == 0) {
+        n_bad = wave_sum_i32(n_bad), n_degen = wave_sum_i32(n_degen), n_cov = wave_sum_i32(n_cov), n_large = wave_sum_i32(n_large);
+        if (lane == 0) {                     // integer sums: independent of the order of arrival
+            int32_t* st = stats + 4 * pose;
+            if (n_bad) atomicAdd(st, n_bad);
+            if (n_degen) atomicAdd(st + 1, n_degen);
+            if (n_cov) atomicAdd(st + 2, n_cov);
+            if (n_large) atomicAdd(st + 3, n_large);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void raster_resolve_kernel(unsigned* __restrict__ zbuf, size_t npix) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256)
+        if (zbuf[i] == ZFAR) zbuf[i] = 0u;
+}
+
+bool sizes_ok(int V, int F, int N) {
+    return V >= 1 && V <= OSSID_RASTER_MAX_VERTICES && F >= 0 && F <= OSSID_RASTER_MAX_FACES && N >= 1 &&
+           N <= OSSID_RASTER_MAX_POSES;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ossid_raster_workspace_bytes(int V, int F, int N) {
+    if (!sizes_ok(V, F, N)) return 0;
+    return (size_t)N * (size_t)V * sizeof(VRec);
+}
+
+int ossid_raster_depth(const float* vertices, int V, const int32_t* faces, int F, const float* transforms, int N, float fx,
+                       float fy, float cx, float cy, int H, int W, float pixel_offset, float z_near, void* workspace,
+                       size_t workspace_bytes, float* depth_out, int32_t* stats, void* stream) {
+    const size_t need = ossid_raster_workspace_bytes(V, F, N);
+    if (need == 0 || !vertices || (F > 0 && !faces) || !transforms || !workspace || workspace_bytes < need || !depth_out ||
+        H <= 0 || W <= 0 || (long long)H * W > OSSID_RASTER_MAX_PIXELS || ((uintptr_t)workspace & 15) != 0 ||
+        !(pixel_offset >= 0.0f && pixel_offset <= 1.0f) || !(z_near >= 0.0f) || !std::isfinite(z_near))
+        return OSSID_EINVAL;
+    const int o = (int)std::nearbyint((double)pixel_offset * 256.0);       // round half to even
+    const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
+    hipStream_t s = (hipStream_t)stream;
+    VRec* rec = (VRec*)workspace;
+    unsigned* zbuf = (unsigned*)depth_out;
+    size_t work = npix > nv ? npix : nv;
+    int blocks = (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192);
+    hipLaunchKernelGGL(raster_prepare_kernel, dim3(blocks), dim3(256), 0, s, vertices, V, transforms, N, fx, fy, cx, cy, z_near,
+                       rec, zbuf, npix, stats);
+    if (F > 0) {
+        long long tpw = ((long long)F * N + TARGET_WAVES - 1) / TARGET_WAVES;
+        tpw = tpw < 1 ? 1 : (tpw > 64 ? 64 : tpw);
+        const long long groups = (F + tpw - 1) / tpw;
+        // more waves per workgroup only once each wave is down to one triangle: every wave repeats the setup
+        long long nw = tpw == 1 ? RESIDENT_WAVES / (groups * N) : 1;
+        nw = nw < 1 ? 1 : (nw > MAX_WAVES ? MAX_WAVES : nw);
+        hipLaunchKernelGGL(raster_tri_kernel, dim3((unsigned)groups, N), dim3(64 * (unsigned)nw), 0, s, faces, F, V, rec, H, W, o,
+                           (int)tpw, zbuf, stats);
+    }
+    blocks = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
+    hipLaunchKernelGGL(raster_resolve_kernel, dim3(blocks), dim3(256), 0, s, zbuf, npix);
+    return ossid_launch_status();
+}
+
+}  // extern "C"

@@ -50,9 +50,10 @@ def _call(name, *args):
     _lib.check(rc, name)
 
 
-def read_ply(path):
-    """BOP-style PLY (ASCII or binary little-endian) -> (points f64 [V,3], normals f64 [V,3]) from the vertex element's
-    x y z nx ny nz; every other element and property (faces, colours, texture coordinates) is skipped."""
+def _ply_walk(path, lists_of=None):
+    """The header / body walk shared by read_ply and render.read_ply_mesh -> (vertex columns {name: f64 [V]} or None,
+    {property name: list of int arrays, one per row} of the list properties of element `lists_of`, or None when that
+    element is absent / not asked for). Elements and properties nobody asked for are skipped."""
     types = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
              "double": "f8", "float64": "f8"}
@@ -81,7 +82,7 @@ def read_ply(path):
         if fmt not in ("ascii", "binary_little_endian"):
             raise ValueError("%s: PLY format %r is not supported (ascii, binary_little_endian)" % (path, fmt))
         body = f.read()
-    vert = None
+    vert, lists = None, None
     if fmt == "ascii":
         lines = body.decode("ascii").split("\n")
         pos = 0
@@ -97,6 +98,17 @@ def read_ply(path):
                 if any(isinstance(p[1], tuple) for p in props):
                     raise ValueError("%s: list property on the vertex element" % path)
                 vert = {nm: np.array([float(r[k]) for r in rows]) for k, nm in enumerate(names)}
+            elif name == lists_of:
+                lists = {p[0]: [] for p in props if isinstance(p[1], tuple)}
+                for r in rows:
+                    k = 0
+                    for pn, t in props:
+                        if isinstance(t, tuple):
+                            cnt = int(r[k])
+                            lists[pn].append(np.array([int(float(q)) for q in r[k + 1:k + 1 + cnt]], dtype=np.int64))
+                            k += 1 + cnt
+                        else:
+                            k += 1
     else:
         pos = 0
         for name, n, props in elements:
@@ -109,13 +121,26 @@ def read_ply(path):
             else:
                 if name == "vertex":
                     raise ValueError("%s: list property on the vertex element" % path)
+                keep = name == lists_of
+                if keep:
+                    lists = {p[0]: [] for p in props if isinstance(p[1], tuple)}
                 for _ in range(n):
-                    for _pn, t in props:
+                    for pn, t in props:
                         if isinstance(t, tuple):
                             cnt = np.frombuffer(body, dtype="<" + t[1], count=1, offset=pos)[0]
-                            pos += np.dtype(t[1]).itemsize + int(cnt) * np.dtype(t[2]).itemsize
+                            pos += np.dtype(t[1]).itemsize
+                            if keep:
+                                lists[pn].append(np.frombuffer(body, dtype="<" + t[2], count=int(cnt), offset=pos).astype(np.int64))
+                            pos += int(cnt) * np.dtype(t[2]).itemsize
                         else:
                             pos += np.dtype(t).itemsize
+    return vert, lists
+
+
+def read_ply(path):
+    """BOP-style PLY (ASCII or binary little-endian) -> (points f64 [V,3], normals f64 [V,3]) from the vertex element's
+    x y z nx ny nz; every other element and property (faces, colours, texture coordinates) is skipped."""
+    vert, _ = _ply_walk(path)
     if vert is None:
         raise ValueError("%s: no vertex element" % path)
     missing = [k for k in ("x", "y", "z", "nx", "ny", "nz") if k not in vert]

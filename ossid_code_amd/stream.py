@@ -6,7 +6,8 @@ scripts/online_learning.py:314-591 (SURVEY.md 8d cfg-5, 8e "full online stream")
        SIFT is out of scope)
     -> per-hypothesis ADD/ADI (:452) -> Zephyr score (networkInference, :464) -> argmax (:466-469)
     -> optional ICP refinement of the chosen pose (icpRefinement, :471-480; OnlineStream(icp_max_dist=...))
-    -> predicted depth (point-splat renderer for pyrender, :485) -> visibility mask (:500)
+    -> predicted depth (:485-493: the mesh rasteriser of SPEC.md section 7 with OnlineStream(meshes=...), otherwise
+       the point-splat stand-in) -> visibility mask (:500)
     -> if score > threshold: pseudo-label joins the finetune set (:506-516)
     -> when the set reaches the next multiple of finetune_interval: finetune DTOID (:517-533)
 
@@ -21,7 +22,7 @@ import time
 import numpy as np
 import torch
 
-from . import pipeline, ppf
+from . import pipeline, ppf, render
 from .hostutil import K2meta
 from .scoring import networkInference, pose_errors
 
@@ -80,14 +81,18 @@ class OnlineStream:
     ppf_models (None = off): dict obj_id -> ppf.PPFModel built in metres; hypotheses then come from the frame's depth
     inside the DTOID boxes (ppf.PPFModel.find_hypotheses, mask as online_learning.py:384-405 builds it), timed under
     times["ppf"], `frame["pose_hypos"]` is not read, and the result carries "n_hypos" and the hypotheses ("ppf_hypos"). ppf_kwargs go to find_hypotheses
-    ({"DensePoseRefinement": True} refines the hypotheses, SPEC.md 6.9)."""
+    ({"DensePoseRefinement": True} refines the hypotheses, SPEC.md 6.9).
+    meshes (None = off): dict obj_id -> render.Mesh in metres; the pseudo-label step then renders the mesh of
+    frame["obj_id"] at the chosen pose (render.render_depth, pixel_offset = mesh_pixel_offset: 0 is this package's pixel
+    convention, under which the render lines up with the observed depth) instead of splatting the model points."""
 
     def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None,
-                 icp_max_dist=None, ppf_models=None, ppf_kwargs=None):
+                 icp_max_dist=None, ppf_models=None, ppf_kwargs=None, meshes=None, mesh_pixel_offset=0.0):
         self.detector, self.scorer, self.dataset = detector, scorer, score_dataset
         self.threshold, self.symmetric, self.finetune_fn = confident_threshold, symmetric, finetune_fn
         self.icp_max_dist = icp_max_dist
         self.ppf_models, self.ppf_kwargs = ppf_models, dict(ppf_kwargs or {})
+        self.meshes, self.mesh_pixel_offset = meshes, float(mesh_pixel_offset)
         keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ()) + \
             (("ppf",) if ppf_models is not None else ())
         self.times = {k: 0.0 for k in keys}
@@ -135,6 +140,10 @@ class OnlineStream:
             pred_pose, pred_err = refined, refined_err
 
         def pseudo():
+            if self.meshes is not None:
+                pred_depth = render.render_depth(self.meshes[int(frame["obj_id"])], pred_pose, frame["cam_K"], (H, W),
+                                                 pixel_offset=self.mesh_pixel_offset)
+                return pipeline.visibility_and_iou(frame["depth"], pred_depth)[:2]
             pred_depth = pipeline.render_depth_points(pred_pose, frame["model_points"], frame["cam_K"], (H, W), radius=1)
             return pipeline.visibility_and_iou(frame["depth"], pred_depth)[:2]
         _pred_mask, pred_mask_visib = self._timed("pseudo_label", pseudo)
