@@ -208,7 +208,7 @@ typedef struct ossid_conv_desc {
 int ossid_conv_split_bf16(void);
 size_t ossid_conv_packed_floats(int Cout, int Cin, int taps);
 size_t ossid_conv_packed_floats_form(int Cout, int Cin, int taps, int exact);
-/* w [Cout][Cin][taps] -> the operand layout of ossid_conv_nhwc_fwd (common.h, ossid_conv_pack_quad). dgrad != 0: the layer
+/* w [Cout][Cin][taps] -> the operand layout of ossid_conv_nhwc_fwd (csrc/pack.hip). dgrad != 0: the layer
  * of the DATA gradient (Cin output channels, Cout reduction channels, taps reversed; needs ossid_conv_packed_floats(Cin,
  * Cout, taps) floats). exact: the form of the launches that will read it. ossid_conv_pack_weights = (dgrad 0, exact 0). */
 int ossid_conv_pack_weights_form(const float* w, int Cout, int Cin, int taps, int dgrad, int exact, float* wpk, void* stream);

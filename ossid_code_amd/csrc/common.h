@@ -79,121 +79,12 @@ static inline int ossid_ensure_dyn_lds(const void* fn, size_t bytes, OssidLdsAtt
         if (rc_ != OSSID_OK) return rc_;                                          \
     } while (0)
 
-// Winograd F(2x2, 3x3) filter transform U = G g G^T (G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]) in the packed layout of
-// csrc/wino.hip. w is the forward weight [Cout][Cin][3][3]; dgrad != 0 packs the data gradient's layer (M = Cin output
-// channels, K = Cout reduction channels, filter rotated by 180 degrees). Element i is one 16-byte unit.
-//   split-bf16 form (default):  [ceil(M/32)][K/16][16 xi][2 parts][64 lanes][8 bf16] -- lane (c,h) of (mt, chunk, xi, part)
-//       holds U_xi[32mt+c][16chunk+8h+0..7] as bf16: part 0 = hi = bf16(U), part 1 = lo = bf16(U - hi); the kernel forms
-//       U*V ~ hi*vh + hi*vl + lo*vh on v_mfma_f32_32x32x16_bf16 (the dropped lo*vl term is ~2^-16 of the product)
-//   exact-f32 form (-DOSSID_WINO_F32): [ceil(M/32)][K/8][16 xi][64 lanes][4 floats] -- lane (c,h) of (mt, kb, xi) holds
-//       U_xi[32mt+c][8kb+4h+0..3]
-// Both have the same size (ossid_conv_wino_packed_floats).
-__device__ __forceinline__ float ossid_wino_u(const float* __restrict__ w, int Cout, int Cin, int dgrad, int m, int k, int xi) {
-    const int ti = xi >> 2, tj = xi & 3;
-    const float* g = dgrad ? w + ((size_t)k * Cin + m) * 9 : w + ((size_t)m * Cin + k) * 9;
-    float t[3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        const float g0 = dgrad ? g[8 - b] : g[b], g1 = dgrad ? g[5 - b] : g[3 + b], g2 = dgrad ? g[2 - b] : g[6 + b];
-        t[b] = ti == 0 ? g0 : (ti == 1 ? 0.5f * (g0 + g1 + g2) : (ti == 2 ? 0.5f * (g0 - g1 + g2) : g2));
-    }
-    return tj == 0 ? t[0] : (tj == 1 ? 0.5f * (t[0] + t[1] + t[2]) : (tj == 2 ? 0.5f * (t[0] - t[1] + t[2]) : t[2]));
-}
-
-__device__ __forceinline__ float4 ossid_wino_pack_quad(const float* __restrict__ w, int Cout, int Cin, int dgrad, size_t i) {
-    const int lane = (int)(i & 63);
-    size_t r = i >> 6;
-    const int K = dgrad ? Cout : Cin, M = dgrad ? Cin : Cout;
-#ifndef OSSID_WINO_F32
-    const int part = (int)(r & 1);
-    r >>= 1;
-    const int xi = (int)(r & 15);
-    r >>= 4;
-    const int KC = K / 16;
-    const int ch = (int)(r % KC), mt = (int)(r / KC);
-    const int m = mt * 32 + (lane & 31), k0 = ch * 16 + 8 * (lane >> 5);
-    union {
-        __bf16 hv[8];
-        float4 f;
-    } o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float u = m < M ? ossid_wino_u(w, Cout, Cin, dgrad, m, k0 + e, xi) : 0.0f;
-        const __bf16 hi = (__bf16)u;
-        o.hv[e] = part == 0 ? hi : (__bf16)(u - (float)hi);
-    }
-    return o.f;
-#else
-    const int xi = (int)(r & 15);
-    r >>= 4;
-    const int KB = K / 8;
-    const int kb = (int)(r % KB), mt = (int)(r / KB);
-    const int m = mt * 32 + (lane & 31), k0 = kb * 8 + 4 * (lane >> 5);
-    float v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = m < M ? ossid_wino_u(w, Cout, Cin, dgrad, m, k0 + e, xi) : 0.0f;
-    return make_float4(v[0], v[1], v[2], v[3]);
-#endif
-}
-
-// Direct-convolution weights (csrc/conv.hip): element i = one 16-byte unit of the packed layout of a layer with M output and
-// K reduction channels. Forward (dgrad == 0): M = Cout, K = Cin, value w[m][k][tap]; data gradient: M = Cin, K = Cout,
-// value w[k][m][taps-1-tap] (transposed, rotated by 180 degrees). w is [Cout][Cin][taps].
-//   split-bf16 form (default):  [ceil(M/32)][K/16][taps][2 parts][64 lanes][8 bf16] -- lane (c,h) of (mt, u, tap, part) holds
-//       W[32mt+c][16u+8h+0..7][tap]: part 0 = hi = bf16(W), part 1 = lo = bf16(W - hi)
-//   exact-f32 form (exact == 1; every layer of a -DOSSID_CONV_F32 build): [ceil(M/32)][K/8][taps][64 lanes][4 floats] --
-//       lane (c,h) holds W[32mt+c][8kb+4h+0..3][tap]
-//   three-way split (exact == 2): as the split form with [3 parts] -- p0 = bf16(W), p1 = bf16(W - p0), p2 = bf16(W - p0 - p1)
-// The first two have the same size (ossid_conv_packed_floats), the third 1.5 x that (ossid_conv_packed_floats_form).
+// the direct convolutions' default arithmetic: 1 = split-bf16 operands, 0 = the exact-f32 instruction (formats: csrc/pack.hip)
 #ifdef OSSID_CONV_F32
 #define OSSID_CONV_SB 0
 #else
 #define OSSID_CONV_SB 1
 #endif
-__device__ __forceinline__ float4 ossid_conv_pack_quad(const float* __restrict__ w, int Cout, int Cin, int taps, int dgrad, int exact,
-                                                       size_t i) {
-    const int lane = (int)(i & 63);
-    size_t r = i >> 6;
-    const int K = dgrad ? Cout : Cin, M = dgrad ? Cin : Cout;
-    auto at = [&](int m, int k, int tap) {
-        return dgrad ? w[((size_t)k * Cin + m) * taps + (taps - 1 - tap)] : w[((size_t)m * Cin + k) * taps + tap];
-    };
-    if (OSSID_CONV_SB && exact != 1) {
-        const int parts = exact == 2 ? 3 : 2;
-        const int part = (int)(r % parts);
-        r /= parts;
-        const int tap = (int)(r % taps);
-        r /= taps;
-        const int KU = K / 16;
-        const int u = (int)(r % KU), mt = (int)(r / KU);
-        const int m = mt * 32 + (lane & 31), k0 = u * 16 + 8 * (lane >> 5);
-        union {
-            __bf16 hv[8];
-            float4 f;
-        } o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float v = m < M ? at(m, k0 + e, tap) : 0.0f;
-            __bf16 pc = (__bf16)v;
-            for (int k = 0; k < part; ++k) {
-                v -= (float)pc;
-                pc = (__bf16)v;
-            }
-            o.hv[e] = pc;
-        }
-        return o.f;
-    }
-    const int tap = (int)(r % taps);
-    r /= taps;
-    const int KB = K / 8;
-    const int kb = (int)(r % KB), mt = (int)(r / KB);
-    const int m = mt * 32 + (lane & 31), k0 = kb * 8 + 4 * (lane >> 5);
-    float v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = m < M ? at(m, k0 + e, tap) : 0.0f;
-    return make_float4(v[0], v[1], v[2], v[3]);
-}
-
 // 64-lane wave reductions (xor butterfly; every lane ends with the result)
 __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
@@ -203,6 +94,21 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 __device__ __forceinline__ float wave_max_f32(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ int wave_min_i32(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
     return v;
 }
 

@@ -26,45 +26,11 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ v16f mfma(float a, float b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// Split-bf16 arithmetic (kernel template argument FORM = 1; chosen per launch, see ossid_conv_desc::exact): every f32 operand is a pair
-// of bf16 values, x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16 significant bits together), and a 16-channel slice
-// of the reduction is three v_mfma_f32_32x32x16_bf16 -- w_lo*x_hi + w_hi*x_lo + w_hi*x_hi, accumulated in f32 -- instead of
-// eight v_mfma_f32_32x32x2_f32: 96 pipe cycles instead of 512. The dropped w_lo*x_lo term is ~2^-16 of a product; measured
-// against float64 the results sit at ~5e-6 of the output scale (exact form: ~1e-6), tests hold 2e-5. Weights are split when
-// they are packed (common.h, ossid_conv_pack_quad), activations when they are staged into LDS ([position][hi of the chunk's
-// channels | lo ...] bf16: an MFMA operand is one ds_read_b128 of 8 channels).
-// FORM = 2, the three-way split: x = p0 + p1 + p2 with p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1) -- 24
-// significant bits, i.e. the f32 value itself up to its last bit -- and six products per slice (all pairs (i, j) with
-// i + j <= 2; the dropped ones are <= 2^-24 of a product, the size of f32's own rounding): f32-level accuracy (measured
-// like the exact form: ~1e-6 of the output scale) at 192 pipe cycles per 16-channel slice instead of 512. For the layers
-// whose output a ReLU / max-pool decides on in training (ossid_conv_desc::exact = 2).
-__device__ __forceinline__ v16f mfma6(const float4 (&w)[3], const float4& x0, const float4& x1, const float4& x2, v16f c) {
-    const v8bf a0 = __builtin_bit_cast(v8bf, w[0]), a1 = __builtin_bit_cast(v8bf, w[1]), a2 = __builtin_bit_cast(v8bf, w[2]);
-    const v8bf b0 = __builtin_bit_cast(v8bf, x0), b1 = __builtin_bit_cast(v8bf, x1), b2 = __builtin_bit_cast(v8bf, x2);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, c, 0, 0, 0);          // smallest terms first
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
-}
-__device__ __forceinline__ v16f mfma3(const float4& whi, const float4& wlo, const float4& xhi, const float4& xlo, v16f c) {
-    const v8bf ah = __builtin_bit_cast(v8bf, whi), al = __builtin_bit_cast(v8bf, wlo);
-    const v8bf bh = __builtin_bit_cast(v8bf, xhi), bl = __builtin_bit_cast(v8bf, xlo);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-}
+// (the split-bf16 and three-way-split arithmetic of FORM = 1 / 2 -- mfma3 / mfma6 -- is described in csrc/mfma.h)
 
 // One float4 of padding per patch position: a wave's ds_read_b128 takes the same 16 bytes of 32 consecutive positions, a
 // lane stride of KCH*4 bytes -- 64 / 128 / 256 / 512 bytes, i.e. every lane of a 16-lane group on the same banks. On the f32
@@ -315,21 +281,10 @@ __device__ __forceinline__ void conv_nhwc_body(const ConvArgs& A) {
             for (int e = 0; e < NLD; ++e) {
                 if (lidx[e] < 0) continue;
                 const float v[4] = {st[e].x, st[e].y, st[e].z, st[e].w};
-                union {
-                    __bf16 b[4];
-                    uint2 u;
-                } pc[3];
+                uint2 pc[WPQ];
+                split_bf16(v, pc);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float r = v[i];
-#pragma unroll
-                    for (int k = 0; k < WPQ; ++k) {
-                        pc[k].b[i] = (__bf16)r;
-                        r -= (float)pc[k].b[i];          // exact: the remainder is representable
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < WPQ; ++k) p2[lidx[e] + F4 * k] = pc[k].u;
+                for (int k = 0; k < WPQ; ++k) p2[lidx[e] + F4 * k] = pc[k];
             }
         } else {
 #pragma unroll
@@ -515,14 +470,6 @@ __global__ __launch_bounds__(256, 2) void conv_nhwc_kernel_w2(const ConvArgs A) 
     conv_nhwc_body<FORM, WM, WK, NT, ROWSEG, NLD, TAPS, KCH, NPH>(A);
 }
 
-// weight repack on the device: w [Cout][Cin][taps] (torch layout, taps = kh*kw) -> wpk (see the file header)
-__global__ __launch_bounds__(256) void pack_conv_kernel(const float* __restrict__ w, int Cout, int Cin, int taps, int dgrad,
-                                                        int exact, float4* __restrict__ wpk, size_t total) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    wpk[i] = ossid_conv_pack_quad(w, Cout, Cin, taps, dgrad, exact, i);
-}
-
 template <int FORM, int WM, int WK, int NT, int ROWSEG, int NLD, int TAPS, int KCH, int NPH = 1>
 int launch_conv_form(ConvArgs a, int B, hipStream_t s) {
     constexpr int WN = 4 / (WM * WK), BPX = WN * NT * 32, F4 = KCH / 4;
@@ -585,28 +532,6 @@ int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
 extern "C" {
 
 int ossid_conv_split_bf16(void) { return OSSID_CONV_SB; }
-
-size_t ossid_conv_packed_floats(int Cout, int Cin, int taps) {
-    return (size_t)((Cout + 31) / 32) * (Cin / 8) * taps * 64 * 4;
-}
-
-size_t ossid_conv_packed_floats_form(int Cout, int Cin, int taps, int exact) {
-    const size_t n = ossid_conv_packed_floats(Cout, Cin, taps);
-    return (exact == 2 && OSSID_CONV_SB) ? n / 2 * 3 : n;       // three pieces per value instead of two
-}
-
-int ossid_conv_pack_weights_form(const float* w, int Cout, int Cin, int taps, int dgrad, int exact, float* wpk, void* stream) {
-    if (!w || !wpk || Cout <= 0 || Cin <= 0 || (dgrad ? Cout : Cin) % 16 || (taps != 1 && taps != 9 && taps != 4)) return OSSID_EINVAL;
-    if (exact < 0 || exact > 2) return OSSID_EINVAL;
-    const size_t total = (dgrad ? ossid_conv_packed_floats_form(Cin, Cout, taps, exact) : ossid_conv_packed_floats_form(Cout, Cin, taps, exact)) / 4;
-    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       Cout, Cin, taps, dgrad ? 1 : 0, exact, (float4*)wpk, total);
-    return ossid_launch_status();
-}
-
-int ossid_conv_pack_weights(const float* w, int Cout, int Cin, int taps, float* wpk, void* stream) {
-    return ossid_conv_pack_weights_form(w, Cout, Cin, taps, 0, 0, wpk, stream);
-}
 
 int ossid_conv_nhwc_fwd(const ossid_conv_desc* d, void* stream) {
     if (!d) return OSSID_EINVAL;

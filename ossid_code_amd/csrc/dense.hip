@@ -31,19 +31,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ v16f mfma3(const float4& whi, const float4& wlo, const float4& xhi, const float4& xlo, v16f c) {
-    const v8bf ah = __builtin_bit_cast(v8bf, whi), al = __builtin_bit_cast(v8bf, wlo);
-    const v8bf bh = __builtin_bit_cast(v8bf, xhi), bl = __builtin_bit_cast(v8bf, xlo);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-}
 
 // compile-time loop: the body sees its index as a constant BEFORE the optimiser's first scalar-replacement pass (a `#pragma
 // unroll` loop is unrolled after it: register arrays indexed by the loop variable then live in scratch memory)
@@ -57,7 +47,6 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 // Pointers read from the device table are generic to the compiler (flat_load: slower, and counted on lgkmcnt as well); they
 // are global addresses by contract.
-typedef float v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ldg(const void* p) {
     const v4f v = *(const v4f __attribute__((address_space(1)))*)(unsigned long long)p;
     return make_float4(v.x, v.y, v.z, v.w);
@@ -306,17 +295,10 @@ __global__ __launch_bounds__(256) void dense_layer_kernel(const DenseArgs A) {
             float v[4];
             v[0] = okf * fmaxf(st[e].x * s2.x + t2.x, 0.f), v[1] = okf * fmaxf(st[e].y * s2.y + t2.y, 0.f);
             v[2] = okf * fmaxf(st[e].z * s2.z + t2.z, 0.f), v[3] = okf * fmaxf(st[e].w * s2.w + t2.w, 0.f);
-            union {
-                __bf16 b4[4];
-                uint2 u2;
-            } ph, pl;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ph.b4[i] = (__bf16)v[i];
-                pl.b4[i] = (__bf16)(v[i] - (float)ph.b4[i]);
-            }
-            p2[(pos * PSTR + u * 4) * 2 + jj] = ph.u2;
-            p2[(pos * PSTR + u * 4) * 2 + 4 + jj] = pl.u2;
+            uint2 pc[2];
+            split_bf16(v, pc);
+            p2[(pos * PSTR + u * 4) * 2 + jj] = pc[0];
+            p2[(pos * PSTR + u * 4) * 2 + 4 + jj] = pc[1];
         }
     }
     __syncthreads();
@@ -454,17 +436,10 @@ __global__ __launch_bounds__(256) void dense_entry_kernel(const EntryArgs A) {
             float v[4];
             v[0] = fmaxf(st[e].x * s1.x + t1.x, 0.f), v[1] = fmaxf(st[e].y * s1.y + t1.y, 0.f);
             v[2] = fmaxf(st[e].z * s1.z + t1.z, 0.f), v[3] = fmaxf(st[e].w * s1.w + t1.w, 0.f);
-            union {
-                __bf16 b4[4];
-                uint2 u2;
-            } ph, pl;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ph.b4[i] = (__bf16)v[i];
-                pl.b4[i] = (__bf16)(v[i] - (float)ph.b4[i]);
-            }
-            p2[(pos * ESTR + u * 4) * 2 + jj] = ph.u2;
-            p2[(pos * ESTR + u * 4) * 2 + 4 + jj] = pl.u2;
+            uint2 pc[2];
+            split_bf16(v, pc);
+            p2[(pos * ESTR + u * 4) * 2 + jj] = pc[0];
+            p2[(pos * ESTR + u * 4) * 2 + 4 + jj] = pc[1];
         }
     }
     __syncthreads();

@@ -19,11 +19,9 @@
 //   grid      persistent workgroups walk the stages; wave w owns channel tiles w, w + 4, ...; one partial row [2][c] of the
 //             column sums per workgroup, summed in a fixed order by ossid_bn_fold_bwd (bit-reproducible, no float atomics)
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 
 constexpr int DB_MID = 128, DB_PXS = 64;
 constexpr int DB_PSTR = DB_MID / 16 * 4 + 1;            // float4 per pixel in LDS: 8 units x (hi, lo) x 2 halves + 1 of padding
@@ -78,17 +76,10 @@ __global__ __launch_bounds__(256, 2) void dense_dgrad1_acc_kernel(const DenseBwd
                 v[0] = (v[0] + zb.x * sa[e].x) + zk.x, v[1] = (v[1] + zb.y * sa[e].y) + zk.y;
                 v[2] = (v[2] + zb.z * sa[e].z) + zk.z, v[3] = (v[3] + zb.w * sa[e].w) + zk.w;
             }
-            union {
-                __bf16 b4[4];
-                uint2 u2;
-            } ph, pl;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ph.b4[i] = (__bf16)v[i];
-                pl.b4[i] = (__bf16)(v[i] - (float)ph.b4[i]);
-            }
-            p2[(px * DB_PSTR + u * 4) * 2 + jj] = ph.u2;
-            p2[(px * DB_PSTR + u * 4) * 2 + 4 + jj] = pl.u2;
+            uint2 pc[2];
+            split_bf16(v, pc);
+            p2[(px * DB_PSTR + u * 4) * 2 + jj] = pc[0];
+            p2[(px * DB_PSTR + u * 4) * 2 + 4 + jj] = pc[1];
         }
     };
     if ((int)blockIdx.x < A.nstages) fetch(blockIdx.x);
@@ -129,11 +120,7 @@ __global__ __launch_bounds__(256, 2) void dense_dgrad1_acc_kernel(const DenseBwd
                 const float4* zp = zl + (size_t)(pt * 32 + n) * DB_PSTR + h;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    const v8bf ah = __builtin_bit_cast(v8bf, zp[u * 4]), alo = __builtin_bit_cast(v8bf, zp[u * 4 + 2]);
-                    const v8bf bh = __builtin_bit_cast(v8bf, w[u][0]), bl = __builtin_bit_cast(v8bf, w[u][1]);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo, bh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+                    acc = mfma3(zp[u * 4], zp[u * 4 + 2], w[u][0], w[u][1], acc);
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -224,21 +211,10 @@ __global__ __launch_bounds__(256, 2) void dense_fwd1_stats_kernel(const DenseFwd
             const int px = (tid >> 4) + 16 * e;
             float v[4] = {fmaxf(st[e].x * ps.x + pt.x, 0.f), fmaxf(st[e].y * ps.y + pt.y, 0.f), fmaxf(st[e].z * ps.z + pt.z, 0.f),
                           fmaxf(st[e].w * ps.w + pt.w, 0.f)};
-            union {
-                __bf16 b4[4];
-                uint2 u2;
-            } pc[3];
+            uint2 pc[3];
+            split_bf16(v, pc);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float r = v[i];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    pc[k].b4[i] = (__bf16)r;
-                    r -= (float)pc[k].b4[i];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) p2[(px * DF_PSTR + u * 6 + k * 2) * 2 + jj] = pc[k].u2;
+            for (int k = 0; k < 3; ++k) p2[(px * DF_PSTR + u * 6 + k * 2) * 2 + jj] = pc[k];
         }
     };
     const float4* W4 = A.wpk + (size_t)wave * units * 3 * 64 + lane;
@@ -463,17 +439,10 @@ __global__ __launch_bounds__(256, 2) void dense_dgrad3_mask_kernel(const DenseBw
             const int yy = y0 - 1 + pr, xx = x0 - 1 + pc;
             const float f = (pos < D3_NPOS && yy >= 0 && yy < H && xx >= 0 && xx < W) ? 1.0f : 0.0f;      // zero padding
             const float v[4] = {f * st[e].x, f * st[e].y, f * st[e].z, f * st[e].w};
-            union {
-                __bf16 b4[4];
-                uint2 u2;
-            } ph, pl;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ph.b4[i] = (__bf16)v[i];
-                pl.b4[i] = (__bf16)(v[i] - (float)ph.b4[i]);
-            }
-            p2[(pos * D3_PSTR + u * 4) * 2 + jj] = ph.u2;
-            p2[(pos * D3_PSTR + u * 4) * 2 + 4 + jj] = pl.u2;
+            uint2 q[2];
+            split_bf16(v, q);
+            p2[(pos * D3_PSTR + u * 4) * 2 + jj] = q[0];
+            p2[(pos * D3_PSTR + u * 4) * 2 + 4 + jj] = q[1];
         }
     };
     const int p0 = (n >> 3) * D3_PC + (n & 7);           // patch position of tap (0, 0) for this lane's pixel (as the A operand's row)
@@ -506,11 +475,7 @@ __global__ __launch_bounds__(256, 2) void dense_dgrad3_mask_kernel(const DenseBw
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const float4* px4 = pb + ((tap / 3) * D3_PC + tap % 3) * D3_PSTR + u * 4;
-                const v8bf ah = __builtin_bit_cast(v8bf, px4[0]), alo = __builtin_bit_cast(v8bf, px4[2]);
-                const v8bf bh = __builtin_bit_cast(v8bf, w[u][tap][0]), bl = __builtin_bit_cast(v8bf, w[u][tap][1]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo, bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+                acc = mfma3(px4[0], px4[2], w[u][tap][0], w[u][tap][1], acc);
             }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {

@@ -36,12 +36,6 @@ struct IcpShared {
     int n[3], go;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // f32 cell coordinate of one axis; float rounding stays far below the cell margin (see icp_grid)
 __device__ __forceinline__ float cell_coord(float x, float lo, float inv_h) { return floorf((x - lo) * inv_h); }
 

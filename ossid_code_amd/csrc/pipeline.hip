@@ -10,17 +10,6 @@
 
 namespace {
 
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
-    return v;
-}
-
 // ---- (1a) processData: depth -> xyz map, resize (bilinear, pixel-centre aligned like cv2.INTER_LINEAR), /255, CHW ----
 // img u8 [Ho][Wo][3], depth f32 [Ho][Wo], mask f32 [Ho][Wo] in [0,1] -> img_out [3][H][W], xyz_out [3][H][W], mask_out [H][W].
 // Same size in and out (the LM-O / YCB-V case: 480x640 native) is an exact copy.

@@ -16,14 +16,9 @@
 // coalesced 16-B load per lane feeds four MFMAs. The max-pool over a group's samples is a
 // butterfly reduce-scatter across the 32 lanes (16 shuffles per 32 channels).
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ v16f mfma(float a, float b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
 
 // accumulator tile initialised with the folded bias: register 4q+e of lane half h <- b[32mt+8q+4h+e]
 __device__ __forceinline__ v16f bias_tile(const float* __restrict__ b, int mt, int h) {
@@ -241,46 +236,6 @@ __device__ __forceinline__ void stream_last_layer(const float4* __restrict__ W4,
         }
         epi(mt, acc);
     }
-}
-
-// Max over the 32 columns (lanes of one half) of each of the 16 rows of an accumulator tile.
-// Returns, in lane i = lane&31, the maximum of register r(i) = 8*b4 + 4*b3 + 2*b2 + b1 (bits of i);
-// lanes i and i^1 hold the same value. 16 shuffles instead of 80.
-__device__ __forceinline__ float reduce_scatter_max(const v16f& v, int lane) {
-    float w[8], x[4], y[2], z;
-    const bool b4 = lane & 16, b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float send = b4 ? v[j] : v[j + 8];
-        float keep = b4 ? v[j + 8] : v[j];
-        w[j] = fmaxf(keep, __shfl_xor(send, 16));
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float send = b3 ? w[j] : w[j + 4];
-        float keep = b3 ? w[j + 4] : w[j];
-        x[j] = fmaxf(keep, __shfl_xor(send, 8));
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        float send = b2 ? x[j] : x[j + 2];
-        float keep = b2 ? x[j + 2] : x[j];
-        y[j] = fmaxf(keep, __shfl_xor(send, 4));
-    }
-    {
-        float send = b1 ? y[0] : y[1];
-        float keep = b1 ? y[1] : y[0];
-        z = fmaxf(keep, __shfl_xor(send, 2));
-    }
-    z = fmaxf(z, __shfl_xor(z, 1));
-    return z;
-}
-
-// channel (within a 32-row tile) that reduce_scatter_max leaves in this lane
-__device__ __forceinline__ int scatter_row(int lane) {
-    int i = lane & 31, h = lane >> 5;
-    int r = ((i >> 4) & 1) * 8 + ((i >> 3) & 1) * 4 + ((i >> 2) & 1) * 2 + ((i >> 1) & 1);
-    return (r & 3) + 8 * (r >> 2) + 4 * h;
 }
 
 // ---- furthest point sampling: one workgroup per point set -----------------------------------------
@@ -849,7 +804,6 @@ __global__ __launch_bounds__(256, 1) void sa3_kernel(const float* __restrict__ f
                                                      const float* __restrict__ b3, float* __restrict__ feat3) {
     __shared__ float red[4][1024];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c = lane & 31;
-    const int row = scatter_row(lane);
     const int n = blockIdx.x;
     for (int i = tid; i < 4096; i += 256) (&red[0][0])[i] = -INFINITY;
     __syncthreads();

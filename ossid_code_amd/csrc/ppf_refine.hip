@@ -264,12 +264,6 @@ __global__ __launch_bounds__(256) void refine_init_kernel(const double* __restri
     w.done[h] = 0;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // nearest refinement model point of x within the level's grid, ties to the lowest index -> index (or -1 when none
 // within thr2)
 __device__ __forceinline__ int probe(const GridView& g, int lev, const float* x, float thr2) {
@@ -348,11 +342,11 @@ __global__ __launch_bounds__(RNT) void refine_corr_kernel(const float* __restric
     if (MODE == 0) {
 #pragma unroll
         for (int q = 0; q < NMOM; ++q) {
-            const double v = wave_sum(acc[q]);
+            const double v = wave_sum_f64(acc[q]);
             if (lane == 0) red[wv][q] = v;
         }
     }
-    const double pv = wave_sum((double)pairs);
+    const double pv = wave_sum_f64((double)pairs);
     if (lane == 0) red[wv][NMOM] = pv;
     __syncthreads();
     if (threadIdx.x < NPART && (MODE == 0 || threadIdx.x == NMOM)) {

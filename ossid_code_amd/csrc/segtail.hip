@@ -22,14 +22,13 @@
 // ONE ds_read_b128 of four consecutive channels of its pixel (k-group g = l/16 <-> channels 16*cb + 4g + i for the i-th
 // MFMA of the quad); the 18 weight quads (9 taps x 2 channel blocks) live in registers for the whole workgroup.
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int ST_TH = 14, ST_TW = 30;            // output tile
 constexpr int ST_MH = ST_TH + 2, ST_MW = ST_TW + 2;   // first-conv ("mid") region: 16 x 32 = 32 MFMA column tiles
-constexpr int ST_CIN = 32, ST_CMID = 16;
+constexpr int ST_CIN = 32;
 constexpr int ST_PSTRIDE = 36;                   // floats per staged source pixel (32 + 4: conflict-free ds_read_b128)
 constexpr int ST_MSTRIDE = 20;                   // floats per mid pixel (16 + 4)
 constexpr int ST_PR = 12, ST_PC = 20;            // source patch capacity (rows, cols) -- checked on the host
@@ -250,8 +249,6 @@ __global__ __launch_bounds__(256, 2) void seg_tail_kernel(const SegTailArgs A, c
 }
 
 #ifndef OSSID_SEGTAIL_F32
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-
 // Packed weights of the split form: [15 operands][hi, lo][64 lanes] 16 bytes. Operand o = combo * 3 + dx with combo 0 / 1 / 2
 // = kernel row ky, 3 = rows 0 + 1 merged, 4 = rows 1 + 2 merged (the row merging of the f32 kernel, done once here);
 // lane (co = l % 16, g = l / 16) holds channels 8g .. 8g + 7 of W_o[co] as bf16.
@@ -294,19 +291,11 @@ __global__ __launch_bounds__(256, 2) void seg_tail_sb_kernel(const SegTailArgs A
             const int p = i >> 3, j = i & 7;
             const int r = p / nc, cc = p - r * nc;
             const float4 v = *(const float4*)(A.x + ((size_t)(b * A.Hs + sr0 + r) * A.Ws + sc0 + cc) * A.in_cs + 4 * j);
-            const float f[4] = {v.x, v.y, v.z, v.w};
-            union {
-                __bf16 h[4];
-                uint2 u;
-            } hi, lo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                hi.h[e] = (__bf16)f[e];
-                lo.h[e] = (__bf16)(f[e] - (float)hi.h[e]);
-            }
+            uint2 pc[2];
+            split_bf16({v.x, v.y, v.z, v.w}, pc);
             char* px = (char*)(patch + (size_t)(r * ST_PC + cc) * ST_PSTRIDE);
-            *(uint2*)(px + 8 * j) = hi.u;
-            *(uint2*)(px + 64 + 8 * j) = lo.u;
+            *(uint2*)(px + 8 * j) = pc[0];
+            *(uint2*)(px + 64 + 8 * j) = pc[1];
         }
         if (tid < 144) w2s[tid] = w2[(tid & 15) * 9 + (tid >> 4)];
         if (tid < ST_PSTRIDE / 4) *(float4*)(patch + (size_t)ST_PR * ST_PC * ST_PSTRIDE + 4 * tid) = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -24,12 +24,9 @@
 //   this tile's MFMAs), each wave takes a channel tile x two rows; the row-pair sums meet in LDS in a fixed order,
 //   workgroups write partial [64][147] slabs that a second kernel adds in a fixed order (bit-reproducible, no float atomics).
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ v16f mfma(float a, float b, v16f c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 constexpr int KS = 7, ST = 2, CIN = 3, PADS = 3, CO = 64;
 constexpr int NTAP = CIN * KS * KS;                 // 147

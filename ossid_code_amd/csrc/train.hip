@@ -10,19 +10,13 @@
 //   upsample_bwd        gradient of F.interpolate(mode="nearest") (network.py:354-357): window sums
 //   wgrad_kernel        weight gradient of the 3x3 / 1x1 convolutions on the f32 matrix cores, operands staged through
 //                       LDS, the input's BatchNorm(+ReLU) prologue re-applied on the fly, deterministic split-K
-//   pack_dgrad_kernel   conv weights -> MFMA layout of the TRANSPOSED, 180-degree-rotated kernel: the data gradient is
-//                       ossid_conv_nhwc_fwd on dy with these
+// (the data gradient is ossid_conv_nhwc_fwd on dy with the weights packed TRANSPOSED and rotated by 180 degrees: csrc/pack.hip)
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ v16f mfma(float a, float b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
 
 // =====================================================================================================================
 // generic per-channel elementwise pass with column sums
@@ -382,135 +376,6 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float4* __restr
     dsrc[i] = s;
 }
 
-// every convolution weight of the training step packed in ONE launch (forward and data-gradient layouts): `table` has
-// one row per (layer, layout): {w, wpk, first block, Cout, Cin, taps, kind}; a block finds its row by binary search
-struct PackRow {
-    const float* w;
-    float4* wpk;
-    long long first_block;      // prefix sum of blocks (256 float4 each)
-    int Cout, Cin, taps, kind;  // kind 0: forward layout, 1: data-gradient layout, 2 / 3: their Winograd forms, 4 / 5: 0 / 1 for exact-f32 launches, 6 / 7: for three-way-split launches
-};
-
-// A thread packs EVERYTHING that derives from one lane's group of reduction channels of one output row: all taps and all
-// bf16 pieces (direct layouts), all 16 transform positions and both pieces (Winograd layouts). Round 3 had one thread per
-// 16-byte output unit, each gathering its 8 (direct) or 72 (Winograd) source weights again: 2 reads per weight for the direct
-// layouts, 32 for the Winograd ones, 4 bytes at a time -- 1.5 ms per step for 0.5 GB of traffic. Here a weight is read once per
-// layout (a thread's 8 x taps source values are contiguous in the forward layouts, 8 runs of `taps` in the data-gradient ones),
-// and a wave's stores are whole 1 KB units. The grid and the table are unchanged (first_block counts 256 output units per
-// block): a row simply needs fewer of its blocks, the rest return at once.
-__global__ __launch_bounds__(256) void pack_all_kernel(const PackRow* __restrict__ table, int n_rows) {
-    int lo = 0, hi = n_rows - 1;
-    const long long b = blockIdx.x;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_block <= b) lo = mid; else hi = mid - 1;
-    }
-    const PackRow R = table[lo];
-    const size_t i = (size_t)(b - R.first_block) * 256 + threadIdx.x;
-    const float* __restrict__ w = R.w;
-    const int Cout = R.Cout, Cin = R.Cin;
-    if (R.kind == 2 || R.kind == 3) {      // Winograd layouts (csrc/wino.hip)
-#ifndef OSSID_WINO_F32
-        const int dgrad = R.kind == 3;
-        const int K = dgrad ? Cout : Cin, M = dgrad ? Cin : Cout, KC = K / 16, M32 = (M + 31) / 32;
-        if (i >= (size_t)M32 * KC * 64) return;
-        const int lane = (int)(i & 63);
-        const size_t r = i >> 6;
-        const int ch = (int)(r % KC), mt = (int)(r / KC);
-        const int m = mt * 32 + (lane & 31), k0 = ch * 16 + 8 * (lane >> 5);
-        union Oct {
-            __bf16 hv[8];
-            float4 f;
-        } hi_o[16], lo_o[16];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float g[9];
-            if (m < M) {
-                const float* src = dgrad ? w + ((size_t)(k0 + e) * Cin + m) * 9 : w + ((size_t)m * Cin + k0 + e) * 9;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) g[t] = src[t];
-            }
-#pragma unroll
-            for (int xi = 0; xi < 16; ++xi) {
-                float u = 0.0f;
-                if (m < M) {                                   // (the arithmetic of ossid_wino_u, on the values loaded above)
-                    const int ti = xi >> 2, tj = xi & 3;
-                    float t3[3];
-#pragma unroll
-                    for (int bb = 0; bb < 3; ++bb) {
-                        const float g0 = dgrad ? g[8 - bb] : g[bb], g1 = dgrad ? g[5 - bb] : g[3 + bb], g2 = dgrad ? g[2 - bb] : g[6 + bb];
-                        t3[bb] = ti == 0 ? g0 : (ti == 1 ? 0.5f * (g0 + g1 + g2) : (ti == 2 ? 0.5f * (g0 - g1 + g2) : g2));
-                    }
-                    u = tj == 0 ? t3[0] : (tj == 1 ? 0.5f * (t3[0] + t3[1] + t3[2]) : (tj == 2 ? 0.5f * (t3[0] - t3[1] + t3[2]) : t3[2]));
-                }
-                const __bf16 h = (__bf16)u;
-                hi_o[xi].hv[e] = h;
-                lo_o[xi].hv[e] = (__bf16)(u - (float)h);
-            }
-        }
-        float4* out = R.wpk + (((size_t)mt * KC + ch) * 16) * 2 * 64 + lane;
-#pragma unroll
-        for (int xi = 0; xi < 16; ++xi) {
-            out[(size_t)(xi * 2 + 0) * 64] = hi_o[xi].f;
-            out[(size_t)(xi * 2 + 1) * 64] = lo_o[xi].f;
-        }
-#else
-        const int K8 = (R.kind == 2 ? R.Cin : R.Cout) / 8, M32 = ((R.kind == 2 ? R.Cout : R.Cin) + 31) / 32;
-        if (i < (size_t)M32 * K8 * 16 * 64) R.wpk[i] = ossid_wino_pack_quad(R.w, R.Cout, R.Cin, R.kind == 3, i);
-#endif
-        return;
-    }
-    if (R.kind < 0 || R.kind > 7) return;
-    const int dgrad = R.kind & 1, exact = R.kind >= 6 ? 2 : (R.kind >= 4 ? 1 : 0);
-    const int taps = R.taps;
-    const int K = dgrad ? Cout : Cin, M = dgrad ? Cin : Cout, MT = (M + 31) / 32;
-    auto at = [&](int m, int k, int tap) {
-        return dgrad ? w[((size_t)k * Cin + m) * taps + (taps - 1 - tap)] : w[((size_t)m * Cin + k) * taps + tap];
-    };
-    if (OSSID_CONV_SB && exact != 1) {     // split forms: [mt][K/16][taps][parts][64 lanes] x 8 bf16
-        const int parts = exact == 2 ? 3 : 2, KU = K / 16;
-        if (i >= (size_t)MT * KU * 64) return;
-        const int lane = (int)(i & 63);
-        const size_t r = i >> 6;
-        const int u = (int)(r % KU), mt = (int)(r / KU);
-        const int m = mt * 32 + (lane & 31), k0 = u * 16 + 8 * (lane >> 5);
-        float4* out = R.wpk + (((size_t)mt * KU + u) * taps) * parts * 64 + lane;
-        for (int tap = 0; tap < taps; ++tap) {
-            union {
-                __bf16 hv[8];
-                float4 f;
-            } o[3];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float v = m < M ? at(m, k0 + e, tap) : 0.0f;
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    const __bf16 pc = (__bf16)v;
-                    o[p].hv[e] = pc;
-                    v -= (float)pc;
-                }
-            }
-            for (int p = 0; p < parts; ++p) out[((size_t)tap * parts + p) * 64] = o[p].f;
-        }
-        return;
-    }
-    {                                      // exact-f32 form: [mt][K/8][taps][64 lanes] x 4 floats
-        const int KB = K / 8;
-        if (i >= (size_t)MT * KB * 64) return;
-        const int lane = (int)(i & 63);
-        const size_t r = i >> 6;
-        const int kb = (int)(r % KB), mt = (int)(r / KB);
-        const int m = mt * 32 + (lane & 31), k0 = kb * 8 + 4 * (lane >> 5);
-        float4* out = R.wpk + (((size_t)mt * KB + kb) * taps) * 64 + lane;
-        for (int tap = 0; tap < taps; ++tap) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = m < M ? at(m, k0 + e, tap) : 0.0f;
-            out[(size_t)tap * 64] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    }
-}
-
 // =====================================================================================================================
 // weight gradient: dW[co][ci][tap] = sum_px dY[px][co] * P(X)[px + tap][ci],  P = the forward's input prologue
 // (per-channel affine (+ReLU) on real pixels, zero outside the image). GEMM with the PIXELS on K:
@@ -743,8 +608,6 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& A, const int L) {
 // (dy_lo*x_hi + dy_hi*x_lo + dy_hi*x_hi) instead of eight f32 ones. Row pitch of an image: channels * 2 bytes padded so that
 // (pitch mod 256) is 64 or 192 -- the four rows of a block then sit on four different quarter-sets of the 64 banks.
 // One LDS buffer (the images of one chunk), the next chunk's global loads in flight in registers under the MFMAs.
-typedef __bf16 v8bf16 __attribute__((ext_vector_type(8)));
-typedef short v4i16 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ constexpr int wgrad_sb_pitch(int channels) {      // bytes
     return channels == 128 ? 320 : (channels == 64 ? 192 : (channels == 32 ? 64 : channels * 2 + 64));
@@ -843,18 +706,10 @@ __device__ __forceinline__ void wgrad_sb_body(const WgradArgs& A, const int L) {
         }
     };
     auto split_store = [&](const float4& f, char* hi_at, int part_stride) {
-        const float v[4] = {f.x, f.y, f.z, f.w};
-        union {
-            __bf16 b[4];
-            uint2 u;
-        } hi, lo;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            hi.b[i] = (__bf16)v[i];
-            lo.b[i] = (__bf16)(v[i] - (float)hi.b[i]);
-        }
-        *(uint2*)hi_at = hi.u;
-        *(uint2*)(hi_at + part_stride) = lo.u;
+        uint2 pc[2];
+        split_bf16({f.x, f.y, f.z, f.w}, pc);
+        *(uint2*)hi_at = pc[0];
+        *(uint2*)(hi_at + part_stride) = pc[1];
     };
     auto stage_write = [&]() {
 #pragma unroll
@@ -880,7 +735,7 @@ __device__ __forceinline__ void wgrad_sb_body(const WgradArgs& A, const int L) {
         const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(at + 4 * pitch));
         typedef short v8i16 __attribute__((ext_vector_type(8)));
         const v8i16 v = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(v8bf16, v);
+        return __builtin_bit_cast(v8bf, v);
     };
 
     long long ch = split;
@@ -901,7 +756,7 @@ __device__ __forceinline__ void wgrad_sb_body(const WgradArgs& A, const int L) {
         if (nxt < A.n_chunks) stage_load(gb, gy, gcr);       // in flight under this chunk's MFMAs
 #pragma unroll 1
         for (int k = wk; k < ksteps; k += WK) {
-            v8bf16 a[TM][2], bv[KYB][TN][KX][2];
+            v8bf a[TM][2], bv[KYB][TN][KX][2];
 #pragma unroll
             for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -926,9 +781,7 @@ __device__ __forceinline__ void wgrad_sb_body(const WgradArgs& A, const int L) {
 #pragma unroll
                         for (int kx = 0; kx < KX; ++kx) {
                             const int t = ((kr * TM + m) * TN + n) * KX + kx;
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], bv[kr][n][kx][0], acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bv[kr][n][kx][1], acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], bv[kr][n][kx][0], acc[t], 0, 0, 0);
+                            acc[t] = mfma3(a[m][0], a[m][1], bv[kr][n][kx][0], bv[kr][n][kx][1], acc[t]);
                         }
         }
         __syncthreads();                                      // every wave has read this chunk's images
@@ -1630,14 +1483,6 @@ int ossid_colsum_finalize(const float* partials, int n_partials, int C, float* s
                                   (hipStream_t)stream);
 }
 
-int ossid_conv_pack_weights_table(const ossid_pack_row* rows_device, int n_rows, long long total_blocks, void* stream) {
-    if (!rows_device || n_rows <= 0 || total_blocks <= 0 || total_blocks > 0x7fffffffLL) return OSSID_EINVAL;
-    static_assert(sizeof(PackRow) == sizeof(ossid_pack_row), "pack row layout");
-    hipLaunchKernelGGL(pack_all_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const PackRow*)rows_device, n_rows);
-    return ossid_launch_status();
-}
-
 int ossid_avgpool2_nhwc(const float* x, int B, int H, int W, int C, int stride, float* out, int backward, void* stream) {
     if (!x || !out || B <= 0 || H < 2 || W < 2 || C <= 0 || C % 4 || (stride != 1 && stride != 2)) return OSSID_EINVAL;
     const int Ho = (H - 2) / stride + 1, Wo = (W - 2) / stride + 1;
@@ -1662,11 +1507,6 @@ int ossid_upsample_nearest_bwd_nhwc(const float* dup, int B, int Hs, int Ws, int
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float4*)dup, Hs, Ws, H, W, C / 4, row_start, col_start, total, (float4*)dsrc);
     return ossid_launch_status();
-}
-
-int ossid_conv_pack_weights_dgrad(const float* w, int Cout, int Cin, int taps, float* wpk, void* stream) {
-    if (taps != 1 && taps != 9) return OSSID_EINVAL;
-    return ossid_conv_pack_weights_form(w, Cout, Cin, taps, 1, 0, wpk, stream);
 }
 
 // Weight gradients go to csrc/wgrad_fc.hip (the decoder's few-channel 3x3 layers) and csrc/wgrad_t9.hip (the dense blocks'

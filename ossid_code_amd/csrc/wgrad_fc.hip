@@ -19,11 +19,9 @@
 // four blocks against 1.64 ms for the split-bf16 grouped kernel of csrc/train.hip, tools/wgrad_group_bench.py: with 128 input
 // channels that kernel's staging is amortised over four column tiles per tap and the 3-product arithmetic wins.)
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct FcArgs {
     const float *x, *dy, *pre_scale, *pre_shift;

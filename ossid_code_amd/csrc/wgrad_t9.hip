@@ -18,12 +18,9 @@
 // Arithmetic: dy_lo * x_hi + dy_hi * x_lo + dy_hi * x_hi per product, f32 accumulation, as train.hip's split form. A
 // -DOSSID_WGRAD_F32 build does not use this file (ossid_wgrad_t9_takes returns false).
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef __bf16 v8bf16 __attribute__((ext_vector_type(8)));
-typedef short v4i16 __attribute__((ext_vector_type(4)));
 
 constexpr int T9_CIN = 128;                            // input channels of a job (a block of the layer's)
 constexpr int T9_TH = 4, T9_TW = 16, T9_PH = T9_TH + 2, T9_PW = T9_TW + 2;
@@ -102,18 +99,10 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
         }
     };
     auto split_store = [&](const float4& fv, char* hi_at, int part_stride) {
-        const float v[4] = {fv.x, fv.y, fv.z, fv.w};
-        union {
-            __bf16 b[4];
-            uint2 u;
-        } hi, lo;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            hi.b[i] = (__bf16)v[i];
-            lo.b[i] = (__bf16)(v[i] - (float)hi.b[i]);
-        }
-        *(uint2*)hi_at = hi.u;
-        *(uint2*)(hi_at + part_stride) = lo.u;
+        uint2 pc[2];
+        split_bf16({fv.x, fv.y, fv.z, fv.w}, pc);
+        *(uint2*)hi_at = pc[0];
+        *(uint2*)(hi_at + part_stride) = pc[1];
     };
     auto commit = [&](int tile) {
         const int tx = tile % A.tiles_x, r1 = tile / A.tiles_x;
@@ -152,7 +141,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
         const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(at + 4 * pitch));
         typedef short v8i16 __attribute__((ext_vector_type(8)));
         const v8i16 v = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(v8bf16, v);
+        return __builtin_bit_cast(v8bf, v);
     };
 
     if (wg < A.ntiles) fetch(wg);
@@ -163,7 +152,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
         if (tile + A.nwg < A.ntiles) fetch(tile + A.nwg);  // in flight under this tile's MFMAs
 #pragma unroll 1
         for (int r = 0; r < T9_TH; ++r) {
-            v8bf16 a_hi[TM], a_lo[TM];
+            v8bf a_hi[TM], a_lo[TM];
 #pragma unroll
             for (int m = 0; m < TM; ++m) {
                 a_hi[m] = tr8(a_base + (size_t)(r * T9_TW) * PD + m * 64, PD);
@@ -174,13 +163,11 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
                     const char* at = b_base + (size_t)((r + ky) * T9_PW + kx) * T9_PX;
-                    const v8bf16 b_hi = tr8(at, T9_PX), b_lo = tr8(at + T9_XIMG, T9_PX);
+                    const v8bf b_hi = tr8(at, T9_PX), b_lo = tr8(at + T9_XIMG, T9_PX);
                     const int t = ky * 3 + kx;
 #pragma unroll
                     for (int m = 0; m < TM; ++m) {
-                        acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo[m], b_hi, acc[m][t], 0, 0, 0);
-                        acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi[m], b_lo, acc[m][t], 0, 0, 0);
-                        acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi[m], b_hi, acc[m][t], 0, 0, 0);
+                        acc[m][t] = mfma3(a_hi[m], a_lo[m], b_hi, b_lo, acc[m][t]);
                     }
                 }
         }
@@ -306,18 +293,10 @@ __global__ __launch_bounds__(256, 1) void wgrad_t1_kernel(const T1Args A) {
         }
     };
     auto split_store = [&](const float4& fv, char* hi_at, int part_stride) {
-        const float v[4] = {fv.x, fv.y, fv.z, fv.w};
-        union {
-            __bf16 b[4];
-            uint2 u;
-        } hi, lo;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            hi.b[i] = (__bf16)v[i];
-            lo.b[i] = (__bf16)(v[i] - (float)hi.b[i]);
-        }
-        *(uint2*)hi_at = hi.u;
-        *(uint2*)(hi_at + part_stride) = lo.u;
+        uint2 pc[2];
+        split_bf16({fv.x, fv.y, fv.z, fv.w}, pc);
+        *(uint2*)hi_at = pc[0];
+        *(uint2*)(hi_at + part_stride) = pc[1];
     };
     auto commit = [&](int stage) {
         const long long p0 = (long long)stage * T1_PXS;
@@ -352,7 +331,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_t1_kernel(const T1Args A) {
         const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(at + 4 * pitch));
         typedef short v8i16 __attribute__((ext_vector_type(8)));
         const v8i16 v = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(v8bf16, v);
+        return __builtin_bit_cast(v8bf, v);
     };
 
     if (wg < A.nstages) fetch(wg);
@@ -363,16 +342,14 @@ __global__ __launch_bounds__(256, 1) void wgrad_t1_kernel(const T1Args A) {
         if (stage + A.nwg < A.nstages) fetch(stage + A.nwg);
 #pragma unroll 1
         for (int k = 0; k < T1_PXS / 16; ++k) {
-            const v8bf16 a_hi = tr8(a_base + (size_t)(16 * k) * T1_PD, T1_PD);
-            const v8bf16 a_lo = tr8(a_base + T1_DIMG + (size_t)(16 * k) * T1_PD, T1_PD);
+            const v8bf a_hi = tr8(a_base + (size_t)(16 * k) * T1_PD, T1_PD);
+            const v8bf a_lo = tr8(a_base + T1_DIMG + (size_t)(16 * k) * T1_PD, T1_PD);
 #pragma unroll
             for (int n = 0; n < 8; ++n) {
                 if (n < ntn) {
                     const char* at = b_base + (size_t)(16 * k) * T1_PXB + n * 64;
-                    const v8bf16 b_hi = tr8(at, T1_PXB), b_lo = tr8(at + T1_XIMG, T1_PXB);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_hi, acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_lo, acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_hi, acc[n], 0, 0, 0);
+                    const v8bf b_hi = tr8(at, T1_PXB), b_lo = tr8(at + T1_XIMG, T1_PXB);
+                    acc[n] = mfma3(a_hi, a_lo, b_hi, b_lo, acc[n]);
                 }
             }
         }

@@ -27,20 +27,13 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
 typedef int v4i32 __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));      // (vector arithmetic lowers to v_pk_add_f32 with neg modifiers)
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ v16f mfma(float a, float b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 
 struct WinoArgs {
     const float* x;
@@ -231,7 +224,7 @@ __device__ __forceinline__ void wino_conv_body(const WinoArgs& A, const int bloc
     // rows of B^T d for this half (loaded patch rows p, q, s = rows ih, ih+1, ih+2 of d), then the column transform
     auto transform_write = [&](int buf, int ci0) {
         stage_affine(ci0);
-        v4f* o = (v4f*)(vb + (size_t)buf * VBUF + (size_t)tl * F4 + j);
+        [[maybe_unused]] v4f* o = (v4f*)(vb + (size_t)buf * VBUF + (size_t)tl * F4 + j);      // (the exact-f32 branch's; declared inside it, the split build's instruction order changes)
         // a - b as fma(b, -1, a): exact, and one v_pk_fma_f32 per two floats where a plain subtraction is scalarised
         const v4f m1 = {-1.f, -1.f, -1.f, -1.f};
         auto sub = [&](v4f x, v4f y) { return __builtin_elementwise_fma(y, m1, x); };
@@ -370,9 +363,7 @@ __device__ __forceinline__ void wino_conv_body(const WinoArgs& A, const int bloc
             const v8bf vh = __builtin_bit_cast(v8bf, bh), vl = __builtin_bit_cast(v8bf, bl);
             const int en = e < 7 ? e + 1 : e;               // next position's operands are read under this one's MFMAs
             bh = pb[(size_t)en * 32 * F4 + sh], bl = pb[(size_t)en * 32 * F4 + sl];
-            acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo, vh, acc[e], 0, 0, 0);
-            acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, vl, acc[e], 0, 0, 0);
-            acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi, vh, acc[e], 0, 0, 0);
+            acc[e] = mfma3(ahi, alo, vh, vl, acc[e]);
             wq[e & 1][0] = W4[(size_t)unit_of(p0 + e + 2, 0) * 64 + lane];
             wq[e & 1][1] = W4[(size_t)unit_of(p0 + e + 2, 1) * 64 + lane];
             __builtin_amdgcn_sched_barrier(0);      // keep this order: the compiler would sink the loads to their use
@@ -564,15 +555,6 @@ __global__ __launch_bounds__(128 * CT) void wino_finish_pair_kernel(const WinoPa
     else wino_finish_body<CT>(G.b, v - G.n0, part, G.t.ks, blockIdx.y);
 }
 
-// U = G g G^T packed as the kernel streams it. dgrad != 0: the weights of the data gradient (the transposed layer:
-// output channels = the forward's inputs, filter rotated by 180 degrees), w stays the forward [Cout][Cin][3][3].
-__global__ __launch_bounds__(256) void wino_pack_kernel(const float* __restrict__ w, int Cout, int Cin, int dgrad,
-                                                        float4* __restrict__ wpk, size_t total) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    wpk[i] = ossid_wino_pack_quad(w, Cout, Cin, dgrad, i);
-}
-
 }  // namespace
 
 extern "C" {
@@ -583,18 +565,6 @@ int ossid_conv_wino_split_bf16(void) {
 #else
     return 1;
 #endif
-}
-
-size_t ossid_conv_wino_packed_floats(int Cout, int Cin) {
-    return (size_t)((Cout + 31) / 32) * (Cin / 8) * 16 * 64 * 4;
-}
-
-int ossid_conv_pack_weights_wino(const float* w, int Cout, int Cin, int dgrad, float* wpk, void* stream) {
-    if (!w || !wpk || Cout <= 0 || Cin <= 0 || (dgrad ? Cout : Cin) % 16) return OSSID_EINVAL;
-    const size_t total = (dgrad ? ossid_conv_wino_packed_floats(Cin, Cout) : ossid_conv_wino_packed_floats(Cout, Cin)) / 4;
-    hipLaunchKernelGGL(wino_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, Cout,
-                       Cin, dgrad, (float4*)wpk, total);
-    return ossid_launch_status();
 }
 
 static int wino_args(const ossid_conv_desc* d, WinoArgs& a, long& nwg) {

@@ -390,12 +390,6 @@ int ossid_zephyr_featurize(const float* rgbd, int H, int W, const float* transfo
 // workgroup into LDS for ADI (M^2 distance evaluations per hypothesis), sums by wave butterfly + LDS combine.
 namespace {
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __device__ __forceinline__ void xform(const double* __restrict__ T, double x, double y, double z, double& ox, double& oy,
                                       double& oz) {
     ox = T[0] * x + T[1] * y + T[2] * z + T[3];

@@ -179,23 +179,29 @@ def test_wino_pair_launch_equals_two_launches(T):
 
 
 def test_pack_table_winograd_rows_equal_the_standalone_pack(T):
-    """ossid_conv_pack_weights_table kinds 2 / 3 (the one-launch pack of a training step) write the same bytes as
-    ossid_conv_pack_weights_wino."""
+    """ossid_conv_pack_weights_table (the one-launch pack of a training step: a block finds its row by binary search, a
+    row starts at its block offset) writes the same bytes as the one-row launches behind ossid_conv_pack_weights_wino
+    (kinds 2 / 3) and ossid_conv_pack_weights_form (the direct kinds), zero padding of ragged channel tiles included."""
     class Conv:
         pass
+    wino, direct = ("wino_fwd", "wino_dgrad"), ("fwd", "dgrad", "fwd_exact", "dgrad_exact", "fwd_x6")
     g = torch.Generator().manual_seed(8)
-    convs = []
-    for cout, cin in ((64, 64), (96, 128)):      # both layouts exist for these (the plan skips layouts the step never asks for)
+    convs, kinds = [], {}
+    # every layout exists for these shapes (the plan skips layouts the step never asks for); 48 output channels (3x3) and 48
+    # input channels (1x1: the data gradient's output channels) leave the last 32-channel tile half empty
+    for cout, cin, k, ks in ((64, 64, 3, wino), (96, 128, 3, wino + direct), (48, 64, 3, direct), (64, 48, 1, direct)):
         c = Conv()
-        c.weight = (torch.randn(cout, cin, 3, 3, generator=g) * 0.1).cuda()
+        c.weight = (torch.randn(cout, cin, k, k, generator=g) * 0.1).cuda()
         convs.append(c)
-    want = {(i, k): T._pack(c.weight, k).clone() for i, c in enumerate(convs) for k in ("wino_fwd", "wino_dgrad")}
+        kinds[c] = ks
+    want = {(i, k): T._pack(c.weight, k).clone() for i, c in enumerate(convs) for k in kinds[c]}
     for c in convs:
-        for k in ("wino_fwd", "wino_dgrad"):
+        for k in kinds[c]:
             T._Packed.get(c.weight, k).zero_()
-    plan = T.PackPlan(convs, {c: ("wino_fwd", "wino_dgrad") for c in convs})
+    plan = T.PackPlan(convs, kinds)
     plan.run()
+    assert len(plan.keys) == len(want)
     for i, c in enumerate(convs):
-        for k in ("wino_fwd", "wino_dgrad"):
+        for k in kinds[c]:
             assert torch.equal(T._Packed.get(c.weight, k), want[(i, k)]), (i, k)
     T.end_step()
