@@ -840,6 +840,27 @@ int ossid_raster_depth(const float* vertices, int V, const int32_t* faces, int F
                        float fy, float cx, float cy, int H, int W, float pixel_offset, float z_near, void* workspace,
                        size_t workspace_bytes, float* depth_out, int32_t* stats, void* stream);
 
+/* 8f-3c  templates from a vertex-coloured mesh, in place of the offline Blender renders the reference cuts out in
+ * datasets/render_dataset.py:251-331 (processRenderGrid: mask -> square box padded 1.1x, image * mask, resized) and loads
+ * in datasets/template_dataset.py:60-117. SPEC.md 7.11-7.14 (csrc/raster.hip).
+ * ossid_raster_color: ossid_raster_depth's inputs plus colors u8 [V][3] (RGB) and one camera per pose, intrinsics
+ * f32 [N][4] = fx, fy, cx, cy. The workspace (16-byte aligned, ossid_raster_color_workspace_bytes(V, F, N, H, W) bytes,
+ * 0 = bad arguments) holds the projected vertices and one 64-bit visibility key per (pose, pixel):
+ * bits(z) << 32 | face index, reduced by a minimum -- the nearest depth and, among equal depths, the lowest index of
+ * `faces`. -> color_out u8 [N][H][W][3] (perspective-correct, unlit, 0 where nothing is drawn), depth_out f32 [N][H][W]
+ * (bit-equal to ossid_raster_depth's when all poses share one camera), face_id_out int32 [N][H][W] (may be NULL; the
+ * winner, -1 where nothing is drawn), stats as ossid_raster_depth. Three launches, nothing read back, capturable.
+ * ossid_template_reduce: the exact s x s box filter over such renders at S = s T: color u8 [N][S][S][3],
+ * depth f32 [N][S][S] -> img_out f32 [N][3][T][T] = ((sum of covered colours + s*s/2) / (s*s)) / 255 (integer division),
+ * mask_out f32 [N][1][T][T] = covered samples / (s*s). 1 <= s <= 8, 1 <= T <= 512, 1 <= N <= OSSID_RASTER_MAX_POSES. */
+size_t ossid_raster_color_workspace_bytes(int V, int F, int N, int H, int W);
+int ossid_raster_color(const float* vertices, int V, const int32_t* faces, int F, const uint8_t* colors,
+                       const float* transforms, int N, const float* intrinsics, int H, int W, float pixel_offset, float z_near,
+                       void* workspace, size_t workspace_bytes, uint8_t* color_out, float* depth_out, int32_t* face_id_out,
+                       int32_t* stats, void* stream);
+int ossid_template_reduce(const uint8_t* color, const float* depth, int N, int T, int s, float* img_out, float* mask_out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,9 @@ _PROTOS = {
     "ossid_ppf_refine_match": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _i, _i, _i, _f, _f, _vp, _sz, _vp, _vp]),
     "ossid_raster_workspace_bytes": (_sz, [_i, _i, _i]),
     "ossid_raster_depth": (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp]),
+    "ossid_raster_color_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ossid_raster_color": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ossid_template_reduce": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),

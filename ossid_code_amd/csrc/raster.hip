@@ -16,6 +16,12 @@
 //             only fall, so a sample that is already hidden costs no atomic, and a stale load only costs a useless one;
 //   resolve   +inf -> 0.
 // A minimum does not depend on the order of arrival: the image is bit-reproducible whatever the schedule.
+//
+// ossid_raster_color (SPEC 7.11-7.12; the template renders of datasets/render_dataset.py:251-331) runs the same vertex
+// stage and the same triangle walk over a visibility buffer: one 64-bit key (bits(z) << 32 | face index) per sample in
+// the workspace, so that the minimum is the nearest depth and, among equal depths, the lowest face index. Its resolve
+// redoes the winner's setup per pixel, recomputes the exact edge functions and interpolates the vertex colours
+// perspective-correctly. ossid_template_reduce (7.13) is the s x s box filter that makes a template of such a render.
 #include <limits.h>
 
 #include <cmath>
@@ -29,12 +35,30 @@ constexpr int TARGET_WAVES = 2048;    // 256 CUs x 8: below this many full waves
 constexpr int MAX_WAVES = 16;         // waves per workgroup that share the large boxes of a call with few triangles
 constexpr int RESIDENT_WAVES = 8192;  // 256 CUs x 32: extra waves per workgroup are added only while all stay resident
 constexpr unsigned ZFAR = 0x7f800000u;
+constexpr unsigned long long KFAR = ~0ull;   // empty visibility key: above every (bits(z) << 32 | face)
 
 struct __attribute__((aligned(16))) VRec {
     int sx, sy;      // snapped window coordinates (1/256 pixel); sx == INT_MIN: unusable vertex
     double rz;       // 1 / (double) Z
 };
 static_assert(sizeof(VRec) == 16, "vertex record");
+
+// SPEC 7.2 for vertex k under transform T (f32 [4][4] row-major) and one camera.
+__device__ __forceinline__ VRec project_vertex(const float* __restrict__ vertices, int k, const float* __restrict__ T, float fx,
+                                               float fy, float cx, float cy, float z_near) {
+    const float x = vertices[3 * (size_t)k], y = vertices[3 * (size_t)k + 1], z = vertices[3 * (size_t)k + 2];
+    const float X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+    const float Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+    const float Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    const float u = (X / Z) * fx + cx, v = (Y / Z) * fy + cy;
+    const bool ok = (Z > z_near) && isfinite(X) && isfinite(Y) && isfinite(Z) && (fabsf(u) < 1048576.0f) &&
+                    (fabsf(v) < 1048576.0f);      // NaN u, v fail the comparisons
+    VRec r;
+    r.sx = ok ? (int)rintf(u * 256.0f) : INT_MIN;
+    r.sy = ok ? (int)rintf(v * 256.0f) : 0;
+    r.rz = ok ? 1.0 / (double)Z : 0.0;
+    return r;
+}
 
 __global__ __launch_bounds__(256) void raster_prepare_kernel(const float* __restrict__ vertices, int V,
                                                              const float* __restrict__ transforms, int N, float fx, float fy,
@@ -47,19 +71,24 @@ __global__ __launch_bounds__(256) void raster_prepare_kernel(const float* __rest
     const size_t nv = (size_t)N * V;
     for (size_t i = tid; i < nv; i += nthreads) {
         const int pose = (int)(i / V), k = (int)(i - (size_t)pose * V);
-        const float* T = transforms + 16 * (size_t)pose;
-        const float x = vertices[3 * (size_t)k], y = vertices[3 * (size_t)k + 1], z = vertices[3 * (size_t)k + 2];
-        const float X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-        const float Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-        const float Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-        const float u = (X / Z) * fx + cx, v = (Y / Z) * fy + cy;
-        const bool ok = (Z > z_near) && isfinite(X) && isfinite(Y) && isfinite(Z) && (fabsf(u) < 1048576.0f) &&
-                        (fabsf(v) < 1048576.0f);      // NaN u, v fail the comparisons
-        VRec r;
-        r.sx = ok ? (int)rintf(u * 256.0f) : INT_MIN;
-        r.sy = ok ? (int)rintf(v * 256.0f) : 0;
-        r.rz = ok ? 1.0 / (double)Z : 0.0;
-        rec[i] = r;
+        rec[i] = project_vertex(vertices, k, transforms + 16 * (size_t)pose, fx, fy, cx, cy, z_near);
+    }
+}
+
+// The same with one camera per pose (intrinsics f32 [N][4] = fx, fy, cx, cy) and the visibility buffer cleared to KFAR.
+__global__ __launch_bounds__(256) void raster_prepare_color_kernel(const float* __restrict__ vertices, int V,
+                                                                   const float* __restrict__ transforms, int N,
+                                                                   const float* __restrict__ intrinsics, float z_near,
+                                                                   VRec* __restrict__ rec, unsigned long long* __restrict__ keys,
+                                                                   size_t npix, int32_t* __restrict__ stats) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nthreads = (size_t)gridDim.x * 256;
+    for (size_t i = tid; i < npix; i += nthreads) keys[i] = KFAR;
+    if (stats && tid < (size_t)4 * N) stats[tid] = 0;
+    const size_t nv = (size_t)N * V;
+    for (size_t i = tid; i < nv; i += nthreads) {
+        const int pose = (int)(i / V), k = (int)(i - (size_t)pose * V);
+        const float* c = intrinsics + 4 * (size_t)pose;
+        rec[i] = project_vertex(vertices, k, transforms + 16 * (size_t)pose, c[0], c[1], c[2], c[3], z_near);
     }
 }
 
@@ -78,8 +107,10 @@ __device__ __forceinline__ bool edge_in(int ax, int ay, int bx, int by, int px, 
     return e > 0 || (e == 0 && (dy > 0 || (dy == 0 && dx < 0)));
 }
 
-// Sample of pixel (x, y): coverage, perspective-correct depth, z-buffer update. Returns whether it was covered.
-__device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, int o, int W, unsigned* __restrict__ zb) {
+// Sample of pixel (x, y): coverage, perspective-correct depth, buffer update. Returns whether it was covered. ZB is
+// unsigned (z-buffer: the float's bits) or unsigned long long (visibility buffer: bits << 32 | face, SPEC 7.11).
+template <typename ZB>
+__device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, int o, int W, ZB* __restrict__ zb, unsigned face) {
     const int px = 256 * x + o, py = 256 * y + o;
     long long w0, w1, w2;
     const bool in2 = edge_in(t.x0, t.y0, t.x1, t.y1, px, py, w2);
@@ -88,14 +119,21 @@ __device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, i
     if (!(in0 && in1 && in2)) return false;
     const double den = ((double)w0 * t.r0 + (double)w1 * t.r1) + (double)w2 * t.r2;
     const unsigned zbits = __float_as_uint((float)(area / den));
-    unsigned* p = zb + (size_t)y * W + x;
-    if (zbits < *p) atomicMin(p, zbits);
+    ZB* p = zb + (size_t)y * W + x;
+    if constexpr (sizeof(ZB) == 4) {
+        if (zbits < *p) atomicMin(p, zbits);
+    } else {
+        // one 8-byte load (never two halves of different keys); keys only fall, so a stale one costs a useless atomic
+        const unsigned long long key = ((unsigned long long)zbits << 32) | face;
+        if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
+    }
     return true;
 }
 
+template <typename ZB>
 __global__ __launch_bounds__(64 * MAX_WAVES) void raster_tri_kernel(const int32_t* __restrict__ faces, int F, int V,
                                                         const VRec* __restrict__ rec, int H, int W, int o, int tpw,
-                                                        unsigned* __restrict__ zbuf, int32_t* __restrict__ stats) {
+                                                        ZB* __restrict__ zbuf, int32_t* __restrict__ stats) {
     // every wave of the workgroup sets up the same tpw triangles; wave 0 walks the small boxes and keeps the statistics,
     // all waves share the large boxes
     const int pose = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -106,7 +144,7 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void raster_tri_kernel(const int32_
     }
     const long long tri = (long long)blockIdx.x * tpw + lane;
     const VRec* vr = rec + (size_t)pose * V;
-    unsigned* zb = zbuf + (size_t)pose * H * W;
+    ZB* zb = zbuf + (size_t)pose * H * W;
     Tri t = {};
     long long A = 0;
     int n_bad = 0, n_degen = 0, n_cov = 0, n_large = 0;
@@ -144,7 +182,7 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void raster_tri_kernel(const int32_
                     } else if (wv == 0) {
                         bool cov = false;
                         for (int y = t.ya; y <= t.yb; ++y)
-                            for (int x = t.xa; x <= t.xb; ++x) cov |= shade(t, (double)A, x, y, o, W, zb);
+                            for (int x = t.xa; x <= t.xb; ++x) cov |= shade(t, (double)A, x, y, o, W, zb, (unsigned)tri);
                         n_cov = cov;
                     }
                 }
@@ -163,11 +201,12 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void raster_tri_kernel(const int32_
         s.r0 = __shfl(t.r0, src), s.r1 = __shfl(t.r1, src), s.r2 = __shfl(t.r2, src);
         s.xa = __shfl(t.xa, src), s.ya = __shfl(t.ya, src), s.xb = __shfl(t.xb, src), s.yb = __shfl(t.yb, src);
         const double area = (double)__shfl(A, src);
+        const unsigned face = (unsigned)(blockIdx.x * tpw + src);
         bool cov = false;
         for (int y0 = s.ya + 8 * wv; y0 <= s.yb; y0 += 8 * nw)
             for (int x0 = s.xa; x0 <= s.xb; x0 += 8) {
                 const int x = x0 + lx, y = y0 + ly;
-                if (x <= s.xb && y <= s.yb) cov |= shade(s, area, x, y, o, W, zb);
+                if (x <= s.xb && y <= s.yb) cov |= shade(s, area, x, y, o, W, zb, face);
             }
         if (__ballot(cov) != 0ull && lane == src) n_cov = 1;
     }
@@ -193,9 +232,100 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(unsigned* __restric
         if (zbuf[i] == ZFAR) zbuf[i] = 0u;
 }
 
+// SPEC 7.11-7.12, one thread per (pose, pixel): the winner's setup again (three records, area, the A < 0 swap -- the
+// colours swap with the vertices), the exact edge functions at the sample, colour in f64 with the written parenthesisation.
+__global__ __launch_bounds__(256) void raster_resolve_color_kernel(const unsigned long long* __restrict__ keys,
+                                                                   const int32_t* __restrict__ faces, int V,
+                                                                   const VRec* __restrict__ rec,
+                                                                   const unsigned char* __restrict__ colors, int H, int W, int o,
+                                                                   size_t npix, unsigned char* __restrict__ color_out,
+                                                                   float* __restrict__ depth_out, int32_t* __restrict__ face_out) {
+    const size_t hw = (size_t)H * W;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
+        const unsigned long long key = keys[i];
+        float z = 0.0f;
+        int face = -1, c[3] = {0, 0, 0};
+        if (key != KFAR) {
+            const int pose = (int)(i / hw);
+            const int pix = (int)(i - (size_t)pose * hw), y = pix / W, x = pix - y * W;
+            face = (int)(unsigned)key;                   // written by a usable triangle: its indices lie in [0, V)
+            z = __uint_as_float((unsigned)(key >> 32));
+            const VRec* vr = rec + (size_t)pose * V;
+            int i0 = faces[3 * (size_t)face], i1 = faces[3 * (size_t)face + 1], i2 = faces[3 * (size_t)face + 2];
+            VRec a = vr[i0], b = vr[i1], d = vr[i2];
+            const long long A = (long long)(b.sx - a.sx) * (long long)(d.sy - a.sy) - (long long)(b.sy - a.sy) * (long long)(d.sx - a.sx);
+            if (A < 0) {
+                const VRec s = b;
+                b = d, d = s;
+                const int j = i1;
+                i1 = i2, i2 = j;
+            }
+            const int px = 256 * x + o, py = 256 * y + o;
+            long long w0, w1, w2;
+            edge_in(a.sx, a.sy, b.sx, b.sy, px, py, w2);
+            edge_in(b.sx, b.sy, d.sx, d.sy, px, py, w0);
+            edge_in(d.sx, d.sy, a.sx, a.sy, px, py, w1);
+            const double b0 = (double)w0 * a.rz, b1 = (double)w1 * b.rz, b2 = (double)w2 * d.rz;
+            const double den = (b0 + b1) + b2;
+            const unsigned char *c0 = colors + 3 * (size_t)i0, *c1 = colors + 3 * (size_t)i1, *c2 = colors + 3 * (size_t)i2;
+            for (int ch = 0; ch < 3; ++ch) {
+                const double v = ((b0 * (double)c0[ch] + b1 * (double)c1[ch]) + b2 * (double)c2[ch]) / den;
+                c[ch] = min(255, max(0, (int)rint(v)));
+            }
+        }
+        depth_out[i] = z;
+        color_out[3 * i] = (unsigned char)c[0], color_out[3 * i + 1] = (unsigned char)c[1], color_out[3 * i + 2] = (unsigned char)c[2];
+        if (face_out) face_out[i] = face;
+    }
+}
+
+// SPEC 7.13, one thread per output pixel: the s x s box over a supersampled render, uncovered samples count as 0.
+__global__ __launch_bounds__(256) void template_reduce_kernel(const unsigned char* __restrict__ color,
+                                                              const float* __restrict__ depth, int N, int T, int s,
+                                                              float* __restrict__ img_out, float* __restrict__ mask_out) {
+    const size_t nout = (size_t)N * T * T;
+    const int S = s * T, s2 = s * s;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nout; i += (size_t)gridDim.x * 256) {
+        const int n = (int)(i / ((size_t)T * T));
+        const int pix = (int)(i - (size_t)n * T * T), y = pix / T, x = pix - y * T;
+        int sum[3] = {0, 0, 0}, cnt = 0;
+        for (int dy = 0; dy < s; ++dy) {
+            const size_t row = ((size_t)n * S + (size_t)(y * s + dy)) * S + (size_t)x * s;
+            for (int dx = 0; dx < s; ++dx)
+                if (depth[row + dx] > 0.0f) {
+                    const unsigned char* c = color + 3 * (row + dx);
+                    sum[0] += c[0], sum[1] += c[1], sum[2] += c[2], ++cnt;
+                }
+        }
+        for (int ch = 0; ch < 3; ++ch)
+            img_out[((size_t)n * 3 + ch) * T * T + pix] = (float)((sum[ch] + s2 / 2) / s2) / 255.0f;
+        mask_out[i] = (float)cnt / (float)s2;
+    }
+}
+
 bool sizes_ok(int V, int F, int N) {
     return V >= 1 && V <= OSSID_RASTER_MAX_VERTICES && F >= 0 && F <= OSSID_RASTER_MAX_FACES && N >= 1 &&
            N <= OSSID_RASTER_MAX_POSES;
+}
+
+bool frame_ok(int H, int W, float pixel_offset, float z_near) {
+    return H > 0 && W > 0 && (long long)H * W <= OSSID_RASTER_MAX_PIXELS && pixel_offset >= 0.0f && pixel_offset <= 1.0f &&
+           z_near >= 0.0f && std::isfinite(z_near);
+}
+
+int grid_for(size_t work) { return (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192); }
+
+template <typename ZB>
+void launch_triangles(const int32_t* faces, int F, int V, int N, const VRec* rec, int H, int W, int o, ZB* zbuf, int32_t* stats,
+                      hipStream_t s) {
+    long long tpw = ((long long)F * N + TARGET_WAVES - 1) / TARGET_WAVES;
+    tpw = tpw < 1 ? 1 : (tpw > 64 ? 64 : tpw);
+    const long long groups = (F + tpw - 1) / tpw;
+    // more waves per workgroup only once each wave is down to one triangle: every wave repeats the setup
+    long long nw = tpw == 1 ? RESIDENT_WAVES / (groups * N) : 1;
+    nw = nw < 1 ? 1 : (nw > MAX_WAVES ? MAX_WAVES : nw);
+    hipLaunchKernelGGL(raster_tri_kernel<ZB>, dim3((unsigned)groups, N), dim3(64 * (unsigned)nw), 0, s, faces, F, V, rec, H, W, o,
+                       (int)tpw, zbuf, stats);
 }
 
 }  // namespace
@@ -212,30 +342,53 @@ int ossid_raster_depth(const float* vertices, int V, const int32_t* faces, int F
                        size_t workspace_bytes, float* depth_out, int32_t* stats, void* stream) {
     const size_t need = ossid_raster_workspace_bytes(V, F, N);
     if (need == 0 || !vertices || (F > 0 && !faces) || !transforms || !workspace || workspace_bytes < need || !depth_out ||
-        H <= 0 || W <= 0 || (long long)H * W > OSSID_RASTER_MAX_PIXELS || ((uintptr_t)workspace & 15) != 0 ||
-        !(pixel_offset >= 0.0f && pixel_offset <= 1.0f) || !(z_near >= 0.0f) || !std::isfinite(z_near))
+        ((uintptr_t)workspace & 15) != 0 || !frame_ok(H, W, pixel_offset, z_near))
         return OSSID_EINVAL;
     const int o = (int)std::nearbyint((double)pixel_offset * 256.0);       // round half to even
     const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
     hipStream_t s = (hipStream_t)stream;
     VRec* rec = (VRec*)workspace;
     unsigned* zbuf = (unsigned*)depth_out;
-    size_t work = npix > nv ? npix : nv;
-    int blocks = (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192);
-    hipLaunchKernelGGL(raster_prepare_kernel, dim3(blocks), dim3(256), 0, s, vertices, V, transforms, N, fx, fy, cx, cy, z_near,
-                       rec, zbuf, npix, stats);
-    if (F > 0) {
-        long long tpw = ((long long)F * N + TARGET_WAVES - 1) / TARGET_WAVES;
-        tpw = tpw < 1 ? 1 : (tpw > 64 ? 64 : tpw);
-        const long long groups = (F + tpw - 1) / tpw;
-        // more waves per workgroup only once each wave is down to one triangle: every wave repeats the setup
-        long long nw = tpw == 1 ? RESIDENT_WAVES / (groups * N) : 1;
-        nw = nw < 1 ? 1 : (nw > MAX_WAVES ? MAX_WAVES : nw);
-        hipLaunchKernelGGL(raster_tri_kernel, dim3((unsigned)groups, N), dim3(64 * (unsigned)nw), 0, s, faces, F, V, rec, H, W, o,
-                           (int)tpw, zbuf, stats);
-    }
-    blocks = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
-    hipLaunchKernelGGL(raster_resolve_kernel, dim3(blocks), dim3(256), 0, s, zbuf, npix);
+    hipLaunchKernelGGL(raster_prepare_kernel, dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0, s, vertices, V, transforms, N,
+                       fx, fy, cx, cy, z_near, rec, zbuf, npix, stats);
+    if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, zbuf, stats, s);
+    hipLaunchKernelGGL(raster_resolve_kernel, dim3(grid_for(npix)), dim3(256), 0, s, zbuf, npix);
+    return ossid_launch_status();
+}
+
+size_t ossid_raster_color_workspace_bytes(int V, int F, int N, int H, int W) {
+    if (!sizes_ok(V, F, N) || H <= 0 || W <= 0 || (long long)H * W > OSSID_RASTER_MAX_PIXELS) return 0;
+    return (size_t)N * (size_t)V * sizeof(VRec) + (size_t)N * (size_t)H * (size_t)W * sizeof(unsigned long long);
+}
+
+int ossid_raster_color(const float* vertices, int V, const int32_t* faces, int F, const uint8_t* colors,
+                       const float* transforms, int N, const float* intrinsics, int H, int W, float pixel_offset, float z_near,
+                       void* workspace, size_t workspace_bytes, uint8_t* color_out, float* depth_out, int32_t* face_id_out,
+                       int32_t* stats, void* stream) {
+    const size_t need = ossid_raster_color_workspace_bytes(V, F, N, H, W);
+    if (need == 0 || !vertices || (F > 0 && !faces) || !colors || !transforms || !intrinsics || !workspace ||
+        workspace_bytes < need || !color_out || !depth_out || ((uintptr_t)workspace & 15) != 0 ||
+        !frame_ok(H, W, pixel_offset, z_near))
+        return OSSID_EINVAL;
+    const int o = (int)std::nearbyint((double)pixel_offset * 256.0);
+    const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
+    hipStream_t s = (hipStream_t)stream;
+    VRec* rec = (VRec*)workspace;
+    unsigned long long* keys = (unsigned long long*)((char*)workspace + nv * sizeof(VRec));
+    hipLaunchKernelGGL(raster_prepare_color_kernel, dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0, s, vertices, V,
+                       transforms, N, intrinsics, z_near, rec, keys, npix, stats);
+    if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, keys, stats, s);
+    hipLaunchKernelGGL(raster_resolve_color_kernel, dim3(grid_for(npix)), dim3(256), 0, s, keys, faces, V, rec, colors, H, W, o,
+                       npix, color_out, depth_out, face_id_out);
+    return ossid_launch_status();
+}
+
+int ossid_template_reduce(const uint8_t* color, const float* depth, int N, int T, int s, float* img_out, float* mask_out,
+                          void* stream) {
+    if (!color || !depth || !img_out || !mask_out || N < 1 || N > OSSID_RASTER_MAX_POSES || T < 1 || T > 512 || s < 1 || s > 8)
+        return OSSID_EINVAL;
+    hipLaunchKernelGGL(template_reduce_kernel, dim3(grid_for((size_t)N * T * T)), dim3(256), 0, (hipStream_t)stream, color, depth,
+                       N, T, s, img_out, mask_out);
     return ossid_launch_status();
 }
 

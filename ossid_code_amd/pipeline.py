@@ -221,7 +221,7 @@ class TemplateBank:
 
     def __init__(self, n_local_test=160, sample_from=10):
         self.n_local_test, self.sample_from = int(n_local_test), int(sample_from)
-        self.img, self.mask, self.quats = {}, {}, {}
+        self.img, self.mask, self.quats, self.template_z = {}, {}, {}, {}
 
     def add(self, obj_id, imgs, masks, grid_quats=None):
         dev = _dev()
@@ -234,6 +234,16 @@ class TemplateBank:
         self.mask[obj_id] = (m if m.dim() == 4 else m[:, None]).contiguous()
         if grid_quats is not None:
             self.quats[obj_id] = np.asarray(grid_quats, dtype=np.float64)
+
+    def add_mesh(self, obj_id, mesh, **render_templates_kwargs):
+        """The object's templates rendered from its vertex-coloured mesh (render.render_templates, SPEC 7.13-7.14; the
+        keyword arguments are its own, cam_K is required): fills img / mask / quats, keeps template_z [n] (the value
+        forwardTestTime's z filter takes per view), returns render_templates' info."""
+        from .render import render_templates
+        img, mask, info = render_templates(mesh, **render_templates_kwargs)
+        self.add(obj_id, img, mask, info["quats"])
+        self.template_z[obj_id] = np.asarray(info["template_z"], dtype=np.float64)
+        return info
 
     def view(self, obj_id, view_id):
         return self.img[obj_id][int(view_id)], self.mask[obj_id][int(view_id)]

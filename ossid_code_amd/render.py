@@ -8,6 +8,10 @@ OpenGL rasterisation that scripts/online_learning.py reaches through zephyr.util
 
 Renderer is the drop-in (host arrays out); render_depth is the device form that OnlineStream uses: a batch of poses in,
 a device tensor out, three launches on the current stream and no host copy or synchronisation.
+
+render_color is the same rasteriser with vertex colours (SPEC 7.11-7.12), and render_templates makes the detector's
+templates out of it (SPEC 7.13-7.14): what the reference renders offline with Blender, cuts out in
+datasets/render_dataset.py:251-331 and loads in datasets/template_dataset.py:60-117. view_grid is the set of viewpoints.
 """
 import numpy as np
 import torch
@@ -21,10 +25,11 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def read_ply_mesh(path):
+def read_ply_mesh(path, with_colors=False):
     """BOP-style PLY (ASCII or binary little-endian) -> (vertices f64 [V,3], faces int32 [F,3]). Faces come from the face
     element's list property vertex_indices (or vertex_index); polygons with more than three vertices are
-    fan-triangulated (0, i, i+1). Normals are not required."""
+    fan-triangulated (0, i, i+1). Normals are not required. with_colors=True also returns the vertex colours, u8 [V,3],
+    from the properties red green blue (or diffuse_red diffuse_green diffuse_blue)."""
     vert, lists = _ply_walk(path, lists_of="face")
     if vert is None:
         raise ValueError("%s: no vertex element" % path)
@@ -45,7 +50,16 @@ def read_ply_mesh(path):
             raise ValueError("%s: face %d has a vertex index outside [0, %d)" % (path, k, len(V)))
         for i in range(1, len(r) - 1):
             tris.append((r[0], r[i], r[i + 1]))
-    return V, np.asarray(tris, dtype=np.int32).reshape(-1, 3)
+    F = np.asarray(tris, dtype=np.int32).reshape(-1, 3)
+    if not with_colors:
+        return V, F
+    for names in (("red", "green", "blue"), ("diffuse_red", "diffuse_green", "diffuse_blue")):
+        if all(k in vert for k in names):
+            C = np.stack([vert[k] for k in names], 1).reshape(-1, 3)
+            if C.min(initial=0.0) < 0.0 or C.max(initial=0.0) > 255.0 or np.any(C != np.rint(C)):
+                raise ValueError("%s: vertex colours must be integers in [0, 255]" % path)
+            return V, F, C.astype(np.uint8)
+    raise ValueError("%s: the vertex element has no red green blue (or diffuse_red ...) properties" % path)
 
 
 def _check_mesh(vertices, faces):
@@ -65,18 +79,38 @@ def _check_mesh(vertices, faces):
     return V, np.ascontiguousarray(F, dtype=np.int32)
 
 
-class Mesh:
-    """A triangle mesh resident on the device: vertices f32(v * scale) (the product in float64), faces int32, and the
-    rasteriser's workspace, grown on demand. scale = 0.001 is the Renderer's mm2m."""
+def _check_colors(colors, n_vertices):
+    """u8 [V,3], or floats in [0, 1] -> rint(255 c)."""
+    C = np.asarray(colors)
+    if C.shape != (n_vertices, 3):
+        raise ValueError("colors must be [V,3] = [%d,3], got %s" % (n_vertices, C.shape))
+    if C.dtype == np.uint8:
+        return np.ascontiguousarray(C)
+    if not np.issubdtype(C.dtype, np.floating):
+        raise ValueError("colors must be uint8 or floats in [0, 1], got %s" % C.dtype)
+    C = C.astype(np.float64)
+    if not (np.isfinite(C).all() and C.min(initial=0.0) >= 0.0 and C.max(initial=0.0) <= 1.0):
+        raise ValueError("float colors must lie in [0, 1]")
+    return np.rint(255.0 * C).astype(np.uint8)
 
-    def __init__(self, vertices, faces, scale=1.0, device=None):
+
+class Mesh:
+    """A triangle mesh resident on the device: vertices f32(v * scale) (the product in float64), faces int32, optional
+    vertex colours u8 [V,3], and the rasteriser's workspaces, grown on demand. scale = 0.001 is the Renderer's mm2m."""
+
+    colors = None
+    _ws = _ws_color = None
+
+    def __init__(self, vertices, faces, scale=1.0, device=None, colors=None):
         V, F = _check_mesh(vertices, faces)
+        C = None if colors is None else _check_colors(colors, len(V))
         self.scale = float(scale)
         self.n_vertices, self.n_faces = len(V), len(F)
         self.device = torch.device(device) if device is not None else _dev()
         self.vertices = torch.from_numpy((V * self.scale).astype(np.float32)).to(self.device).contiguous()
         self.faces = torch.from_numpy(F).to(self.device).contiguous()
-        self._ws = None
+        self.colors = None if C is None else torch.from_numpy(C).to(self.device).contiguous()
+        self._ws = self._ws_color = None
 
     def workspace(self, n_poses):
         need = int(_lib.fn("ossid_raster_workspace_bytes")(self.n_vertices, self.n_faces, int(n_poses)))
@@ -86,6 +120,16 @@ class Mesh:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def color_workspace(self, n_poses, H, W):
+        need = int(_lib.fn("ossid_raster_color_workspace_bytes")(self.n_vertices, self.n_faces, int(n_poses), H, W))
+        if need == 0:
+            raise ValueError("mesh rendering: bad sizes (V %d, F %d, N %d, frame %d x %d)"
+                             % (self.n_vertices, self.n_faces, n_poses, H, W))
+        if self._ws_color is None or self._ws_color.numel() < need:
+            self._ws_color = None                     # 8 bytes per sample: let go of the old one before asking for more
+            self._ws_color = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws_color
+
 
 def _intrinsics(cam_K):
     K = np.asarray(cam_K, dtype=np.float64)
@@ -94,10 +138,8 @@ def _intrinsics(cam_K):
     return tuple(float(np.float32(v)) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
 
 
-def render_depth(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, return_stats=False):
-    """Depth (camera-space Z in the mesh's scaled units, 0 = nothing drawn) of `mesh` at every pose: poses [4,4] or
-    [N,4,4] (numpy, or a tensor on any device) -> f32 device tensor [H,W] or [N,H,W]; with return_stats also the int32
-    device tensor [N,4] ([4]) of SPEC 7's statistics. Nothing is copied to the host and nothing waits for the device."""
+def _check_call(what, poses, hw, pixel_offset, z_near):
+    """The argument checks shared by render_depth and render_color -> (poses as a tensor, single, N, H, W)."""
     T = poses if torch.is_tensor(poses) else torch.from_numpy(np.asarray(poses, dtype=np.float64))
     if T.dim() not in (2, 3) or tuple(T.shape[-2:]) != (4, 4):
         raise ValueError("poses must be [4,4] or [N,4,4], got %s" % (tuple(T.shape),))
@@ -105,13 +147,21 @@ def render_depth(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, return_s
     N = 1 if single else int(T.shape[0])
     H, W = int(hw[0]), int(hw[1])
     if not 1 <= N <= _lib.RASTER_MAX_POSES:
-        raise ValueError("render_depth takes 1 to %d poses, got %d" % (_lib.RASTER_MAX_POSES, N))
+        raise ValueError("%s takes 1 to %d poses, got %d" % (what, _lib.RASTER_MAX_POSES, N))
     if H <= 0 or W <= 0 or H * W > _lib.RASTER_MAX_PIXELS:
-        raise ValueError("render_depth: frame %d x %d is outside (0, %d] pixels" % (H, W, _lib.RASTER_MAX_PIXELS))
+        raise ValueError("%s: frame %d x %d is outside (0, %d] pixels" % (what, H, W, _lib.RASTER_MAX_PIXELS))
     if not 0.0 <= float(pixel_offset) <= 1.0:
         raise ValueError("pixel_offset must lie in [0, 1], got %r" % (pixel_offset,))
     if not (float(z_near) >= 0.0 and np.isfinite(z_near)):
         raise ValueError("z_near must be finite and >= 0, got %r" % (z_near,))
+    return T, single, N, H, W
+
+
+def render_depth(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, return_stats=False):
+    """Depth (camera-space Z in the mesh's scaled units, 0 = nothing drawn) of `mesh` at every pose: poses [4,4] or
+    [N,4,4] (numpy, or a tensor on any device) -> f32 device tensor [H,W] or [N,H,W]; with return_stats also the int32
+    device tensor [N,4] ([4]) of SPEC 7's statistics. Nothing is copied to the host and nothing waits for the device."""
+    T, single, N, H, W = _check_call("render_depth", poses, hw, pixel_offset, z_near)
     fx, fy, cx, cy = _intrinsics(cam_K)
     dev = mesh.device
     T = T.to(dev, torch.float32).reshape(N, 4, 4).contiguous()
@@ -128,6 +178,184 @@ def render_depth(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, return_s
     if single:
         depth, stats = depth[0], (None if stats is None else stats[0])
     return (depth, stats) if return_stats else depth
+
+
+def render_color(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, intrinsics=None, return_face_id=False,
+                 return_stats=False):
+    """Colour and depth of a vertex-coloured `mesh` at every pose (SPEC 7.11-7.12): poses as render_depth ->
+    device tensors (color u8 [N,H,W,3], depth f32 [N,H,W][, face_id int32 [N,H,W]][, stats int32 [N,4]]); a single [4,4]
+    pose drops the leading axis. Colours are interpolated perspective-correctly and unlit; face_id is the index in the
+    mesh's faces of the triangle seen, -1 where nothing is drawn. `intrinsics` [N,4] (fx, fy, cx, cy per pose) replaces
+    cam_K, which may then be None. The depth equals render_depth's bit for bit. Nothing is copied to the host."""
+    if getattr(mesh, "colors", None) is None:
+        raise ValueError("render_color: the mesh has no vertex colours (Mesh(..., colors=...), "
+                         "read_ply_mesh(path, with_colors=True))")
+    T, single, N, H, W = _check_call("render_color", poses, hw, pixel_offset, z_near)
+    dev = mesh.device
+    if intrinsics is None:
+        key = _intrinsics(cam_K) + (N,)
+        if getattr(mesh, "_cams", (None, None))[0] != key:        # kept: a repeated call uploads nothing (capturable)
+            mesh._cams = (key, torch.from_numpy(np.tile(np.asarray(key[:4], dtype=np.float32), (N, 1))).to(dev))
+        cams = mesh._cams[1]
+    elif torch.is_tensor(intrinsics) and intrinsics.is_cuda:
+        # a device tensor is used as it is and not read back; non-finite values make the pose's vertices unusable (7.2)
+        if tuple(intrinsics.shape) != (N, 4):
+            raise ValueError("intrinsics must be [N,4] = [%d,4] (fx, fy, cx, cy per pose), got %s" % (N, tuple(intrinsics.shape)))
+        cams = intrinsics.to(dev, torch.float32).contiguous()
+    else:
+        cams = intrinsics.numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics)
+        if cams.shape != (N, 4):
+            raise ValueError("intrinsics must be [N,4] = [%d,4] (fx, fy, cx, cy per pose), got %s" % (N, cams.shape))
+        cams = np.ascontiguousarray(cams, dtype=np.float32)
+        if not np.isfinite(cams).all():
+            raise ValueError("intrinsics must be finite")
+        cams = torch.from_numpy(cams).to(dev)
+    T = T.to(dev, torch.float32).reshape(N, 4, 4).contiguous()
+    ws = mesh.color_workspace(N, H, W)
+    color = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+    depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+    face = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_face_id else None
+    stats = torch.empty(N, 4, dtype=torch.int32, device=dev) if return_stats else None
+    with _lib.on_device(dev):
+        rc = _lib.fn("ossid_raster_color")(mesh.vertices.data_ptr(), mesh.n_vertices,
+                                           mesh.faces.data_ptr() if mesh.n_faces else None, mesh.n_faces,
+                                           mesh.colors.data_ptr(), T.data_ptr(), N, cams.data_ptr(), H, W, float(pixel_offset),
+                                           float(z_near), ws.data_ptr(), ws.numel(), color.data_ptr(), depth.data_ptr(),
+                                           None if face is None else face.data_ptr(),
+                                           None if stats is None else stats.data_ptr(), _lib.stream())
+    _lib.check(rc, "ossid_raster_color")
+    out = [color, depth] + ([face] if return_face_id else []) + ([stats] if return_stats else [])
+    return tuple(t[0] for t in out) if single else tuple(out)
+
+
+# ---- templates from a mesh (SPEC 7.13-7.14) ------------------------------------------------------------------------------
+def _icosphere_vertices(level):
+    """Unit icosphere vertices in SPEC 7.14's order: the 12 of the icosahedron, then per subdivision the midpoints in
+    the order the faces (and within a face the edges ab, bc, ca) first need them."""
+    g = (1.0 + np.sqrt(5.0)) / 2.0
+    verts = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1),
+             (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    verts = [np.asarray(v, dtype=np.float64) / np.sqrt(1.0 + g * g) for v in verts]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+             (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7),
+             (9, 8, 1)]
+    for _ in range(level):
+        middle, nxt = {}, []
+        for a, b, c in faces:
+            m = []
+            for i, j in ((a, b), (b, c), (c, a)):
+                key = (min(i, j), max(i, j))
+                if key not in middle:
+                    p = verts[i] + verts[j]
+                    verts.append(p / np.sqrt(p @ p))
+                    middle[key] = len(verts) - 1
+                m.append(middle[key])
+            ab, bc, ca = m
+            nxt.extend(((a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)))
+        faces = nxt
+    return np.stack(verts)
+
+
+def view_grid(level=2, inplane=1):
+    """Object-to-camera rotations of the template viewpoints -> f64 [n_vertices * inplane, 3, 3]: cameras on the
+    vertices p of an icosphere of subdivision `level` (12, 42, 162, 642 of them) looking at the origin. forward = -p,
+    right = normalise(up x forward) with up = (0, 0, 1), or (0, 1, 0) when |up x forward| < 1e-6, down = forward x right;
+    the rows of R are right, down, forward. Each view is followed by its `inplane` - 1 rotations about the optical axis
+    by k 2 pi / inplane: view id = vertex * inplane + k."""
+    level, inplane = int(level), int(inplane)
+    if not 0 <= level <= 5:
+        raise ValueError("view_grid: level must lie in [0, 5], got %d" % level)
+    if inplane < 1:
+        raise ValueError("view_grid: inplane must be >= 1, got %d" % inplane)
+    out = []
+    for p in _icosphere_vertices(level):
+        fwd = -p
+        right = np.cross((0.0, 0.0, 1.0), fwd)
+        if np.sqrt(right @ right) < 1e-6:
+            right = np.cross((0.0, 1.0, 0.0), fwd)
+        right = right / np.sqrt(right @ right)
+        R = np.stack([right, np.cross(fwd, right), fwd])
+        for k in range(inplane):
+            a = k * 2.0 * np.pi / inplane
+            c, s = (1.0, 0.0) if k == 0 else (np.cos(a), np.sin(a))
+            out.append(np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]) @ R)
+    return np.stack(out)
+
+
+def _frame_views(vertices, rotations, distance, cam_K, S, T, pad, z_near):
+    """SPEC 7.14 in float64, on the device the (f32) vertices live on -> (intrinsics f64 [n,4] of the virtual cameras at
+    S x S, template_z f64 [n]) as numpy."""
+    fx, fy = float(cam_K[0][0]), float(cam_K[1][1])
+    P = vertices.to(torch.float64)
+    R = torch.from_numpy(rotations).to(P.device)
+    m = np.empty(len(rotations))
+    zmin = np.empty(len(rotations))
+    for a in range(0, len(rotations), 16):                 # [16, V, 3] at a time
+        C = torch.einsum("nij,vj->nvi", R[a:a + 16], P)
+        Z = C[..., 2] + distance
+        zmin[a:a + 16] = Z.min(1).values.cpu().numpy()
+        Zs = torch.where(Z > 0, Z, torch.ones_like(Z))
+        ext = torch.maximum((fx * C[..., 0] / Zs).abs(), (fy * C[..., 1] / Zs).abs())
+        m[a:a + 16] = ext.max(1).values.cpu().numpy()
+    if not (zmin > z_near).all():
+        v = int(np.argmin(zmin))
+        raise ValueError("render_templates: at distance = %g view %d has a vertex at Z = %g <= z_near = %g: raise `distance`"
+                         % (distance, v, zmin[v], z_near))
+    h = np.maximum(pad * m, 5.0)
+    cams = np.stack([fx * S / (2.0 * h), fy * S / (2.0 * h), np.full(len(h), S / 2.0), np.full(len(h), S / 2.0)], 1)
+    return cams, -distance * 2.0 * h / T
+
+
+def render_templates(mesh, rotations=None, size=124, supersample=4, distance=0.8, cam_K=None, pad=1.1, z_near=0.05,
+                     views_per_call=32):
+    """The detector's templates of a vertex-coloured mesh (SPEC 7.13-7.14) -> (img f32 [n,3,T,T] in [0, 1],
+    mask f32 [n,1,T,T], info) on the mesh's device, T = size. View v shows the mesh under rotations[v] (default
+    view_grid()) at `distance` on the optical axis, through a virtual camera derived from cam_K that frames the object
+    with the margin `pad`, rendered at supersample x T and reduced by the exact box filter. info: "rotations" f64
+    [n,3,3], "quats" f64 [n,4] (xyzw), "intrinsics" f32 [n,4] of the virtual cameras, "template_z" f64 [n], the value
+    DtoidNet.forwardTestTime's z filter takes. views_per_call bounds the memory: 8 bytes x (supersample T)^2 per view."""
+    if getattr(mesh, "colors", None) is None:
+        raise ValueError("render_templates: the mesh has no vertex colours (Mesh(..., colors=...), "
+                         "read_ply_mesh(path, with_colors=True))")
+    if cam_K is None:
+        raise ValueError("render_templates: cam_K is required (the camera the templates will be matched under)")
+    K = np.asarray(cam_K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("cam_K must be [3,3], got %s" % (K.shape,))
+    T, s, per = int(size), int(supersample), int(views_per_call)
+    if not 1 <= s <= 8:
+        raise ValueError("supersample must lie in [1, 8], got %r" % (supersample,))
+    if not 1 <= T <= 512:
+        raise ValueError("size must lie in [1, 512], got %r" % (size,))
+    if not 1 <= per <= _lib.RASTER_MAX_POSES:
+        raise ValueError("views_per_call must lie in [1, %d], got %r" % (_lib.RASTER_MAX_POSES, views_per_call))
+    if not (float(distance) > 0.0 and np.isfinite(distance)):
+        raise ValueError("distance must be finite and > 0, got %r" % (distance,))
+    if not (float(pad) > 0.0 and np.isfinite(pad)):
+        raise ValueError("pad must be finite and > 0, got %r" % (pad,))
+    if not (float(z_near) >= 0.0 and np.isfinite(z_near)):
+        raise ValueError("z_near must be finite and >= 0, got %r" % (z_near,))
+    R = view_grid() if rotations is None else np.array(rotations, dtype=np.float64)
+    if R.ndim != 3 or R.shape[1:] != (3, 3) or len(R) < 1:
+        raise ValueError("rotations must be [n,3,3] with n >= 1, got %s" % (R.shape,))
+    S, n = s * T, len(R)
+    cams, template_z = _frame_views(mesh.vertices, R, float(distance), K, S, T, float(pad), float(z_near))
+    cams = cams.astype(np.float32)
+    poses = np.tile(np.eye(4), (n, 1, 1))
+    poses[:, :3, :3], poses[:, 2, 3] = R, float(distance)
+    dev = mesh.device
+    img = torch.empty(n, 3, T, T, dtype=torch.float32, device=dev)
+    mask = torch.empty(n, 1, T, T, dtype=torch.float32, device=dev)
+    for a in range(0, n, per):
+        b = min(n, a + per)
+        color, depth = render_color(mesh, poses[a:b], None, (S, S), 0.5, z_near, intrinsics=cams[a:b])
+        with _lib.on_device(dev):
+            rc = _lib.fn("ossid_template_reduce")(color.data_ptr(), depth.data_ptr(), b - a, T, s, img[a:b].data_ptr(),
+                                                  mask[a:b].data_ptr(), _lib.stream())
+        _lib.check(rc, "ossid_template_reduce")
+    from .pipeline import _rotmat_to_quat
+    info = {"rotations": R, "quats": np.stack([_rotmat_to_quat(r) for r in R]), "intrinsics": cams, "template_z": template_z}
+    return img, mask, info
 
 
 class _Node:
@@ -177,6 +405,7 @@ class Renderer:
         """-> (None, depth f32 numpy [H,W] in the scaled units, 0 = background). Several objects share one image: the
         nearest positive depth per pixel."""
         if not depth_only:
+            # the drop-in stays depth only; colour is reached through render_color / render_templates
             raise ValueError("Renderer.render: depth_only=False is not supported (this build renders depth only; "
                              "scripts/online_learning.py:493 passes depth_only=True)")
         out = None

@@ -6,6 +6,7 @@
   the pseudo_label stage of OnlineStream per frame with the splat and with the mesh.
 
     python3 tools/bench_render.py [--out profiles/render_mesh.json] [--commit ID]
+    python3 tools/bench_render.py --color [--out profiles/render_color.json]      render_color against render_depth, see below
     rocprofv3 --kernel-trace --stats -d out -- python3 tools/bench_render.py --trace     (a few untimed calls per workload)
 
 Times are HIP events around `reps` back-to-back calls after a warm-up, the median of `rounds` such windows.
@@ -86,9 +87,72 @@ def stream_stage_ms(meshes, n_warm=2, n_timed=8):
     return {k: 1e3 * v / n_timed for k, v in stream.times.items()}
 
 
+def per_call_ms(fn, warm=3, calls=20):
+    """Median, min and max of `calls` single calls, each between its own pair of device events, after `warm` untimed ones."""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(calls):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return {"ms": float(np.median(out)), "ms_min": float(min(out)), "ms_max": float(max(out)), "calls": calls, "warm": warm}
+
+
+def color_against_depth(trace):
+    """render_color against render_depth (the depth-only entry) on the same call (SPEC 7.11-7.12): level 5 and level 7 of
+    the coloured test mesh, 32 poses at 640 x 480 and the 162 template views at 496 x 496. The depth-only entry has one
+    camera per call, so for the template views both sides use the first view's virtual camera. Also the wall time of
+    render_templates for the 162-view grid (host clock around synchronised work)."""
+    import time
+
+    import ref_raster_color as rc
+    K = synth.CAM_K
+    res = {}
+    for level in (5, 7):
+        V, F = rr.bump_mesh(level)
+        mesh = render.Mesh(V, F, colors=rc.axis_colors(V)[0])
+        R = render.view_grid(2)
+        cams, _tz = render._frame_views(mesh.vertices, R, 0.8, K, 496, 124, 1.1, 0.05)
+        Kv = rc.cam_matrix(*[float(np.float32(x)) for x in cams[0]])
+        views = np.tile(np.eye(4), (len(R), 1, 1))
+        views[:, :3, :3], views[:, 2, 3] = R, 0.8
+        for name, poses, cam, hw in (("frames_32x640x480", batch_of(rp.gt_pose(0), 32), K, HW), ("views_162x496x496", views, Kv, (496, 496))):
+            T = torch.from_numpy(poses).to("cuda", torch.float32)
+            depth_fn = lambda: render.render_depth(mesh, T, cam, hw)  # noqa: E731
+            color_fn = lambda: render.render_color(mesh, T, cam, hw)  # noqa: E731
+            if trace:
+                for _ in range(3):
+                    depth_fn(), color_fn()
+                torch.cuda.synchronize()
+                continue
+            assert torch.equal(depth_fn(), color_fn()[1])
+            row = {"depth": per_call_ms(depth_fn), "color": per_call_ms(color_fn), "triangles": mesh.n_faces, "poses": len(poses),
+                   "frame": list(hw)}
+            row["ratio"] = row["color"]["ms"] / row["depth"]["ms"]
+            res["level%d_%s" % (level, name)] = row
+            print("level", level, name, row, flush=True)
+        if not trace:
+            walls = []
+            for _ in range(4):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                render.render_templates(mesh, cam_K=K)
+                torch.cuda.synchronize()
+                walls.append(1e3 * (time.perf_counter() - t0))
+            res["level%d_render_templates_162_wall_ms" % level] = {"first": walls[0], "median_of_next_3": float(np.median(walls[1:]))}
+            print("level", level, "render_templates", walls, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "render_mesh.json"))
+    ap.add_argument("--out", default=None, help="profiles/render_mesh.json, or profiles/render_color.json with --color")
+    ap.add_argument("--color", action="store_true", help="time render_color against render_depth and render_templates")
     ap.add_argument("--commit", default=None)
     ap.add_argument("--trace", action="store_true", help="a few untimed calls per workload, for a kernel trace")
     ap.add_argument("--no-stream", action="store_true", help="skip the OnlineStream stage timing")
@@ -96,6 +160,12 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_render.py needs the GPU: there is nothing to time without one")
     torch.cuda.set_device(0)
+    args.out = args.out or os.path.join(ROOT, "profiles", "render_color.json" if args.color else "render_mesh.json")
+    if args.color:
+        res = {"render_color_against_render_depth": color_against_depth(args.trace)}
+        if not args.trace:
+            write(res, args)
+        return
     K = synth.CAM_K
     res = {"render_depth": {}, "frame": list(HW)}
     for name, level, T in workloads():
@@ -129,6 +199,10 @@ def main():
             "mesh_level5": stream_stage_ms({1: render.Mesh(*rr.bump_mesh(5))})["pseudo_label"],
             "mesh_level7": stream_stage_ms({1: render.Mesh(*rr.bump_mesh(7))})["pseudo_label"]}
         print("pseudo_label", res["pseudo_label_stage_ms_per_frame"], flush=True)
+    write(res, args)
+
+
+def write(res, args):
     commit = args.commit
     if commit is None:
         try:
