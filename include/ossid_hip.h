@@ -861,6 +861,32 @@ int ossid_raster_color(const float* vertices, int V, const int32_t* faces, int F
 int ossid_template_reduce(const uint8_t* color, const float* depth, int N, int T, int s, float* img_out, float* mask_out,
                           void* stream);
 
+/* 8f-4  the BOP-19 pose errors the reference's run ends with (scripts/online_learning.py:603-608:
+ * saveResultsBop(..., run_eval_script=True); utils/bop_utils.py:51-53 shells out to bop_toolkit's scripts/eval_bop19.py
+ * --renderer_type=cpp, which is not part of the reference tree). SPEC.md section 8 (csrc/bop_eval.hip): this build's own
+ * restatement of the published definitions, parity with bop_toolkit unpinned. One length unit throughout, the caller's.
+ * ossid_bop_vsd (8.3-8.5): depth_obs f32 [Fr][H][W] (a value that is not > 0 is invalid), cams f32 [Fr][4] = fx, fy, cx,
+ * cy per frame, z_est and z_gt f32 [N][H][W] = ossid_raster_depth's renders (pixel_offset 0) of the estimates and of
+ * their ground truths with the frame's camera, frame_host int32 [N] and taus_host f64 [T] in HOST memory (checked here,
+ * passed on as kernel arguments) -> counts int32 [N][T+2] = (n_U, n_I, c_0 .. c_{T-1}), errors f64 [N][T]. A call may be a
+ * chunk of a longer list. Integer counts by atomicAdd: bit-reproducible. Launches only, nothing read back, capturable --
+ * with frame_host and taus_host read at call time: a captured graph replays with the frames and taus it was captured
+ * with (the device buffers are read at replay as usual).
+ * ossid_bop_mssd_mspd (8.7): vertices f32 [V][3], symmetries f64 [S][4][4] row-major (8.6), pose_est and pose_gt f64
+ * [N][4][4], cams and frame_host as above -> mssd, mspd f64 [N] (mspd in pixels; +inf when a vertex is at Z <= 0 or not
+ * finite under either pose for every symmetry).
+ * OSSID_EINVAL before any launch: T outside [1, OSSID_BOP_MAX_TAUS], S outside [1, OSSID_BOP_MAX_SYMMETRIES], N < 1,
+ * Fr < 1, a frame index outside [0, Fr), diameter not > 0, delta not >= 0, a non-finite tau, V outside
+ * [1, OSSID_RASTER_MAX_VERTICES], H W outside (0, OSSID_RASTER_MAX_PIXELS], a NULL pointer. */
+#define OSSID_BOP_MAX_TAUS 16
+#define OSSID_BOP_MAX_SYMMETRIES 4096
+int ossid_bop_vsd(const float* depth_obs, const float* cams, int Fr, int H, int W, const float* z_est, const float* z_gt,
+                  const int32_t* frame_host, int N, double diameter, double delta, const double* taus_host, int T,
+                  int32_t* counts, double* errors, void* stream);
+int ossid_bop_mssd_mspd(const float* vertices, int V, const double* symmetries, int S, const double* pose_est,
+                        const double* pose_gt, const float* cams, int Fr, const int32_t* frame_host, int N, double* mssd,
+                        double* mspd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

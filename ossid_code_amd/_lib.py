@@ -96,6 +96,8 @@ _PROTOS = {
     "ossid_raster_color_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ossid_raster_color": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ossid_template_reduce": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ossid_bop_vsd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _i, _vp, _vp, _vp]),
+    "ossid_bop_mssd_mspd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -216,6 +218,8 @@ RASTER_MAX_VERTICES = 1 << 22  # OSSID_RASTER_MAX_VERTICES
 RASTER_MAX_FACES = 1 << 22     # OSSID_RASTER_MAX_FACES
 RASTER_MAX_POSES = 256         # OSSID_RASTER_MAX_POSES
 RASTER_MAX_PIXELS = 1 << 24    # OSSID_RASTER_MAX_PIXELS
+BOP_MAX_TAUS = 16              # OSSID_BOP_MAX_TAUS
+BOP_MAX_SYMMETRIES = 4096      # OSSID_BOP_MAX_SYMMETRIES
 
 ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
 

@@ -19,8 +19,10 @@ install() registers this package's mirrors under the module paths the script imp
                                                           device rasteriser of SPEC.md section 7, depth only)
 
 resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF unless install(ppf=True), the
-renderer unless install(renderer=True), BOP tooling, datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
-`ossid` package is importable, just these attributes are overridden on it, nothing else is shadowed.
+renderer unless install(renderer=True), datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
+`ossid` package is importable, just these attributes are overridden on it, nothing else is shadowed. The BOP evaluation the
+run ends with is a script the reference shells out to, not an import: tools/eval_bop19.py (bop_eval.py, SPEC.md section 8)
+takes its command line, see INTEGRATION.md.
 """
 import importlib
 import sys

@@ -1,0 +1,300 @@
+// BOP-19 pose errors (SPEC.md section 8): what the reference's run ends with -- scripts/online_learning.py:603-608 calls
+// saveResultsBop(..., run_eval_script=True), and utils/bop_utils.py:51-53 shells out to bop_toolkit's
+// scripts/eval_bop19.py --renderer_type=cpp. bop_toolkit is absent from the reference tree: the definitions are this
+// build's own restatement of the published ones (Hodan et al., BOP Challenge 2020, section 2.2).
+//
+// ossid_bop_vsd (8.3-8.5). The two renders come from ossid_raster_depth. Launches on the caller's stream, nothing read back:
+//   zero      counts = 0;
+//   cost      grid (tiles of TILE pixels, estimates of a chunk). A lane takes four consecutive pixels per step (one
+//             16-byte load per image where the image size allows, scalar loads otherwise). A wave whose 256 pixels are
+//             empty in both renders does nothing more -- exact: such a pixel is in neither V_gt nor V_est -- and does not
+//             load the observed depth. Otherwise distances, visibility and the T comparisons are computed in registers
+//             in f64, every flag is counted by ballot + popcount into wave-uniform integers, the waves' counts meet in
+//             LDS, and the workgroup issues one integer atomicAdd per non-zero counter. Integer sums do not depend on
+//             the order of arrival: the counts are bit-reproducible;
+//   finalise  e_k = (c_k + (n_U - n_I)) / n_U in f64, 1 when n_U = 0.
+//
+// ossid_bop_mssd_mspd (8.7). One workgroup per (estimate, SC symmetries): SC threads compose G = pose_gt . S each and hand
+// it on through LDS; the vertices stream through coalesced, each is transformed and projected under pose_est once and then
+// compared against the chunk's transforms held in registers (SC of them, fewer in the last chunk: S = 1 pays for one);
+// running maxima of the squared distances per lane, reduced across the wave by shuffles and across the waves in LDS; the
+// minimum over the chunks by atomicMin on the 64-bit pattern of the non-negative double (it orders like the value; the
+// outputs start at +inf). Max and min do not depend on order.
+//
+// frame[] and taus[] are host arrays (checked before any launch) and travel as kernel arguments, CHUNK estimates per launch:
+// a captured graph replays with the values they had at capture.
+#include <cmath>
+
+#include "common.h"
+
+namespace {
+
+constexpr int CHUNK = 256;            // estimates per launch: frame indices travel in the kernel arguments
+constexpr int TILE = 2048;            // pixels per workgroup of the cost kernel: 256 lanes x 4 pixels x 2 steps
+constexpr int SC = 4;                 // symmetries per workgroup, held in registers (12 doubles each)
+constexpr unsigned long long DINF = 0x7ff0000000000000ull;
+
+struct FrameIdx {
+    int32_t f[CHUNK];
+};
+struct Taus {
+    double t[OSSID_BOP_MAX_TAUS];
+};
+
+__global__ __launch_bounds__(256) void bop_zero_kernel(int32_t* __restrict__ counts, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) counts[i] = 0;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void bop_vsd_kernel(const float* __restrict__ depth_obs, const float* __restrict__ cams,
+                                                      int H, int W, const float* __restrict__ z_est,
+                                                      const float* __restrict__ z_gt, FrameIdx frames, double diameter,
+                                                      double delta, Taus taus, int T, int32_t* __restrict__ counts) {
+    const int n = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t hw = (size_t)H * W;
+    const int fr = frames.f[n];
+    const float* ze = z_est + (size_t)n * hw;
+    const float* zg = z_gt + (size_t)n * hw;
+    const float* ob = depth_obs + (size_t)fr * hw;
+    const double fx = (double)cams[4 * fr], fy = (double)cams[4 * fr + 1], cx = (double)cams[4 * fr + 2],
+                 cy = (double)cams[4 * fr + 3];
+    int nU = 0, nI = 0, c[OSSID_BOP_MAX_TAUS];      // wave-uniform
+#pragma unroll
+    for (int k = 0; k < OSSID_BOP_MAX_TAUS; ++k) c[k] = 0;
+    const size_t tile0 = (size_t)blockIdx.x * TILE;
+    for (int step = 0; step < TILE / 1024; ++step) {
+        const size_t i0 = tile0 + (size_t)step * 1024 + 4 * (size_t)threadIdx.x;
+        float e[4] = {0.0f, 0.0f, 0.0f, 0.0f}, g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (VEC) {                                   // hw % 4 == 0 and 16-byte aligned bases: i0 + 3 < hw iff i0 < hw
+            if (i0 < hw) {
+                const float4 a = *reinterpret_cast<const float4*>(ze + i0), b = *reinterpret_cast<const float4*>(zg + i0);
+                e[0] = a.x, e[1] = a.y, e[2] = a.z, e[3] = a.w, g[0] = b.x, g[1] = b.y, g[2] = b.z, g[3] = b.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (i0 + j < hw) e[j] = ze[i0 + j], g[j] = zg[i0 + j];
+        }
+        const bool any = e[0] > 0.0f || e[1] > 0.0f || e[2] > 0.0f || e[3] > 0.0f || g[0] > 0.0f || g[1] > 0.0f ||
+                         g[2] > 0.0f || g[3] > 0.0f;
+        if (__ballot(any) == 0ull) continue;         // wave-uniform
+        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (any) {
+            if (VEC) {
+                const float4 a = *reinterpret_cast<const float4*>(ob + i0);
+                o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (i0 + j < hw) o[j] = ob[i0 + j];
+            }
+        }
+        int y = (int)(i0 / (size_t)W), x = (int)(i0 - (size_t)y * W);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bool inU = false, inI = false;
+            double d = 0.0;
+            if (e[j] > 0.0f || g[j] > 0.0f) {
+                const double a = ((double)x - cx) / fx, b = ((double)y - cy) / fy;
+                const double s = sqrt((a * a + b * b) + 1.0);
+                const double De = (double)e[j] * s, Dg = (double)g[j] * s, Do = (double)o[j] * s;
+                const bool oinv = !(o[j] > 0.0f);
+                const bool vg = Dg > 0.0 && (oinv || Dg - Do <= delta);
+                const bool ve = (De > 0.0 && (oinv || De - Do <= delta)) || (vg && De > 0.0);
+                inU = vg || ve, inI = vg && ve;
+                d = fabs(Dg - De) / diameter;
+            }
+            nU += __popcll(__ballot(inU));
+            const unsigned long long bi = __ballot(inI);
+            if (bi != 0ull) {
+                nI += __popcll(bi);
+#pragma unroll
+                for (int k = 0; k < OSSID_BOP_MAX_TAUS; ++k)
+                    if (k < T) c[k] += __popcll(__ballot(inI && d >= taus.t[k]));
+            }
+            if (++x == W) x = 0, ++y;
+        }
+    }
+    __shared__ int part[4][OSSID_BOP_MAX_TAUS + 2];
+    if (lane == 0) {
+        part[wv][0] = nU, part[wv][1] = nI;
+#pragma unroll
+        for (int k = 0; k < OSSID_BOP_MAX_TAUS; ++k) part[wv][2 + k] = c[k];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < T + 2) {
+        const int v = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+        if (v) atomicAdd(counts + (size_t)n * (T + 2) + threadIdx.x, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void bop_vsd_finalize_kernel(const int32_t* __restrict__ counts, int N, int T,
+                                                               double* __restrict__ errors) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)N * T) return;
+    const int n = (int)(i / T), k = (int)(i - (size_t)n * T);
+    const int32_t* r = counts + (size_t)n * (T + 2);
+    const int nU = r[0], nI = r[1];
+    errors[i] = nU == 0 ? 1.0 : (double)(r[2 + k] + (nU - nI)) / (double)nU;
+}
+
+__global__ __launch_bounds__(256) void bop_inf_kernel(unsigned long long* __restrict__ a, unsigned long long* __restrict__ b,
+                                                      int N) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < N) a[i] = DINF, b[i] = DINF;
+}
+
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double w = __shfl_xor(v, m);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ bool fin(double v) { return fabs(v) < INFINITY; }     // false for NaN and +-inf
+
+__global__ __launch_bounds__(256) void bop_mssd_mspd_kernel(const float* __restrict__ vertices, int V,
+                                                            const double* __restrict__ syms, int S,
+                                                            const double* __restrict__ pose_est,
+                                                            const double* __restrict__ pose_gt,
+                                                            const float* __restrict__ cams, FrameIdx frames,
+                                                            unsigned long long* __restrict__ mssd,
+                                                            unsigned long long* __restrict__ mspd) {
+    const int n = blockIdx.y, s0 = blockIdx.x * SC, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ double Gs[SC][12];
+    __shared__ double red[4][2 * SC];
+    const double* Pg = pose_gt + 16 * (size_t)n;
+    if (threadIdx.x < SC) {
+        // slots past the end hold the last transform and are never compared (live below)
+        const double* Sm = syms + 16 * (size_t)min(s0 + (int)threadIdx.x, S - 1);
+        for (int r = 0; r < 3; ++r) {
+            const double a0 = Pg[4 * r], a1 = Pg[4 * r + 1], a2 = Pg[4 * r + 2];
+            for (int col = 0; col < 3; ++col) Gs[threadIdx.x][4 * r + col] = (a0 * Sm[col] + a1 * Sm[4 + col]) + a2 * Sm[8 + col];
+            Gs[threadIdx.x][4 * r + 3] = ((a0 * Sm[3] + a1 * Sm[7]) + a2 * Sm[11]) + Pg[4 * r + 3];
+        }
+    }
+    __syncthreads();
+    double G[SC][12], E[12];
+#pragma unroll
+    for (int s = 0; s < SC; ++s)
+#pragma unroll
+        for (int j = 0; j < 12; ++j) G[s][j] = Gs[s][j];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) E[j] = pose_est[16 * (size_t)n + j];
+    const int fr = frames.f[n];
+    const double fx = (double)cams[4 * fr], fy = (double)cams[4 * fr + 1], cx = (double)cams[4 * fr + 2],
+                 cy = (double)cams[4 * fr + 3];
+    const int live = min(SC, S - s0);                // transforms of this chunk that exist
+    double m3[SC], m2[SC];
+#pragma unroll
+    for (int s = 0; s < SC; ++s) m3[s] = 0.0, m2[s] = 0.0;
+    for (int v = threadIdx.x; v < V; v += 256) {
+        const double x = (double)vertices[3 * (size_t)v], y = (double)vertices[3 * (size_t)v + 1],
+                     z = (double)vertices[3 * (size_t)v + 2];
+        const double Xe = ((E[0] * x + E[1] * y) + E[2] * z) + E[3];
+        const double Ye = ((E[4] * x + E[5] * y) + E[6] * z) + E[7];
+        const double Ze = ((E[8] * x + E[9] * y) + E[10] * z) + E[11];
+        const double ue = (Xe / Ze) * fx + cx, ve = (Ye / Ze) * fy + cy;
+        const bool oke = Ze > 0.0 && fin(Xe) && fin(Ye) && fin(Ze) && fin(ue) && fin(ve);
+#pragma unroll
+        for (int s = 0; s < SC; ++s) {
+            if (s >= live) break;                    // workgroup-uniform: S = 1 pays for one transform, not SC
+            const double Xg = ((G[s][0] * x + G[s][1] * y) + G[s][2] * z) + G[s][3];
+            const double Yg = ((G[s][4] * x + G[s][5] * y) + G[s][6] * z) + G[s][7];
+            const double Zg = ((G[s][8] * x + G[s][9] * y) + G[s][10] * z) + G[s][11];
+            const double dx = Xe - Xg, dy = Ye - Yg, dz = Ze - Zg;
+            double q = (dx * dx + dy * dy) + dz * dz;
+            q = q == q ? q : (double)INFINITY;       // NaN counts as +inf
+            m3[s] = q > m3[s] ? q : m3[s];
+            const double ug = (Xg / Zg) * fx + cx, vg = (Yg / Zg) * fy + cy;
+            const bool ok = oke && Zg > 0.0 && fin(Xg) && fin(Yg) && fin(Zg) && fin(ug) && fin(vg);
+            const double du = ue - ug, dv = ve - vg;
+            const double p = ok ? du * du + dv * dv : (double)INFINITY;
+            m2[s] = p > m2[s] ? p : m2[s];
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < SC; ++s) {
+        const double a = wave_max_f64(m3[s]), b = wave_max_f64(m2[s]);
+        if (lane == 0) red[wv][s] = a, red[wv][SC + s] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const int off = threadIdx.x * SC;            // 0: MSSD, 1: MSPD
+        double best = INFINITY;
+        for (int s = 0; s < live; ++s) {
+            double m = red[0][off + s];
+            for (int w = 1; w < 4; ++w) m = red[w][off + s] > m ? red[w][off + s] : m;
+            best = m < best ? m : best;
+        }
+        // sqrt is monotone and correctly rounded: the root of the min-max of the squares is the min-max of the roots
+        atomicMin((threadIdx.x == 0 ? mssd : mspd) + n, (unsigned long long)__double_as_longlong(sqrt(best)));
+    }
+}
+
+bool frames_ok(const int32_t* frame_host, int N, int Fr) {
+    for (int i = 0; i < N; ++i)
+        if (frame_host[i] < 0 || frame_host[i] >= Fr) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ossid_bop_vsd(const float* depth_obs, const float* cams, int Fr, int H, int W, const float* z_est, const float* z_gt,
+                  const int32_t* frame_host, int N, double diameter, double delta, const double* taus_host, int T,
+                  int32_t* counts, double* errors, void* stream) {
+    if (!depth_obs || !cams || !z_est || !z_gt || !frame_host || !taus_host || !counts || !errors || Fr < 1 || N < 1 || H <= 0 ||
+        W <= 0 || (long long)H * W > OSSID_RASTER_MAX_PIXELS || T < 1 || T > OSSID_BOP_MAX_TAUS || !(diameter > 0.0) ||
+        !std::isfinite(diameter) || !(delta >= 0.0) || !std::isfinite(delta) || !frames_ok(frame_host, N, Fr))
+        return OSSID_EINVAL;
+    Taus taus = {};
+    for (int k = 0; k < T; ++k) {
+        if (!std::isfinite(taus_host[k])) return OSSID_EINVAL;
+        taus.t[k] = taus_host[k];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t hw = (size_t)H * W, ncount = (size_t)N * (T + 2);
+    const bool vec = hw % 4 == 0 && (((uintptr_t)depth_obs | (uintptr_t)z_est | (uintptr_t)z_gt) & 15) == 0;
+    hipLaunchKernelGGL(bop_zero_kernel, dim3((unsigned)((ncount + 255) / 256 < 1024 ? (ncount + 255) / 256 : 1024)), dim3(256), 0, s,
+                       counts, ncount);
+    const unsigned tiles = (unsigned)((hw + TILE - 1) / TILE);
+    for (int a = 0; a < N; a += CHUNK) {
+        const int nb = N - a < CHUNK ? N - a : CHUNK;
+        FrameIdx fi = {};
+        for (int i = 0; i < nb; ++i) fi.f[i] = frame_host[a + i];
+        if (vec)
+            hipLaunchKernelGGL(bop_vsd_kernel<true>, dim3(tiles, nb), dim3(256), 0, s, depth_obs, cams, H, W, z_est + (size_t)a * hw,
+                               z_gt + (size_t)a * hw, fi, diameter, delta, taus, T, counts + (size_t)a * (T + 2));
+        else
+            hipLaunchKernelGGL(bop_vsd_kernel<false>, dim3(tiles, nb), dim3(256), 0, s, depth_obs, cams, H, W, z_est + (size_t)a * hw,
+                               z_gt + (size_t)a * hw, fi, diameter, delta, taus, T, counts + (size_t)a * (T + 2));
+    }
+    hipLaunchKernelGGL(bop_vsd_finalize_kernel, dim3((unsigned)(((size_t)N * T + 255) / 256)), dim3(256), 0, s, counts, N, T, errors);
+    return ossid_launch_status();
+}
+
+int ossid_bop_mssd_mspd(const float* vertices, int V, const double* symmetries, int S, const double* pose_est,
+                        const double* pose_gt, const float* cams, int Fr, const int32_t* frame_host, int N, double* mssd,
+                        double* mspd, void* stream) {
+    if (!vertices || !symmetries || !pose_est || !pose_gt || !cams || !frame_host || !mssd || !mspd || V < 1 ||
+        V > OSSID_RASTER_MAX_VERTICES || S < 1 || S > OSSID_BOP_MAX_SYMMETRIES || Fr < 1 || N < 1 || !frames_ok(frame_host, N, Fr))
+        return OSSID_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bop_inf_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (unsigned long long*)mssd,
+                       (unsigned long long*)mspd, N);
+    for (int a = 0; a < N; a += CHUNK) {
+        const int nb = N - a < CHUNK ? N - a : CHUNK;
+        FrameIdx fi = {};
+        for (int i = 0; i < nb; ++i) fi.f[i] = frame_host[a + i];
+        hipLaunchKernelGGL(bop_mssd_mspd_kernel, dim3((unsigned)((S + SC - 1) / SC), nb), dim3(256), 0, s, vertices, V, symmetries, S,
+                           pose_est + 16 * (size_t)a, pose_gt + 16 * (size_t)a, cams, fi, (unsigned long long*)mssd + a,
+                           (unsigned long long*)mspd + a);
+    }
+    return ossid_launch_status();
+}
+
+}  // extern "C"
