@@ -90,29 +90,67 @@ __device__ __forceinline__ v16f mfma4(float4 a, const v16f& x, int q4, v16f acc)
 // sched_barrier between groups keeps the compiler from re-merging them (G quads = 4G MFMAs = 256G cycles
 // of matrix work cover the L2 latency of the next group's loads).
 
+// A weight load of the two forms sa3_kernel uses is ONE global_load_dwordx4 with no address arithmetic in the vector pipe:
+// a group of G <= 8 consecutive quads shares a base in scalar registers (the layer's uniform pointer plus the group's
+// offset, one scalar add per group), the lane's 16-byte slot is a 32-bit offset register computed once per kernel, and
+// the quad's place in the group is the instruction's immediate (13 bits, signed: the base points at the group's middle).
+// The group's offset goes through an empty asm: seen through, the compiler folds lane and base into one 64-bit vector pointer per
+// kernel and then adds every group's offset to it with a v_add_co / v_addc pair.
+// s_waitcnt operand that waits for the vector-memory counter alone (gfx9 encoding: vmcnt in bits 3:0 and 15:14, the
+// export and LDS / scalar counters at their maxima = not waited for)
+constexpr int vmcnt_only(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
+
+template <int G>
+__device__ __forceinline__ const char* group_base(const float* __restrict__ Wu, int quad0) {
+    static_assert(G <= 8, "a group must fit the immediate offset");
+    int off = quad0 * 1024 + (G > 4 ? 4096 : 0);
+    asm("" : "+s"(off));               // (the offset, not the pointer: a laundered pointer loses its address space)
+    return (const char*)Wu + off;
+}
+template <int G>
+__device__ __forceinline__ float4 load_quad(const char* gb, unsigned lane_off, int i) {
+    return *(const float4*)(gb + lane_off + (i * 1024 - (G > 4 ? 4096 : 0)));
+}
+
 // Fully unrolled form for layers whose output tiles stay in registers (Y[t][mt] statically indexed).
 template <int KT, int MT, int NT, int G, class Epi>
-__device__ __forceinline__ void stream_layer(const float4* __restrict__ W4, const float* __restrict__ bias,
+__device__ __forceinline__ void stream_layer(const float* __restrict__ Wu, unsigned lane_off, const float* __restrict__ bias,
                                              const v16f (&X)[NT][KT], int h, Epi&& epi) {
-    constexpr int QPM = KT * 4, TOTAL = MT * QPM, NG = TOTAL / G;
-    static_assert(TOTAL % G == 0, "group size must divide the quad count");
+    constexpr int QPM = KT * 4, TOTAL = MT * QPM, NG = TOTAL / G, NGM = QPM / G;
+    static_assert(QPM % G == 0 && NGM >= 2, "an m-tile must be at least two whole groups");
     float4 cur[G], nxt[G];
+    {
+        const char* gb = group_base<G>(Wu, 0);
 #pragma unroll
-    for (int i = 0; i < G; ++i) cur[i] = W4[(size_t)i * 64];
+        for (int i = 0; i < G; ++i) cur[i] = load_quad<G>(gb, lane_off, i);
+    }
+    // the bias tile of an m-tile is fetched with the weights of its first group, a group ahead (its one consumer, the
+    // m-tile's first MFMA, would otherwise sit on an L2 latency sixteen times per layer)
+    v16f bt = bias_tile(bias, 0, h);
     v16f acc[NT];
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        if (g + 1 < NG) {
+        const bool more = g + 1 < NG, bias_too = more && (g + 1) % NGM == 0;
+        if (more) {
+            const char* gb = group_base<G>(Wu, (g + 1) * G);
 #pragma unroll
-            for (int i = 0; i < G; ++i) nxt[i] = W4[(size_t)((g + 1) * G + i) * 64];
+            for (int i = 0; i < G; ++i) nxt[i] = load_quad<G>(gb, lane_off, i);
         }
+        if (bias_too) bt = bias_tile(bias, (g + 1) / NGM, h);
         __builtin_amdgcn_sched_barrier(0);   // the prefetch stays AHEAD of this group's MFMAs
+        // one wait per group (loads return in order: all but the ones just issued have landed), not one per quad
+        if (!more)
+            __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
+        else if (bias_too)
+            __builtin_amdgcn_s_waitcnt(vmcnt_only(G + 4));
+        else
+            __builtin_amdgcn_s_waitcnt(vmcnt_only(G));
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             const int quad = g * G + i, mt = quad / QPM, kq = quad % QPM, kt = kq / 4, q = kq % 4;
             if (kq == 0) {
 #pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t] = bias_tile(bias, mt, h);
+                for (int t = 0; t < NT; ++t) acc[t] = bt;
             }
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[t] = mfma4(cur[i], X[t][kt], 4 * q, acc[t]);
@@ -201,29 +239,39 @@ __device__ __forceinline__ float pool_swapped(const v16f& a) {
 }
 
 template <int KT, int NT, int G, class Epi>
-__device__ __forceinline__ void stream_last_layer(const float4* __restrict__ W4, const float* __restrict__ bias,
-                                                  const v16f (&X)[NT][KT], int c, int MT, Epi&& epi) {
+__device__ __forceinline__ void stream_last_layer(const float* __restrict__ Wu, unsigned lane_off,
+                                                  const float* __restrict__ bias, const v16f (&X)[NT][KT], int c, int MT,
+                                                  Epi&& epi) {
     constexpr int QPM = KT * 4, NG = QPM / G;
     static_assert(QPM % G == 0, "group size must divide the quads per m-tile");
-    const int last = MT * QPM - 1;
     float4 cur[G], nxt[G];
+    {
+        const char* gb = group_base<G>(Wu, 0);
 #pragma unroll
-    for (int i = 0; i < G; ++i) cur[i] = W4[(size_t)i * 64];
+        for (int i = 0; i < G; ++i) cur[i] = load_quad<G>(gb, lane_off, i);
+    }
+    const float* wm = Wu;                  // this m-tile's quads: uniform, advanced once per m-tile
+    float bvn = bias[c];                   // the lane's bias, fetched an m-tile ahead
 #pragma unroll 1
     for (int mt = 0; mt < MT; ++mt) {
         v16f acc[NT];
-        const float bv = bias[mt * 32 + c];
+        const float bv = bvn;
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[t] = splat16(bv);
+        // the group after this m-tile's last is the next m-tile's first; after the last m-tile the prefetch wraps to quad 0
+        // (loaded for nothing, in bounds) instead of clamping every address
+        const float* wn = mt + 1 < MT ? wm + QPM * 256 : Wu;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
+            const char* gb = g + 1 < NG ? group_base<G>(wm, (g + 1) * G) : group_base<G>(wn, 0);
 #pragma unroll
-            for (int i = 0; i < G; ++i) {
-                int nq = mt * QPM + (g + 1) * G + i;
-                nq = nq > last ? last : nq;
-                nxt[i] = W4[(size_t)nq * 64];
-            }
+            for (int i = 0; i < G; ++i) nxt[i] = load_quad<G>(gb, lane_off, i);
+            if (g == 0) bvn = bias[(mt + 1 < MT ? mt + 1 : mt) * 32 + c];
             __builtin_amdgcn_sched_barrier(0);
+            if (g == 0)                      // one wait per group, as in stream_layer
+                __builtin_amdgcn_s_waitcnt(vmcnt_only(G + 1));
+            else
+                __builtin_amdgcn_s_waitcnt(vmcnt_only(G));
 #pragma unroll
             for (int i = 0; i < G; ++i) {
                 const int kq = g * G + i, kt = kq / 4, q = kq % 4;
@@ -235,6 +283,7 @@ __device__ __forceinline__ void stream_last_layer(const float4* __restrict__ W4,
             for (int i = 0; i < G; ++i) cur[i] = nxt[i];
         }
         epi(mt, acc);
+        wm = wn;
     }
 }
 
@@ -519,6 +568,19 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
 // allocator keeps them on the vector side's books and copies each one back (v_accvgpr_read) before the MFMA that uses it.
 __device__ __forceinline__ void pin_acc(float4& w) { asm volatile("" : "+a"(w.x), "+a"(w.y), "+a"(w.z), "+a"(w.w)); }
 
+// An activation tile that only MFMAs will read from here on (sa3_kernel: 384 activation registers live beside the weight
+// stream). Left to the allocator, the tiles that do not fit in the vector half are SPILLED to the accumulator half and
+// copied back one register at a time in front of every MFMA that reads them (v_accvgpr_read + a hazard nop, per MFMA);
+// pinned, they are written there once and the MFMAs take them as operands in place.
+__device__ __forceinline__ void pin_acc16(v16f& a) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        float t = a[i];
+        asm volatile("" : "+a"(t));
+        a[i] = t;
+    }
+}
+
 template <int N>
 __device__ __forceinline__ void load_quads(float4 (&w)[N], const float* __restrict__ Wp, int lane) {
 #pragma unroll
@@ -676,121 +738,184 @@ __global__ __launch_bounds__(256, 2) void p2_kernel(const float* __restrict__ fe
 }
 
 // ---- SA2: (P gather + xyz columns) -> relu -> 128 -> 256 -> max over 64 samples ----------------------
-// One wave per centre, its two 32-sample column tiles one after the other (a tile holds 64 + 64
-// activation registers); the first tile's pooled maxima wait in the output row and are merged by the
-// same lane when the second tile is done.
-// Weights: the last layer's 128 KB stay resident in LDS; the middle layer's 64 KB do not fit beside them, so they go
-// round a two-slot LDS RING of 8 KB chunks (8 quads = half an output tile) filled by LDS-DMA (global_load_lds_dwordx4:
-// the packed quad image is lane-linear, one 1 KB wave-instruction per quad, no VGPRs): the 8 waves walk the layer in
-// step, each issues one quad of chunk k+1 right after the barrier that publishes chunk k, and the 2 x 32 MFMAs per
-// SIMD of a chunk cover the L2 latency of the next. (Streaming this layer through registers from L2 instead ran the
-// matrix core at ~62 % for a third of the kernel's work.)
-constexpr int SA2_CPW = 8;
-constexpr int SA2_THREADS = 512;                       // 8 waves = the whole CU at two waves per SIMD
-constexpr int SA2_CHUNK = 8 * 256;                     // floats per ring slot: 8 quads x 64 lanes x 4
-constexpr int SA2_W3 = 0, SA2_B3 = 32768, SA2_B2 = SA2_B3 + 256, SA2_WX = SA2_B2 + 128, SA2_RING = SA2_WX + 384,
-              SA2_KEEP = SA2_RING + 2 * SA2_CHUNK,
-              SA2_LDS_FLOATS = SA2_KEEP + 8 * 256;   // W3p 128 KB | b3 | b2 | wxyz | ring 16 KB | keep 8 KB = 158 720 B
+// Persistent like sa1_kernel: one 4-wave workgroup per CU, one wave per SIMD, every wave walking a contiguous slice of the
+// B * np2 centres, a centre's two 32-sample column tiles one after the other. What sa1 measured holds here: the kernel's
+// loss is its count of vector / LDS / memory instructions, so the design keeps operands where an MFMA reads them in place.
+//   middle layer 128 -> 128: its 64 weight quads are loaded once per wave and pinned to the AGPR half (256 registers): no
+//     LDS ring, no LDS-DMA, no barrier after the prologue -- the four waves run free of each other;
+//   last layer 128 -> 256: its 128 KB stay in LDS for the kernel's lifetime (they do not fit beside the middle layer), read
+//     one group of four quads ahead of the MFMAs that use them, with one s_waitcnt per group; b2 is read from LDS a tile
+//     ahead (its four ready-made tiles would take the budget past 256 vector registers), and b3 too, as ready-made
+//     accumulator tiles of the swapped form (16 copies of the lane's bias: four ds_read_b128 instead of 16 v_mov);
+//   xyz columns: X1 = relu(fma(wz,dz, fma(wy,dy, fma(wx,dx, P)))) is the matrix core's own chain. The gathered P quads
+//     already have the accumulator layout (register 4q+e of half h = channel 32kt+8q+4h+e, column = sample), so an m-tile
+//     of X1 is two MFMAs with P as the C operand: k = (x, y), then k = (z, 0). The padding product fma(0, 0, acc) returns
+//     acc (a -0 becomes +0, which the ReLU that follows does anyway);
+//   the first tile's pooled maxima wait in 8 registers, not in LDS.
+// Register budget per lane: AGPR half = W2 256. Vector half: X1 64 (the next tile's 16-quad gather lands in the same
+// registers under the last layer, when X1 is dead) + Y2 64 + accumulator 16 + W3 read buffers 32 + the bias tile read
+// ahead 16 + xyz weights 8 + kept maxima 8 + addressing. tests/test_pn2_resources_sa2_sa3.py holds the build to zero scratch.
+constexpr int SA2_W3 = 0, SA2_B2 = 32768, SA2_B3S = SA2_B2 + 128,
+              SA2_LDS_FLOATS = SA2_B3S + 8 * 4 * 32 * 4;   // W3p 128 KB | b2 | b3 splat tiles 16 KB = 147 968 B
 
-
-__global__ __launch_bounds__(SA2_THREADS, 2) void sa2_kernel(const float* __restrict__ P, const float* __restrict__ xyz1,
-                                                             int np1, const int* __restrict__ ball,
-                                                             const float* __restrict__ cxyz, int np2, int total,
-                                                             const float* __restrict__ wxyz,
-                                                             const float* __restrict__ W2p, const float* __restrict__ b2,
-                                                             const float* __restrict__ W3p, const float* __restrict__ b3,
-                                                             float* __restrict__ feat) {
+__global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P, const float* __restrict__ xyz1,
+                                                     int np1, const int* __restrict__ ball,
+                                                     const float* __restrict__ cxyz, int np2, int total,
+                                                     const float* __restrict__ wxyz,
+                                                     const float* __restrict__ W2p, const float* __restrict__ b2,
+                                                     const float* __restrict__ W3p, const float* __restrict__ b3,
+                                                     float* __restrict__ feat) {
     extern __shared__ __attribute__((aligned(16))) float wl[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, c = lane & 31;
-    // chunk g of the middle layer = quads 8g..8g+7; this wave moves quad 8g+wave into slot g&1
-    const float4* W2q = (const float4*)W2p + (size_t)wave * 64 + lane;
-    float* ring_mine = wl + SA2_RING + wave * 256;
-    lds_dma_quad(W2q, ring_mine);
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
     stage_lds(wl + SA2_W3, W3p, 32768);
-    stage_lds(wl + SA2_B3, b3, 256);
     stage_lds(wl + SA2_B2, b2, 128);
-    stage_lds(wl + SA2_WX, wxyz, 384);
-    float* keep = wl + SA2_KEEP + wave * 256 + c;          // the first tile's pooled maxima of this wave's centre
-
-    // The 8 waves keep step through the ring's barriers, so a tile's gather must not sit between them: the sample
-    // indices of tile it+1 are fetched under tile it's first chunk and its 16 P quads + xyz under tile it's last layer.
-    constexpr int NTILE = SA2_CPW * 2;
-    const int centre0 = (blockIdx.x * (SA2_THREADS / 64) + wave) * SA2_CPW;
-    auto centre_of = [&](int it) { return min(centre0 + (it >> 1), total - 1); };
-    float4 pvn[16];
-    float nx, ny, nz, ncx, ncy, ncz;
-    int inext;
-    auto fetch_index = [&](int it) {
-        const int ce = centre_of(it);
-        inext = ball[(size_t)ce * 64 + (it & 1) * 32 + c];
-        ncx = cxyz[(size_t)ce * 3], ncy = cxyz[(size_t)ce * 3 + 1], ncz = cxyz[(size_t)ce * 3 + 2];
-    };
-    auto fetch_rows = [&](int it) {
-        const size_t pt = (size_t)(centre_of(it) / np2) * np1 + inext;
-        nx = xyz1[pt * 3], ny = xyz1[pt * 3 + 1], nz = xyz1[pt * 3 + 2];
+    {   // b3 as ready-made accumulator tiles of the swapped form: [m-tile][register quad][channel c] x 4 copies of b3[32 mt + c]
+        const float v = b3[threadIdx.x];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) pvn[j] = *(const float4*)(P + pt * 128 + (j >> 2) * 32 + 8 * (j & 3) + 4 * h);
+        for (int q = 0; q < 4; ++q)
+            *(float4*)(wl + SA2_B3S + (((threadIdx.x >> 5) * 4 + q) * 32 + (threadIdx.x & 31)) * 4) = make_float4(v, v, v, v);
+    }
+    __syncthreads();                   // the only barrier: every wave passes it before any may leave
+    const int gw = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = gridDim.x * 4;
+    const int per = total / nw, rem = total % nw;
+    const int first = gw * per + min(gw, rem), end = first + per + (gw < rem ? 1 : 0);
+    if (first >= end) return;          // fewer centres than waves
+    float4 w2[64];
+    load_quads(w2, W2p, lane);
+    // A operands of the xyz step for m-tile kt: lane half 0 carries (wx, wz), half 1 (wy, 0), of channel 32 kt + c
+    float a_xy[4], a_z[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+        a_xy[kt] = wxyz[h * 128 + kt * 32 + c];
+        const float z = wxyz[256 + kt * 32 + c];
+        a_z[kt] = h ? 0.0f : z;
+    }
+
+    // Tiles are numbered 2 * centre + t. The gather of tile it + 1 is issued a tile ahead, in two steps (there is no
+    // partner wave to cover a memory latency): its sample index and centre under tile it's first layers, its 16 P quads and
+    // the sample's xyz under tile it's last layer. (hn, cn) = hypothesis and centre of the NEXT tile, kept by counting.
+    const int it_end = 2 * end;
+    int cn = first, hn = first / np2, rn = first % np2;
+    int inext;
+    float s_xy, s_z, c_xy, c_z;        // sample and centre coordinates: half 0 holds (x, z), half 1 (y, -)
+    v16f X1[4];
+    auto fetch_index = [&](int t) {
+        inext = ball[(size_t)cn * 64 + t * 32 + c];
+        c_xy = cxyz[(size_t)cn * 3 + h], c_z = cxyz[(size_t)cn * 3 + 2];
+    };
+    auto fetch_rows = [&]() {
+        int i0 = inext;
+        asm volatile("" : "+v"(i0));   // consumed HERE, not behind its load (see sa1_kernel)
+        const size_t pt = (size_t)hn * np1 + i0;
+        s_xy = xyz1[pt * 3 + h], s_z = xyz1[pt * 3 + 2];
+        const float* r = P + pt * 128 + 4 * h;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 v = *(const float4*)(r + kt * 32 + 8 * q);
+                X1[kt][4 * q + 0] = v.x;
+                X1[kt][4 * q + 1] = v.y;
+                X1[kt][4 * q + 2] = v.z;
+                X1[kt][4 * q + 3] = v.w;
+            }
     };
     fetch_index(0);
-    fetch_rows(0);
+    fetch_rows();
+    constexpr int G = 4;               // W3 quads per LDS read group: 16 MFMAs = 1024 pipe cycles cover the next group's reads
+    float4 cur[G], nxt[G];
+    {
+        const float4* w3 = (const float4*)(wl + SA2_W3) + lane;
+#pragma unroll
+        for (int i = 0; i < G; ++i) cur[i] = w3[i * 64];
+    }
+    // the last layer's accumulator starts as 16 copies of the lane's bias: four 16-byte LDS reads of a ready-made tile
+    // instead of 16 register moves, issued an m-tile ahead like the weights
+    auto b3_tile = [&](const float* w, int mt) {
+        v16f a;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 t = *(const float4*)(w + SA2_B3S + ((mt * 4 + q) * 32 + c) * 4);
+            a[4 * q + 0] = t.x, a[4 * q + 1] = t.y, a[4 * q + 2] = t.z, a[4 * q + 3] = t.w;
+        }
+        return a;
+    };
+    v16f bs = b3_tile(wl, 0);
+    float kp[8];
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) kp[mt] = 0.0f;
 #pragma unroll 1
-    for (int it = 0; it < NTILE; ++it) {
-        const float* w = wl + opaque_zero();
+    for (int it = 2 * first; it < it_end; ++it) {
+        const float* w = wl + opaque_zero();      // keeps the LDS reads of this iteration inside it
         const int t = it & 1;
-        const bool live = centre0 + (it >> 1) < total;       // a spare wave keeps step with the ring, stores nothing
-        float* out = feat + (size_t)centre_of(it) * 256 + c;
-        const float dx = nx - ncx, dy = ny - ncy, dz = nz - ncz;
-        v16f X1[1][4], Y2[1][4];
-        v16f acc;
+        const float d_xy = s_xy - c_xy, d_z = h ? 0.0f : s_z - c_z;
 #pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            lds_dma_wait_all();       // this wave's piece of chunk g (issued a chunk ago) has landed ...
-            __syncthreads();          // ... everyone's has, and nobody reads slot (g+1)&1 any more
-            if (!(it == NTILE - 1 && g == 7))
-                lds_dma_quad(W2q + (size_t)(((g + 1) & 7) * 8) * 64, ring_mine + ((g + 1) & 1) * SA2_CHUNK);
-            if (g == 0) {
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int off = kt * 32 + 8 * q + 4 * h;
-                        const float4 p = pvn[kt * 4 + q];
-                        float4 wx = *(const float4*)(w + SA2_WX + off), wy = *(const float4*)(w + SA2_WX + 128 + off),
-                               wz = *(const float4*)(w + SA2_WX + 256 + off);
-                        X1[0][kt][4 * q + 0] = fmaxf(fmaf(wz.x, dz, fmaf(wy.x, dy, fmaf(wx.x, dx, p.x))), 0.0f);
-                        X1[0][kt][4 * q + 1] = fmaxf(fmaf(wz.y, dz, fmaf(wy.y, dy, fmaf(wx.y, dx, p.y))), 0.0f);
-                        X1[0][kt][4 * q + 2] = fmaxf(fmaf(wz.z, dz, fmaf(wy.z, dy, fmaf(wx.z, dx, p.z))), 0.0f);
-                        X1[0][kt][4 * q + 3] = fmaxf(fmaf(wz.w, dz, fmaf(wy.w, dy, fmaf(wx.w, dx, p.w))), 0.0f);
-                        if (q == 3) __builtin_amdgcn_sched_barrier(0);   // keep the LDS reads of later rows from piling up
-                    }
-                fetch_index(min(it + 1, NTILE - 1));          // retired by the next barrier's wait, under this chunk
-            }
-            const float4* rb = (const float4*)(w + SA2_RING + (g & 1) * SA2_CHUNK) + lane;
-            float4 a[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] = rb[j * 64];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int quad = g * 8 + j, mt = quad / 16, kq = quad % 16, kt = kq / 4, q = kq % 4;
-                if (kq == 0) acc = bias_tile(w + SA2_B2, mt, h);
-                acc = mfma4(a[j], X1[0][kt], 4 * q, acc);
-                if (kq == 15) Y2[0][mt] = relu16(acc);
+        for (int kt = 0; kt < 4; ++kt) X1[kt] = relu16(mfma(a_z[kt], d_z, mfma(a_xy[kt], d_xy, X1[kt])));
+        // the next tile: the other half of this centre, or the first half of the next one (the last tile prefetches itself)
+        int tn = 1;
+        if (it + 1 < it_end) {
+            tn = t ^ 1;
+            if (t) {
+                ++cn;
+                if (++rn == np2) rn = 0, ++hn;
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        fetch_rows(min(it + 1, NTILE - 1));                    // in flight under the last layer
+        fetch_index(tn);
         __builtin_amdgcn_sched_barrier(0);
-        stream_last_layer<4, 1, 4>((const float4*)(w + SA2_W3) + lane, w + SA2_B3, Y2, c, 8,
-                                   [&](int mt, v16f(&acc3)[1]) {
-                                       float r = pool_swapped(acc3[0]);
-                                       if (h == 0) {
-                                           if (t == 0) {
-                                               keep[mt * 32] = r;
-                                           } else if (live) {
-                                               out[mt * 32] = fmaxf(r, keep[mt * 32]);
-                                           }
-                                       }
-                                   });
+        v16f Y2[4];
+        v16f bt = bias_tile(w + SA2_B2, 0, h);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            v16f acc = bt;
+            if (mt < 3) bt = bias_tile(w + SA2_B2, mt + 1, h);   // read a tile ahead: nobody covers an LDS latency here
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int kq = 0; kq < 16; ++kq) acc = mfma4(w2[mt * 16 + kq], X1[kq / 4], 4 * (kq % 4), acc);
+            Y2[mt] = relu16(acc);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_rows();                                          // in flight under the last layer; X1 is dead
+        __builtin_amdgcn_sched_barrier(0);
+        // last layer, operands swapped (see mfma4_swapped); the read of the group after the last wraps to quad 0, which is
+        // the next tile's first
+        const float4* w3 = (const float4*)(w + SA2_W3) + lane;
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt) {
+            v16f acc = bs;
+#pragma unroll
+            for (int g = 0; g < 16 / G; ++g) {
+                constexpr int LASTG = 16 / G - 1;
+#pragma unroll
+                for (int i = 0; i < G; ++i) nxt[i] = w3[((mt * 16 + (g + 1) * G + i) & 127) * 64];
+                if (g == LASTG) bs = b3_tile(w, (mt + 1) & 7);
+                __builtin_amdgcn_sched_barrier(0);
+                // ONE wait for the group, not one per quad: LDS reads return in order, so everything but the reads just
+                // issued (G weight quads, and the 4 of the bias tile behind the m-tile's last group) has landed
+                if (g == LASTG)
+                    __builtin_amdgcn_s_waitcnt(0xC07F | ((G + 4) << 8));   // lgkmcnt(G + 4)
+                else
+                    __builtin_amdgcn_s_waitcnt(0xC07F | (G << 8));         // lgkmcnt(G)
+#pragma unroll
+                for (int i = 0; i < G; ++i) {
+                    const int kq = g * G + i;
+                    acc = mfma4_swapped(Y2[kq / 4], 4 * (kq % 4), cur[i], acc);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < G; ++i) cur[i] = nxt[i];
+            }
+            kp[mt] = max1(pool_swapped(acc), kp[mt]);          // pooled values are >= +0: the 0 of a fresh centre is neutral
+        }
+        if (t) {
+            // both lane halves hold every tile's 32 maxima, so one full-wave store writes two m-tiles (lane = 32 h + c)
+            float* out = feat + (size_t)(it >> 1) * 256 + lane;
+#pragma unroll
+            for (int mt = 0; mt < 8; mt += 2) out[mt * 32] = h ? kp[mt + 1] : kp[mt];
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) kp[mt] = 0.0f;
+        }
     }
 }
 
@@ -852,11 +977,14 @@ __global__ __launch_bounds__(256, 1) void sa3_kernel(const float* __restrict__ f
 #pragma unroll
             for (int mt = 0; mt < 8; ++mt) ac[mt] = an[mt];
         }
+        // Y1 and the first half of Y2 are from here on only MFMA operands: they move to the accumulator half of the register
+        // file once, as they are made, and the MFMAs read them there (see pin_acc16)
 #pragma unroll
-        for (int mt = 0; mt < 8; ++mt) Y1[0][mt] = relu16(Y1[0][mt]);
-        stream_layer<8, 16, 1, 4>((const float4*)W2p + lane, b2, Y1, h,
-                                  [&](int mt, v16f(&acc)[1]) { Y2[0][mt] = relu16(acc[0]); });
-        stream_last_layer<16, 1, 8>((const float4*)W3p + lane, b3, Y2, c, 32, [&](int mt, v16f(&acc)[1]) {
+        for (int mt = 0; mt < 8; ++mt) Y1[0][mt] = relu16(Y1[0][mt]), pin_acc16(Y1[0][mt]);
+        stream_layer<8, 16, 1, 4>(W2p, lane * 16, b2, Y1, h, [&](int mt, v16f(&acc)[1]) { Y2[0][mt] = relu16(acc[0]); });
+#pragma unroll
+        for (int mt = 0; mt < 8; ++mt) pin_acc16(Y2[0][mt]);
+        stream_last_layer<16, 1, 8>(W3p, lane * 16, b3, Y2, c, 32, [&](int mt, v16f(&acc)[1]) {
             const float v = pool_swapped(acc[0]);
             if (h == 0) {
                 float* sl = &red[wave][mt * 32 + c];
@@ -1088,8 +1216,8 @@ int pn2_ball1(const Pn2Call& c) { return launch_ball(c.point_x, 8, c.B, c.M, c.w
 int pn2_fps2(const Pn2Call& c) { return launch_fps(c.ws.xyz1, 3, c.B, c.np1, c.np2, c.ws.fps2, c.ws.xyz2, c.s); }
 int pn2_ball2(const Pn2Call& c) { return launch_ball(c.ws.xyz1, 3, c.B, c.np1, c.ws.xyz2, c.np2, c.w->radius2, c.ws.ball2, c.s); }
 
-// persistent grid of sa1_kernel: one 4-wave workgroup per CU (one wave per SIMD), cached per device
-int sa1_grid() {
+// persistent grid of sa1_kernel and sa2_kernel: one 4-wave workgroup per CU (one wave per SIMD), cached per device
+int persistent_grid() {
     static int cache[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -1104,7 +1232,7 @@ int sa1_grid() {
 int pn2_sa1(const Pn2Call& c) {
     const float* blob = c.w->blob;
     const int total = c.B * c.np1;
-    hipLaunchKernelGGL(sa1_kernel, dim3(sa1_grid()), dim3(256), 0, c.s, c.point_x, c.M, c.ws.ball1, c.ws.xyz1, c.np1, total,
+    hipLaunchKernelGGL(sa1_kernel, dim3(persistent_grid()), dim3(256), 0, c.s, c.point_x, c.M, c.ws.ball1, c.ws.xyz1, c.np1, total,
                        blob + c.w->w_off[0], blob + c.w->b_off[0], blob + c.w->w_off[1], blob + c.w->b_off[1],
                        blob + c.w->w_off[2], blob + c.w->b_off[2], c.ws.feat1);
     return ossid_launch_status();
@@ -1119,10 +1247,8 @@ int pn2_p2(const Pn2Call& c) {
 int pn2_sa2(const Pn2Call& c) {
     const float* blob = c.w->blob;
     const int total = c.B * c.np2;
-    const int per_wg = (SA2_THREADS / 64) * SA2_CPW;
-    const int grid = (total + per_wg - 1) / per_wg;
     OSSID_ENSURE_LDS(sa2_kernel, (size_t)SA2_LDS_FLOATS * 4);
-    hipLaunchKernelGGL(sa2_kernel, dim3(grid), dim3(SA2_THREADS), SA2_LDS_FLOATS * 4, c.s, c.ws.p2, c.ws.xyz1, c.np1, c.ws.ball2,
+    hipLaunchKernelGGL(sa2_kernel, dim3(persistent_grid()), dim3(256), SA2_LDS_FLOATS * 4, c.s, c.ws.p2, c.ws.xyz1, c.np1, c.ws.ball2,
                        c.ws.xyz2, c.np2, total, blob + c.w->wxyz2_off, blob + c.w->w_off[4], blob + c.w->b_off[4],
                        blob + c.w->w_off[5], blob + c.w->b_off[5], c.ws.feat2);
     return ossid_launch_status();
