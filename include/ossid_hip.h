@@ -887,6 +887,50 @@ int ossid_bop_mssd_mspd(const float* vertices, int V, const double* symmetries, 
                         const double* pose_gt, const float* cams, int Fr, const int32_t* frame_host, int N, double* mssd,
                         double* mspd, void* stream);
 
+/* 8f-6  the scorer's model cloud from the object's mesh (scripts/online_learning.py:303-311 loads model_points /
+ * model_colors / model_normals from zephyr_model_data/{lmo,ycbv}/model_cloud_XX.npz, a download made by a script that is
+ * in neither tree). SPEC.md section 9 (csrc/model_cloud.hip): this build's own definition, parity with zephyr's clouds
+ * unpinned. Raw device pointers, caller-owned memory, launches only: nothing allocates, synchronises or is read back.
+ * vertices f32 [V][3], faces int32 [F][3], colors u8 [V][3]; a face with an index outside [0, V) never votes and weighs 0.
+ *
+ * ossid_cloud_votes (9.2, online_learning.py:303-311): face_id int32 [n][H][W] (ossid_raster_color's face_id_out of n
+ * views; a value outside [0, F) is no face), centres f64 [n][3] = the views' camera centres in the mesh's frame ->
+ * votes int32 [F][2] += (samples that see the face from its front, t >= 0; from its back). The buffer ACCUMULATES: the
+ * caller zeroes it before the first chunk of views. Integer atomicAdd after a run-length count per wave: bit-reproducible.
+ *
+ * ossid_cloud_weights (9.3, online_learning.py:303-311): votes -> weights u64 [F] (w_f, 0 = not usable), prefix u64 [F]
+ * (inclusive sums in face order; prefix[F-1] = Wt, 0 = no usable face), normals f32 [F][3] (unit, turned to the side that
+ * got more votes; 0 for a face that is not usable). Workspace: ossid_cloud_workspace_bytes(F) bytes (0 = bad F), 8-byte
+ * aligned.
+ *
+ * ossid_cloud_candidates (9.4, online_learning.py:303-311): K stratified samples of the weighted faces -> points f32
+ * [K][3], normals f32 [K][3], colors f32 [K][3] (in [0, 1]), face int32 [K] (-1 and zeros everywhere when Wt = 0). A face
+ * that got more votes from its back is read as (p0, p2, p1): the cloud does not depend on how the mesh is wound.
+ *
+ * ossid_cloud_fps (9.5, online_learning.py:303-311): farthest-point sampling of M of K arbitrary FINITE f32 points
+ * [K][3], from point 0, lowest index among equal maxima -> selection int32 [M] in pick order, radius f32 [M] (the
+ * largest distance^2 to the earlier picks when pick j was chosen; radius[0] = +inf). One workgroup of 1024 threads.
+ *
+ * ossid_mesh_diameter (9.6, online_learning.py:303-311; what models_info.json calls `diameter`): out f64 [2] =
+ * (D^2, D), D^2 the largest squared distance between two of the V <= OSSID_MESH_DIAMETER_MAX_VERTICES vertices.
+ *
+ * OSSID_EINVAL before any launch: a NULL pointer, V < 1, F outside [1, OSSID_RASTER_MAX_FACES], n < 1, H W outside
+ * (0, OSSID_RASTER_MAX_PIXELS], M outside [1, OSSID_CLOUD_MAX_POINTS], K outside [M, OSSID_CLOUD_MAX_CANDIDATES] (fps)
+ * or [1, OSSID_CLOUD_MAX_CANDIDATES] (candidates), a workspace that is too small. */
+#define OSSID_CLOUD_MAX_POINTS 4096
+#define OSSID_CLOUD_MAX_CANDIDATES 32768
+#define OSSID_MESH_DIAMETER_MAX_VERTICES 262144
+size_t ossid_cloud_workspace_bytes(int F);
+int ossid_cloud_votes(const int32_t* face_id, int n, int H, int W, const float* vertices, int V, const int32_t* faces, int F,
+                      const double* centres, int32_t* votes, void* stream);
+int ossid_cloud_weights(const float* vertices, int V, const int32_t* faces, int F, const int32_t* votes, void* workspace,
+                        size_t workspace_bytes, uint64_t* weights, uint64_t* prefix, float* normals, void* stream);
+int ossid_cloud_candidates(const float* vertices, int V, const int32_t* faces, int F, const uint8_t* colors,
+                           const int32_t* votes, const uint64_t* prefix, const float* normals, int K, float* points_out,
+                           float* normals_out, float* colors_out, int32_t* face_out, void* stream);
+int ossid_cloud_fps(const float* points, int K, int M, int32_t* selection, float* radius, void* stream);
+int ossid_mesh_diameter(const float* vertices, int V, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

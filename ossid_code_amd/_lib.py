@@ -98,6 +98,12 @@ _PROTOS = {
     "ossid_template_reduce": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_bop_vsd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _i, _vp, _vp, _vp]),
     "ossid_bop_mssd_mspd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "ossid_cloud_workspace_bytes": (_sz, [_i]),
+    "ossid_cloud_votes": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "ossid_cloud_weights": (_i, [_vp, _i, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ossid_cloud_candidates": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ossid_cloud_fps": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "ossid_mesh_diameter": (_i, [_vp, _i, _vp, _vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -220,6 +226,9 @@ RASTER_MAX_POSES = 256         # OSSID_RASTER_MAX_POSES
 RASTER_MAX_PIXELS = 1 << 24    # OSSID_RASTER_MAX_PIXELS
 BOP_MAX_TAUS = 16              # OSSID_BOP_MAX_TAUS
 BOP_MAX_SYMMETRIES = 4096      # OSSID_BOP_MAX_SYMMETRIES
+CLOUD_MAX_POINTS = 4096        # OSSID_CLOUD_MAX_POINTS
+CLOUD_MAX_CANDIDATES = 32768   # OSSID_CLOUD_MAX_CANDIDATES
+MESH_DIAMETER_MAX_VERTICES = 262144   # OSSID_MESH_DIAMETER_MAX_VERTICES
 
 ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
 

@@ -22,7 +22,7 @@ import time
 import numpy as np
 import torch
 
-from . import pipeline, ppf, render
+from . import model_cloud, pipeline, ppf, render
 from .hostutil import K2meta
 from .scoring import networkInference, pose_errors
 
@@ -84,7 +84,10 @@ class OnlineStream:
     ({"DensePoseRefinement": True} refines the hypotheses, SPEC.md 6.9).
     meshes (None = off): dict obj_id -> render.Mesh in metres; the pseudo-label step then renders the mesh of
     frame["obj_id"] at the chosen pose (render.render_depth, pixel_offset = mesh_pixel_offset: 0 is this package's pixel
-    convention, under which the render lines up with the observed depth) instead of splatting the model points."""
+    convention, under which the render lines up with the observed depth) instead of splatting the model points. A frame
+    WITHOUT "model_points" whose object's mesh has vertex colours is scored with the mesh's own cloud
+    (model_cloud.sample_model_cloud(mesh), SPEC.md section 9), built at the object's first frame and kept;
+    a frame that carries its cloud is processed exactly as without meshes."""
 
     def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None,
                  icp_max_dist=None, ppf_models=None, ppf_kwargs=None, meshes=None, mesh_pixel_offset=0.0):
@@ -93,6 +96,7 @@ class OnlineStream:
         self.icp_max_dist = icp_max_dist
         self.ppf_models, self.ppf_kwargs = ppf_models, dict(ppf_kwargs or {})
         self.meshes, self.mesh_pixel_offset = meshes, float(mesh_pixel_offset)
+        self._clouds = {}
         keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ()) + \
             (("ppf",) if ppf_models is not None else ())
         self.times = {k: 0.0 for k in keys}
@@ -106,10 +110,26 @@ class OnlineStream:
         self.times[key] += time.perf_counter() - t0
         return out
 
+    def _with_cloud(self, frame):
+        """The frame itself if it carries model_points; otherwise a copy with the cloud of its object's mesh."""
+        if "model_points" in frame:
+            return frame
+        obj = int(frame["obj_id"])
+        mesh = None if self.meshes is None else self.meshes.get(obj)
+        if mesh is None or getattr(mesh, "colors", None) is None:
+            raise KeyError("frame of object %d has no model_points, and OnlineStream(meshes=...) holds no vertex-coloured "
+                           "mesh of it to sample them from" % obj)
+        if obj not in self._clouds:
+            cloud = model_cloud.sample_model_cloud(mesh)
+            # host arrays, as the frames of a stream carry them (pose_errors and the ICP take numpy)
+            self._clouds[obj] = {k: v.cpu().numpy() for k, v in cloud.as_dict().items()}
+        return {**frame, **self._clouds[obj]}
+
     def process(self, frame):
         """frame: dict with img uint8 [H,W,3], depth [H,W], cam_K, limg [n_t,3,124,124], lmask [n_t,1,124,124], obj_id,
         pose_hypos [N,4,4], pose_gt [4,4], model_points/normals/colors [M,3]. Returns the per-frame result dict."""
         dev = next(self.detector.parameters()).device
+        frame = self._with_cloud(frame)
         self.n_processed += 1
         img_t = torch.from_numpy(np.ascontiguousarray(frame["img"])).to(dev).permute(2, 0, 1).float().div_(255.0)[None]
         batch = {"img": img_t, "obj_id": torch.tensor([int(frame["obj_id"])]), "limg": frame["limg"][None].to(dev),
