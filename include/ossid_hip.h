@@ -931,6 +931,43 @@ int ossid_cloud_candidates(const float* vertices, int V, const int32_t* faces, i
 int ossid_cloud_fps(const float* points, int K, int M, int32_t* selection, float* radius, void* stream);
 int ossid_mesh_diameter(const float* vertices, int V, double* out, void* stream);
 
+/* 8f-7  detection mAP, the second figure the reference's run ends with (scripts/online_learning.py:615-618 ->
+ * evalFinetuneResults, utils/detection.py:137-187, which shells out to an external script that is in neither tree). The
+ * metric's arithmetic that IS in the reference tree: utils/detection_metrics.py:20-156,158-191 (DetectionMetric.calculate_mAP,
+ * find_jaccard_overlap). SPEC.md section 10 (csrc/det_eval.hip): its sequential loop in an order-free form -- a detection is
+ * a true positive iff it is the highest-ranked claimer of its ground truth. Raw device pointers, caller-owned memory,
+ * launches only: nothing allocates, synchronises or is read back. A pointer may be NULL when its array is empty.
+ *
+ * ossid_det_claim (10.2-10.4): det_box f32 [N][4] = x1, y1, x2, y2 (16-byte aligned), det_score f32 [N], det_cls int32 [N]
+ * in [0, C), det_image int32 [N] in [0, I), gt_box f32 [G][4] (16-byte aligned), gt_cls int32 [G], gt_offset int32 [I+1]
+ * (CSR: image i owns the ground truths [gt_offset[i], gt_offset[i+1])) -> best_gt int32 [N] (-1 = none), best_iou f32 [N]
+ * (0 then), sort_key int64 [N] = (cls << 32) | (0xFFFFFFFF - m(score)), m the order-preserving map of the float's bits
+ * with -0 read as +0. The caller sorts the keys ascending and STABLY; the permutation is `order`, and class c owns the
+ * ranks [class_offset[c], class_offset[c+1]) of it.
+ *
+ * ossid_det_match (10.5-10.8): order int32 [N], class_offset int32 [C+1], gt_difficult u8 [G] (NULL = none is),
+ * iou_thr_host f32 [T] in HOST memory (read at call time, passed on as kernel arguments) -> status u8 [T][N] by INPUT
+ * index (0 false positive: no match, 1 true positive, 2 ignored: its ground truth is difficult, 3 false positive:
+ * duplicate), n_easy int32 [C], p11 f32 [T][C][11], ap11 f32 [T][C], apa f64 [T][C], map11 f32 [T], mapa f64 [T], and,
+ * each unless NULL, the curves in RANK order: ctp, cfp int32 [T][N], prec, rec, env f32 [T][N]. Workspace:
+ * ossid_det_eval_workspace_bytes(N, G, C, T) bytes (0 = a size outside its cap), 8-byte aligned. Integer atomicMin /
+ * atomicMax / atomicAdd and fixed-order f64 sums only: bit-reproducible.
+ *
+ * OSSID_EINVAL before any launch: N outside [0, 2^22], G outside [0, 2^20], I outside [1, 2^20], C outside [1, 4096], T
+ * outside [1, OSSID_DET_MAX_THRESHOLDS], a non-finite threshold, a NULL pointer to a non-empty array, a misaligned box
+ * array or workspace, a workspace that is too small. The CONTENTS of the device arrays (finite numbers, indices inside their
+ * ranges, ground truths grouped by image) are the caller's to check -- det_eval.py does; an index outside its range reads
+ * nothing out of bounds here: such a detection has no candidate, such a rank is a false positive. */
+#define OSSID_DET_MAX_THRESHOLDS 16
+size_t ossid_det_eval_workspace_bytes(int N, int G, int C, int T);
+int ossid_det_claim(const float* det_box, const float* det_score, const int32_t* det_cls, const int32_t* det_image, int N,
+                    const float* gt_box, const int32_t* gt_cls, const int32_t* gt_offset, int G, int I, int C, int32_t* best_gt,
+                    float* best_iou, int64_t* sort_key, void* stream);
+int ossid_det_match(const int32_t* best_gt, const float* best_iou, const int32_t* order, const int32_t* class_offset, int N,
+                    const int32_t* gt_cls, const uint8_t* gt_difficult, int G, int C, const float* iou_thr_host, int T,
+                    void* workspace, size_t workspace_bytes, uint8_t* status, int32_t* n_easy, float* p11, float* ap11, double* apa,
+                    float* map11, double* mapa, int32_t* ctp, int32_t* cfp, float* prec, float* rec, float* env, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,9 @@ _PROTOS = {
     "ossid_cloud_candidates": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ossid_cloud_fps": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "ossid_mesh_diameter": (_i, [_vp, _i, _vp, _vp]),
+    "ossid_det_eval_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ossid_det_claim": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ossid_det_match": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _sz] + [_vp] * 12 + [_vp]),
     "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
     "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -229,6 +232,7 @@ BOP_MAX_SYMMETRIES = 4096      # OSSID_BOP_MAX_SYMMETRIES
 CLOUD_MAX_POINTS = 4096        # OSSID_CLOUD_MAX_POINTS
 CLOUD_MAX_CANDIDATES = 32768   # OSSID_CLOUD_MAX_CANDIDATES
 MESH_DIAMETER_MAX_VERTICES = 262144   # OSSID_MESH_DIAMETER_MAX_VERTICES
+DET_MAX_THRESHOLDS = 16        # OSSID_DET_MAX_THRESHOLDS
 
 ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
 

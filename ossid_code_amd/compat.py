@@ -17,6 +17,7 @@ install() registers this package's mirrors under the module paths the script imp
                                                           install(ppf=True, ppf_dense_refinement=True))
     from zephyr.utils.renderer import Renderer, blend      (only with install(renderer=True): render.Renderer, the
                                                           device rasteriser of SPEC.md section 7, depth only)
+    from ossid.utils.detection import evalFinetuneResults  (only with install(det_eval=True): det_eval's, SPEC.md section 10)
 
 resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF unless install(ppf=True), the
 renderer unless install(renderer=True), datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
@@ -45,7 +46,7 @@ def _module(name, made=None):
         return mod
 
 
-def install(ppf=False, ppf_dense_refinement=False, renderer=False):
+def install(ppf=False, ppf_dense_refinement=False, renderer=False, det_eval=False):
     """ppf=True also maps zephyr.utils.halcon_wrapper.PPFModel to this build's device PPF (SPEC.md section 6), whose
     find_surface_model defaults to DensePoseRefinement='false'; with ppf_dense_refinement=True as well it maps
     ppf.PPFModelDense instead, whose default is Halcon's 'true' (SPEC.md 6.9), so the LM-O call (:446, no keyword) gets
@@ -53,7 +54,10 @@ def install(ppf=False, ppf_dense_refinement=False, renderer=False):
     renderer=True maps zephyr.utils.renderer.Renderer to render.Renderer (:485-493). The script's import line also names
     `blend`, which it never calls: when -- and only when -- no real zephyr.utils.renderer imports and the module had to
     be synthesised, render.blend (a plain alpha blend, a placeholder of unknown fidelity) is set so that the line
-    imports. By default a user with pyrender keeps pyrender."""
+    imports. By default a user with pyrender keeps pyrender.
+    det_eval=True maps ossid.utils.detection.{runMapEval, evalFinetuneResults} (:615-618) and
+    ossid.utils.detection_metrics.DetectionMetric to det_eval's (SPEC.md section 10): the mAP the run ends with, without the
+    external script. By default the reference's own stay."""
     from . import dtoid, hostutil, pipeline, scoring, zephyr
     table = {
         "zephyr.datasets.score_dataset": {"ScoreDataset": zephyr.ScoreDataset},
@@ -73,6 +77,10 @@ def install(ppf=False, ppf_dense_refinement=False, renderer=False):
     if renderer:
         from . import render
         table["zephyr.utils.renderer"] = {"Renderer": render.Renderer}
+    if det_eval:
+        from . import det_eval as det_mod
+        table["ossid.utils.detection"] = {"runMapEval": det_mod.runMapEval, "evalFinetuneResults": det_mod.evalFinetuneResults}
+        table["ossid.utils.detection_metrics"] = {"DetectionMetric": det_mod.DetectionMetric}
     for modname, attrs in table.items():
         made = set()
         mod = _module(modname, made)
