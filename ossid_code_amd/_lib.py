@@ -1,244 +1,44 @@
-"""ctypes binding of libossid_hip.so (include/ossid_hip.h). There is no CPU fallback: if the library is
-missing, or a call returns a non-zero status, the caller gets an exception."""
+"""ctypes binding of libossid_hip.so, built at import from include/ossid_hip.h (_abi.py reads it): the header is the only
+statement of the ABI. There is no CPU fallback: if the library is missing, or a call returns a non-zero status, the caller
+gets an exception."""
 import ctypes as C
 import os
 
 import torch
 
+from . import _abi
 from ._build import LIB_PATH
 
 _lib = None
 
-OSSID_OK = 0
-
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "ossid_hip.h")) as _h:
+    _CONSTS, _STRUCTS, _DECLS = _abi.parse(_h.read())
 
-class PN2Weights(C.Structure):
-    """struct ossid_pn2_weights (include/ossid_hip.h)."""
-    _fields_ = [("blob", _vp), ("w_off", C.c_int64 * 12), ("b_off", C.c_int64 * 12), ("wxyz2_off", C.c_int64),
-                ("npoint1", C.c_int32), ("npoint2", C.c_int32), ("radius1", _f), ("radius2", _f)]
+# every `#define OSSID_X n` of the header as X: ABI_VERSION, PN2_NSTAGES, SEQ_MAX_INT, SEQ_MAX_FP (used below), ICP_MAX_POINTS,
+# RASTER_MAX_POSES ... (used by the wrappers)
+globals().update((k[len("OSSID_"):], v) for k, v in _CONSTS.items())
+OSSID_OK = _CONSTS["OSSID_OK"]
 
-
-class ConvDesc(C.Structure):
-    """struct ossid_conv_desc (include/ossid_hip.h)."""
-    _fields_ = [(n, _vp) for n in ("x", "wpk", "bias", "pre_scale", "pre_shift", "post_scale", "post_shift", "out")] + \
-               [(n, C.c_int32) for n in ("batch", "height", "width", "cin", "cout", "taps", "act", "pre_relu",
-                                         "src_height", "src_width", "in_channel_stride", "out_channel_stride",
-                                         "out_channel_offset", "pre_batch_stride")] + [("in_batch_stride", C.c_int64)] + \
-               [("scratch", _vp), ("scratch_bytes", C.c_int64), ("exact", C.c_int32)]
+# the header's descriptor structs under the binding's names, fields as declared
+_STRUCT_NAMES = {"ossid_pn2_weights": "PN2Weights", "ossid_conv_desc": "ConvDesc", "ossid_wgrad_desc": "WgradDesc",
+                 "ossid_chan_op_desc": "ChanOpDesc", "ossid_pack_row": "PackRow", "ossid_seq_op": "SeqOp"}
 
 
-class WgradDesc(C.Structure):
-    """struct ossid_wgrad_desc (include/ossid_hip.h)."""
-    _fields_ = [(n, _vp) for n in ("x", "dy", "pre_scale", "pre_shift", "dw", "workspace")] + [("workspace_bytes", _sz)] + \
-               [(n, C.c_int32) for n in ("batch", "height", "width", "cin", "cout", "taps", "pre_relu", "accumulate",
-                                         "in_channel_stride", "dy_channel_stride", "src_height", "src_width")] + \
-               [(n, _vp) for n in ("dy_add", "dy_add_scale", "dy_add_shift")]
+def _structure(cname, pyname):
+    fields = [(f, _abi.ctype(t) * n if n else _abi.ctype(t)) for f, t, n in _STRUCTS[cname]]
+    return type(pyname, (C.Structure,), {"_fields_": fields, "__doc__": "struct %s (include/ossid_hip.h)." % cname})
 
 
-class ChanOpDesc(C.Structure):
-    """struct ossid_chan_op_desc (include/ossid_hip.h)."""
-    _fields_ = [(n, _vp) for n in ("g", "x", "out", "alpha", "beta", "kappa", "mask_scale", "mask_shift", "partials",
-                                   "sums", "pivot")] + [("n_rows", C.c_int64)] + \
-               [(n, C.c_int32) for n in ("channels", "g_stride", "x_stride", "out_stride", "mask_mode", "accumulate",
-                                         "sum_mode", "sums_row_stride", "defer_finalize")]
+globals().update((_STRUCT_NAMES[c], _structure(c, _STRUCT_NAMES[c])) for c in _STRUCTS)
 
-
-class PackRow(C.Structure):
-    """struct ossid_pack_row (include/ossid_hip.h)."""
-    _fields_ = [("w", _vp), ("wpk", _vp), ("first_block", C.c_int64), ("cout", C.c_int32), ("cin", C.c_int32),
-                ("taps", C.c_int32), ("kind", C.c_int32)]
-
-
-SEQ_MAX_INT, SEQ_MAX_FP = 24, 8
-
-
-class SeqOp(C.Structure):
-    """struct ossid_seq_op (include/ossid_hip.h)."""
-    _fields_ = [("fn", _vp), ("event", _vp), ("slot", C.c_int32), ("wait_for", C.c_int32), ("n_int", C.c_int32),
-                ("n_fp", C.c_int32), ("iarg", C.c_uint64 * SEQ_MAX_INT), ("fparg", C.c_uint64 * SEQ_MAX_FP)]
-
-
-_PROTOS = {
-    "ossid_abi_version": (_i, [C.c_char_p, _i]),
-    "ossid_conv_wino_split_bf16": (_i, []),
-    "ossid_conv_split_bf16": (_i, []),
-    "ossid_conv_wgrad_split_bf16": (_i, []),
-    "ossid_seg_tail_split_bf16": (_i, []),
-    "ossid_zephyr_prep_frame_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ossid_zephyr_prep_frame_f32": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "ossid_zephyr_prep_model": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
-    "ossid_zephyr_project_uv": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp]),
-    "ossid_zephyr_inconst_count": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp]),
-    "ossid_zephyr_featurize": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp]),
-    "ossid_pose_errors": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ossid_dtoid_prep_sample": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
-    "ossid_mask_bbox_heatmap": (_i, [_vp, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
-    "ossid_render_depth_points": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_visib_mask_iou": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
-    "ossid_icp_refine": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_ppf_sample_workspace_bytes": (_sz, [_i]),
-    "ossid_ppf_sample": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_ppf_model_table_words": (C.c_int64, [_i, _f, _f]),
-    "ossid_ppf_model_table": (_i, [_vp, _vp, _i, _f, _f, _vp, _vp, C.c_int64, _vp, _sz, _vp]),
-    "ossid_ppf_scene_normals": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp]),
-    "ossid_ppf_vote_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ossid_ppf_vote": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
-    "ossid_ppf_cluster": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
-    "ossid_ppf_refine_grid_bytes": (_sz, [_i, _i, _f, _f]),
-    "ossid_ppf_refine_model_grid": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp]),
-    "ossid_ppf_refine_workspace_bytes": (_sz, [_i, _i]),
-    "ossid_ppf_refine": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_ppf_refine_match": (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _i, _i, _i, _f, _f, _vp, _sz, _vp, _vp]),
-    "ossid_raster_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ossid_raster_depth": (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp]),
-    "ossid_raster_color_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ossid_raster_color": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_template_reduce": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_bop_vsd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _i, _vp, _vp, _vp]),
-    "ossid_bop_mssd_mspd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "ossid_cloud_workspace_bytes": (_sz, [_i]),
-    "ossid_cloud_votes": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "ossid_cloud_weights": (_i, [_vp, _i, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "ossid_cloud_candidates": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_cloud_fps": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "ossid_mesh_diameter": (_i, [_vp, _i, _vp, _vp]),
-    "ossid_det_eval_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ossid_det_claim": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "ossid_det_match": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _sz] + [_vp] * 12 + [_vp]),
-    "ossid_pn2_fps": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_pn2_ball_query": (_i, [_vp, _i, _i, _i, _vp, _i, _f, _i, _vp, _vp]),
-    "ossid_pn2_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ossid_pn2_score": (_i, [_vp, _i, _i, C.POINTER(PN2Weights), _vp, _sz, _vp] + [_vp] * 7 + [_vp, _vp]),
-    "ossid_pn2_stage_names": (C.c_char_p, []),
-    "ossid_event_create": (_i, [C.POINTER(_vp)]),
-    "ossid_event_destroy": (_i, [_vp]),
-    "ossid_event_record": (_i, [_vp, _vp]),
-    "ossid_event_elapsed_ms": (_i, [_vp, _vp, C.POINTER(_f)]),
-    "ossid_pn2_kernel_names": (C.c_char_p, []),
-    "ossid_dw_xcorr_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
-    "ossid_dw_xcorr_nhwc_bcast": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_dw_xcorr_bwd_x": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ossid_dw_xcorr_bwd_k": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ossid_conv_packed_floats": (_sz, [_i, _i, _i]),
-    "ossid_conv_pack_weights": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "ossid_conv_pack_weights_form": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_conv_packed_floats_form": (C.c_size_t, [_i, _i, _i, _i]),
-    "ossid_conv_nhwc_fwd": (_i, [_vp, _vp]),
-    "ossid_seg_tail_packed_floats": (_sz, []),
-    "ossid_seg_tail_pack_weights": (_i, [_vp, _vp, _vp]),
-    "ossid_seg_tail_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_conv3x3_wgrad_splits": (_i, [_i, _i, _i, _i, _i]),
-    "ossid_conv3x3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ossid_conv3x3_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp]),
-    "ossid_conv_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "ossid_conv_wgrad": (_i, [_vp, _vp]),
-    "ossid_conv_wgrad_group_workspace_bytes": (_sz, [_vp, _i]),
-    "ossid_conv_wgrad_group": (_i, [_vp, _i, _vp, _sz, _vp]),
-    "ossid_conv_pack_weights_dgrad": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "ossid_conv_wino_packed_floats": (C.c_size_t, [_i, _i]),
-    "ossid_conv_pack_weights_wino": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "ossid_conv3x3_wino_fwd": (_i, [_vp, _vp]),
-    "ossid_conv3x3_wino_workspace_bytes": (_sz, [_vp]),
-    "ossid_conv3x3_wino_pair_workspace_bytes": (_sz, [_vp, _vp]),
-    "ossid_conv3x3_wino_fwd_pair": (_i, [_vp, _vp, _vp]),
-    "ossid_fill_zero": (_i, [_vp, _sz, _vp]),
-    "ossid_seg_bce_iou_workspace_bytes": (_sz, [_i]),
-    "ossid_seg_bce_iou_fwd": (_i, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ossid_conv3x3_c1_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "ossid_conv3x3_c1_dgrad": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_conv3x3_c1_wgrad_workspace_bytes": (_sz, []),
-    "ossid_conv3x3_c1_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
-    "ossid_stem_weight_relayout": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ossid_chan_op_partials": (_i, [C.c_longlong, _i]),
-    "ossid_chan_op": (_i, [_vp, _vp]),
-    "ossid_bn_fold_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_bn_fold_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "ossid_conv_pack_weights_table": (_i, [_vp, _i, C.c_longlong, _vp]),
-    "ossid_colsum_finalize": (_i, [_vp, _i, _i, _vp, _i, _vp]),
-    "ossid_avgpool2_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    "ossid_upsample_nearest_bwd_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "ossid_focal_smoothl1_loss_workspace_floats": (_sz, [_i, _i]),
-    "ossid_focal_smoothl1_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_focal_smoothl1_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_im2col_stem": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "ossid_conv1x1_c1_fwd": (_i, [_vp, C.c_longlong, _i, _vp, _vp, _i, _vp, _vp]),
-    "ossid_conv1x1_c1_bwd_workspace_floats": (_sz, [C.c_longlong, _i]),
-    "ossid_conv1x1_c1_bwd": (_i, [_vp, _vp, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_spatial_mean": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_small_matmul": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ossid_detect_post_workspace_bytes": (_sz, [_i, _i]),
-    "ossid_detect_post": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_detect_emit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, C.c_longlong, _vp, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_dense_fwd1_stats_partials": (_i, [C.c_longlong]),
-    "ossid_dense_fwd1_stats": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp]),
-    "ossid_bn_fold_fwd_tail": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_bn_fold_fwd_rows": (_i, [_vp, _vp, _i, _i, C.c_double, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_dense_dgrad3_mask_partials": (_i, [_i, _i, _i]),
-    "ossid_dense_dgrad3_mask": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_dense_dgrad1_acc_partials": (_i, [C.c_longlong]),
-    "ossid_dense_dgrad1_acc": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_dense_fused_available": (_i, []),
-    "ossid_dense_table_bytes": (_sz, [_i]),
-    "ossid_dense_entry": (_i, [_vp, _i, _i, C.c_longlong, _i, _vp, _vp, _vp]),
-    "ossid_dense_layer": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_stem_conv_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "ossid_stem_conv_wgrad_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ossid_stem_conv_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _i, _vp]),
-    "ossid_stem_tail_nhwc": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_stem_tail_pool_nhwc": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "ossid_bn_relu_avgpool2_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
-    "ossid_maxpool_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_dw_add_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_dw_add_stats_partials": (_i, [_i, _i, _i, _i]),
-    "ossid_dw_add_stats_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "ossid_stem_pool_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_stem_pool_bwd_partials": (_i, [_i, _i, _i, _i]),
-    "ossid_stem_pool_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_dw_bwd_k_workspace_floats": (_sz, [_i, _i, _i, _i]),
-    "ossid_dw_bwd_k_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_resample_taps_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
-    "ossid_maxpool_idx_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ossid_maxpool_bwd_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_topk_workspace_bytes": (_sz, [_i, _i]),
-    "ossid_topk": (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
-    "ossid_nms_workspace_bytes": (_sz, [_i]),
-    "ossid_nms": (_i, [_vp, _i, _f, _vp, _sz, _vp, _vp, _vp]),
-    "ossid_decode_clip_boxes": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp]),
-    "ossid_gather_rows": (_i, [_vp, _i, C.c_longlong, _vp, _i, _i, _vp, _vp]),
-    "ossid_dot_expand": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ossid_bias_elu_affine_slice": (_i, [_vp, C.c_longlong, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "ossid_bcast_sub_epilogue": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
-    "ossid_amsgrad_step": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp]),
-    "ossid_seq_replay": (_i, [C.POINTER(SeqOp), _i, C.POINTER(_vp), _i, C.POINTER(_i)]),
-    "ossid_seq_release": (_i, [C.POINTER(SeqOp), _i]),
-    "ossid_seq_probe": (_i, [C.c_int32, _f, _vp, C.c_double, C.c_int64, C.c_int32, _f, _sz, C.c_int32, C.c_int32, C.c_int32,
-                             C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_double), _vp]),
-}
-
-
-ICP_MAX_POINTS = 2048   # OSSID_ICP_MAX_POINTS of include/ossid_hip.h
-PPF_MAX_MODEL_POINTS = 4096    # OSSID_PPF_MAX_MODEL_POINTS
-PPF_MAX_SCENE_SAMPLES = 8192   # OSSID_PPF_MAX_SCENE_SAMPLES
-PPF_MAX_REFINE_MODEL_POINTS = 16384   # OSSID_PPF_MAX_REFINE_MODEL_POINTS
-PPF_MAX_REFINE_SCENE_POINTS = 65536   # OSSID_PPF_MAX_REFINE_SCENE_POINTS
-RASTER_MAX_VERTICES = 1 << 22  # OSSID_RASTER_MAX_VERTICES
-RASTER_MAX_FACES = 1 << 22     # OSSID_RASTER_MAX_FACES
-RASTER_MAX_POSES = 256         # OSSID_RASTER_MAX_POSES
-RASTER_MAX_PIXELS = 1 << 24    # OSSID_RASTER_MAX_PIXELS
-BOP_MAX_TAUS = 16              # OSSID_BOP_MAX_TAUS
-BOP_MAX_SYMMETRIES = 4096      # OSSID_BOP_MAX_SYMMETRIES
-CLOUD_MAX_POINTS = 4096        # OSSID_CLOUD_MAX_POINTS
-CLOUD_MAX_CANDIDATES = 32768   # OSSID_CLOUD_MAX_CANDIDATES
-MESH_DIAMETER_MAX_VERTICES = 262144   # OSSID_MESH_DIAMETER_MAX_VERTICES
-DET_MAX_THRESHOLDS = 16        # OSSID_DET_MAX_THRESHOLDS
-
-ABI_VERSION = 6      # OSSID_ABI_VERSION of include/ossid_hip.h: the struct layouts below (tests/test_abi.py compares the two)
+# name -> (restype, [argtypes]) of every entry point the header declares; every pointer but char* is c_void_p
+_PROTOS = {name: (_abi.ctype(ret), [_abi.ctype(t) for t in params]) for name, (ret, params) in _DECLS.items()}
 
 
 def exported_symbols():
-    """Names include/ossid_hip.h declares (kept in step by tests/test_abi.py)."""
+    """Names include/ossid_hip.h declares."""
     return sorted(_PROTOS)
 
 
@@ -602,9 +402,6 @@ def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
             raise RuntimeError("the OSSID hot path runs on the GPU only (got a %s tensor)" % t.device)
-
-
-PN2_NSTAGES = 9
 
 
 class StageEvents:

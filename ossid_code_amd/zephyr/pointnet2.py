@@ -10,6 +10,7 @@ Linear) so a state_dict saved from that architecture loads key for key. The forw
 torch: the parameters are folded (BN into the convolution), permuted into SPEC.md's canonical channel order,
 packed into the MFMA operand layout of csrc/pn2.hip and handed to libossid_hip.so.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -211,6 +212,7 @@ class PointNet2SSG(nn.Module):
                        feat3=torch.empty(B, 1024, **f32))
         f = _lib.fn("ossid_pn2_score")
         wsb = _lib.fn("ossid_pn2_workspace_bytes")
+        w_ref = ctypes.byref(w)
 
         def launch(b0, nb, events):
             nbytes = wsb(nb, M, np1, np2)
@@ -218,7 +220,7 @@ class PointNet2SSG(nn.Module):
             dargs = [None] * 7
             if dbg is not None:
                 dargs = [dbg[k][b0:b0 + nb].data_ptr() for k in ("fps1", "ball1", "feat1", "fps2", "ball2", "feat2", "feat3")]
-            rc = f(point_x[b0:b0 + nb].data_ptr(), nb, M, w, ws.data_ptr(), nbytes, scores[b0:b0 + nb].data_ptr(),
+            rc = f(point_x[b0:b0 + nb].data_ptr(), nb, M, w_ref, ws.data_ptr(), nbytes, scores[b0:b0 + nb].data_ptr(),
                    *dargs, None if events is None else events.arr, _lib.stream())
             _lib.check(rc, "ossid_pn2_score")
 
