@@ -289,14 +289,16 @@ __device__ __forceinline__ void stream_last_layer(const float* __restrict__ Wu, 
 
 // ---- furthest point sampling: one workgroup per point set -----------------------------------------
 // LDS: pts[n] = (x,y,z,|p|^2), tmp[n] running min distance. One barrier per pick: the four waves'
-// (best, index) pairs go through a double-buffered 4-entry LDS slot.
+// (best, index) pairs go through a double-buffered 4-entry LDS slot. (The slot is carved from the dynamic LDS too: the
+// launcher raises the kernel's dynamic limit to the whole 160 KiB, which a kernel with static LDS beside it is refused.)
+constexpr int FPS_LDS_SLOT_BYTES = 2 * 4 * 8;
 __global__ __launch_bounds__(256) void fps_kernel(const float* __restrict__ xyz, int stride, int n, int npoint,
                                                   int* __restrict__ idx_out, float* __restrict__ new_xyz) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4* pts = (float4*)smem;
     float* tmp = (float*)(pts + n);
-    __shared__ float rbest[2][4];
-    __shared__ int rbesti[2][4];
+    float (*rbest)[4] = (float (*)[4])(tmp + n);
+    int (*rbesti)[4] = (int (*)[4])(tmp + n + 8);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* base = xyz + (size_t)blockIdx.x * n * stride;
     for (int k = tid; k < n; k += 256) {
@@ -372,35 +374,135 @@ __global__ __launch_bounds__(256) void fps_kernel(const float* __restrict__ xyz,
 // pick costs P distance updates per lane (VALU), one DPP max-scan across the wave, one ballot and one LDS hand-off
 // between the four waves. Because lower lanes (and lower waves) own lower indices, "first maximum in index order"
 // -- pointnet2's tie rule -- is simply the lowest lane holding the maximum: no (value, index) pair reduction.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_max(float v) {
-    // lanes with no source lane keep `old` = -2 (below every candidate: distances are >= 0, the sentinel is -1)
-    int src = __float_as_int(v);
-    int moved = __builtin_amdgcn_update_dpp(__float_as_int(-2.0f), src, CTRL, ROW_MASK, 0xf, false);
-    return fmaxf(v, __int_as_float(moved));
+//
+// What a pick costs is what this kernel costs: 1000 workgroups x 4 waves x 511 picks issue every instruction of the pick
+// loop, at four waves per SIMD, and the vector pipe is the limit (profiles/r10_sampling_before.txt). So the loop is
+// written for instruction COUNT:
+//   distances     x and y of the points (2i, 2i+1) sit in adjacent registers and go through the packed f32 instructions
+//                 as a PAIR: dx, dy, dx*dx, dy*dy, + = 5 v_pk for two points. (Packing dx with dy of ONE point, as the
+//                 compiler does by itself, makes every packed instruction wait for the one before it.) The operation
+//                 order is SPEC 4.1's, (dx*dx + dy*dy) + dz*dz, each operation rounded on its own.
+//   running min   one v_min_f32 per point (min1: fminf() puts a canonicalising v_max x, x in front of it, since the
+//                 compiler cannot see that a value carried round the loop is no signalling NaN; a distance never is).
+//   arg-max       running distances are >= +0 or the sentinel -1, never NaN and never -0, so as SIGNED INTEGERS they order
+//                 exactly as floats. The lane maximum is v_max3_i32 (P/2 instructions), the wave scan is v_max_i32 in
+//                 its DPP form (one instruction per step), and no index travels with the value: the winner's index is
+//                 recovered afterwards from P ballots "tmp[j] == wave maximum" -- the lowest lane of mask j is the first
+//                 lane whose j-th point holds the maximum, lane * P + j is its index, and the smallest of those is the
+//                 first maximum in index order. The rest of that is scalar. The sentinel needs no case of its own: with
+//                 nothing selectable every value is -1, the first maximum is lane 0 / j 0 of wave 0 = index 0, which
+//                 is what pointnet2 keeps.
+//   hand-off      lane 0 of each wave writes (maximum, index) as one 8-byte LDS word, double-buffered; after the pick's
+//                 one barrier every lane reads the four pairs with two ds_read_b128, takes the first wave holding the
+//                 largest maximum and reads that point's coordinates for the next pick.
+//   output        the picked indices collect in LDS (one ds_write per pick, no global store and so no vmcnt wait in
+//                 front of the barrier) and leave, with their coordinates, in one coalesced pass after the last pick.
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// min of two floats as ONE instruction (see max1; here the second operand is carried round a loop)
+__device__ __forceinline__ float min1(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
 }
 
-// inclusive max-scan of a wave64 (gfx9 DPP: row_shr 1,2,4,8 then row_bcast 15 / 31); lane 63 ends with the maximum
-__device__ __forceinline__ float wave_max_dpp(float v) {
-    v = dpp_max<0x111, 0xf>(v);   // row_shr:1
-    v = dpp_max<0x112, 0xf>(v);   // row_shr:2
-    v = dpp_max<0x114, 0xf>(v);   // row_shr:4
-    v = dpp_max<0x118, 0xf>(v);   // row_shr:8
-    v = dpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v = dpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+// one step of the wave's max-scan: lanes with no source lane (and rows outside ROW_MASK) keep their own value. `old` is
+// the identity of the signed max, which lets the compiler fold the move into v_max_i32's own DPP form.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_imax(int v) {
+    const int moved = __builtin_amdgcn_update_dpp((int)0x80000000, v, CTRL, ROW_MASK, 0xf, false);
+    return max(v, moved);
+}
+
+// maximum of a wave64 (gfx9 DPP: row_shr 1,2,4,8 then row_bcast 15 / 31 leave it in lane 63), as a wave-uniform value
+__device__ __forceinline__ int wave_imax_dpp(int v) {
+    v = dpp_imax<0x111, 0xf>(v);   // row_shr:1
+    v = dpp_imax<0x112, 0xf>(v);   // row_shr:2
+    v = dpp_imax<0x114, 0xf>(v);   // row_shr:4
+    v = dpp_imax<0x118, 0xf>(v);   // row_shr:8
+    v = dpp_imax<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+    v = dpp_imax<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+constexpr int FPS_REG_MAX_N = 256 * 12;   // the register form's limits: 12 points per lane,
+constexpr int FPS_REG_MAX_NPOINT = 3072;  // and the picked-index list beside the points in 64 KiB of LDS
+
+// the pick loop. A pick travels as the LDS ADDRESS of its point (pts + 16 * index, made in scalar registers by the wave
+// that found it), so the next pick's coordinates are read with no address arithmetic; picked[jj] receives pick jj in that
+// form, one pick late (by the lanes that are writing anyway). Returns the last pick.
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) const v2f lds_v2f;
+typedef __attribute__((address_space(3))) const v4f lds_v4f;
+
+template <int P, bool PLANAR>
+__device__ __forceinline__ unsigned fps_pick_loop(const v2f (&X)[P / 2], const v2f (&Y)[P / 2], const v2f (&Z)[P / 2],
+                                                  float (&tmp)[P], unsigned pts_addr, unsigned* picked, int2 (*slot)[4],
+                                                  int npoint, int lane, int wave) {
+    unsigned old = pts_addr;   // index 0
+    for (int jj = 1; jj < npoint; ++jj) {
+        float pox, poy, poz = 0.0f;
+        if (PLANAR) {
+            const v2f po = *(lds_v2f*)(size_t)old;
+            pox = po.x, poy = po.y;
+        } else {
+            const v4f po = *(lds_v4f*)(size_t)old;
+            pox = po.x, poy = po.y, poz = po.z;
+        }
+#pragma unroll
+        for (int i = 0; i < P / 2; ++i) {
+            const v2f dx = X[i] - pox, dy = Y[i] - poy;
+            v2f d = dx * dx + dy * dy;
+            if (!PLANAR) {
+                const v2f dz = Z[i] - poz;
+                d = d + dz * dz;
+            }
+            tmp[2 * i] = min1(d.x, tmp[2 * i]);
+            tmp[2 * i + 1] = min1(d.y, tmp[2 * i + 1]);
+        }
+        int m = __float_as_int(tmp[0]);
+#pragma unroll
+        for (int j = 1; j < P; ++j) m = max(m, __float_as_int(tmp[j]));
+        const int wmax = wave_imax_dpp(m);
+        // the wave's first maximum: the lowest lane that holds one, and in it the lowest j (scalar from here on)
+        unsigned long long mk[P], any = 0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            mk[j] = __ballot(__float_as_int(tmp[j]) == wmax);
+            any |= mk[j];
+        }
+        const int src = __builtin_ctzll(any);   // (some lane holds the maximum: `any` is never 0)
+        int jsel = P - 1;
+#pragma unroll
+        for (int j = P - 2; j >= 0; --j) jsel = ((mk[j] >> src) & 1) ? j : jsel;
+        const unsigned wpick = pts_addr + 16u * (unsigned)(wave * (64 * P) + src * P + jsel);
+        const int buf = jj & 1;
+        if (lane == 0) {
+            slot[buf][wave] = make_int2(wmax, (int)wpick);
+            picked[jj - 1] = old;
+        }
+        __syncthreads();
+        const int4 a = *(const int4*)&slot[buf][0], b = *(const int4*)&slot[buf][2];
+        const int M = max(max(a.x, a.z), max(b.x, b.z));
+        // the FIRST wave with the largest maximum: an equal maximum in a later wave has a higher index
+        old = (unsigned)(a.x == M ? a.y : a.z == M ? a.w : b.x == M ? b.y : b.w);
+    }
+    return old;
 }
 
 template <int P>
 __global__ __launch_bounds__(256) void fps_reg_kernel(const float* __restrict__ xyz, int stride, int n, int npoint,
                                                       int* __restrict__ idx_out, float* __restrict__ new_xyz) {
+    static_assert(P % 2 == 0, "points go through the packed instructions in pairs");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* pts = (float4*)smem;   // read-only copy for the "current point" broadcast
-    __shared__ float rbest[2][4];
-    __shared__ int rbesti[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float4* pts = (float4*)smem;        // read-only copy for the "current point" broadcast
+    unsigned* picked = (unsigned*)(pts + n);   // the picks, in order, as LDS addresses of their points
+    const unsigned pts_addr = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+    __shared__ __attribute__((aligned(16))) int2 slot[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float* base = xyz + (size_t)blockIdx.x * n * stride;
-    float px[P], py[P], pz[P], tmp[P];
+    v2f X[P / 2], Y[P / 2], Z[P / 2];
+    float tmp[P];
     int anyz = 0;
 #pragma unroll
     for (int j = 0; j < P; ++j) {
@@ -412,87 +514,155 @@ __global__ __launch_bounds__(256) void fps_reg_kernel(const float* __restrict__ 
             z = base[(size_t)k * stride + 2];
             pts[k] = make_float4(x, y, z, 0.f);
         }
-        px[j] = x, py[j] = y, pz[j] = z;
+        X[j / 2][j % 2] = x, Y[j / 2][j % 2] = y, Z[j / 2][j % 2] = z;
         anyz |= (z != 0.0f);
         // a point that may never be picked (|p|^2 <= 1e-3, or padding) gets running distance -1: min(d, -1) stays -1
-        // and -1 never beats the initial best of -1, which is exactly pointnet2's `continue`
+        // and -1 never beats a live point's distance (>= 0), which is exactly pointnet2's `continue`
         tmp[j] = ((k < n) && (((x * x + y * y) + z * z) > 1e-3f)) ? 1e10f : -1.0f;
     }
     // the scorer's point sets are planar (SPEC 3.4: channel 2 is 0): with every z == 0 the dz terms are exact zeros and
     // can be skipped without changing a single bit; any non-zero z in the set selects the general loop
     const bool planar = !__syncthreads_or(anyz);
-    int old = 0;
+    const unsigned last = planar ? fps_pick_loop<P, true>(X, Y, Z, tmp, pts_addr, picked, slot, npoint, lane, wave)
+                                 : fps_pick_loop<P, false>(X, Y, Z, tmp, pts_addr, picked, slot, npoint, lane, wave);
+    if (tid == 0) picked[npoint - 1] = last;
+    __syncthreads();
     int* io = idx_out + (size_t)blockIdx.x * npoint;
     float* xo = new_xyz + (size_t)blockIdx.x * npoint * 3;
-    if (tid == 0) {
-        io[0] = 0;
-        xo[0] = pts[0].x;
-        xo[1] = pts[0].y;
-        xo[2] = pts[0].z;
-    }
-    for (int jj = 1; jj < npoint; ++jj) {
-        const float4 po = pts[old];
-        float best = -1.0f;
-        int besti = 0;
-        if (planar) {
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                const float dx = px[j] - po.x, dy = py[j] - po.y;
-                const float d2 = fminf(dx * dx + dy * dy, tmp[j]);
-                tmp[j] = d2;
-                if (d2 > best) {
-                    best = d2;
-                    besti = tid * P + j;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                const float dx = px[j] - po.x, dy = py[j] - po.y, dz = pz[j] - po.z;
-                const float d2 = fminf((dx * dx + dy * dy) + dz * dz, tmp[j]);
-                tmp[j] = d2;
-                if (d2 > best) {
-                    best = d2;
-                    besti = tid * P + j;
-                }
-            }
-        }
-        const float wmax = wave_max_dpp(best);
-        const unsigned long long who = __ballot(best == wmax);
-        const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)who) - 1);
-        const int widx = __builtin_amdgcn_readlane(besti, src);
-        const int buf = jj & 1;
-        if (lane == 0) {
-            rbest[buf][wave] = wmax;
-            rbesti[buf][wave] = widx;
-        }
-        __syncthreads();
-        float b = rbest[buf][0];
-        int bi = rbesti[buf][0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const float ob = rbest[buf][w];
-            if (ob > b) {   // strict: an equal maximum in a later wave has a higher index
-                b = ob;
-                bi = rbesti[buf][w];
-            }
-        }
-        old = (b > -1.0f) ? bi : 0;   // nothing selectable (all points at the origin): pointnet2 keeps index 0
-        if (tid == 0) {
-            io[jj] = old;
-            const float4 p = pts[old];
-            xo[3 * jj] = p.x;
-            xo[3 * jj + 1] = p.y;
-            xo[3 * jj + 2] = p.z;
-        }
+    for (int j = tid; j < npoint; j += 256) {
+        const int k = (int)((picked[j] - pts_addr) >> 4);
+        const float4 p = pts[k];
+        io[j] = k;
+        xo[3 * j] = p.x;
+        xo[3 * j + 1] = p.y;
+        xo[3 * j + 2] = p.z;
     }
 }
 
-// ---- ball query: one wave per centre, 64 candidate points per ballot -------------------------------
+// ---- ball query, register-resident form: the whole point set in every wave's registers ------------------
+// A workgroup of BQR_WAVES waves stages the point set once in LDS (coordinate planes, padded to NCH chunks of 64 with NaN,
+// which is inside no ball: the tail of the last chunk needs no bound check and no mask), every wave copies ALL of it into
+// registers -- lane l holds point 64 c + l of every chunk c, x (y, z) of chunks 2i and 2i+1 in adjacent registers -- and
+// then walks the centres wave, wave + W, ... of its hypothesis. Per centre nothing is read but the centre itself (a
+// wave-uniform scalar load, issued a centre ahead), and a chunk costs, with its hits:
+//   2.5 (4 with z)  distances of two chunks at a time in the packed f32 instructions, `cx - p.x` and the operation
+//                   order of the oracle, each operation rounded on its own
+//   1               the compare, whose result IS the chunk's ballot over 64 consecutive indices, in scalar registers
+//   2               v_mbcnt_lo / v_mbcnt_hi: the lane's rank among the chunk's hits
+//   2               address (rank * 4 + the scalar base that carries the running count) and ds_write_b32 of 64 c + lane
+//                   (which the compiler keeps as a register per chunk, made once per wave)
+// and everything else -- count (s_bcnt1), early exit -- is scalar. Hits go to a row of the wave in LDS; the row has room
+// for a whole group of BQR_GROUP chunks past the 64th hit, so the body of a group has no bound check, and
+// "64 found" is tested once per group. The centre's 64 indices, padded with the first hit (= row[0]), then leave as one
+// coalesced 256-byte store. There is no wait inside the chunk loop: the only LDS traffic are the writes.
+//
+// The planar fast path skips the dz term where it is an exact +0 for every pair the workgroup looks at, which changes no
+// bit: it is taken when every point AND every centre of the workgroup has z == 0 (a workgroup-wide OR while staging, as in
+// fps_reg_kernel; the scorer's sets are planar and their centres are members). A centre off the plane selects the general path.
+//
+// 8 waves per workgroup: NCH = 48 with z needs 144 registers for the points alone, over the 128 a 16-wave workgroup
+// can have; at 8 waves the 8/16/32-chunk forms stay within 128 registers, so two workgroups share a CU (4 waves per SIMD),
+// and the LDS for two (2 x (12 B x 2048 + 10 KiB)) is there. A workgroup covers up to BQR_CPB = 256 centres of one hypothesis
+// (SA1: two workgroups per hypothesis, 2000 over the chip's 512 places). Measured at 1000 x 2048 points, 512 centres each
+// (profiles/r10_sampling_after.txt): 256 centres per workgroup 0.247 ms, 512 centres 0.254 ms (staging twice costs less than
+// the coarser tail), BQR_GROUP = 2 instead of 4 0.259 ms.
+constexpr int BQ_CPB = 512;       // centres per workgroup, LDS form
+constexpr int BQR_CPB = 256;      // centres per workgroup, register form
+constexpr int BQR_WAVES = 8, BQR_THREADS = 64 * BQR_WAVES;
+constexpr int BQR_GROUP = 4;                          // chunks between two tests of the count
+constexpr int BQR_ROW = 64 * (BQR_GROUP + 1);         // ints per wave: slots < 64 + 64 * BQR_GROUP inside a group
+constexpr int BQR_MAX_N = 64 * 48;
+
+typedef __attribute__((address_space(3))) int lds_int;
+
+template <int NCH, bool PLANAR>
+__device__ __forceinline__ void ball_reg_centres(const float* xs, const float* ys, const float* zs, int* row,
+                                                 const float* __restrict__ cen, int* __restrict__ out, int jbeg, int jend,
+                                                 float r2, int lane) {
+    v2f X[NCH / 2], Y[NCH / 2], Z[PLANAR ? 1 : NCH / 2];
+#pragma unroll
+    for (int i = 0; i < NCH / 2; ++i) {
+        X[i] = v2f{xs[128 * i + lane], xs[128 * i + 64 + lane]};
+        Y[i] = v2f{ys[128 * i + lane], ys[128 * i + 64 + lane]};
+        if (!PLANAR) Z[i] = v2f{zs[128 * i + lane], zs[128 * i + 64 + lane]};
+    }
+    const unsigned row_addr = (unsigned)(size_t)(lds_int*)row;   // (LDS addresses are 32 bits)
+    float cx = 0.f, cy = 0.f, cz = 0.f;
+    if (jbeg < jend) cx = cen[3 * (size_t)jbeg], cy = cen[3 * (size_t)jbeg + 1], cz = cen[3 * (size_t)jbeg + 2];
+    for (int j = jbeg; j < jend; j += BQR_WAVES) {
+        const float ccx = cx, ccy = cy, ccz = cz;
+        const int jn = min(j + BQR_WAVES, jend - 1);   // the next centre, a centre ahead (the last one reads itself again)
+        cx = cen[3 * (size_t)jn], cy = cen[3 * (size_t)jn + 1], cz = cen[3 * (size_t)jn + 2];
+        int cnt = 0;
+#pragma unroll
+        for (int g = 0; g < NCH / BQR_GROUP; ++g) {
+#pragma unroll
+            for (int i = g * (BQR_GROUP / 2); i < (g + 1) * (BQR_GROUP / 2); ++i) {
+                const v2f dx = ccx - X[i], dy = ccy - Y[i];
+                v2f d = dx * dx + dy * dy;
+                if (!PLANAR) {
+                    const v2f dz = ccz - Z[i];
+                    d = d + dz * dz;
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const bool hit = d[h] < r2;
+                    const unsigned long long mk = __ballot(hit);
+                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32),
+                                                               __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0));
+                    // the slot's address is rank * 4 + a SCALAR base; seen through, the compiler adds count and rank in the
+                    // vector pipe first
+                    unsigned base = row_addr + 4 * cnt;
+                    asm("" : "+s"(base));
+                    if (hit) *(lds_int*)(size_t)(base + 4 * rank) = (2 * i + h) * 64 + lane;
+                    cnt += __popcll(mk);
+                }
+            }
+            if (cnt >= 64) break;
+        }
+        // row[0] is the first hit; with no hit at all the row is stale and the answer is 0 everywhere
+        const int mine = row[lane];
+        int first = __builtin_amdgcn_readfirstlane(mine);
+        first = cnt > 0 ? first : 0;
+        out[(size_t)j * 64 + lane] = lane < cnt ? mine : first;
+    }
+}
+
+template <int NCH>
+__global__ __launch_bounds__(BQR_THREADS, NCH <= 32 ? 4 : 2) void ball_query_reg_kernel(const float* __restrict__ xyz, int stride, int n,
+                                                                     const float* __restrict__ new_xyz, int npoint,
+                                                                     float r2, int* __restrict__ idx) {
+    static_assert(NCH % BQR_GROUP == 0 && BQR_GROUP % 2 == 0, "whole groups of chunk pairs");
+    constexpr int N = 64 * NCH;
+    __shared__ float xs[N], ys[N], zs[N];
+    __shared__ int rows[BQR_WAVES][BQR_ROW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x;
+    const float* base = xyz + (size_t)b * n * stride;
+    const float nan = __builtin_nanf("");
+    int offplane = 0;
+    for (int k = tid; k < N; k += BQR_THREADS) {
+        float x = nan, y = nan, z = 0.0f;
+        if (k < n) x = base[(size_t)k * stride], y = base[(size_t)k * stride + 1], z = base[(size_t)k * stride + 2];
+        xs[k] = x, ys[k] = y, zs[k] = z;
+        offplane |= (z != 0.0f);
+    }
+    const int jbeg = blockIdx.y * BQR_CPB, jend = min(jbeg + BQR_CPB, npoint);
+    const float* cen = new_xyz + (size_t)b * npoint * 3;
+    for (int j = jbeg + tid; j < jend; j += BQR_THREADS) offplane |= (cen[3 * (size_t)j + 2] != 0.0f);
+    const bool planar = !__syncthreads_or(offplane);
+    int* out = idx + (size_t)b * npoint * 64;
+    if (planar)
+        ball_reg_centres<NCH, true>(xs, ys, zs, rows[wave], cen, out, jbeg + wave, jend, r2, lane);
+    else
+        ball_reg_centres<NCH, false>(xs, ys, zs, rows[wave], cen, out, jbeg + wave, jend, r2, lane);
+}
+
+// ---- ball query, LDS form: the fallback for point sets over BQR_MAX_N points ----------------------------
+// One wave per centre, 64 candidate points per ballot, the points read from LDS chunk by chunk.
 // A workgroup of 16 waves stages the point set ONCE in LDS and covers up to 512 centres (all of SA1's): with 64 centres
 // per 4-wave workgroup the same 2048 points were staged eight times per hypothesis (and the strided 12-of-32-byte row
 // reads cost twice their bytes), which was most of the kernel.
-constexpr int BQ_CPB = 512;       // centres per workgroup
 constexpr int BQ_THREADS = 1024;
 __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __restrict__ xyz, int stride, int n,
                                                                 const float* __restrict__ new_xyz, int npoint, float r2,
@@ -1110,29 +1280,46 @@ Workspace carve(char* base, int B, int M, int np1, int np2) {
 
 template <int P>
 int launch_fps_reg(const float* xyz, int stride, int B, int n, int npoint, int* idx, float* new_xyz, hipStream_t s) {
-    hipLaunchKernelGGL(fps_reg_kernel<P>, dim3(B), dim3(256), (size_t)n * 16, s, xyz, stride, n, npoint, idx, new_xyz);
+    // points (16 B each) and the picked-index list: at most 3072 * 16 + 3072 * 4 bytes, under the 64 KiB every launch may have
+    const size_t lds = (size_t)n * 16 + (size_t)npoint * 4;
+    hipLaunchKernelGGL(fps_reg_kernel<P>, dim3(B), dim3(256), lds, s, xyz, stride, n, npoint, idx, new_xyz);
     return ossid_launch_status();
 }
 
 int launch_fps(const float* xyz, int stride, int B, int n, int npoint, int* idx, float* new_xyz, hipStream_t s) {
-    if (n <= 256 * 2) return launch_fps_reg<2>(xyz, stride, B, n, npoint, idx, new_xyz, s);
-    if (n <= 256 * 4) return launch_fps_reg<4>(xyz, stride, B, n, npoint, idx, new_xyz, s);
-    if (n <= 256 * 8) return launch_fps_reg<8>(xyz, stride, B, n, npoint, idx, new_xyz, s);
-    if (n <= 256 * 12) return launch_fps_reg<12>(xyz, stride, B, n, npoint, idx, new_xyz, s);
-    // larger sets: points and running distances in LDS
-    size_t lds = (size_t)n * 20;
+    if (n <= FPS_REG_MAX_N && npoint <= FPS_REG_MAX_NPOINT) {
+        if (n <= 256 * 2) return launch_fps_reg<2>(xyz, stride, B, n, npoint, idx, new_xyz, s);
+        if (n <= 256 * 4) return launch_fps_reg<4>(xyz, stride, B, n, npoint, idx, new_xyz, s);
+        if (n <= 256 * 8) return launch_fps_reg<8>(xyz, stride, B, n, npoint, idx, new_xyz, s);
+        return launch_fps_reg<12>(xyz, stride, B, n, npoint, idx, new_xyz, s);
+    }
+    // larger sets (or more picks than the register form lists): points and running distances in LDS
+    size_t lds = (size_t)n * 20 + FPS_LDS_SLOT_BYTES;
     if (lds > 160 * 1024 - 1024) return OSSID_EINVAL;
     OSSID_ENSURE_LDS(fps_kernel, lds);
     hipLaunchKernelGGL(fps_kernel, dim3(B), dim3(256), lds, s, xyz, stride, n, npoint, idx, new_xyz);
     return ossid_launch_status();
 }
 
+template <int NCH>
+int launch_ball_reg(const float* xyz, int stride, int B, int n, const float* new_xyz, int npoint, float r2, int* idx,
+                    hipStream_t s) {
+    hipLaunchKernelGGL(ball_query_reg_kernel<NCH>, dim3(B, (npoint + BQR_CPB - 1) / BQR_CPB), dim3(BQR_THREADS), 0, s, xyz,
+                       stride, n, new_xyz, npoint, r2, idx);
+    return ossid_launch_status();
+}
+
 int launch_ball(const float* xyz, int stride, int B, int n, const float* new_xyz, int npoint, float radius, int* idx,
                 hipStream_t s) {
+    const float r2 = radius * radius;
+    if (n <= 64 * 8) return launch_ball_reg<8>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
+    if (n <= 64 * 16) return launch_ball_reg<16>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
+    if (n <= 64 * 32) return launch_ball_reg<32>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
+    if (n <= BQR_MAX_N) return launch_ball_reg<48>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
+    // larger sets: the points stay in LDS
     size_t lds = (size_t)n * 16;
     if (lds > 160 * 1024 - 1024) return OSSID_EINVAL;
     OSSID_ENSURE_LDS(ball_query_kernel, lds);
-    const float r2 = radius * radius;
     hipLaunchKernelGGL(ball_query_kernel, dim3(B, (npoint + BQ_CPB - 1) / BQ_CPB), dim3(BQ_THREADS), lds, s, xyz, stride,
                        n, new_xyz, npoint, r2, idx);
     return ossid_launch_status();
@@ -1183,7 +1370,7 @@ int ossid_event_elapsed_ms(void* start, void* stop, float* ms_out_host) {
 }
 
 const char* ossid_pn2_kernel_names(void) {
-    return "fps_reg_kernel,fps_kernel,ball_query_kernel,sa1_kernel,p2_kernel,sa2_kernel,sa3_kernel,fc_head_kernel";
+    return "fps_reg_kernel,fps_kernel,ball_query_reg_kernel,ball_query_kernel,sa1_kernel,p2_kernel,sa2_kernel,sa3_kernel,fc_head_kernel";
 }
 
 // The nine stages of ossid_pn2_score, one launcher each.
