@@ -968,6 +968,46 @@ int ossid_det_match(const int32_t* best_gt, const float* best_iou, const int32_t
                     void* workspace, size_t workspace_bytes, uint8_t* status, int32_t* n_easy, float* p11, float* ap11, double* apa,
                     float* map11, double* mapa, int32_t* ctp, int32_t* cfp, float* prec, float* rec, float* env, void* stream);
 
+/* 8f-6  Keypoint-feature pose hypotheses (scripts/online_learning.py:52-76 getFeaturizedModels, :427 featurizeScene, :435
+ * FeatureModel.match: zephyr's SIFT featurization in the reference), SPEC.md section 11. Raw device pointers, caller-owned
+ * memory; counts that depend on the data stay on the device, so one frame is one launch chain with no host round trip.
+ * Integer arithmetic, min / max and integer atomics only where results meet: bit-reproducible.
+ *
+ * ossid_feat_pyramid (11.1): img u8 [H][W][3] RGB -> pyramid, an int32 buffer of ossid_feat_pyramid_bytes(H, W, octaves)
+ * bytes (0 = bad sizes: a side below 8, H W above OSSID_RASTER_MAX_PIXELS, octaves outside [1, OSSID_FEAT_MAX_OCTAVES]):
+ * per octave o (side (side + 1) / 2 of the one before; an octave with a side below 8 and those after it do not exist) five
+ * levels [5][Ho][Wo], octaves back to back, then two scratch planes.
+ * ossid_feat_detect (11.2): depth f32 [H][W], mask u8 [H][W] -> keypoints int32 [max_keypoints][4] = (o, s, y, x) in
+ * ascending order, count int32 [2] = the true number of keypoints, 1 iff it exceeds max_keypoints (then only the first
+ * max_keypoints rows are written and every later stage treats the frame as having none). max_keypoints <=
+ * OSSID_FEAT_MAX_KEYPOINTS. Workspace: ossid_feat_detect_workspace_bytes(H, W, octaves) bytes.
+ * ossid_feat_describe (11.3-11.5), rows [0, count): bins int32 [max_keypoints] (orientation bin, -1 = window left the
+ * image), descriptors u8 [max_keypoints][128] (values 0 .. 127), frames f64 [max_keypoints][4][4], ok u8 [max_keypoints]
+ * (0 = dropped: its descriptor and frame rows are zero).
+ * ossid_feat_match (11.7): the nearest of the Nm <= OSSID_FEAT_MAX_MODEL_FEATURES model descriptors u8 [Nm][128] for every
+ * scene row with ok != 0 -> match int32 [max_keypoints][3] = (j, d2, w), (-1, 0, 0) for a skipped row or Nm = 0. Descriptor
+ * arrays 16-byte aligned; workspace ossid_feat_match_workspace_bytes(max_keypoints) bytes, 8-byte aligned.
+ * ossid_feat_hypotheses (11.8): T_i = F_s,i F_m,j^-1 -> cand_poses f64 [max_keypoints][4][4] and peaks int32
+ * [max_keypoints][3] = (j, 0, w), the inputs of ossid_ppf_cluster(peaks, cand_poses, count, max_keypoints, 1, 1024, D, ...). */
+#define OSSID_FEAT_MAX_KEYPOINTS 4096
+#define OSSID_FEAT_MAX_MODEL_FEATURES 65536
+#define OSSID_FEAT_MAX_OCTAVES 3
+size_t ossid_feat_pyramid_bytes(int H, int W, int octaves);
+int ossid_feat_pyramid(const uint8_t* img, int H, int W, int octaves, void* pyramid, size_t pyramid_bytes, void* stream);
+size_t ossid_feat_detect_workspace_bytes(int H, int W, int octaves);
+int ossid_feat_detect(const void* pyramid, int H, int W, int octaves, const float* depth, const uint8_t* mask, int contrast,
+                      int max_keypoints, void* workspace, size_t workspace_bytes, int32_t* keypoints, int32_t* count,
+                      void* stream);
+int ossid_feat_describe(const void* pyramid, int H, int W, int octaves, const float* depth, float fx, float fy, float cx,
+                        float cy, const int32_t* keypoints, const int32_t* count, int max_keypoints, int32_t* bins,
+                        uint8_t* descriptors, double* frames, uint8_t* ok, void* stream);
+size_t ossid_feat_match_workspace_bytes(int max_keypoints);
+int ossid_feat_match(const uint8_t* scene_descriptors, const uint8_t* scene_ok, const int32_t* count, int max_keypoints,
+                     const uint8_t* model_descriptors, int Nm, void* workspace, size_t workspace_bytes, int32_t* match,
+                     void* stream);
+int ossid_feat_hypotheses(const int32_t* match, const double* scene_frames, const int32_t* count, int max_keypoints,
+                          const double* model_frames, int Nm, int32_t* peaks, double* cand_poses, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,9 @@ install() registers this package's mirrors under the module paths the script imp
     from zephyr.utils.renderer import Renderer, blend      (only with install(renderer=True): render.Renderer, the
                                                           device rasteriser of SPEC.md section 7, depth only)
     from ossid.utils.detection import evalFinetuneResults  (only with install(det_eval=True): det_eval's, SPEC.md section 10)
+    from zephyr.full_pipeline.model_featurization import FeatureModel          (only with install(sift=True): the keypoint-
+    from zephyr.full_pipeline.scene_featurization import featurizeScene         feature hypotheses of --use_sift_hypos,
+                                                                                features.py, SPEC.md section 11)
 
 resolve to the MI355X path. Only these names are provided; everything else the script imports (Halcon PPF unless install(ppf=True), the
 renderer unless install(renderer=True), datasets) stays with the reference / zephyr installation -- when a real `zephyr` or
@@ -46,7 +49,7 @@ def _module(name, made=None):
         return mod
 
 
-def install(ppf=False, ppf_dense_refinement=False, renderer=False, det_eval=False):
+def install(ppf=False, ppf_dense_refinement=False, renderer=False, det_eval=False, sift=False):
     """ppf=True also maps zephyr.utils.halcon_wrapper.PPFModel to this build's device PPF (SPEC.md section 6), whose
     find_surface_model defaults to DensePoseRefinement='false'; with ppf_dense_refinement=True as well it maps
     ppf.PPFModelDense instead, whose default is Halcon's 'true' (SPEC.md 6.9), so the LM-O call (:446, no keyword) gets
@@ -57,7 +60,10 @@ def install(ppf=False, ppf_dense_refinement=False, renderer=False, det_eval=Fals
     imports. By default a user with pyrender keeps pyrender.
     det_eval=True maps ossid.utils.detection.{runMapEval, evalFinetuneResults} (:615-618) and
     ossid.utils.detection_metrics.DetectionMetric to det_eval's (SPEC.md section 10): the mAP the run ends with, without the
-    external script. By default the reference's own stay."""
+    external script. By default the reference's own stay.
+    sift=True maps zephyr.full_pipeline.model_featurization.FeatureModel and
+    zephyr.full_pipeline.scene_featurization.featurizeScene (:52-76, :427-435, --use_sift_hypos) to features.py's
+    (SPEC.md section 11: this build's own keypoint features, not zephyr's SIFT). By default zephyr's own stay."""
     from . import dtoid, hostutil, pipeline, scoring, zephyr
     table = {
         "zephyr.datasets.score_dataset": {"ScoreDataset": zephyr.ScoreDataset},
@@ -81,6 +87,10 @@ def install(ppf=False, ppf_dense_refinement=False, renderer=False, det_eval=Fals
         from . import det_eval as det_mod
         table["ossid.utils.detection"] = {"runMapEval": det_mod.runMapEval, "evalFinetuneResults": det_mod.evalFinetuneResults}
         table["ossid.utils.detection_metrics"] = {"DetectionMetric": det_mod.DetectionMetric}
+    if sift:
+        from . import features
+        table["zephyr.full_pipeline.model_featurization"] = {"FeatureModel": features.FeatureModel}
+        table["zephyr.full_pipeline.scene_featurization"] = {"featurizeScene": features.featurizeScene}
     for modname, attrs in table.items():
         made = set()
         mod = _module(modname, made)

@@ -2,8 +2,9 @@
 scripts/online_learning.py:314-591 (SURVEY.md 8d cfg-5, 8e "full online stream"):
 
     detect (DtoidNet.forwardTestTime)                       :346
-    -> pose hypotheses (GIVEN per frame, or device PPF with OnlineStream(ppf_models=...), :384-418 / :441-447;
-       SIFT is out of scope)
+    -> pose hypotheses (GIVEN per frame, or device PPF with OnlineStream(ppf_models=...), :384-418 / :441-447, and
+       the keypoint-feature hypotheses of --use_sift_hypos with OnlineStream(feature_models=...), :427-437, put in
+       front of the PPF ones as :437 does)
     -> per-hypothesis ADD/ADI (:452) -> Zephyr score (networkInference, :464) -> argmax (:466-469)
     -> optional ICP refinement of the chosen pose (icpRefinement, :471-480; OnlineStream(icp_max_dist=...))
     -> predicted depth (:485-493: the mesh rasteriser of SPEC.md section 7 with OnlineStream(meshes=...), otherwise
@@ -22,7 +23,7 @@ import time
 import numpy as np
 import torch
 
-from . import model_cloud, pipeline, ppf, render
+from . import features, model_cloud, pipeline, ppf, render
 from .hostutil import K2meta
 from .scoring import networkInference, pose_errors
 
@@ -82,6 +83,10 @@ class OnlineStream:
     inside the DTOID boxes (ppf.PPFModel.find_hypotheses, mask as online_learning.py:384-405 builds it), timed under
     times["ppf"], `frame["pose_hypos"]` is not read, and the result carries "n_hypos" and the hypotheses ("ppf_hypos"). ppf_kwargs go to find_hypotheses
     ({"DensePoseRefinement": True} refines the hypotheses, SPEC.md 6.9).
+    feature_models (None = off): dict obj_id -> features.FeatureModel built in metres; its hypotheses (SPEC.md section 11,
+    from the frame's image and depth inside the same mask) are put in front of the PPF ones, timed under times["sift"],
+    and the result carries "n_feature_hypos"; with feature models only, `frame["pose_hypos"]` is not read either and a
+    frame without any hypothesis gets one identity pose.
     meshes (None = off): dict obj_id -> render.Mesh in metres; the pseudo-label step then renders the mesh of
     frame["obj_id"] at the chosen pose (render.render_depth, pixel_offset = mesh_pixel_offset: 0 is this package's pixel
     convention, under which the render lines up with the observed depth) instead of splatting the model points. A frame
@@ -90,15 +95,17 @@ class OnlineStream:
     a frame that carries its cloud is processed exactly as without meshes."""
 
     def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None,
-                 icp_max_dist=None, ppf_models=None, ppf_kwargs=None, meshes=None, mesh_pixel_offset=0.0):
+                 icp_max_dist=None, ppf_models=None, ppf_kwargs=None, meshes=None, mesh_pixel_offset=0.0,
+                 feature_models=None, feature_kwargs=None):
         self.detector, self.scorer, self.dataset = detector, scorer, score_dataset
         self.threshold, self.symmetric, self.finetune_fn = confident_threshold, symmetric, finetune_fn
         self.icp_max_dist = icp_max_dist
         self.ppf_models, self.ppf_kwargs = ppf_models, dict(ppf_kwargs or {})
         self.meshes, self.mesh_pixel_offset = meshes, float(mesh_pixel_offset)
+        self.feature_models, self.feature_kwargs = feature_models, dict(feature_kwargs or {})
         self._clouds = {}
         keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ()) + \
-            (("ppf",) if ppf_models is not None else ())
+            (("ppf",) if ppf_models is not None else ()) + (("sift",) if feature_models is not None else ())
         self.times = {k: 0.0 for k in keys}
         self.n_processed = 0
 
@@ -135,8 +142,17 @@ class OnlineStream:
         batch = {"img": img_t, "obj_id": torch.tensor([int(frame["obj_id"])]), "limg": frame["limg"][None].to(dev),
                  "lmask": frame["lmask"][None].to(dev)}
         det = self._timed("detect", lambda: self.detector.forwardTestTime(batch))
-        hypos = frame["pose_hypos"] if self.ppf_models is None else \
-            self._timed("ppf", lambda: self._ppf_hypotheses(frame, det))
+        n_feat = None
+        if self.ppf_models is None and self.feature_models is None:
+            hypos = frame["pose_hypos"]
+        else:
+            hypos = None if self.ppf_models is None else self._timed("ppf", lambda: self._ppf_hypotheses(frame, det))
+            if self.feature_models is not None:
+                feat = self._timed("sift", lambda: self._feature_hypotheses(frame, det))
+                n_feat = len(feat)
+                hypos = feat if hypos is None else np.concatenate([feat, hypos], axis=0)       # :437
+                if len(hypos) == 0:
+                    hypos = np.eye(4)[None]
         pp_err = self._timed("pose_err", lambda: pose_errors(hypos, frame["pose_gt"], frame["model_points"],
                                                              self.symmetric))
         data = {k: frame[k] for k in ("img", "depth", "cam_K", "model_points", "model_normals", "model_colors")}
@@ -174,10 +190,11 @@ class OnlineStream:
         return {"pred_pose": pred_pose, "pred_score": pred_score, "pred_err": pred_err,
                 "confident": confident, "dtoid_score": det["pred_scores"][:1], "dtoid_bbox": det["pred_bbox"][:1],
                 "pred_mask_visib": pred_mask_visib, "sample": sample, **({"icp": icp} if icp is not None else {}),
-                **({"n_hypos": len(hypos), "ppf_hypos": hypos} if self.ppf_models is not None else {})}
+                **({"n_hypos": len(hypos), "ppf_hypos": hypos} if self.ppf_models is not None else {}),
+                **({"n_hypos": len(hypos), "n_feature_hypos": n_feat} if n_feat is not None else {})}
 
-    def _ppf_hypotheses(self, frame, det):
-        """online_learning.py:384-405 (mask from the expanded DTOID boxes) and :441-447 (PPF on the masked depth)."""
+    def _detection_mask(self, frame, det):
+        """online_learning.py:384-405: the mask from the expanded DTOID boxes -> (depth f32 [H,W], mask u8 [H,W])."""
         depth = np.asarray(frame["depth"], dtype=np.float32)
         H, W = depth.shape
         mask = np.zeros((H, W), dtype=np.uint8)
@@ -188,6 +205,22 @@ class OnlineStream:
                 continue
             x1, y1, x2, y2 = pipeline.expand_box(x1, y1, x2, y2, H, W, 1.2)
             mask[int(y1):int(y2), int(x1):int(x2)] = 1
+        return depth, mask
+
+    def _feature_hypotheses(self, frame, det):
+        """online_learning.py:427-435 on the device -> poses f64 [n,4,4], n >= 0."""
+        depth, mask = self._detection_mask(frame, det)
+        model = self.feature_models[int(frame["obj_id"])]
+        poses, _scores, info = model.find_hypotheses(depth, frame["img"], mask, frame["cam_K"], **self.feature_kwargs)
+        n, found = (int(v) for v in info[:2].cpu().numpy())
+        if found > features.MAX_KEYPOINTS:
+            raise ValueError("OnlineStream: the frame has %d keypoints, more than the %d the feature stage takes; raise "
+                             "feature_kwargs['contrast']" % (found, features.MAX_KEYPOINTS))
+        return poses[:n].cpu().numpy()
+
+    def _ppf_hypotheses(self, frame, det):
+        """The mask of :384-405 and :441-447 (PPF on the masked depth)."""
+        depth, mask = self._detection_mask(frame, det)
         model = self.ppf_models[int(frame["obj_id"])]
         out = model.find_hypotheses(depth, mask, frame["cam_K"], **self.ppf_kwargs)
         poses, info = out[0], out[2]
