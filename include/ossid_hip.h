@@ -136,6 +136,80 @@ int ossid_event_elapsed_ms(void* start, void* stop, float* ms_out_host);
 /* Names of the kernels the scorer launches, for profile post-processing (static string). */
 const char* ossid_pn2_kernel_names(void);
 
+/* ---------------------------------------------------------------------------------------------
+ * Z3t  PointNet2SSG in training mode (csrc/pn2_train.hip, SPEC.md 12)
+ *     the module scripts/online_learning.py:212-227 builds and loads; restates pointnet2_ops' PointnetSAModule,
+ *     SharedMLP (Conv2d 1x1 no bias, BatchNorm2d, ReLU) and the classification head with batch-statistics BatchNorm
+ *     and dropout, in TORCH's channel order (xyz first), and the backward pass to every parameter. zephyr's own
+ *     training recipe is in neither tree: unpinned.
+ * Layers 0..10 are the BatchNorm layers (SA1 x3, SA2 x3, SA3 x3, FC x2), layer 11 the last linear layer.
+ * w[l] is torch's [cout][cin] matrix. run_mean / run_var (each may be NULL) are updated in place as torch does
+ * (momentum 0.1, unbiased variance): hand in staging copies and copy_ them into the module's buffers.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct ossid_pn2_train_params {
+    const float* w[12];
+    const float* gamma[11];
+    const float* beta[11];
+    const float* bias;
+    float* run_mean[11];
+    float* run_var[11];
+    int32_t npoint1, npoint2;
+    float radius1, radius2;
+} ossid_pn2_train_params;
+
+typedef struct ossid_pn2_train_grads {
+    float* w[12];
+    float* gamma[11];
+    float* beta[11];
+    float* bias;
+} ossid_pn2_train_grads;
+
+/* The decisions the forward took (every pointer may be NULL): relu[l] u8 [rows of layer l][C_l], 1 where the ReLU
+ * passed; argmax[m] i32 [B][npoint][C] of the three poolings (the row within the group: sample 0..63 for SA1 and
+ * SA2, point 0..npoint2-1 for SA3); the sampling and grouping indices as ossid_pn2_score exports them. */
+typedef struct ossid_pn2_train_dbg {
+    uint8_t* relu[11];
+    int32_t* argmax[3];
+    int32_t* fps1;
+    int32_t* ball1;
+    int32_t* fps2;
+    int32_t* ball2;
+} ossid_pn2_train_dbg;
+
+/* 0 for a shape the training path refuses (B < 2, M < npoint1, npoint % 32 != 0, npoint1 < npoint2). */
+size_t ossid_pn2_train_workspace_bytes(int B, int M, int npoint1, int npoint2);
+
+/* point_x [B][M][8], keep_mask u8 [B][256] (1 = kept; kept values are scaled by 1/(1-p_drop)) -> scores [B].
+ * The workspace (>= ossid_pn2_train_workspace_bytes, 256-byte aligned) keeps what the backward pass needs.
+ * OSSID_EINVAL: a refused shape, a short or misaligned workspace, a NULL parameter. */
+int ossid_pn2_train_forward(const float* point_x, int B, int M, const ossid_pn2_train_params* w,
+                            const uint8_t* keep_mask, float p_drop, void* workspace, size_t workspace_bytes,
+                            float* scores, const ossid_pn2_train_dbg* dbg, void* stream);
+/* dscores [B] -> the gradient of every parameter (fresh values, not accumulated), from the workspace the forward
+ * call left. It works in place on the workspace: ONE backward per forward. */
+int ossid_pn2_train_backward(const float* dscores, int B, int M, const ossid_pn2_train_params* w, float p_drop,
+                             void* workspace, size_t workspace_bytes, const ossid_pn2_train_grads* g, void* stream);
+
+/* The stage kernels on their own (row-major f32 matrices):
+ * Z[R][C] = X[R][Kp] (columns 0..Kr) . W[C][Kr]^T;  dX[R][N] = dZ[R][C] . W[C][ldw] (columns 0..N);
+ * dW[C][Kr] = dZ[R][C]^T . X[R][Kp] (columns 0..Kr), split over rows and combined in split order. */
+int ossid_pn2_train_linear_fwd(const float* X, int R, int Kp, const float* W, int Kr, int C, float* Z, void* stream);
+int ossid_pn2_train_linear_dgrad(const float* dZ, int R, int C, const float* W, int ldw, int N, float* dX,
+                                 void* stream);
+size_t ossid_pn2_train_wgrad_workspace_bytes(int R, int C, int Kr);
+int ossid_pn2_train_linear_wgrad(const float* dZ, int R, int C, const float* X, int Kp, int Kr, float* dW,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* out[b][i][:] = sum over e (ascending) with idx[b][e] == i of dG[b][e][:]; dG [B][E][Cf], idx [B][E], out [B][n][Cf] */
+int ossid_pn2_train_ungroup(const float* dG, const int32_t* idx, int B, int E, int n, int Cf, float* out,
+                            void* stream);
+/* per-channel batch mean, 1/sqrt(biased variance + 1e-5) and (var may be NULL) the biased variance of Z[R][C], C <= 1024 */
+size_t ossid_pn2_train_bn_stats_workspace_bytes(void);
+int ossid_pn2_train_bn_stats(const float* Z, int R, int C, void* workspace, size_t workspace_bytes, float* mean,
+                             float* rstd, float* var, void* stream);
+/* out[g][c] = max over s < S of relu(bn(Z[g*S+s][c])), argmax = the first such s */
+int ossid_pn2_train_bn_relu_pool(const float* Z, int G, int S, int C, const float* mean, const float* rstd,
+                                 const float* gamma, const float* beta, float* out, int32_t* argmax, void* stream);
+
 /* =============================================================================================
  * DTOID ops (paths under /root/reference/python/ossid/models/dtoid)
  * ============================================================================================= */

@@ -9,6 +9,11 @@ Sequential(Conv2d 1x1 no-bias, BatchNorm2d, ReLU) x3; fc_layer = Linear/BN1d/ReL
 Linear) so a state_dict saved from that architecture loads key for key. The forward pass does not run in
 torch: the parameters are folded (BN into the convolution), permuted into SPEC.md's canonical channel order,
 packed into the MFMA operand layout of csrc/pn2.hip and handed to libossid_hip.so.
+
+Training mode (SPEC.md 12): forward() of a module in .train() runs csrc/pn2_train.hip through a torch.autograd.Function --
+pointnet2_ops' PointnetSAModule / SharedMLP and the classification head with batch-statistics BatchNorm and dropout, in
+torch's own channel order -- so `model.train(); loss.backward(); optimizer.step()` fits the module the reference builds at
+scripts/online_learning.py:212-227 on this build's features. zephyr's own training recipe is in neither tree: unpinned.
 """
 import ctypes
 import os
@@ -174,12 +179,13 @@ class PointNet2SSG(nn.Module):
             self._packed = (key, dblob, st)
         return self._packed[2]
 
-    def _workspace(self, nbytes, device):
+    def _workspace(self, nbytes, device, kind="score"):
         """Grow-only scratch buffer, one per (device, stream): frames in flight on different HIP streams must not
-        share stage buffers."""
+        share stage buffers. The training path's (kind "train") lives from a forward to its backward, apart from the
+        inference path's."""
         if self._ws is None:
             self._ws = {}
-        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+        key = (str(device), torch.cuda.current_stream(device).cuda_stream) + (() if kind == "score" else (kind,))
         ws = self._ws.get(key)
         if ws is None or ws.numel() < nbytes:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -229,6 +235,156 @@ class PointNet2SSG(nn.Module):
                 launch(b0, min(self.MAX_CHUNK, B - b0), stage_events)
         return (scores, dbg) if debug else scores
 
-    def forward(self, data):
+    def forward(self, data, keep_mask=None, generator=None, debug=None):
+        """Eval mode: score(). Training mode (SPEC.md 12): [B, 1] scores with a grad_fn, from csrc/pn2_train.hip.
+        keep_mask: the dropout keep-mask, bool / u8 [B, 256] (default: drawn on the host from `generator`, a CPU
+        torch.Generator, with the module's p); debug: a dict that receives the decisions the forward took."""
         x = data["point_x"] if isinstance(data, dict) else data
-        return self.score(x).unsqueeze(1)
+        if not self.training:
+            return self.score(x).unsqueeze(1)
+        return self.train_forward(x, keep_mask, generator, debug)
+
+    # ---- training path ----------------------------------------------------------------------------------------------
+    def train_layers(self):
+        """([12 Conv2d / Linear], [11 BatchNorm]) in the kernels' layer order: SA1 x3, SA2 x3, SA3 x3, FC1, FC2, last."""
+        lin, bns = [], []
+        for sa in self.SA_modules:
+            seq = sa.mlps[0]
+            for li in range(3):
+                lin.append(seq[3 * li])
+                bns.append(seq[3 * li + 1])
+        fc = self.fc_layer
+        return lin + [fc[0], fc[3], fc[7]], bns + [fc[1], fc[4]]
+
+    def draw_keep_mask(self, B, generator=None):
+        """u8 [B, 256] on the host: 1 with probability 1 - p."""
+        p = float(self.fc_layer[6].p)
+        return (torch.rand(B, 256, generator=generator) >= p).to(torch.uint8)
+
+    def train_forward(self, point_x, keep_mask=None, generator=None, debug=None):
+        if point_x.dtype != torch.float32 or point_x.dim() != 3 or point_x.shape[2] != 8:
+            raise ValueError("point_x must be float32 [B, M, 8]")
+        if point_x.requires_grad:
+            raise ValueError("no gradient is defined for point_x: the featurizer is not trained (SPEC.md 12)")
+        B, M, _ = point_x.shape
+        if B < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s"
+                             % (torch.Size([B, 512]),))
+        np1 = self.SA_modules[0].npoint
+        if M < np1:
+            raise ValueError("need at least npoint=%d model points per hypothesis, got %d" % (np1, M))
+        if keep_mask is None:
+            keep_mask = self.draw_keep_mask(B, generator)
+        keep_mask = keep_mask.to(device=point_x.device, dtype=torch.uint8).contiguous()
+        if keep_mask.shape != (B, 256):
+            raise ValueError("keep_mask must be [B, 256]")
+        lin, bns = self.train_layers()
+        params = [m.weight for m in lin] + [b.weight for b in bns] + [b.bias for b in bns] + [lin[11].bias]
+        return _TrainFn.apply(self, point_x.contiguous(), keep_mask, debug, *params)
+
+    def _train_backend_for(self, point_x):
+        backend = getattr(self, "_train_backend", None)
+        return backend if backend is not None else HipTrainBackend()
+
+
+class HipTrainBackend:
+    """The two C-ABI calls of the training path. A backend is what _TrainFn needs: forward(model, x, W, gamma, beta, bias,
+    run_mean, run_var, keep, p, debug) -> (scores [B], state) updating run_mean / run_var in place, and
+    backward(state, dscores [B]) -> (dW list, dgamma list, dbeta list, dbias), every gradient in the flat [cout, cin] /
+    [C] / [1] layout of the kernels."""
+
+    def forward(self, model, x, W, gamma, beta, bias, run_mean, run_var, keep, p, debug):
+        _lib.require_cuda(x, keep, *W)
+        dev = x.device
+        B, M, _ = x.shape
+        np1, np2 = model.SA_modules[0].npoint, model.SA_modules[1].npoint
+        st = _lib.PN2TrainParams()
+        tensors = [t.contiguous().float() for t in W + gamma + beta + [bias]]
+        for i in range(12):
+            st.w[i] = tensors[i].data_ptr()
+        for i in range(11):
+            st.gamma[i], st.beta[i] = tensors[12 + i].data_ptr(), tensors[23 + i].data_ptr()
+            st.run_mean[i], st.run_var[i] = run_mean[i].data_ptr(), run_var[i].data_ptr()
+        st.bias = tensors[34].data_ptr()
+        st.npoint1, st.npoint2 = np1, np2
+        st.radius1, st.radius2 = model.SA_modules[0].radius, model.SA_modules[1].radius
+        nbytes = _lib.fn("ossid_pn2_train_workspace_bytes")(B, M, np1, np2)
+        if nbytes == 0:
+            raise ValueError("the training path refuses B=%d, M=%d, npoint=%d/%d (SPEC.md 12)" % (B, M, np1, np2))
+        ws = model._workspace(nbytes, dev, kind="train")
+        scores = torch.empty(B, dtype=torch.float32, device=dev)
+        dbg = None
+        if debug is not None:
+            C = LAYER_C[:11]
+            rows = [B * np1 * 64] * 3 + [B * np2 * 64] * 3 + [B * np2] * 3 + [B] * 2
+            i32, u8 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.uint8, device=dev)
+            debug.update(relu=[torch.empty(r, c, **u8) for r, c in zip(rows, C)],
+                         argmax=[torch.empty(B, np1, 128, **i32), torch.empty(B, np2, 256, **i32), torch.empty(B, 1, 1024, **i32)],
+                         fps1=torch.empty(B, np1, **i32), ball1=torch.empty(B, np1, 64, **i32),
+                         fps2=torch.empty(B, np2, **i32), ball2=torch.empty(B, np2, 64, **i32))
+            dbg = _lib.PN2TrainDbg()
+            for i in range(11):
+                dbg.relu[i] = debug["relu"][i].data_ptr()
+            for i in range(3):
+                dbg.argmax[i] = debug["argmax"][i].data_ptr()
+            for k in ("fps1", "ball1", "fps2", "ball2"):
+                setattr(dbg, k, debug[k].data_ptr())
+        with torch.cuda.device(dev):
+            rc = _lib.fn("ossid_pn2_train_forward")(x.data_ptr(), B, M, ctypes.byref(st), keep.data_ptr(), float(p),
+                                                    ws.data_ptr(), nbytes, scores.data_ptr(),
+                                                    None if dbg is None else ctypes.byref(dbg), _lib.stream())
+        _lib.check(rc, "ossid_pn2_train_forward")
+        return scores, (st, tensors, ws, nbytes, B, M, float(p), dev)
+
+    def backward(self, state, dscores):
+        st, tensors, ws, nbytes, B, M, p, dev = state
+        grads = [torch.empty_like(t) for t in tensors]
+        g = _lib.PN2TrainGrads()
+        for i in range(12):
+            g.w[i] = grads[i].data_ptr()
+        for i in range(11):
+            g.gamma[i], g.beta[i] = grads[12 + i].data_ptr(), grads[23 + i].data_ptr()
+        g.bias = grads[34].data_ptr()
+        dscores = dscores.contiguous().float()
+        with torch.cuda.device(dev):
+            rc = _lib.fn("ossid_pn2_train_backward")(dscores.data_ptr(), B, M, ctypes.byref(st), p, ws.data_ptr(), nbytes,
+                                                     ctypes.byref(g), _lib.stream())
+        _lib.check(rc, "ossid_pn2_train_backward")
+        return grads[:12], grads[12:23], grads[23:34], grads[34]
+
+
+class _TrainFn(torch.autograd.Function):
+    """Scores of the training-mode forward as a function of the 35 parameters (12 weights, 11 gamma, 11 beta, the last bias).
+    point_x gets no gradient. The running statistics are updated through copy_ from staging tensors, so the buffers' version
+    counters move and the inference path's packed-weight cache (PointNet2SSG._version_key) sees the change."""
+
+    @staticmethod
+    def forward(ctx, model, point_x, keep, debug, *params):
+        lin, bns = model.train_layers()
+        backend = model._train_backend_for(point_x)
+        W = [p.detach().reshape(p.shape[0], -1) for p in params[:12]]
+        gamma, beta, bias = [p.detach() for p in params[12:23]], [p.detach() for p in params[23:34]], params[34].detach()
+        stage = torch.cat([b.running_mean for b in bns] + [b.running_var for b in bns]).to(torch.float32)
+        sizes = [b.num_features for b in bns]
+        parts = list(torch.split(stage, sizes + sizes))
+        scores, state = backend.forward(model, point_x, W, gamma, beta, bias, parts[:11], parts[11:], keep,
+                                        float(model.fc_layer[6].p), debug)
+        for b, m, v in zip(bns, parts[:11], parts[11:]):
+            b.running_mean.copy_(m)
+            b.running_var.copy_(v)
+            b.num_batches_tracked.add_(1)
+        model._train_gen = getattr(model, "_train_gen", 0) + 1
+        ctx.model, ctx.backend, ctx.state, ctx.gen = model, backend, state, model._train_gen
+        ctx.shapes = [p.shape for p in params]
+        return scores.unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, dscores):
+        if ctx.state is None or ctx.gen != ctx.model._train_gen:
+            raise RuntimeError("PointNet2SSG's training workspace holds one forward pass and its backward runs in place: "
+                               "call backward once, before the next training-mode forward")
+        dW, dgamma, dbeta, dbias = ctx.backend.backward(ctx.state, dscores[:, 0])
+        ctx.state = None
+        flat = list(dW) + list(dgamma) + list(dbeta) + [dbias]
+        grads = [g.reshape(s) if need else None for g, s, need in zip(flat, ctx.shapes, ctx.needs_input_grad[4:])]
+        return (None, None, None, None) + tuple(grads)
