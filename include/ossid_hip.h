@@ -1082,6 +1082,75 @@ int ossid_feat_match(const uint8_t* scene_descriptors, const uint8_t* scene_ok, 
 int ossid_feat_hypotheses(const int32_t* match, const double* scene_frames, const int32_t* count, int max_keypoints,
                           const double* model_frames, int Nm, int32_t* peaks, double* cand_poses, void* stream);
 
+/* 8f-8  cluttered multi-object RGB-D scenes with BOP ground truth, in place of the offline BlenderProc renders the
+ * reference pre-trains on (datasets/render_dataset.py:81-189, datasets/dtoid_dataset.py:97-235) and of the depth corruption
+ * it applies to them (utils/augmentation.py:5-26). SPEC.md section 13 (csrc/scene.hip): this build's own definition. Raw
+ * device pointers, caller-owned memory, launches only: nothing allocates, synchronises or is read back; capturable.
+ *
+ * ossid_scene_desc -- a mesh atlas: vertices f32 [Vt][3], colors u8 [Vt][3], faces int32 [Ft][3] with indices LOCAL to
+ * their mesh, meshes int32 [K][4] = (v0, nv, f0, nf); a draw list: instance_mesh int32 [I], transforms f32 [I][4][4]
+ * row-major, scene_first int32 [S+1] (the instances of scene s are [scene_first[s], scene_first[s+1]); an empty scene is
+ * legal), cams f32 [S][4] = fx, fy, cx, cy; and offsets int32 [I+1][2], the caller's prefix sums over the instances of
+ * (ossid_scene_work_items(nf of the instance's mesh), nv of the instance's mesh), whose totals are work_items and records.
+ * background u8 [Sb][H][W][3], Sb = 1 or S, may be NULL. Outputs: color_out u8 [S][H][W][3] (the background, or 0, where
+ * nothing is drawn), depth_out f32 [S][H][W] (0 there), instance_out int32 [S][H][W] (the index into the draw list, -1
+ * there), face_out int32 [S][H][W] (may be NULL; -1 there), facing_out f32 [S][H][W] (may be NULL; 0 there; SPEC 13.4),
+ * amodal_out u32 [I][H][ceil(W / 32)]: bit x & 31 of word x >> 5 of row y is set iff a triangle of the instance covers the
+ * sample of pixel (x, y), whatever hides it. pixel_offset and z_near as ossid_raster_depth.
+ *
+ * ossid_scene_render: one 64-bit key per (scene, pixel), bits(z) << 32 | instance - scene_first[s] << 22 | face, reduced by a
+ * minimum: the nearest depth, among equal depths the lowest instance, then the lowest face. Per pixel the depth, colour
+ * and face are those of ossid_raster_color's render of the winning instance alone, bit for bit. The workspace (16-byte
+ * aligned, ossid_scene_workspace_bytes(records, S, H, W) bytes, 0 = bad sizes) holds the projected vertices and the keys.
+ * Three launches. The CONTENTS of the device arrays are the caller's to check (scenes.py does); an instance whose table
+ * entries lead outside an array is not drawn.
+ *
+ * ossid_scene_gt_info (13.5): amodal, instance_img = instance_out, sensor_depth f32 [S][H][W] -> gt_info int32 [I][12] =
+ * (px_count_all, px_count_visib, px_count_valid, bbox_obj x y w h, bbox_visib x y w h, 0); an empty box is four -1s.
+ * Integer atomics only: bit-reproducible. Three launches.
+ *
+ * ossid_scene_sensor (13.6): depth, facing f32 [S][H][W], thresholds f32 [S], n_rects int32 [S] (values are clamped to
+ * [0, OSSID_SCENE_MAX_RECTS]), rects int32 [S][OSSID_SCENE_MAX_RECTS][4] = (r0, r1, c0, c1): a pixel keeps its depth iff
+ * facing >= thresholds[s] and it lies in no rectangle (rows [r0, r1), columns [c0, c1)). q = rint((double) z * units) of a
+ * kept pixel, 0 when that is not in [0, 65535] -> depth_u16 u16 [S][H][W] = q, depth_out f32 = (float)((double) q *
+ * unit_inv), keep u8 (may be NULL). One launch; no random numbers.
+ *
+ * OSSID_EINVAL before any launch: a NULL pointer that is not optional, S outside [1, OSSID_SCENE_MAX_SCENES], I outside
+ * [0, S * OSSID_SCENE_MAX_INSTANCES], H W outside (0, OSSID_RASTER_MAX_PIXELS], K < 1, Vt outside [1, 2^29], Ft outside
+ * [0, 2^29], work_items outside [0, 2^30], records < 0, Sb not 1 or S with a background, pixel_offset outside [0, 1], z_near negative or not finite, units or unit_inv not positive and finite, a
+ * workspace that is too small or misaligned. */
+#define OSSID_SCENE_MAX_SCENES 256
+#define OSSID_SCENE_MAX_INSTANCES 1024
+#define OSSID_SCENE_MAX_RECTS 6
+typedef struct ossid_scene_desc {
+    const float* vertices;
+    const uint8_t* colors;
+    const int32_t* faces;
+    const int32_t* meshes;
+    const int32_t* instance_mesh;
+    const float* transforms;
+    const int32_t* scene_first;
+    const float* cams;
+    const int32_t* offsets;
+    const uint8_t* background;
+    uint8_t* color_out;
+    float* depth_out;
+    int32_t* instance_out;
+    int32_t* face_out;
+    float* facing_out;
+    uint32_t* amodal_out;
+    int32_t Vt, Ft, K, I, S, H, W, Sb, work_items, records;
+    float pixel_offset, z_near;
+} ossid_scene_desc;
+int ossid_scene_work_items(int n_faces);
+size_t ossid_scene_workspace_bytes(int records, int S, int H, int W);
+int ossid_scene_render(const ossid_scene_desc* desc_host, void* workspace, size_t workspace_bytes, void* stream);
+int ossid_scene_gt_info(const uint32_t* amodal, const int32_t* instance_img, const float* sensor_depth,
+                        const int32_t* scene_first, int I, int S, int H, int W, int32_t* gt_info, void* stream);
+int ossid_scene_sensor(const float* depth, const float* facing, int S, int H, int W, const float* thresholds,
+                       const int32_t* n_rects, const int32_t* rects, double units, double unit_inv, uint16_t* depth_u16,
+                       float* depth_out, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

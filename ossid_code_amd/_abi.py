@@ -9,7 +9,7 @@ import re
 # C scalar -> ctypes. Every pointer is c_void_p (it takes byref(), arrays, pointer instances, None and plain addresses),
 # except char*, which is c_char_p.
 SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
-           "uint8_t": C.c_uint8, "long long": C.c_longlong, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+           "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "long long": C.c_longlong, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
 _POINTEES = ("void", "char")        # what may be pointed to besides SCALARS and the header's own structs
 
 

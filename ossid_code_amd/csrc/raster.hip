@@ -22,43 +22,18 @@
 // the workspace, so that the minimum is the nearest depth and, among equal depths, the lowest face index. Its resolve
 // redoes the winner's setup per pixel, recomputes the exact edge functions and interpolates the vertex colours
 // perspective-correctly. ossid_template_reduce (7.13) is the s x s box filter that makes a template of such a render.
-#include <limits.h>
-
+//
+// The arithmetic of a sample (vertex stage, setup, edge functions, depth, colour) lives in raster_common.h, shared with
+// csrc/scene.hip.
 #include <cmath>
 
-#include "common.h"
+#include "raster_common.h"
 
 namespace {
 
-constexpr int COOP_MIN = 64;          // clipped boxes with more samples than one wave covers in a step go to the wave
 constexpr int TARGET_WAVES = 2048;    // 256 CUs x 8: below this many full waves the triangles are spread thinner
 constexpr int MAX_WAVES = 16;         // waves per workgroup that share the large boxes of a call with few triangles
 constexpr int RESIDENT_WAVES = 8192;  // 256 CUs x 32: extra waves per workgroup are added only while all stay resident
-constexpr unsigned ZFAR = 0x7f800000u;
-constexpr unsigned long long KFAR = ~0ull;   // empty visibility key: above every (bits(z) << 32 | face)
-
-struct __attribute__((aligned(16))) VRec {
-    int sx, sy;      // snapped window coordinates (1/256 pixel); sx == INT_MIN: unusable vertex
-    double rz;       // 1 / (double) Z
-};
-static_assert(sizeof(VRec) == 16, "vertex record");
-
-// SPEC 7.2 for vertex k under transform T (f32 [4][4] row-major) and one camera.
-__device__ __forceinline__ VRec project_vertex(const float* __restrict__ vertices, int k, const float* __restrict__ T, float fx,
-                                               float fy, float cx, float cy, float z_near) {
-    const float x = vertices[3 * (size_t)k], y = vertices[3 * (size_t)k + 1], z = vertices[3 * (size_t)k + 2];
-    const float X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-    const float Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-    const float Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-    const float u = (X / Z) * fx + cx, v = (Y / Z) * fy + cy;
-    const bool ok = (Z > z_near) && isfinite(X) && isfinite(Y) && isfinite(Z) && (fabsf(u) < 1048576.0f) &&
-                    (fabsf(v) < 1048576.0f);      // NaN u, v fail the comparisons
-    VRec r;
-    r.sx = ok ? (int)rintf(u * 256.0f) : INT_MIN;
-    r.sy = ok ? (int)rintf(v * 256.0f) : 0;
-    r.rz = ok ? 1.0 / (double)Z : 0.0;
-    return r;
-}
 
 __global__ __launch_bounds__(256) void raster_prepare_kernel(const float* __restrict__ vertices, int V,
                                                              const float* __restrict__ transforms, int N, float fx, float fy,
@@ -92,33 +67,12 @@ __global__ __launch_bounds__(256) void raster_prepare_color_kernel(const float* 
     }
 }
 
-// One triangle after setup: vertices ordered so that the area A is positive.
-struct Tri {
-    int x0, y0, x1, y1, x2, y2;
-    double r0, r1, r2;
-    int xa, ya, xb, yb;      // clipped box of pixels whose sample can lie inside (inclusive)
-};
-
-// E_ab(p) = dx (py - ay) - dy (px - ax). dx, dy and both offsets fit 31 bits (29-bit coordinates; a sample of the
-// clipped box lies within the triangle's extent), so each product is a 32 x 32 -> 64 multiply and the int64 result exact.
-__device__ __forceinline__ bool edge_in(int ax, int ay, int bx, int by, int px, int py, long long& e) {
-    const int dx = bx - ax, dy = by - ay;
-    e = (long long)dx * (long long)(py - ay) - (long long)dy * (long long)(px - ax);
-    return e > 0 || (e == 0 && (dy > 0 || (dy == 0 && dx < 0)));
-}
-
 // Sample of pixel (x, y): coverage, perspective-correct depth, buffer update. Returns whether it was covered. ZB is
 // unsigned (z-buffer: the float's bits) or unsigned long long (visibility buffer: bits << 32 | face, SPEC 7.11).
 template <typename ZB>
 __device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, int o, int W, ZB* __restrict__ zb, unsigned face) {
-    const int px = 256 * x + o, py = 256 * y + o;
-    long long w0, w1, w2;
-    const bool in2 = edge_in(t.x0, t.y0, t.x1, t.y1, px, py, w2);
-    const bool in0 = edge_in(t.x1, t.y1, t.x2, t.y2, px, py, w0);
-    const bool in1 = edge_in(t.x2, t.y2, t.x0, t.y0, px, py, w1);
-    if (!(in0 && in1 && in2)) return false;
-    const double den = ((double)w0 * t.r0 + (double)w1 * t.r1) + (double)w2 * t.r2;
-    const unsigned zbits = __float_as_uint((float)(area / den));
+    unsigned zbits;
+    if (!sample_depth(t, area, x, y, o, zbits)) return false;
     ZB* p = zb + (size_t)y * W + x;
     if constexpr (sizeof(ZB) == 4) {
         if (zbits < *p) atomicMin(p, zbits);
@@ -159,33 +113,17 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void raster_tri_kernel(const int32_
         }
         if (bad) {
             n_bad = 1;
-        } else {
-            A = (long long)(b.sx - a.sx) * (long long)(c.sy - a.sy) - (long long)(b.sy - a.sy) * (long long)(c.sx - a.sx);
-            if (A == 0) {
-                n_degen = 1;
-            } else {
-                if (A < 0) {
-                    const VRec s = b;
-                    b = c, c = s, A = -A;
-                }
-                t.x0 = a.sx, t.y0 = a.sy, t.x1 = b.sx, t.y1 = b.sy, t.x2 = c.sx, t.y2 = c.sy;
-                t.r0 = a.rz, t.r1 = b.rz, t.r2 = c.rz;
-                // pixels x with min <= 256 x + o <= max: ceil and floor by arithmetic shifts
-                t.xa = max(0, (min(min(t.x0, t.x1), t.x2) - o + 255) >> 8);
-                t.xb = min(W - 1, (max(max(t.x0, t.x1), t.x2) - o) >> 8);
-                t.ya = max(0, (min(min(t.y0, t.y1), t.y2) - o + 255) >> 8);
-                t.yb = min(H - 1, (max(max(t.y0, t.y1), t.y2) - o) >> 8);
-                if (t.xa <= t.xb && t.ya <= t.yb) {
-                    large = (long long)(t.xb - t.xa + 1) * (t.yb - t.ya + 1) > COOP_MIN;
-                    if (large) {
-                        n_large = 1;
-                    } else if (wv == 0) {
-                        bool cov = false;
-                        for (int y = t.ya; y <= t.yb; ++y)
-                            for (int x = t.xa; x <= t.xb; ++x) cov |= shade(t, (double)A, x, y, o, W, zb, (unsigned)tri);
-                        n_cov = cov;
-                    }
-                }
+        } else if (!tri_setup(a, b, c, o, H, W, t, A)) {
+            n_degen = 1;
+        } else if (t.xa <= t.xb && t.ya <= t.yb) {
+            large = (long long)(t.xb - t.xa + 1) * (t.yb - t.ya + 1) > COOP_MIN;
+            if (large) {
+                n_large = 1;
+            } else if (wv == 0) {
+                bool cov = false;
+                for (int y = t.ya; y <= t.yb; ++y)
+                    for (int x = t.xa; x <= t.xb; ++x) cov |= shade(t, (double)A, x, y, o, W, zb, (unsigned)tri);
+                n_cov = cov;
             }
         }
     }
@@ -250,28 +188,8 @@ __global__ __launch_bounds__(256) void raster_resolve_color_kernel(const unsigne
             const int pix = (int)(i - (size_t)pose * hw), y = pix / W, x = pix - y * W;
             face = (int)(unsigned)key;                   // written by a usable triangle: its indices lie in [0, V)
             z = __uint_as_float((unsigned)(key >> 32));
-            const VRec* vr = rec + (size_t)pose * V;
-            int i0 = faces[3 * (size_t)face], i1 = faces[3 * (size_t)face + 1], i2 = faces[3 * (size_t)face + 2];
-            VRec a = vr[i0], b = vr[i1], d = vr[i2];
-            const long long A = (long long)(b.sx - a.sx) * (long long)(d.sy - a.sy) - (long long)(b.sy - a.sy) * (long long)(d.sx - a.sx);
-            if (A < 0) {
-                const VRec s = b;
-                b = d, d = s;
-                const int j = i1;
-                i1 = i2, i2 = j;
-            }
-            const int px = 256 * x + o, py = 256 * y + o;
-            long long w0, w1, w2;
-            edge_in(a.sx, a.sy, b.sx, b.sy, px, py, w2);
-            edge_in(b.sx, b.sy, d.sx, d.sy, px, py, w0);
-            edge_in(d.sx, d.sy, a.sx, a.sy, px, py, w1);
-            const double b0 = (double)w0 * a.rz, b1 = (double)w1 * b.rz, b2 = (double)w2 * d.rz;
-            const double den = (b0 + b1) + b2;
-            const unsigned char *c0 = colors + 3 * (size_t)i0, *c1 = colors + 3 * (size_t)i1, *c2 = colors + 3 * (size_t)i2;
-            for (int ch = 0; ch < 3; ++ch) {
-                const double v = ((b0 * (double)c0[ch] + b1 * (double)c1[ch]) + b2 * (double)c2[ch]) / den;
-                c[ch] = min(255, max(0, (int)rint(v)));
-            }
+            const size_t f = (size_t)face;
+            sample_color(rec + (size_t)pose * V, colors, faces[3 * f], faces[3 * f + 1], faces[3 * f + 2], x, y, o, c);
         }
         depth_out[i] = z;
         color_out[3 * i] = (unsigned char)c[0], color_out[3 * i + 1] = (unsigned char)c[1], color_out[3 * i + 2] = (unsigned char)c[2];

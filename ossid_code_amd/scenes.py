@@ -1,0 +1,508 @@
+"""Cluttered multi-object RGB-D scenes with BOP ground truth, rendered on the device (csrc/scene.hip, SPEC.md section 13):
+the data the reference gets from offline BlenderProc renders (datasets/render_dataset.py:81-189,
+datasets/dtoid_dataset.py:97-235) and corrupts with utils/augmentation.py:5-26. A directory of vertex-coloured .ply models
+is enough to train the scorer, run the stream and evaluate it:
+
+    atlas = MeshAtlas({obj_id: render.Mesh(V, F, colors=C), ...})          # metres
+    layout = sample_layouts(atlas, 32, 12, cam_K, (480, 640), rng)
+    batch = render_scenes(atlas, layout, (480, 640), sensor=sample_sensor(32, (480, 640), rng))
+    batch.write_bop(root, "synth")        # bop_eval.BopFolder, tools/eval_bop19.py and read_bop_frames read it back
+    for frame in batch.frames(): ...      # the dicts OnlineStream.process / networkInference / make_dtoid_sample take
+
+MeshAtlas, Layout, Sensor and the folder reader and writer are host code and need no device; render_scenes needs one.
+The layout and sensor sampling are build-defined (SPEC 13.7-13.8): host numpy from the caller's Generator.
+"""
+import ctypes
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import render as _render
+
+TABLE_OBJ_ID = 0            # the atlas's own mesh behind the objects; real objects have ids >= 1, as in BOP
+
+
+def _np(a):
+    return a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+class MeshAtlas:
+    """Vertex-coloured meshes packed back to back (SPEC 13.1): vertices f32 [Vt,3], colors u8 [Vt,3], faces int32 [Ft,3]
+    with indices local to their mesh, table int32 [K,4] = (v0, nv, f0, nf), on the host (`*_host`) and on the device of
+    the meshes. meshes: dict obj_id (>= 1) -> render.Mesh with colours, all on one device and in one unit (metres). The
+    last mesh, obj_id TABLE_OBJ_ID, is the unit square [-1, 1]^2 in z = 0 that sample_layouts scales into a table."""
+
+    def __init__(self, meshes, table_color=(128, 120, 110)):
+        if not isinstance(meshes, dict) or len(meshes) < 1:
+            raise ValueError("MeshAtlas: meshes must be a non-empty dict obj_id -> render.Mesh")
+        ids = sorted(int(k) for k in meshes)
+        if ids[0] < 1 or len(set(ids)) != len(ids):
+            raise ValueError("MeshAtlas: object ids must be distinct integers >= 1, got %s" % (ids,))
+        by_id = {int(k): m for k, m in meshes.items()}
+        devices = {str(by_id[i].device) for i in ids if isinstance(by_id[i], _render.Mesh)}
+        for i in ids:
+            m = by_id[i]
+            if not isinstance(m, _render.Mesh) or m.colors is None:
+                raise ValueError("MeshAtlas: object %d is not a render.Mesh with vertex colours (Mesh(..., colors=...))" % i)
+            if m.n_faces > _lib.RASTER_MAX_FACES:
+                raise ValueError("MeshAtlas: object %d has %d faces, at most %d" % (i, m.n_faces, _lib.RASTER_MAX_FACES))
+        if len(devices) != 1:
+            raise ValueError("MeshAtlas: the meshes live on different devices: %s" % sorted(devices))
+        self.device = by_id[ids[0]].device
+        V = [by_id[i].vertices.cpu().numpy() for i in ids] + [np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float32)]
+        C = [by_id[i].colors.cpu().numpy() for i in ids] + [np.tile(np.asarray(table_color, np.uint8), (4, 1))]
+        F = [by_id[i].faces.cpu().numpy().reshape(-1, 3) for i in ids] + [np.array([[0, 1, 2], [0, 2, 3]], np.int32)]
+        self.obj_ids = ids + [TABLE_OBJ_ID]
+        self.index_of = {o: k for k, o in enumerate(self.obj_ids)}
+        nv, nf = np.array([len(v) for v in V]), np.array([len(f) for f in F])
+        v0, f0 = np.concatenate([[0], np.cumsum(nv)[:-1]]), np.concatenate([[0], np.cumsum(nf)[:-1]])
+        if nv.sum() > 1 << 29 or nf.sum() > 1 << 29:
+            raise ValueError("MeshAtlas: %d vertices and %d faces in all, at most 2^29 each" % (nv.sum(), nf.sum()))
+        self.table_host = np.ascontiguousarray(np.stack([v0, nv, f0, nf], 1).astype(np.int32))
+        self.vertices_host = np.ascontiguousarray(np.concatenate(V).astype(np.float32))
+        self.colors_host = np.ascontiguousarray(np.concatenate(C).astype(np.uint8))
+        self.faces_host = np.ascontiguousarray(np.concatenate(F).astype(np.int32))
+        self.vertices, self.colors, self.faces, self.table = (
+            torch.from_numpy(a).to(self.device) for a in (self.vertices_host, self.colors_host, self.faces_host, self.table_host))
+        self.n_meshes = len(self.obj_ids)
+
+    def mesh_arrays(self, obj_id):
+        """(vertices f32 [V,3], faces int32 [F,3], colors u8 [V,3]) of one object, host arrays."""
+        v0, nv, f0, nf = self.table_host[self.index_of[int(obj_id)]]
+        return self.vertices_host[v0:v0 + nv], self.faces_host[f0:f0 + nf], self.colors_host[v0:v0 + nv]
+
+    def radius(self, obj_id):
+        """The largest distance of a vertex from the mesh's origin."""
+        V = self.mesh_arrays(obj_id)[0].astype(np.float64)
+        return float(np.sqrt((V * V).sum(1).max()))
+
+
+class Layout:
+    """A draw list (SPEC 13.1): instance_mesh int32 [I] (index into the atlas's table), transforms f64 [I,4,4]
+    (model -> camera; rows 0-2 are used, so a scale is allowed), scene_first int32 [S+1] (the instances of a scene are
+    contiguous; an empty scene is legal), cams f32 [S,4] = fx, fy, cx, cy."""
+
+    def __init__(self, instance_mesh, transforms, scene_first, cams):
+        self.instance_mesh = np.ascontiguousarray(np.asarray(instance_mesh).reshape(-1), dtype=np.int32)
+        self.transforms = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4, 4))
+        self.scene_first = np.ascontiguousarray(np.asarray(scene_first).reshape(-1), dtype=np.int32)
+        self.cams = np.ascontiguousarray(np.asarray(cams, dtype=np.float64).reshape(-1, 4).astype(np.float32))
+        S, I = len(self.cams), len(self.instance_mesh)
+        if not 1 <= S <= _lib.SCENE_MAX_SCENES:
+            raise ValueError("a layout has 1 to %d scenes, got %d" % (_lib.SCENE_MAX_SCENES, S))
+        if len(self.scene_first) != S + 1 or self.scene_first[0] != 0 or self.scene_first[-1] != I or \
+                np.any(np.diff(self.scene_first) < 0):
+            raise ValueError("scene_first must be non-decreasing [S+1] = [%d] from 0 to I = %d, got %s"
+                             % (S + 1, I, self.scene_first.tolist()))
+        if np.diff(self.scene_first).max(initial=0) > _lib.SCENE_MAX_INSTANCES:
+            raise ValueError("a scene has at most %d instances, got %d"
+                             % (_lib.SCENE_MAX_INSTANCES, np.diff(self.scene_first).max()))
+        if len(self.transforms) != I:
+            raise ValueError("transforms must be [I,4,4] = [%d,4,4], got %s" % (I, self.transforms.shape))
+        if not (np.isfinite(self.transforms).all() and np.isfinite(self.cams).all()):
+            raise ValueError("transforms and cams must be finite")
+
+    @property
+    def n_scenes(self):
+        return len(self.cams)
+
+    @property
+    def n_instances(self):
+        return len(self.instance_mesh)
+
+    def cam_K(self, s):
+        fx, fy, cx, cy = (float(v) for v in self.cams[s])
+        return np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+
+
+class Sensor:
+    """The inputs of SPEC 13.6 per scene: thresholds f32 [S], n_rects int32 [S] in [0, 6], rects int32 [S,6,4] =
+    (r0, r1, c0, c1), rows [r0, r1) and columns [c0, c1)."""
+
+    def __init__(self, thresholds, n_rects, rects):
+        self.thresholds = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1).astype(np.float32))
+        self.n_rects = np.ascontiguousarray(np.asarray(n_rects).reshape(-1), dtype=np.int32)
+        S = len(self.thresholds)
+        self.rects = np.ascontiguousarray(np.asarray(rects).reshape(S, _lib.SCENE_MAX_RECTS, 4), dtype=np.int32)
+        if len(self.n_rects) != S or (S and (self.n_rects.min() < 0 or self.n_rects.max() > _lib.SCENE_MAX_RECTS)):
+            raise ValueError("n_rects must be [S] = [%d] with values in [0, %d]" % (S, _lib.SCENE_MAX_RECTS))
+        if not np.isfinite(self.thresholds).all():
+            raise ValueError("thresholds must be finite")
+
+    @staticmethod
+    def clean(n_scenes):
+        """Quantisation only: every pixel keeps its depth."""
+        return Sensor(np.zeros(n_scenes), np.zeros(n_scenes, np.int32), np.zeros((n_scenes, _lib.SCENE_MAX_RECTS, 4), np.int32))
+
+
+def _check_hw(hw):
+    H, W = int(hw[0]), int(hw[1])
+    if H <= 0 or W <= 0 or H * W > _lib.RASTER_MAX_PIXELS:
+        raise ValueError("frame %d x %d is outside (0, %d] pixels" % (H, W, _lib.RASTER_MAX_PIXELS))
+    return H, W
+
+
+def _uniform_rotation(rng):
+    """Uniform over SO(3): a normalised 4-vector of normals as a quaternion (w, x, y, z)."""
+    q = rng.normal(size=4)
+    w, x, y, z = q / np.sqrt(q @ q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def sample_layouts(atlas, n_scenes, objects_per_scene, cam_K, hw, rng, z_range=(0.5, 1.2), table=True):
+    """SPEC 13.7 (build-defined) -> Layout of n_scenes scenes under the camera cam_K, each with objects_per_scene objects
+    of the atlas: distinct ones while the atlas has enough, drawn with replacement otherwise. Rotations are uniform; a
+    centre has its depth uniform in z_range and its projection uniform over the frame. table=True puts the atlas's
+    square first in every scene, tilted by 15 to 40 degrees so that it recedes towards the top of the image, its nearest
+    edge behind the farthest possible object. The same Generator state gives the same layout."""
+    H, W = _check_hw(hw)
+    S, n = int(n_scenes), int(objects_per_scene)
+    if not isinstance(rng, np.random.Generator):
+        raise ValueError("rng must be a numpy.random.Generator")
+    if not 1 <= S <= _lib.SCENE_MAX_SCENES:
+        raise ValueError("n_scenes must lie in [1, %d], got %r" % (_lib.SCENE_MAX_SCENES, n_scenes))
+    if not 0 <= n <= _lib.SCENE_MAX_INSTANCES - 1:
+        raise ValueError("objects_per_scene must lie in [0, %d], got %r" % (_lib.SCENE_MAX_INSTANCES - 1, objects_per_scene))
+    z0, z1 = float(z_range[0]), float(z_range[1])
+    if not 0.0 < z0 <= z1 < np.inf:
+        raise ValueError("z_range must be 0 < near <= far, got %r" % (z_range,))
+    fx, fy, cx, cy = _render._intrinsics(cam_K)
+    objects = [o for o in atlas.obj_ids if o != TABLE_OBJ_ID]
+    r_max = max(atlas.radius(o) for o in objects)
+    mesh, T, first = [], [], [0]
+    for _ in range(S):
+        if table:
+            a = np.deg2rad(rng.uniform(15.0, 40.0))
+            half = 1.5 * (z1 + r_max) * max(W / fx, H / fy)
+            M = np.eye(4)
+            M[:3, :3] = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(a), np.sin(a)], [0.0, -np.sin(a), np.cos(a)]]) * half
+            M[2, 3] = z1 + r_max + half * np.sin(a)
+            mesh.append(atlas.index_of[TABLE_OBJ_ID])
+            T.append(M)
+        picks = rng.permutation(len(objects))[:n] if n <= len(objects) else rng.integers(0, len(objects), n)
+        for k in picks:
+            z = rng.uniform(z0, z1)
+            u, v = rng.uniform(0.0, W), rng.uniform(0.0, H)
+            M = np.eye(4)
+            M[:3, :3] = _uniform_rotation(rng)
+            M[:3, 3] = ((u - cx) / fx * z, (v - cy) / fy * z, z)
+            mesh.append(atlas.index_of[objects[int(k)]])
+            T.append(M)
+        first.append(len(mesh))
+    return Layout(mesh, np.zeros((0, 4, 4)) if not T else np.stack(T), first, np.tile([fx, fy, cx, cy], (S, 1)))
+
+
+def sample_sensor(n_scenes, hw, rng):
+    """SPEC 13.8, the distributions of utils/augmentation.py:5-26 -> Sensor: the threshold uniform in [0.2, 0.5]; 0 to 6
+    rectangles, each starting at a row and column uniform over the frame with an extent uniform in [H//16, H//4) x
+    [W//16, W//4), its end clipped at H-1 / W-1."""
+    H, W = _check_hw(hw)
+    S = int(n_scenes)
+    if not isinstance(rng, np.random.Generator):
+        raise ValueError("rng must be a numpy.random.Generator")
+    if not 1 <= S <= _lib.SCENE_MAX_SCENES:
+        raise ValueError("n_scenes must lie in [1, %d], got %r" % (_lib.SCENE_MAX_SCENES, n_scenes))
+    if H < 8 or W < 8:
+        raise ValueError("sample_sensor needs a frame of at least 8 x 8 (the extents are drawn from [side//16, side//4))")
+    thresholds = rng.uniform(0.2, 0.5, S)
+    n_rects = rng.integers(0, _lib.SCENE_MAX_RECTS + 1, S)
+    rects = np.zeros((S, _lib.SCENE_MAX_RECTS, 4), dtype=np.int32)
+    for s in range(S):
+        for k in range(int(n_rects[s])):
+            r0, c0 = int(rng.integers(0, H)), int(rng.integers(0, W))
+            r1 = min(H - 1, r0 + int(rng.integers(H // 16, H // 4)))
+            c1 = min(W - 1, c0 + int(rng.integers(W // 16, W // 4)))
+            rects[s, k] = (r0, r1, c0, c1)
+    return Sensor(thresholds, n_rects, rects)
+
+
+def work_offsets(atlas, layout):
+    """int32 [I+1,2]: the prefix sums over the instances of (ossid_scene_work_items(nf), nv) of their meshes -- where an
+    instance's triangle groups start in the flattened work list, and its vertex records in the workspace."""
+    items = _lib.fn("ossid_scene_work_items")
+    per_mesh = np.array([[items(int(nf)), int(nv)] for _v0, nv, _f0, nf in atlas.table_host], dtype=np.int64).reshape(-1, 2)
+    out = np.zeros((layout.n_instances + 1, 2), dtype=np.int64)
+    np.cumsum(per_mesh[layout.instance_mesh], axis=0, out=out[1:])
+    if out[-1].max() > 1 << 30:
+        raise ValueError("the layout makes %d triangle groups and %d vertex records, at most 2^30 each" % tuple(out[-1]))
+    return np.ascontiguousarray(out.astype(np.int32))
+
+
+def _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, depth_scale):
+    H, W = _check_hw(hw)
+    if not isinstance(atlas, MeshAtlas) or not isinstance(layout, Layout):
+        raise ValueError("render_scenes takes a MeshAtlas and a Layout")
+    if layout.n_instances and (layout.instance_mesh.min() < 0 or layout.instance_mesh.max() >= atlas.n_meshes):
+        raise ValueError("instance_mesh outside [0, %d)" % atlas.n_meshes)
+    if not 0.0 <= float(pixel_offset) <= 1.0:
+        raise ValueError("pixel_offset must lie in [0, 1], got %r" % (pixel_offset,))
+    if not (float(z_near) >= 0.0 and np.isfinite(z_near)):
+        raise ValueError("z_near must be finite and >= 0, got %r" % (z_near,))
+    if not (float(depth_scale) > 0.0 and np.isfinite(depth_scale)):
+        raise ValueError("depth_scale must be finite and > 0, got %r" % (depth_scale,))
+    S = layout.n_scenes
+    if sensor is not None and (not isinstance(sensor, Sensor) or len(sensor.thresholds) != S):
+        raise ValueError("sensor must be a Sensor of the layout's %d scenes" % S)
+    if background is not None:
+        shape = tuple(background.shape)
+        if shape not in ((H, W, 3), (1, H, W, 3), (S, H, W, 3)) or \
+                (background.dtype != (torch.uint8 if torch.is_tensor(background) else np.uint8)):
+            raise ValueError("background must be uint8 [H,W,3] or [S,H,W,3] = [%d,%d,%d,3], got %s %s"
+                             % (S, H, W, background.dtype, shape))
+    return H, W
+
+
+def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=0.0, z_near=0.05, depth_scale=1.0):
+    """SPEC 13.2-13.6 -> SceneBatch of device tensors: the layout's scenes drawn with mutual occlusion, the sensor's depth
+    (sensor=None: the clean sensor, quantisation only), the amodal masks and gt_info. pixel_offset 0 is this package's
+    pixel convention, under which the render lines up with depth2xyz (as OnlineStream(mesh_pixel_offset=0.0) assumes).
+    depth_scale is the BOP folder's: the 16-bit depth counts units of depth_scale millimetres (the atlas is in metres).
+    Seven launches on the current stream; nothing is read back."""
+    H, W = _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, depth_scale)
+    from .model_cloud import _refuse_cpu
+    _refuse_cpu(atlas.device)
+    dev = atlas.device
+    S, I = layout.n_scenes, layout.n_instances
+    offsets = work_offsets(atlas, layout)
+    sensor = Sensor.clean(S) if sensor is None else sensor
+    up = lambda a: torch.from_numpy(a).to(dev)
+    d_mesh, d_T, d_first, d_cams, d_off = (up(layout.instance_mesh), up(layout.transforms.astype(np.float32)),
+                                           up(layout.scene_first), up(layout.cams), up(offsets))
+    d_thr, d_nr, d_rects = up(sensor.thresholds), up(sensor.n_rects), up(sensor.rects)
+    bg = None
+    if background is not None:
+        bg = (background if torch.is_tensor(background) else torch.from_numpy(np.ascontiguousarray(background))).to(dev)
+        bg = bg.reshape(-1, H, W, 3).contiguous()
+    Wd = (W + 31) // 32
+    color = torch.empty(S, H, W, 3, dtype=torch.uint8, device=dev)
+    clean = torch.empty(S, H, W, dtype=torch.float32, device=dev)
+    inst = torch.empty(S, H, W, dtype=torch.int32, device=dev)
+    face = torch.empty(S, H, W, dtype=torch.int32, device=dev)
+    facing = torch.empty(S, H, W, dtype=torch.float32, device=dev)
+    amodal = torch.empty(I, H, Wd, dtype=torch.int32, device=dev)
+    depth = torch.empty(S, H, W, dtype=torch.float32, device=dev)
+    u16 = torch.empty(S, H, W, dtype=torch.uint16, device=dev)
+    keep = torch.empty(S, H, W, dtype=torch.uint8, device=dev)
+    gt_info = torch.empty(I, 12, dtype=torch.int32, device=dev)
+    records, items = int(offsets[-1, 1]), int(offsets[-1, 0])
+    need = int(_lib.fn("ossid_scene_workspace_bytes")(records, S, H, W))
+    if need == 0:
+        raise ValueError("render_scenes: bad sizes (%d records, %d scenes of %d x %d)" % (records, S, H, W))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    desc = _lib.SceneDesc(
+        vertices=atlas.vertices.data_ptr(), colors=atlas.colors.data_ptr(), faces=atlas.faces.data_ptr(),
+        meshes=atlas.table.data_ptr(), instance_mesh=d_mesh.data_ptr() if I else None,
+        transforms=d_T.data_ptr() if I else None, scene_first=d_first.data_ptr(), cams=d_cams.data_ptr(),
+        offsets=d_off.data_ptr(), background=None if bg is None else bg.data_ptr(), color_out=color.data_ptr(),
+        depth_out=clean.data_ptr(), instance_out=inst.data_ptr(), face_out=face.data_ptr(), facing_out=facing.data_ptr(),
+        amodal_out=amodal.data_ptr() if I else None, Vt=len(atlas.vertices_host), Ft=len(atlas.faces_host), K=atlas.n_meshes,
+        I=I, S=S, H=H, W=W, Sb=0 if bg is None else int(bg.shape[0]), work_items=items, records=records,
+        pixel_offset=float(pixel_offset), z_near=float(z_near))
+    units, unit_inv = 1000.0 / float(depth_scale), float(depth_scale) / 1000.0
+    with _lib.on_device(dev):
+        _lib.check(_lib.fn("ossid_scene_render")(ctypes.byref(desc), ws.data_ptr(), ws.numel(), _lib.stream()),
+                   "ossid_scene_render")
+        _lib.check(_lib.fn("ossid_scene_sensor")(clean.data_ptr(), facing.data_ptr(), S, H, W, d_thr.data_ptr(), d_nr.data_ptr(),
+                                                 d_rects.data_ptr(), units, unit_inv, u16.data_ptr(), depth.data_ptr(),
+                                                 keep.data_ptr(), _lib.stream()), "ossid_scene_sensor")
+        _lib.check(_lib.fn("ossid_scene_gt_info")(amodal.data_ptr() if I else None, inst.data_ptr(), depth.data_ptr(),
+                                                  d_first.data_ptr(), I, S, H, W, gt_info.data_ptr() if I else None,
+                                                  _lib.stream()), "ossid_scene_gt_info")
+    batch = SceneBatch(atlas, layout, (H, W), color, clean, depth, u16, inst, amodal, gt_info, depth_scale=depth_scale,
+                       face=face, facing=facing, keep=keep)
+    batch.workspace_bytes = need
+    return batch
+
+
+def unpack_amodal(words, W):
+    """Amodal bit masks int32 / uint32 [..., H, ceil(W/32)] -> bool [..., H, W]."""
+    w = np.ascontiguousarray(_np(words)).view(np.uint32)
+    bits = np.unpackbits(w.astype("<u4").view(np.uint8).reshape(w.shape[:-1] + (-1,)), axis=-1, bitorder="little")
+    return bits[..., :W].astype(bool)
+
+
+class SceneBatch:
+    """What render_scenes returns; numpy arrays in place of the tensors make the same object without a device.
+    color u8 [S,H,W,3]; depth_clean f32 [S,H,W] (metres, 0 = nothing drawn); depth f32 (the sensor's, metres) and
+    depth_u16 (what the PNG stores: units of depth_scale millimetres); instance int32 [S,H,W] (index into the layout,
+    -1 = nothing drawn); amodal int32 [I,H,ceil(W/32)] bit masks; gt_info int32 [I,12] (SPEC 13.5); optionally face,
+    facing and keep."""
+
+    workspace_bytes = None
+
+    def __init__(self, atlas, layout, hw, color, depth_clean, depth, depth_u16, instance, amodal, gt_info, depth_scale=1.0,
+                 face=None, facing=None, keep=None):
+        self.atlas, self.layout, self.hw, self.depth_scale = atlas, layout, (int(hw[0]), int(hw[1])), float(depth_scale)
+        self.color, self.depth_clean, self.depth, self.depth_u16 = color, depth_clean, depth, depth_u16
+        self.instance, self.amodal, self.gt_info = instance, amodal, gt_info
+        self.face, self.facing, self.keep = face, facing, keep
+        S, I, (H, W) = layout.n_scenes, layout.n_instances, self.hw
+        want = {"color": (S, H, W, 3), "depth_clean": (S, H, W), "depth": (S, H, W), "depth_u16": (S, H, W),
+                "instance": (S, H, W), "amodal": (I, H, (W + 31) // 32), "gt_info": (I, 12)}
+        for name, shape in want.items():
+            if tuple(getattr(self, name).shape) != shape:
+                raise ValueError("SceneBatch: %s must be %s, got %s" % (name, shape, tuple(getattr(self, name).shape)))
+
+    def _host(self):
+        if getattr(self, "_host_cache", None) is None:
+            H, W = self.hw
+            self._host_cache = {
+                "color": _np(self.color), "depth": _np(self.depth), "depth_u16": _np(self.depth_u16).view(np.uint16),
+                "instance": _np(self.instance), "gt_info": _np(self.gt_info),
+                "amodal": unpack_amodal(self.amodal, W).reshape(self.layout.n_instances, H, W)}
+        return self._host_cache
+
+    def _objects(self):
+        """(scene, instance, index among the scene's objects) of every instance that is not the table."""
+        table = self.atlas.index_of[TABLE_OBJ_ID]
+        for s in range(self.layout.n_scenes):
+            k = 0
+            for i in range(int(self.layout.scene_first[s]), int(self.layout.scene_first[s + 1])):
+                if self.layout.instance_mesh[i] != table:
+                    yield s, i, k
+                    k += 1
+
+    def _frame(self, h, s, i):
+        g = h["gt_info"][i]
+        return {"img": h["color"][s], "depth": h["depth"][s], "cam_K": self.layout.cam_K(s),
+                "obj_id": int(self.atlas.obj_ids[self.layout.instance_mesh[i]]), "pose_gt": self.layout.transforms[i].copy(),
+                "mask_gt": h["amodal"][i], "mask_gt_visib": h["instance"][s] == i,
+                "bbox_visib": tuple(int(v) for v in g[7:11]), "visib_fract": _visib_fract(int(g[1]), int(g[0])),
+                "scene_id": s, "im_id": 0}
+
+    def frames(self):
+        """One dict per (scene, instance that is not the table), host arrays: img u8 [H,W,3], depth f32 [H,W] (the
+        sensor's, metres), cam_K f64 [3,3], obj_id, pose_gt f64 [4,4], mask_gt and mask_gt_visib bool [H,W], bbox_visib
+        (x, y, w, h), visib_fract, scene_id (the scene's index) and im_id (0): what OnlineStream.process,
+        networkInference and pipeline.make_dtoid_sample take, less the model cloud, templates and hypotheses."""
+        h = self._host()
+        for s, i, _k in self._objects():
+            yield self._frame(h, s, i)
+
+    def write_bop(self, root, dataset_name, split="test", depth_scale=1.0, diameters=None):
+        """The standard BOP layout under <root>/<dataset_name> (millimetres): models/ and models_eval/ (obj_%06d.ply,
+        models_info.json), test_targets_bop19.json, and per scene <split>/%06d/ with rgb/, depth/ (16-bit), mask/,
+        mask_visib/, scene_camera.json, scene_gt.json, scene_gt_info.json; every scene holds image 0. depth_scale must be
+        the one the batch was rendered with. diameters: dict obj_id -> diameter in the atlas's unit; None computes them
+        on the device (model_cloud.mesh_diameter)."""
+        from PIL import Image
+        if float(depth_scale) != self.depth_scale:
+            raise ValueError("write_bop: the batch's 16-bit depth was made with depth_scale = %r, not %r"
+                             % (self.depth_scale, depth_scale))
+        h = self._host()
+        base = os.path.join(root, dataset_name)
+        objects = [o for o in self.atlas.obj_ids if o != TABLE_OBJ_ID]
+        if diameters is None:
+            from .model_cloud import mesh_diameter
+            diameters = {o: mesh_diameter(self.atlas.mesh_arrays(o)[0]) for o in objects}
+        info = {}
+        for o in objects:
+            V, F, C = self.atlas.mesh_arrays(o)
+            mm = V.astype(np.float64) * 1000.0
+            lo, size = mm.min(0), mm.max(0) - mm.min(0)
+            info[str(o)] = {"diameter": float(diameters[o]) * 1000.0, "min_x": float(lo[0]), "min_y": float(lo[1]),
+                            "min_z": float(lo[2]), "size_x": float(size[0]), "size_y": float(size[1]), "size_z": float(size[2])}
+            for sub in ("models", "models_eval"):
+                os.makedirs(os.path.join(base, sub), exist_ok=True)
+                write_ply(os.path.join(base, sub, "obj_%06d.ply" % o), mm, F, C)
+        for sub in ("models", "models_eval"):
+            with open(os.path.join(base, sub, "models_info.json"), "w") as f:
+                json.dump(info, f, indent=1)
+        targets = []
+        for s in range(self.layout.n_scenes):
+            scene = os.path.join(base, split, "%06d" % s)
+            for sub in ("rgb", "depth", "mask", "mask_visib"):
+                os.makedirs(os.path.join(scene, sub), exist_ok=True)
+            Image.fromarray(h["color"][s]).save(os.path.join(scene, "rgb", "%06d.png" % 0))
+            Image.fromarray(h["depth_u16"][s]).save(os.path.join(scene, "depth", "%06d.png" % 0))
+            gt, gt_info, count = [], [], {}
+            for s2, i, k in self._objects():
+                if s2 != s:
+                    continue
+                fr = self._frame(h, s, i)
+                g = h["gt_info"][i]
+                Image.fromarray(fr["mask_gt"].astype(np.uint8) * 255).save(os.path.join(scene, "mask", "%06d_%06d.png" % (0, k)))
+                Image.fromarray(fr["mask_gt_visib"].astype(np.uint8) * 255).save(
+                    os.path.join(scene, "mask_visib", "%06d_%06d.png" % (0, k)))
+                T = fr["pose_gt"]
+                gt.append({"cam_R_m2c": [float(v) for v in T[:3, :3].reshape(-1)],
+                           "cam_t_m2c": [float(v) * 1000.0 for v in T[:3, 3]], "obj_id": fr["obj_id"]})
+                gt_info.append({"bbox_obj": [int(v) for v in g[3:7]], "bbox_visib": [int(v) for v in g[7:11]],
+                                "px_count_all": int(g[0]), "px_count_valid": int(g[2]), "px_count_visib": int(g[1]),
+                                "visib_fract": fr["visib_fract"]})
+                count[fr["obj_id"]] = count.get(fr["obj_id"], 0) + 1
+            cam = {"0": {"cam_K": [float(v) for v in self.layout.cam_K(s).reshape(-1)], "depth_scale": self.depth_scale}}
+            for name, obj in (("scene_camera.json", cam), ("scene_gt.json", {"0": gt}), ("scene_gt_info.json", {"0": gt_info})):
+                with open(os.path.join(scene, name), "w") as f:
+                    json.dump(obj, f, indent=1)
+            targets += [{"scene_id": s, "im_id": 0, "obj_id": o, "inst_count": n} for o, n in sorted(count.items())]
+        with open(os.path.join(base, "test_targets_bop19.json"), "w") as f:
+            json.dump(targets, f, indent=1)
+        return base
+
+
+def _visib_fract(visib, amodal):
+    return float(visib) / float(amodal) if amodal > 0 else 0.0
+
+
+def write_ply(path, vertices, faces, colors):
+    """ASCII PLY with x y z (repr of the float64) and uchar red green blue per vertex, and triangle faces."""
+    V, F, C = np.asarray(vertices, dtype=np.float64), np.asarray(faces), np.asarray(colors)
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
+                "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\n"
+                "property list uchar int vertex_indices\nend_header\n" % (len(V), len(F)))
+        f.write("".join("%r %r %r %d %d %d\n" % (float(p[0]), float(p[1]), float(p[2]), c[0], c[1], c[2]) for p, c in zip(V, C)))
+        f.write("".join("3 %d %d %d\n" % (t[0], t[1], t[2]) for t in F))
+
+
+def read_bop_frames(root, dataset_name, split="test"):
+    """The frames of a BOP folder as SceneBatch.frames() yields them (depth in metres, pose_gt in metres): what
+    write_bop wrote comes back bit for bit -- image, sensor depth, masks -- and the pose up to the JSON's float64."""
+    from PIL import Image
+    base = os.path.join(root, dataset_name, split)
+    for name in sorted(os.listdir(base)):
+        scene = os.path.join(base, name)
+        if not (name.isdigit() and os.path.isdir(scene)):
+            continue
+        with open(os.path.join(scene, "scene_camera.json")) as f:
+            cams = json.load(f)
+        with open(os.path.join(scene, "scene_gt.json")) as f:
+            gts = json.load(f)
+        with open(os.path.join(scene, "scene_gt_info.json")) as f:
+            infos = json.load(f)
+        for im in sorted(gts, key=int):
+            im_id, cam = int(im), cams[im]
+            img = np.asarray(Image.open(os.path.join(scene, "rgb", "%06d.png" % im_id)).convert("RGB"))
+            png = np.asarray(Image.open(os.path.join(scene, "depth", "%06d.png" % im_id)))
+            depth = (png.astype(np.float64) * (float(cam.get("depth_scale", 1.0)) / 1000.0)).astype(np.float32)
+            for k, (g, info) in enumerate(zip(gts[im], infos[im])):
+                T = np.eye(4)
+                T[:3, :3] = np.asarray(g["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
+                T[:3, 3] = np.asarray(g["cam_t_m2c"], dtype=np.float64) / 1000.0
+                masks = [np.asarray(Image.open(os.path.join(scene, sub, "%06d_%06d.png" % (im_id, k)))) > 0
+                         for sub in ("mask", "mask_visib")]
+                yield {"img": img, "depth": depth, "cam_K": np.asarray(cam["cam_K"], dtype=np.float64).reshape(3, 3),
+                       "obj_id": int(g["obj_id"]), "pose_gt": T, "mask_gt": masks[0], "mask_gt_visib": masks[1],
+                       "bbox_visib": tuple(int(v) for v in info["bbox_visib"]), "visib_fract": float(info["visib_fract"]),
+                       "scene_id": int(name), "im_id": im_id}
+
+
+def read_models_dir(models_dir, scale=0.001, device=None):
+    """obj_%06d.ply (or any *.ply, numbered in sorted order from 1) of a directory -> dict obj_id -> render.Mesh with
+    colours, scaled (BOP models are in millimetres)."""
+    names = sorted(n for n in os.listdir(models_dir) if n.endswith(".ply"))
+    if not names:
+        raise ValueError("%s holds no .ply model" % models_dir)
+    meshes = {}
+    for k, n in enumerate(names):
+        digits = "".join(c for c in os.path.splitext(n)[0] if c.isdigit())
+        obj_id = int(digits) if n.startswith("obj_") and digits else k + 1
+        V, F, C = _render.read_ply_mesh(os.path.join(models_dir, n), with_colors=True)
+        meshes[obj_id] = _render.Mesh(V, F, scale=scale, device=device, colors=C)
+    return meshes

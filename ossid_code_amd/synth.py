@@ -87,6 +87,19 @@ def make_hypotheses(N=1000, seed=42):
     return T
 
 
+def perturb_pose(pose_gt, N=1000, seed=42):
+    """make_hypotheses around an arbitrary pose -> [N,4,4] float64; row 0 is pose_gt, row k a rotation by N(0, 0.2) rad
+    about a random axis in front of it and a translation off by N(0, 0.01) per axis."""
+    rng = np.random.default_rng(seed + 1)
+    T = np.tile(np.asarray(pose_gt, dtype=np.float64).reshape(4, 4), (N, 1, 1))
+    for k in range(1, N):
+        axis = rng.normal(0, 1.0, 3)
+        axis /= np.linalg.norm(axis)
+        T[k, :3, :3] = _rodrigues(axis, rng.normal(0, 0.2)) @ T[k, :3, :3]
+        T[k, :3, 3] += rng.normal(0, 0.01, 3)
+    return T
+
+
 def make_scoring_inputs(N=1000, M=2048, seed=42, H=480, W=640):
     """The dict networkInference takes (utils/zephyr_utils.py:10; packed at online_learning.py:455-459)."""
     img, depth = make_frame(seed, H, W)

@@ -1,0 +1,188 @@
+"""Times the scene renderer (csrc/scene.hip, SPEC.md section 13) against the route that exists without it, in one call and
+alternating, on the same seeded layout -> profiles/scenes.json:
+
+  scene      scenes.render_scenes: every instance of every scene in one draw list (7 launches);
+  composite  one render.render_color per instance, then a torch composite by (depth, instance) into the scene's frame, the
+             instance's coverage as its amodal mask and the pixel counts -- entry points that predate scene.hip only.
+
+The workload is 32 scenes of 480 x 640 with 12 instances each: a table and 11 objects drawn from four ellipsoids of a
+level-6 icosphere (81 920 faces each; no BOP model ships with the repository). Outputs are checked equal first: colour,
+depth, instance, face, the amodal masks and the amodal / visible pixel counts. Times are HIP events around one call of
+each route, median of `--rounds` alternating rounds after `--warmup`. Launches: the C ABI's own are counted from the
+calls made; torch's are counted as dispatched device operations (each is at least one kernel).
+
+    python3 tools/bench_scenes.py [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
+    rocprofv3 --kernel-trace --stats -d out -- python3 tools/bench_scenes.py --trace       (three untimed calls of `scene`)
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+from torch.utils._python_dispatch import TorchDispatchMode
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import ref_raster as rr   # noqa: E402
+import ref_raster_color as rc   # noqa: E402
+from ossid_code_amd import render, scenes, synth  # noqa: E402
+
+HW = (480, 640)
+AXES = ((0.06, 0.06, 0.06), (0.09, 0.05, 0.04), (0.04, 0.08, 0.06), (0.05, 0.05, 0.10))
+
+
+class CountOps(TorchDispatchMode):
+    """Counts the dispatched operations that touch a device tensor (views and metadata-only ops excluded)."""
+    SKIP = ("view", "reshape", "select", "slice", "expand", "unsqueeze", "squeeze", "alias", "detach", "empty", "as_strided", "_unsafe_view", "permute", "t.")
+
+    def __init__(self):
+        super().__init__()
+        self.n = 0
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        name = func.__name__
+        if not any(name.startswith(s) for s in self.SKIP):
+            self.n += 1
+        return func(*args, **(kwargs or {}))
+
+
+def composite_route(meshes, atlas, layout, T_dev, cams_dev, counter=None):
+    """-> dict of device tensors; counter["c_abi"] gets the number of kernel launches the C ABI made."""
+    H, W = HW
+    S, I = layout.n_scenes, layout.n_instances
+    color = torch.zeros(S, H, W, 3, dtype=torch.uint8, device="cuda")
+    depth = torch.zeros(S, H, W, dtype=torch.float32, device="cuda")
+    inst = torch.full((S, H, W), -1, dtype=torch.int32, device="cuda")
+    face = torch.full((S, H, W), -1, dtype=torch.int32, device="cuda")
+    amodal = torch.empty(I, H, W, dtype=torch.bool, device="cuda")
+    for s in range(S):
+        for i in range(int(layout.scene_first[s]), int(layout.scene_first[s + 1])):
+            mesh = meshes[atlas.obj_ids[layout.instance_mesh[i]]]
+            c, d, f = render.render_color(mesh, T_dev[i], None, HW, pixel_offset=0.0, z_near=0.05, intrinsics=cams_dev[s:s + 1],
+                                          return_face_id=True)
+            if counter is not None:
+                counter["c_abi"] += 3
+            torch.gt(d, 0, out=amodal[i])
+            take = amodal[i] & ((inst[s] < 0) | (d < depth[s]))
+            color[s] = torch.where(take[..., None], c, color[s])
+            depth[s] = torch.where(take, d, depth[s])
+            face[s] = torch.where(take, f, face[s])
+            inst[s].masked_fill_(take, i)
+    px_all = amodal.sum((1, 2), dtype=torch.int32)
+    px_visib = torch.bincount((inst.reshape(-1) + 1).long(), minlength=I + 1)[1:].to(torch.int32)
+    return {"color": color, "depth": depth, "instance": inst, "face": face, "amodal": amodal, "px_all": px_all, "px_visib": px_visib}
+
+
+def unpack_device(words, W):
+    bits = (words[..., None] >> torch.arange(32, device=words.device, dtype=torch.int32)) & 1
+    return bits.reshape(words.shape[0], words.shape[1], -1)[..., :W].bool()
+
+
+def once_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scenes.json"))
+    ap.add_argument("--scenes", type=int, default=32)
+    ap.add_argument("--objects", type=int, default=11, help="objects per scene; the table is one more instance")
+    ap.add_argument("--level", type=int, default=6, help="icosphere level of the objects (6: 81 920 faces)")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--commit", default=None)
+    ap.add_argument("--trace", action="store_true", help="three untimed calls of the scene route, for a kernel trace")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_scenes.py needs the GPU: there is nothing to time without one")
+    torch.cuda.set_device(0)
+    V, F = rr.icosphere(a.level)
+    meshes = {k + 1: render.Mesh(V * np.asarray(ax), F, colors=rc.axis_colors(V * np.asarray(ax))[0]) for k, ax in enumerate(AXES)}
+    atlas = scenes.MeshAtlas(meshes)
+    tv, tf, tc = atlas.mesh_arrays(scenes.TABLE_OBJ_ID)
+    meshes[scenes.TABLE_OBJ_ID] = render.Mesh(tv, tf, colors=tc)           # the composite route draws the table too
+    rng = np.random.default_rng(a.seed)
+    layout = scenes.sample_layouts(atlas, a.scenes, a.objects, synth.CAM_K, HW, rng)
+    sensor = scenes.sample_sensor(a.scenes, HW, rng)
+    scene_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor)  # noqa: E731
+    if a.trace:
+        for _ in range(3):
+            scene_fn()
+        torch.cuda.synchronize()
+        return
+    T_dev = torch.from_numpy(layout.transforms.astype(np.float32)).cuda()
+    cams_dev = torch.from_numpy(layout.cams).cuda()
+    comp_fn = lambda: composite_route(meshes, atlas, layout, T_dev, cams_dev)  # noqa: E731
+
+    # the two routes agree, bit for bit
+    batch, comp = scene_fn(), comp_fn()
+    same = {"color": torch.equal(batch.color, comp["color"]),
+            "depth": torch.equal(batch.depth_clean.view(torch.int32), comp["depth"].view(torch.int32)),
+            "instance": torch.equal(batch.instance, comp["instance"]), "face": torch.equal(batch.face, comp["face"]),
+            "amodal": torch.equal(unpack_device(batch.amodal, HW[1]), comp["amodal"]),
+            "px_count_all": torch.equal(batch.gt_info[:, 0], comp["px_all"]),
+            "px_count_visib": torch.equal(batch.gt_info[:, 1], comp["px_visib"])}
+    print("outputs equal:", same, flush=True)
+    if not all(same.values()):
+        raise SystemExit("the routes disagree: %s" % same)
+    g = batch.gt_info.cpu().numpy()
+    counter = {"c_abi": 0}
+    with CountOps() as ops:
+        composite_route(meshes, atlas, layout, T_dev, cams_dev, counter)
+    comp_ops = ops.n
+    with CountOps() as ops:
+        scene_fn()
+    scene_ops = ops.n
+    ws_comp = max(m._ws_color.numel() for m in meshes.values() if m._ws_color is not None)
+    del batch, comp
+    for _ in range(a.warmup):
+        scene_fn(), comp_fn()
+    torch.cuda.synchronize()
+    t_scene, t_comp = [], []
+    for _ in range(a.rounds):
+        t_scene.append(once_ms(scene_fn)[0])
+        t_comp.append(once_ms(comp_fn)[0])
+    batch = scene_fn()
+    H, W = HW
+    I = layout.n_instances
+    res = {
+        "workload": {"scenes": a.scenes, "instances": I, "instances_per_scene": a.objects + 1, "frame": list(HW),
+                     "faces_per_object": int(len(F)), "faces_drawn": int(atlas.table_host[layout.instance_mesh, 3].sum()),
+                     "seed": a.seed, "visible_instances": int((g[:, 1] > 0).sum()),
+                     "mean_visib_fract": float(np.mean(g[:, 1][g[:, 0] > 0] / g[:, 0][g[:, 0] > 0]))},
+        "outputs_equal": same,
+        "scene": {"ms": float(np.median(t_scene)), "ms_min": float(min(t_scene)), "ms_max": float(max(t_scene)),
+                  "c_abi_launches": 7, "torch_device_ops": scene_ops, "workspace_bytes": int(batch.workspace_bytes),
+                  "amodal_bytes": int(batch.amodal.numel() * 4), "frames_touched": a.scenes},
+        "composite": {"ms": float(np.median(t_comp)), "ms_min": float(min(t_comp)), "ms_max": float(max(t_comp)),
+                      "c_abi_launches": counter["c_abi"], "torch_device_ops": comp_ops, "workspace_bytes": int(ws_comp),
+                      "amodal_bytes": int(I * H * W), "frames_touched": I},
+        "rounds": a.rounds, "warmup": a.warmup}
+    res["ratio_composite_over_scene"] = res["composite"]["ms"] / res["scene"]["ms"]
+    commit = a.commit
+    if commit is None:
+        try:
+            commit = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+        except Exception:
+            commit = "unknown"
+    res.update(commit=commit, box={"gpu": torch.cuda.get_device_name(0), "torch": torch.__version__, "hip": torch.version.hip})
+    print(json.dumps(res), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()

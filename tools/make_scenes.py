@@ -1,0 +1,57 @@
+"""Cluttered RGB-D scenes with BOP ground truth from a folder of vertex-coloured models -> a standard BOP folder:
+
+    python3 tools/make_scenes.py MODELS_DIR OUT_DIR --scenes 32 --objects 6 --seed 0 [--name synth] [--split test]
+                                 [--hw 480 640] [--no-mm2m] [--clean] [--no-table] [--depth_scale 1.0]
+
+Every MODELS_DIR/*.ply (obj_XXXXXX.ply keeps its id; millimetres, as BOP stores them, unless --no-mm2m) goes into one
+atlas; scenes.sample_layouts places the objects, scenes.render_scenes (csrc/scene.hip, SPEC.md section 13) draws them with
+the depth corruption of scenes.sample_sensor (--clean: quantisation only), and SceneBatch.write_bop writes
+OUT_DIR/<name>: what bop_eval.BopFolder, tools/eval_bop19.py and scenes.read_bop_frames read. The same seed gives the same
+folder. At most 256 scenes per call.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ossid_code_amd import scenes, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("models_dir")
+    ap.add_argument("out_dir")
+    ap.add_argument("--scenes", type=int, default=32)
+    ap.add_argument("--objects", type=int, default=6)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--name", default="synth")
+    ap.add_argument("--split", default="test")
+    ap.add_argument("--hw", type=int, nargs=2, default=(480, 640))
+    ap.add_argument("--depth_scale", type=float, default=1.0)
+    ap.add_argument("--no-mm2m", action="store_true", help="the models are already in metres")
+    ap.add_argument("--clean", action="store_true", help="no depth corruption: quantisation only")
+    ap.add_argument("--no-table", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("make_scenes.py renders on the GPU: there is no CPU path")
+    if a.scenes > 256:
+        raise SystemExit("at most 256 scenes per folder and call; use several seeds and names for more")
+    atlas = scenes.MeshAtlas(scenes.read_models_dir(a.models_dir, scale=1.0 if a.no_mm2m else 0.001))
+    rng = np.random.default_rng(a.seed)
+    K = synth.CAM_K * np.array([[a.hw[1] / 640.0], [a.hw[0] / 480.0], [1.0]])
+    layout = scenes.sample_layouts(atlas, a.scenes, a.objects, K, a.hw, rng, table=not a.no_table)
+    sensor = None if a.clean else scenes.sample_sensor(a.scenes, a.hw, rng)
+    batch = scenes.render_scenes(atlas, layout, a.hw, sensor=sensor, depth_scale=a.depth_scale)
+    base = batch.write_bop(a.out_dir, a.name, split=a.split, depth_scale=a.depth_scale)
+    g = batch.gt_info.cpu().numpy()
+    print("%d scenes, %d instances (%d visible) of %d objects -> %s" % (a.scenes, layout.n_instances, int((g[:, 1] > 0).sum()),
+                                                                       atlas.n_meshes - 1, base))
+
+
+if __name__ == "__main__":
+    main()
