@@ -9,7 +9,7 @@
 // ascending, offsets 0,4,1,5,2,6,3,7) -- which is exactly what a chain of 32x32x2 f32 MFMAs
 // produces when lane half h supplies channel 8b+4h+i at step i: D = fma(a_k1,b_k1,fma(a_k0,b_k0,C)).
 //
-// MLP design (sa1/sa2/sa3/p2 kernels): samples sit on the MFMA N axis (lane&31), channels on M.
+// MLP design (sa1/sa2/sa3 kernels): samples sit on the MFMA N axis (lane&31), channels on M.
 // A layer's 32x32 accumulator tile IS the next layer's B operand (register r of lane half h holds
 // channel (r&3)+8(r>>2)+4h), so activations never leave the register file between layers: no LDS,
 // no barriers, 64-wide waves each carrying 32 samples. Weights are pre-packed on the host so one
@@ -50,12 +50,6 @@ __device__ __forceinline__ float max1(float a, float b) {
 __device__ __forceinline__ v16f relu16(v16f a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) a[i] = max1(a[i], 0.0f);
-    return a;
-}
-
-__device__ __forceinline__ v16f max16(v16f a, v16f b) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = max1(a[i], b[i]);
     return a;
 }
 
@@ -162,45 +156,6 @@ __device__ __forceinline__ void stream_layer(const float* __restrict__ Wu, unsig
     }
 }
 
-// Rolled-over-m-tiles form for a group's LAST layer: each 32-channel output tile is consumed (max-pooled)
-// as soon as it is complete, so only one accumulator tile per column tile is live and mt may be dynamic.
-template <int KT, int NT, int G, class Epi>
-__device__ __forceinline__ void stream_layer_rolled(const float4* __restrict__ W4, const float* __restrict__ bias,
-                                                    const v16f (&X)[NT][KT], int h, int MT, Epi&& epi) {
-    constexpr int QPM = KT * 4, NG = QPM / G;
-    static_assert(QPM % G == 0, "group size must divide the quads per m-tile");
-    const int last = MT * QPM - 1;
-    float4 cur[G], nxt[G];
-#pragma unroll
-    for (int i = 0; i < G; ++i) cur[i] = W4[(size_t)i * 64];
-#pragma unroll 1
-    for (int mt = 0; mt < MT; ++mt) {
-        v16f acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = bias_tile(bias, mt, h);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                int nq = mt * QPM + (g + 1) * G + i;  // next group, possibly the next m-tile's first
-                nq = nq > last ? last : nq;
-                nxt[i] = W4[(size_t)nq * 64];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const int kq = g * G + i, kt = kq / 4, q = kq % 4;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t] = mfma4(cur[i], X[t][kt], 4 * q, acc[t]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < G; ++i) cur[i] = nxt[i];
-        }
-        epi(mt, acc);
-    }
-}
-
 // ---- a module's LAST layer, operands swapped ---------------------------------------------------------------
 // D = A.B is symmetric in how lanes index the two non-k dimensions, so feeding the activation register as the A
 // operand and the packed weight as the B operand yields the TRANSPOSED tile: rows (registers) = the 32 samples,
@@ -223,16 +178,35 @@ __device__ __forceinline__ v16f splat16(float v) {
     return a;
 }
 
-// max over the 32 samples of a swapped tile (16 registers x 2 lane halves), ReLU folded in (it commutes with max);
-// every lane returns the pooled value of channel lane&31
+// The pool of a swapped tile is max(0, max_j acc_j): the max over the samples with the ReLU folded in (it commutes with
+// max). It runs on the values' BIT PATTERNS as signed integers: non-negative floats order like their patterns, and every
+// negative float, -0.0 included, is a negative integer and loses to the 0 the chain starts from -- so the integer maximum
+// is the largest positive value, or +0.0, which is what a float max followed by the ReLU returns (SPEC 4: activations are
+// not NaN). A three-input integer max is one plain instruction (v_max3_i32) and needs no canonicalisation: 16 values and
+// the running maximum cost 8 instructions instead of 16.
+// pool_acc folds a tile's 16 registers into a running maximum m >= 0 (0, or what earlier tiles of the centre left);
+// pool_halves merges the two lane halves of TWO m-tiles' running maxima at once: lanes 0-31 return the pooled value of
+// channel lane&31 of tile a, lanes 32-63 that of tile b -- the form a full-wave store of two m-tiles wants.
+__device__ __forceinline__ int pool_acc(const v16f& a, int m) {
+#pragma unroll
+    for (int i = 0; i < 16; i += 2) m = max(max(m, __float_as_int(a[i])), __float_as_int(a[i + 1]));
+    return m;
+}
+__device__ __forceinline__ float pool_halves(int a, int b) {
+    // v_permlane32_swap (gfx950) exchanges the upper 32 lanes of its first operand with the lower 32 of its second: r[0] is
+    // (a's lower half, b's lower half), r[1] is (a's upper half, b's upper half). It is a plain VALU op; __shfl_xor(m, 32)
+    // goes through the LDS crossbar (ds_bpermute: address VGPR, lgkmcnt wait) in the middle of an MFMA stream
+    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false);
+    return __int_as_float(max((int)r[0], (int)r[1]));
+}
+// sa3_kernel's pool: one tile per m-tile, as a float max tree. (The integer form saves 8 of its ~180 non-MFMA instructions
+// per m-tile there and measured nothing, profiles/r11_sa1_p2_pool_after.txt, so sa3 keeps the form it was measured with.)
 __device__ __forceinline__ float pool_swapped(const v16f& a) {
     float m0 = max1(max1(a[0], a[1]), max1(a[2], a[3]));
     float m1 = max1(max1(a[4], a[5]), max1(a[6], a[7]));
     float m2 = max1(max1(a[8], a[9]), max1(a[10], a[11]));
     float m3 = max1(max1(a[12], a[13]), max1(a[14], a[15]));
     float m = max1(max1(m0, m1), max1(m2, m3));
-    // the other lane half's value: v_permlane32_swap (gfx950) is a plain VALU op; __shfl_xor(m, 32) goes through the LDS
-    // crossbar (ds_bpermute: address VGPR, lgkmcnt wait) in the middle of an MFMA stream
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
     m = max1(__uint_as_float(r[0]), __uint_as_float(r[1]));
     return max1(m, 0.0f);
@@ -721,16 +695,24 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
 // registers (the packed image is lane-linear: quad q of a layer is the float4 at W4[q * 64 + lane]) and the folded biases of
 // layers 1-2 as four ready-made accumulator tiles (64 registers, the C operand of each chain's first MFMA), then walks a
 // contiguous slice of the centres. All three layers are fully unrolled over their quads (16 + 128 + 256 = 400 MFMAs per
-// centre): no LDS, no barrier, no operand read between MFMAs.
+// centre) and read no operand between MFMAs. A centre's 128 pooled values go to a row of the wave's own staging tile in LDS
+// (one ds_write2st64_b32 per centre), and once per 32 centres the wave applies the per-point part of SA2's first layer to
+// that tile (sa1_p2_tile: 256 MFMAs, operands and weights read from LDS) and stores P. The layer's weights are staged in LDS
+// once per workgroup behind the kernel's only barrier, in the prologue; after it the four waves run free of each other.
 //
 // What sets this kernel's rate (profiles/r08_sa1_before.txt, r08_sa1_after.txt): it runs at the clock of a bare
 // register-fed MFMA stream, and the time it loses is proportional to the number of vector / LDS instructions per centre --
 // about four to five cycles of matrix time each, wherever they sit in the stream (re-ordering them between the MFMAs of an
 // independent accumulator measured nothing). So the design is about instruction COUNT: no ds_read per weight quad, no bias
-// read, one instruction per ReLU / max (max1), accumulators in vector registers so that ReLU and pool read them in place.
+// read, one instruction per ReLU (max1), one per TWO pooled values (pool_acc), accumulators in vector registers so that ReLU
+// and pool read them in place.
 //
-// Register budget (per lane): weights 200 + bias tiles 64 + last-layer bias 4 + x 8 + Y1 64 + Y2 64 + accumulators 32 + next
-// centre's gather 13 = 449 at the widest point (layer 2). tests/test_pn2_resources.py holds the build to zero scratch.
+// Register budget (per lane), centre loop: weights 200 + bias tiles 64 + last-layer bias 4 + x 8 + Y1 64 + Y2 64 + accumulators
+// 32 + next centre's gather 13 = 449 at the widest point (layer 2). The per-tile phase runs when the layer temporaries
+// (x, Y1, Y2, accumulators: 168) are dead and needs less: the staged tile as B operand 64 + weight quads of the group in use
+// and of the next 32 + one m-tile's accumulator 16 + the next bias tile 16 = 128 beside the same 281 of weights, bias tiles
+// and gather. The build stands at 256 VGPRs + 230 AGPRs (216 before the phase was added: the allocator parks some of its
+// addressing in the AGPR half). tests/test_pn2_resources.py holds the build to zero scratch and 512 registers.
 //
 // The weights are only ever MFMA operands, which may come from the accumulator (AGPR) half of the register file; ReLU and
 // pool are vector instructions, which may not read it. The file is compiled with the VGPR form of the MFMA (_build.py:
@@ -757,19 +739,93 @@ __device__ __forceinline__ void load_quads(float4 (&w)[N], const float* __restri
     for (int q = 0; q < N; ++q) w[q] = ((const float4*)Wp)[q * 64 + lane], pin_acc(w[q]);
 }
 
+__device__ __forceinline__ void stage_lds(float* dst, const float* __restrict__ src, int nfloats) {
+    for (int i = threadIdx.x * 4; i < nfloats; i += blockDim.x * 4) *(float4*)(dst + i) = *(const float4*)(src + i);
+}
+
+// LDS of sa1_kernel (floats): the p2 layer's packed weights [4 m-tiles][16 quads][64 lanes] x 4 | its 128 biases | one
+// staging tile of SA1_ROWS centres x 128 pooled channels per wave. The row pitch of 132 floats puts the 16 lanes of a
+// ds_read_b128 lane group (same lane half, 16 different rows) on 16 different 16-byte slots of the 256-byte bank row.
+constexpr int SA1_ROWS = 32, SA1_PITCH = 132;
+constexpr int SA1_WP = 0, SA1_BP = 16384, SA1_STAGE = SA1_BP + 128,
+              SA1_LDS_FLOATS = SA1_STAGE + 4 * SA1_ROWS * SA1_PITCH;   // 64 KB | 0.5 KB | 4 x 16.5 KB = 133 632 B
+
+// The per-point part of SA2's first layer, p[pt][o] = chain(bias, W[:, :128] . feat1[pt]) (the grouped-xyz columns are
+// applied per sample in sa2_kernel, continuing the same chain), for the SA1_ROWS centres of a wave's staging tile: the
+// tile is the B operand (register 4q+e of lane half h = channel 32kt+8q+4h+e, column = row of the tile), an m-tile is
+// the bias tile as the C operand and then the 16 weight quads in order. Rows >= nvalid are computed and not stored.
+__device__ __forceinline__ void sa1_p2_tile(const float* w, const float* stage, float* __restrict__ P, int row0, int nvalid,
+                                            int lane) {
+    const int h = lane >> 5, c = lane & 31;
+    v16f X[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = *(const float4*)(stage + c * SA1_PITCH + kt * 32 + 8 * q + 4 * h);
+            X[kt][4 * q + 0] = v.x, X[kt][4 * q + 1] = v.y, X[kt][4 * q + 2] = v.z, X[kt][4 * q + 3] = v.w;
+        }
+    constexpr int G = 4, NG = 16 / G;    // weight quads per LDS read group, read a group ahead of the MFMAs that use them
+    const float4* w4 = (const float4*)(w + SA1_WP) + lane;
+    float4 cur[G], nxt[G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) cur[i] = w4[i * 64];
+    v16f bt = bias_tile(w + SA1_BP, 0, h);
+    float* o = P + ((size_t)row0 + c) * 128 + 4 * h;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        v16f acc = bt;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            // the group after the last wraps to quad 0 (read for nothing, in bounds)
+#pragma unroll
+            for (int i = 0; i < G; ++i) nxt[i] = w4[((mt * 16 + (g + 1) * G + i) & 63) * 64];
+            if (g == NG - 1) bt = bias_tile(w + SA1_BP, (mt + 1) & 3, h);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int kq = g * G + i;
+                acc = mfma4(cur[i], X[kq / 4], 4 * (kq % 4), acc);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < G; ++i) cur[i] = nxt[i];
+        }
+        if (c < nvalid) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                *(float4*)(o + mt * 32 + 8 * q) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+        }
+    }
+}
+
+// After a centre's pool, lane 32h+c holds channel 32(mt-1+h)+c of m-tile pair (mt-1, mt): the 128 pooled values go to
+// row (centre - first) % SA1_ROWS of the wave's staging tile in LDS instead of to global memory, and once the tile is full
+// (or the slice ends) the wave applies SA2's per-point layer to it (sa1_p2_tile) and stores P -- what a kernel of its own
+// used to do from a feat1 written to and read back from memory. feat1 itself is written only when the caller wants the
+// debug copy (feat != nullptr). The staging tile is private to the wave and LDS operations of one wave complete in order,
+// so the hand-over from the lanes that write a row to the lanes that read it needs no barrier.
 __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ point_x, int M,
                                                      const int* __restrict__ ball, const float* __restrict__ cxyz,
                                                      int np, int total, const float* __restrict__ W1p,
                                                      const float* __restrict__ b1, const float* __restrict__ W2p,
                                                      const float* __restrict__ b2, const float* __restrict__ W3p,
-                                                     const float* __restrict__ b3, float* __restrict__ feat) {
+                                                     const float* __restrict__ b3, const float* __restrict__ Wpp,
+                                                     const float* __restrict__ bp, float* __restrict__ feat,
+                                                     float* __restrict__ P) {
+    extern __shared__ __attribute__((aligned(16))) float wl[];
     const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    stage_lds(wl + SA1_WP, Wpp, 16384);
+    stage_lds(wl + SA1_BP, bp, 128);
+    __syncthreads();                   // the only barrier: every wave passes it before any may leave
     // this wave's contiguous slice of the centres (consecutive centres mostly share a hypothesis, i.e. a gather base); the
     // wave index is made visibly uniform so that the centre walk lives in scalar registers
-    const int gw = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = gridDim.x * 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gw = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
     const int per = total / nw, rem = total % nw;
     const int first = gw * per + min(gw, rem), end = first + per + (gw < rem ? 1 : 0);
     if (first >= end) return;          // fewer centres than waves: nothing to do, no weights loaded
+    float* stage = wl + SA1_STAGE + wave * (SA1_ROWS * SA1_PITCH);
     float4 w1[2], w2[16], w3[32];
     load_quads(w1, W1p, lane);
     load_quads(w2, W2p, lane);
@@ -802,6 +858,7 @@ __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ p
     };
     fetch_index(first);
     fetch_rows(first);
+    int row = 0;                       // the centre's row in the staging tile
 #pragma unroll 1
     for (int centre = first; centre < end; ++centre) {
         const int next = min(centre + 1, end - 1);            // (the last centre prefetches itself: harmless)
@@ -842,13 +899,14 @@ __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ p
             Y2[0][mt] = relu16(acc[0]);
             Y2[1][mt] = relu16(acc[1]);
         }
-        float* out = feat + (size_t)centre * 128 + lane;   // lane = 32 h + c: half h stores the m-tile after half 0's
+        float* srow = stage + row * SA1_PITCH + lane;       // lane = 32 h + c: half h holds the m-tile after half 0's
         __builtin_amdgcn_sched_barrier(0);
         fetch_rows(next);
         __builtin_amdgcn_sched_barrier(0);
-        // last layer, operands swapped (see mfma4_swapped). After the pool both lane halves hold the tile's 32 maxima, so one
-        // full-wave store writes TWO m-tiles (half h stores tile 2j + h)
-        float pooled[4];
+        // last layer, operands swapped (see mfma4_swapped). The merge of the lane halves takes two m-tiles at once, so one
+        // full-wave write puts TWO m-tiles into the staging row (half h holds tile 2j + h)
+        int pooled[4];
+        float out[2];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             v16f acc[2];
@@ -858,53 +916,22 @@ __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ p
 #pragma unroll
                 for (int t = 0; t < 2; ++t) acc[t] = mfma4_swapped(Y2[t][kq / 4], 4 * (kq % 4), w3[mt * 8 + kq], acc[t]);
             }
-            pooled[mt] = pool_swapped(max16(acc[0], acc[1]));
-            if (mt & 1) out[(mt - 1) * 32] = h ? pooled[mt] : pooled[mt - 1];
+            pooled[mt] = pool_acc(acc[1], pool_acc(acc[0], 0));
+            if (mt & 1) srow[(mt - 1) * 32] = out[mt / 2] = pool_halves(pooled[mt - 1], pooled[mt]);
+        }
+        if (feat) {                    // the debug copy of feat1 (one uniform branch per centre)
+            float* o = feat + (size_t)centre * 128 + lane;
+            o[0] = out[0], o[64] = out[1];
+        }
+        if (row == SA1_ROWS - 1 || centre == end - 1) {
+            // other lanes of this wave wrote the rows a lane reads now: a wavefront-scope fence (no instruction) states it
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            sa1_p2_tile(wl + opaque_zero(), stage, P, centre - row, row + 1, lane);
+            row = 0;
+        } else {
+            ++row;
         }
     }
-}
-
-__device__ __forceinline__ void stage_lds(float* dst, const float* __restrict__ src, int nfloats) {
-    for (int i = threadIdx.x * 4; i < nfloats; i += blockDim.x * 4) *(float4*)(dst + i) = *(const float4*)(src + i);
-}
-
-// ---- P2: per-point part of SA2's first layer: p[pt][o] = chain(bias, W[:, :128] . feat1[pt]) ----------
-// (the grouped-xyz columns are applied per sample in sa2_kernel, continuing the same chain)
-__global__ __launch_bounds__(256, 2) void p2_kernel(const float* __restrict__ feat, int total_tiles,
-                                                    const float* __restrict__ Wp, const float* __restrict__ bias,
-                                                    float* __restrict__ P) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, c = lane & 31;
-    const int tile0 = (blockIdx.x * 4 + wave) * 2;
-    if (tile0 >= total_tiles) return;
-    const bool two = tile0 + 1 < total_tiles;
-    v16f X[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int pt = (tile0 + ((t == 1 && two) ? 1 : 0)) * 32 + c;
-        const float* r = feat + (size_t)pt * 128 + 4 * h;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 v = *(const float4*)(r + kt * 32 + 8 * q);
-                X[t][kt][4 * q + 0] = v.x;
-                X[t][kt][4 * q + 1] = v.y;
-                X[t][kt][4 * q + 2] = v.z;
-                X[t][kt][4 * q + 3] = v.w;
-            }
-    }
-    float* o0 = P + (size_t)(tile0 * 32 + c) * 128 + 4 * h;
-    stream_layer_rolled<4, 2, 8>((const float4*)Wp + lane, bias, X, h, 4, [&](int mt, v16f(&acc)[2]) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            if (t == 1 && !two) break;
-            float* o = o0 + (size_t)t * 32 * 128 + mt * 32;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *(float4*)(o + 8 * q) =
-                    make_float4(acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]);
-        }
-    });
 }
 
 // ---- SA2: (P gather + xyz columns) -> relu -> 128 -> 256 -> max over 64 samples ----------------------
@@ -1011,9 +1038,9 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
         return a;
     };
     v16f bs = b3_tile(wl, 0);
-    float kp[8];
+    int kp[8];                         // the centre's running maxima, as bit patterns (see pool_acc)
 #pragma unroll
-    for (int mt = 0; mt < 8; ++mt) kp[mt] = 0.0f;
+    for (int mt = 0; mt < 8; ++mt) kp[mt] = 0;
 #pragma unroll 1
     for (int it = 2 * first; it < it_end; ++it) {
         const float* w = wl + opaque_zero();      // keeps the LDS reads of this iteration inside it
@@ -1076,15 +1103,18 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
 #pragma unroll
                 for (int i = 0; i < G; ++i) cur[i] = nxt[i];
             }
-            kp[mt] = max1(pool_swapped(acc), kp[mt]);          // pooled values are >= +0: the 0 of a fresh centre is neutral
+            // the kept maximum of the centre's first tile (or the 0 of a fresh centre, which is the ReLU) starts the chain;
+            // the lane halves are merged once per centre, below
+            kp[mt] = pool_acc(acc, kp[mt]);
         }
         if (t) {
-            // both lane halves hold every tile's 32 maxima, so one full-wave store writes two m-tiles (lane = 32 h + c)
+            // after the merge both lane halves hold every tile's 32 maxima, so one full-wave store writes two m-tiles
+            // (lane = 32 h + c)
             float* out = feat + (size_t)(it >> 1) * 256 + lane;
 #pragma unroll
-            for (int mt = 0; mt < 8; mt += 2) out[mt * 32] = h ? kp[mt + 1] : kp[mt];
+            for (int mt = 0; mt < 8; mt += 2) out[mt * 32] = pool_halves(kp[mt], kp[mt + 1]);
 #pragma unroll
-            for (int mt = 0; mt < 8; ++mt) kp[mt] = 0.0f;
+            for (int mt = 0; mt < 8; ++mt) kp[mt] = 0;
         }
     }
 }
@@ -1370,7 +1400,7 @@ int ossid_event_elapsed_ms(void* start, void* stop, float* ms_out_host) {
 }
 
 const char* ossid_pn2_kernel_names(void) {
-    return "fps_reg_kernel,fps_kernel,ball_query_reg_kernel,ball_query_kernel,sa1_kernel,p2_kernel,sa2_kernel,sa3_kernel,fc_head_kernel";
+    return "fps_reg_kernel,fps_kernel,ball_query_reg_kernel,ball_query_kernel,sa1_kernel,sa2_kernel,sa3_kernel,fc_head_kernel";
 }
 
 // The nine stages of ossid_pn2_score, one launcher each.
@@ -1416,21 +1446,20 @@ int persistent_grid() {
     return cache[dev];
 }
 
-int pn2_sa1(const Pn2Call& c) {
+// feat1 leaves sa1_kernel only for the caller's debug copy: SA2 reads the layer applied to it (ws.p2), not feat1 itself
+int pn2_sa1(const Pn2Call& c, bool want_feat1) {
     const float* blob = c.w->blob;
     const int total = c.B * c.np1;
-    hipLaunchKernelGGL(sa1_kernel, dim3(persistent_grid()), dim3(256), 0, c.s, c.point_x, c.M, c.ws.ball1, c.ws.xyz1, c.np1, total,
-                       blob + c.w->w_off[0], blob + c.w->b_off[0], blob + c.w->w_off[1], blob + c.w->b_off[1],
-                       blob + c.w->w_off[2], blob + c.w->b_off[2], c.ws.feat1);
+    OSSID_ENSURE_LDS(sa1_kernel, (size_t)SA1_LDS_FLOATS * 4);
+    hipLaunchKernelGGL(sa1_kernel, dim3(persistent_grid()), dim3(256), SA1_LDS_FLOATS * 4, c.s, c.point_x, c.M, c.ws.ball1,
+                       c.ws.xyz1, c.np1, total, blob + c.w->w_off[0], blob + c.w->b_off[0], blob + c.w->w_off[1],
+                       blob + c.w->b_off[1], blob + c.w->w_off[2], blob + c.w->b_off[2], blob + c.w->w_off[3],
+                       blob + c.w->b_off[3], want_feat1 ? c.ws.feat1 : nullptr, c.ws.p2);
     return ossid_launch_status();
 }
-int pn2_p2(const Pn2Call& c) {
-    const float* blob = c.w->blob;
-    const int tiles = c.B * c.np1 / 32;
-    hipLaunchKernelGGL(p2_kernel, dim3((tiles + 7) / 8), dim3(256), 0, c.s, c.ws.feat1, tiles, blob + c.w->w_off[3],
-                       blob + c.w->b_off[3], c.ws.p2);
-    return ossid_launch_status();
-}
+// the "p2" stage (the per-point part of SA2's first layer) is computed by sa1_kernel: the stage keeps its name and its event
+// marks, and launches nothing
+int pn2_p2(const Pn2Call&) { return OSSID_OK; }
 int pn2_sa2(const Pn2Call& c) {
     const float* blob = c.w->blob;
     const int total = c.B * c.np2;
@@ -1480,7 +1509,7 @@ int ossid_pn2_score(const float* point_x, int B, int M, const ossid_pn2_weights*
     mark();
     if ((rc = pn2_ball1(c))) return rc;
     mark();
-    if ((rc = pn2_sa1(c))) return rc;
+    if ((rc = pn2_sa1(c, dbg_feat1 != nullptr))) return rc;
     mark();
     if ((rc = pn2_p2(c))) return rc;
     mark();

@@ -13,7 +13,7 @@ ap.add_argument("csv")
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 a = ap.parse_args()
-names = ("fps_reg_kernel", "ball_query_reg_kernel", "ball_query_kernel", "sa1_kernel", "p2_kernel", "sa2_kernel", "sa3_kernel", "fc_head_kernel", "featurize_kernel")
+names = ("fps_reg_kernel", "ball_query_reg_kernel", "ball_query_kernel", "sa1_kernel", "sa2_kernel", "sa3_kernel", "fc_head_kernel", "featurize_kernel")
 rows = collections.defaultdict(list)
 with open(a.csv) as f:
     for r in csv.DictReader(f):
