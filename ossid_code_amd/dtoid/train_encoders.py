@@ -129,7 +129,7 @@ STEM_KPAD = 48        # 3 x 3 x 4 = 36 im2col columns padded to the convolution 
 def stem_relayout(src, dst, cout, cin, k, kpad, inverse=False):
     """ossid_stem_weight_relayout: [cout, cin, k, k] -> [cout, kpad] in ossid_im2col_stem's column order, or back."""
     with _lib.on_device(src.device):
-        _lib.check(_lib.fn("ossid_stem_weight_relayout")(src.data_ptr(), dst.data_ptr(), cout, cin, k, kpad, 1 if inverse else 0,
+        _lib.check(_lib.fn("ossid_stem_weight_relayout")(T.dptr(src), T.dptr(dst), cout, cin, k, kpad, 1 if inverse else 0,
                                                          _lib.stream()), "ossid_stem_weight_relayout")
 
 
@@ -335,19 +335,10 @@ def _encoder_backward(mod, gout, sv, side, direct=False):
     grads[stem.bias] = sums[0]
     dw_cols = wgrad_later(None, cols, g, B, H0, W0, STEM_KPAD, 64, 1, key="stem")
     dw_stem = T.grad_home(stem.weight, direct)
-    # everything the side stream reads or writes (the caching allocator must not hand an operand's memory to the next
-    # allocation on THIS stream while the grouped launch is still reading it: outside a recorded sequence -- whose buffers
-    # are persistent -- the intermediate gradients die when this function returns; recording only the outputs left
-    # tests/test_dtoid_gpu.py::test_template_encoder_training_node_matches_module_path[False-*] with one layer's weight
-    # gradient a few 1e-3 off once in a few full-suite runs)
-    touched = [it["dw"] for it in deferred] + [dw_stem, dw_cols]
-    for it in deferred:
-        touched += [it["x"], it["dy"]] + (list(it["pre"]) if it.get("pre") is not None else [])
-
     def weight_gradients():            # one grouped launch, then the stem's from im2col column order back to [64, 4, 3, 3]
         T.wgrad_group(deferred)
         stem_relayout(dw_cols, dw_stem, 64, 4, 3, STEM_KPAD, inverse=True)
-    T._wgrad_async(touched, weight_gradients, dev, side=side)
+    T._wgrad_async(weight_gradients, dev, side=side)
     sv_out = [dw_stem, grads[stem.bias]]
     for p in encoder_params(mod)[2:]:
         sv_out.append(grads[p])
@@ -379,7 +370,7 @@ class TemplateEncoderTrain(torch.autograd.Function):
                     plan.t["out"], plan.t["sv"] = _encoder_forward(mod, plan.t["cols"])
                 plan.fwd = seq
             else:
-                plan.fwd.run((T._cur_stream(dev),))
+                plan.fwd.run((torch.cuda.current_stream(dev),))
             out, sv = T._alias(plan.t["out"]), plan.t["sv"]
             plan.gen += 1
             ctx.gen = plan.gen

@@ -26,10 +26,6 @@ from .. import _lib
 _byref = ctypes.byref
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 def nhwc(x):
     return x.float().contiguous(memory_format=torch.channels_last)
 
@@ -119,9 +115,9 @@ def chan_op(g, n_rows, C, x=None, out=None, g_cs=0, x_cs=0, out_cs=0, alpha=None
     valid until the next deferred chan_op on this stream."""
     d = _lib.ChanOpDesc()
     dev = g.device
-    d.g, d.x, d.out = g.data_ptr(), _p(x), _p(out)
-    d.alpha, d.beta, d.kappa, d.mask_scale, d.mask_shift = _p(alpha), _p(beta), _p(kappa), _p(mask_scale), _p(mask_shift)
-    d.pivot = _p(pivot)
+    d.g, d.x, d.out = g.data_ptr(), dptr(x), dptr(out)
+    d.alpha, d.beta, d.kappa, d.mask_scale, d.mask_shift = dptr(alpha), dptr(beta), dptr(kappa), dptr(mask_scale), dptr(mask_shift)
+    d.pivot = dptr(pivot)
     d.n_rows, d.channels, d.g_stride, d.x_stride, d.out_stride = int(n_rows), int(C), int(g_cs), int(x_cs), int(out_cs)
     d.mask_mode, d.accumulate, d.sum_mode, d.sums_row_stride = int(mask_mode), 1 if accumulate else 0, int(sum_mode), int(sums_row_stride)
     if sum_mode:
@@ -317,7 +313,7 @@ def conv_raw(x, wpk, B, H, W, cin, cout, taps, out, bias=None, pre=None, pre_rel
     """ossid_conv_nhwc_fwd / ossid_conv3x3_wino_fwd on raw channels-last buffers. epi: {"timing_buf": tensor} for the
     -DOSSID_TIMING diagnostic builds only (tools/conv_timeline.py)."""
     d = _lib.ConvDesc()
-    d.x, d.wpk, d.bias, d.out = x.data_ptr(), wpk.data_ptr(), _p(bias), out.data_ptr()
+    d.x, d.wpk, d.bias, d.out = x.data_ptr(), wpk.data_ptr(), dptr(bias), out.data_ptr()
     if pre is not None:
         d.pre_scale, d.pre_shift = pre[0].data_ptr(), pre[1].data_ptr()
     d.in_batch_stride, d.pre_batch_stride = -1, 0
@@ -349,9 +345,9 @@ def wgrad_raw(x, dy, B, H, W, cin, cout, taps, dw, pre=None, pre_relu=False, in_
     dev = dw.device
     nbytes = _lib.fn("ossid_conv_wgrad_workspace_bytes")(B, H, W, cin, cout, taps)
     ws = _scratch("wgrad", nbytes, dev)
-    d.x, d.dy, d.dw, d.workspace, d.workspace_bytes = x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), nbytes
+    d.x, d.dy, d.dw, d.workspace, d.workspace_bytes = dptr(x), dptr(dy), dptr(dw), dptr(ws), nbytes
     if pre is not None:
-        d.pre_scale, d.pre_shift = pre[0].data_ptr(), pre[1].data_ptr()
+        d.pre_scale, d.pre_shift = dptr(pre[0]), dptr(pre[1])
     d.batch, d.height, d.width, d.cin, d.cout, d.taps = B, H, W, cin, cout, taps
     d.pre_relu, d.accumulate = 1 if pre_relu else 0, 1 if accumulate else 0
     d.in_channel_stride, d.dy_channel_stride = int(in_cs), int(dy_cs)
@@ -367,23 +363,20 @@ def wgrad_group(items):
     n = len(items)
     arr = (_lib.WgradDesc * n)()
     for d, it in zip(arr, items):
-        d.x, d.dy, d.dw = it["x"].data_ptr(), it["dy"].data_ptr(), it["dw"].data_ptr()
-        pre = it.get("pre")
-        if pre is not None:
-            d.pre_scale, d.pre_shift = pre[0].data_ptr(), pre[1].data_ptr()
+        d.x, d.dy, d.dw = dptr(it["x"]), dptr(it["dy"]), dptr(it["dw"])
+        d.pre_scale, d.pre_shift = map(dptr, it.get("pre") or (None, None))
         d.batch, d.height, d.width, d.cin, d.cout, d.taps = it["B"], it["H"], it["W"], it["cin"], it["cout"], it["taps"]
         d.pre_relu, d.accumulate = 1 if it.get("pre_relu") else 0, 0
         d.in_channel_stride, d.dy_channel_stride = int(it.get("in_cs", 0)), int(it.get("dy_cs", 0))
-        add = it.get("dy_add")
-        if add is not None:                      # dy = dy + scale * add + shift while it is staged (ossid_wgrad_desc.dy_add)
-            d.dy_add, d.dy_add_scale, d.dy_add_shift = add[0].data_ptr(), add[1].data_ptr(), add[2].data_ptr()
+        # dy = dy + scale * add + shift while it is staged (ossid_wgrad_desc.dy_add)
+        d.dy_add, d.dy_add_scale, d.dy_add_shift = map(dptr, it.get("dy_add") or (None, None, None))
     dev = items[0]["dw"].device
     nbytes = _lib.fn("ossid_conv_wgrad_group_workspace_bytes")(arr, n)
     if nbytes == 0:
         raise RuntimeError("ossid_conv_wgrad_group_workspace_bytes rejected the group")
     ws = _scratch("wgrad_group", nbytes, dev)
     with _lib.on_device(dev):
-        _lib.check(_lib.fn("ossid_conv_wgrad_group")(arr, n, ws.data_ptr(), nbytes, _lib.stream()), "ossid_conv_wgrad_group")
+        _lib.check(_lib.fn("ossid_conv_wgrad_group")(arr, n, dptr(ws), nbytes, _lib.stream()), "ossid_conv_wgrad_group")
 
 
 def bn_fold_fwd(sums, C, n, gamma, beta, eps, momentum, running_mean, running_var, sums_row_stride=0, pivot=None):
@@ -400,9 +393,9 @@ def bn_fold_fwd(sums, C, n, gamma, beta, eps, momentum, running_mean, running_va
             pivot = sums[2]
     out = new_buf((4, C), dev)                                          # scale, shift, mean, rstd
     with _lib.on_device(dev):
-        rc = _lib.fn("ossid_bn_fold_fwd")(None if part is not None else sums.data_ptr(), int(sums_row_stride), _p(part), int(P),
-                                          _p(pivot), C, float(n), _p(gamma), _p(beta), float(eps),
-                                          float(momentum), _p(running_mean), _p(running_var), out[0].data_ptr(),
+        rc = _lib.fn("ossid_bn_fold_fwd")(None if part is not None else sums.data_ptr(), int(sums_row_stride), dptr(part), int(P),
+                                          dptr(pivot), C, float(n), dptr(gamma), dptr(beta), float(eps),
+                                          float(momentum), dptr(running_mean), dptr(running_var), out[0].data_ptr(),
                                           out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), _lib.stream())
     _lib.check(rc, "ossid_bn_fold_fwd")
     return out
@@ -414,9 +407,9 @@ def bn_fold_bwd(dscale, dshift, gamma, mean, rstd, C, n, dgamma, dbeta, coef_x, 
     zero_row: C floats the same launch clears."""
     part, P = partials if partials is not None else (None, 0)
     with _lib.on_device(coef_x.device):
-        rc = _lib.fn("ossid_bn_fold_bwd")(_p(dscale), _p(dshift), _p(part), int(P), _p(gamma), mean.data_ptr(), rstd.data_ptr(),
-                                          C, float(n), _p(dgamma), _p(dbeta), coef_x.data_ptr(), coef_1.data_ptr(),
-                                          1 if accumulate else 0, _p(zero_row), _lib.stream())
+        rc = _lib.fn("ossid_bn_fold_bwd")(dptr(dscale), dptr(dshift), dptr(part), int(P), dptr(gamma), mean.data_ptr(), rstd.data_ptr(),
+                                          C, float(n), dptr(dgamma), dptr(dbeta), coef_x.data_ptr(), coef_1.data_ptr(),
+                                          1 if accumulate else 0, dptr(zero_row), _lib.stream())
     _lib.check(rc, "ossid_bn_fold_bwd")
 
 
@@ -527,14 +520,36 @@ def bn_fold(sums, n, bn):
 
 
 # Weight gradients on a second HIP stream. A convolution's weight gradient feeds nothing but the optimizer, while its data
-# gradient is on the critical path of backward -- a chain of small launches (a dense layer's 3x3 / 1x1 data gradients and
-# the generic passes between them occupy a fraction of the chip each). With WGRAD_SIDE the weight-gradient launches go to
-# a side stream that waits for the main stream at the point of issue; the main stream joins it when the backward pass
-# ends (an autograd engine callback, so a bare loss.backward() is as safe as finetune_step) and wherever gradients are
-# read earlier (GradSync's per-bucket hooks). Tensors the side stream reads are record_stream()ed: the caching allocator
-# then keeps their memory until that work has run.
+# gradient is on the critical path of backward -- a chain of small launches that occupy a fraction of the chip each. With
+# WGRAD_SIDE the weight-gradient launches go to a side stream that waits for the main stream at the point of issue; the main
+# stream joins it when the backward pass ends (an autograd engine callback, so a bare loss.backward() is as safe as
+# finetune_step) and wherever gradients are read earlier (GradSync's per-bucket hooks). The caching allocator must keep what
+# such a launch reads or writes until it has run (record_stream), and nobody lists that by hand: a launcher that may be issued
+# there takes EVERY device address through dptr(), which notes the tensor while _wgrad_async is issuing; that records them.
 WGRAD_SIDE = True
 _wg_streams, _wg_dirty = {}, set()
+_SIDE_OPERANDS = None      # what dptr() noted for the _wgrad_async under way (set around a region like _lib._REC: one process per GPU)
+
+
+def dptr(t):
+    """Device address of a tensor / None, for the C ABI."""
+    if t is None:
+        return None
+    if _SIDE_OPERANDS is not None:
+        _SIDE_OPERANDS.append(t)
+    return t.data_ptr()
+
+
+def _side_operands_of(fn):
+    """Run fn(); the distinct tensor objects it passed to dptr() -- views as they came: record_stream acts on the storage's block."""
+    global _SIDE_OPERANDS
+    prev, _SIDE_OPERANDS = _SIDE_OPERANDS, []
+    try:
+        fn()
+        return list({id(t): t for t in _SIDE_OPERANDS}.values())
+    finally:
+        _SIDE_OPERANDS = prev
+
 
 from ..streams import N_STREAM_CANDIDATES, _side_pools, side_streams  # noqa: E402,F401  (the probe lives in ossid_code_amd/streams.py)
 
@@ -566,38 +581,44 @@ def _grad_taken_unread(w):
     return w.is_leaf and w.grad is None
 
 
-def _wgrad_async(tensors, fn, device, weights=(), side=None):
+def _wgrad_stream(device):
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _wg_streams:
+        _wg_streams[idx] = side_streams(device)["wgrad"]
+    return idx, _wg_streams[idx]
+
+
+def _wgrad_in_flight(idx):
+    # one callback per call, not "one while the set is empty": a backward pass that died in an exception never runs its
+    # callbacks, and a set left non-empty would then suppress the join of every later pass (the join itself is a no-op
+    # when nothing is in flight)
+    torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_stream)
+    _wg_dirty.add(idx)
+
+
+def _wgrad_async(fn, device, weights=(), side=None):
     """Run fn() -- weight-gradient launches writing the `dw` tensors a backward() is about to return -- on the side stream
-    (side=None: decide here, see _wgrad_side_ok). Inside a recorded launch sequence the launches are stored under stream
-    slot 1 behind a wait entry; the replay (_run_seq) does the bookkeeping below."""
+    (side=None: decide here, see _wgrad_side_ok) and record_stream() its operands. Inside a recorded launch sequence the
+    launches are stored under stream slot 1 behind a wait entry; the replay (_run_seq) records none: Seq.keep holds them."""
     if side is None:
         side = _wgrad_side_ok(device, weights)
     if not side:
         return fn()
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    main = torch.cuda.current_stream(idx)
-    st = _wg_streams.get(idx)
-    if st is None:
-        st = _wg_streams[idx] = side_streams(device)["wgrad"]
-    st.wait_stream(main)
+    idx, st = _wgrad_stream(device)
+    st.wait_stream(torch.cuda.current_stream(idx))
     rec = _lib.recording()
     if rec is not None:
         rec.wait(1, 0)
         rec.cur_slot, rec.seq.uses_side = 1, True
     try:
         with torch.cuda.stream(st):
-            fn()
+            operands = _side_operands_of(fn)
     finally:
         if rec is not None:
             rec.cur_slot = 0
-    for t in tensors:
-        if t is not None:
-            t.record_stream(st)
-    # one callback per call, not "one while the set is empty": a backward pass that died in an exception never runs its
-    # callbacks, and a set left non-empty would then suppress the join of every later pass (the join itself is a no-op
-    # when nothing is in flight)
-    torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_stream)
-    _wg_dirty.add(idx)
+    for t in operands:
+        t.record_stream(st)
+    _wgrad_in_flight(idx)
 
 
 USE_WINO = True
@@ -702,9 +723,8 @@ class FusedConv(torch.autograd.Function):
         dw = None
         if need[1]:
             dwb = grad_home(w, _grad_taken_unread(w))     # straight into the flat gradient buffer when autograd will take it over
-            _wgrad_async([x, dv, ps, pt, dwb], lambda: wgrad_raw(x, dv, B, H, W, Cin, Cout, taps, dwb, pre=pre, pre_relu=pre_relu,
-                                                                 src_hw=(Hs, Ws) if (H, W) != (Hs, Ws) else (0, 0)), dev,
-                         weights=(w,))
+            _wgrad_async(lambda: wgrad_raw(x, dv, B, H, W, Cin, Cout, taps, dwb, pre=pre, pre_relu=pre_relu,
+                                           src_hw=(Hs, Ws) if (H, W) != (Hs, Ws) else (0, 0)), dev, weights=(w,))
             dw = _alias(dwb)
         # 3. data gradient
         dx = dps = dpt = None
@@ -783,22 +803,14 @@ def _plan_for(module, key):
     return plan
 
 
-def _cur_stream(dev):
-    return torch.cuda.current_stream(dev)
-
-
 def _run_seq(seq, dev):
     """Replay on the current stream (slot 0) and, if the sequence has side launches, the weight-gradient stream (slot 1),
     with the bookkeeping _wgrad_async does for an eager launch (the end-of-backward join)."""
-    main = _cur_stream(dev)
+    main = torch.cuda.current_stream(dev)
     if seq.uses_side:
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        side = _wg_streams.get(idx)
-        if side is None:
-            side = _wg_streams[idx] = side_streams(dev)["wgrad"]
+        idx, side = _wgrad_stream(dev)
         seq.run((main, side))
-        torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_stream)
-        _wg_dirty.add(idx)
+        _wgrad_in_flight(idx)
     else:
         seq.run((main,))
 
@@ -824,8 +836,8 @@ def bn_fold_fwd_rows(rows, C, n, gamma, beta, eps, momentum, running_mean, runni
     part, counts, P = rows
     out = new_buf((4, C), part.device)
     with _lib.on_device(part.device):
-        rc = _lib.fn("ossid_bn_fold_fwd_rows")(part.data_ptr(), counts.data_ptr(), int(P), C, float(n), _p(gamma), _p(beta), float(eps),
-                                               float(momentum), _p(running_mean), _p(running_var), out[0].data_ptr(),
+        rc = _lib.fn("ossid_bn_fold_fwd_rows")(part.data_ptr(), counts.data_ptr(), int(P), C, float(n), dptr(gamma), dptr(beta), float(eps),
+                                               float(momentum), dptr(running_mean), dptr(running_var), out[0].data_ptr(),
                                                out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), _lib.stream())
     _lib.check(rc, "ossid_bn_fold_fwd_rows")
     return out
@@ -919,7 +931,6 @@ def _dense_backward(G, buf, saved, block, params, C0, side, direct=False):
     mid = int(params[2].shape[0])
     dz_all = new_buf((L, B, H, W, mid), dev)                      # per layer: the 1x1 wgrad runs at the end
     deferred = []                                                 # the block's 2 L weight gradients: ONE grouped launch below
-    side_reads = []                                               # small tensors of this function the grouped launch reads
     da = None
     fused_bwd = (mid == 128 and Ct <= 1024 and N * Ct < (1 << 32) and
                  bool(_lib.fn("ossid_conv_split_bf16")()))
@@ -960,7 +971,6 @@ def _dense_backward(G, buf, saved, block, params, C0, side, direct=False):
         # dz = scale*db*mask + coef_x*y1 + coef_1: a pass of its own, or -- with the fused 1x1 data gradient -- formed while dz is
         # staged, there and in the (deferred) 1x1 weight gradient
         add = (y1, r2[2], r2[3]) if fused_bwd else None
-        side_reads.append(r2)                                     # (the deferred 1x1 weight gradient reads r2[2], r2[3] on the side stream)
         if add is None:
             chan_op(db, N, mid, x=y1, out=db, beta=r2[2], kappa=r2[3])
         # 1x1: weight gradient on relu(bn1(buf[:, :c])) (deferred), data gradient to the c input channels
@@ -980,9 +990,7 @@ def _dense_backward(G, buf, saved, block, params, C0, side, direct=False):
         r1 = new_buf((2, c), dev)
         bn_fold_bwd(None, None, g1, f1[2], f1[3], c, N, r1[0], r1[1], coef[0], coef[1], accumulate=True, partials=s)
         grads[6 * li:6 * li + 6] = [r1[0], r1[1], dw1, r2[0], r2[1], dw2]
-    touched = [G, buf, dz_all] + [t for sv in saved for t in (sv[1], sv[0][0], sv[0][1], sv[2][0], sv[2][1])] + \
-        [it["dw"] for it in deferred] + side_reads
-    _wgrad_async(touched, lambda: wgrad_group(deferred), dev, side=side)
+    _wgrad_async(lambda: wgrad_group(deferred), dev, side=side)
     # the block's input channels, written compactly
     dx = new_buf((B, C0, H, W), dev, channels_last=True)
     chan_op(G, N, C0, x=buf, out=dx, g_cs=Ct, x_cs=Ct, beta=coef[0, :C0], kappa=coef[1, :C0])
@@ -1041,7 +1049,7 @@ class DenseBlockTrain(torch.autograd.Function):
             plan.fwd = seq
             saved = plan.t["saved"]
         else:
-            plan.fwd.run((_cur_stream(dev),))
+            plan.fwd.run((torch.cuda.current_stream(dev),))
             saved = plan.t["saved"]
         out = buf if plan is None else _alias(buf)
         # The OUTPUT must go through save_for_backward: `ctx.buf = buf` would close a cycle ctx -> buf -> grad_fn -> ctx
@@ -1186,6 +1194,15 @@ class AffineAct(torch.autograd.Function):
         return dx, s[1], s[0], None
 
 
+def conv3x3_c1_wgrad_raw(x, g, B, H, W, C, dwb, dbb):
+    """ossid_conv3x3_c1_wgrad: dwb [1,C,3,3], dbb [1] from x [B][H][W][C] and g [B][H][W]."""
+    nbytes = _lib.fn("ossid_conv3x3_c1_wgrad_workspace_bytes")()
+    with _lib.on_device(x.device):
+        ws = _scratch("c1_wgrad", nbytes, x.device)
+        _lib.check(_lib.fn("ossid_conv3x3_c1_wgrad")(dptr(x), dptr(g), B, H, W, C, dptr(ws), nbytes, dptr(dwb), dptr(dbb),
+                                                     _lib.stream()), "ossid_conv3x3_c1_wgrad")
+
+
 class Conv3x3C1(torch.autograd.Function):
     """nn.Conv2d(C, 1, 3, padding=1) on a channels-last x [B,C,H,W] -> [B,1,H,W] (the decoder's seg_final, network.py:362) on the
     vector-ALU kernels of csrc/train.hip (ossid_conv3x3_c1_*): MIOpen's implicit-GEMM kernels for this one-row layer plus
@@ -1198,7 +1215,7 @@ class Conv3x3C1(torch.autograd.Function):
         wc = w.detach().contiguous()
         out = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
         with _lib.on_device(x.device):
-            _lib.check(_lib.fn("ossid_conv3x3_c1_fwd")(x.data_ptr(), B, H, W, C, wc.data_ptr(), _p(None if bias is None else bias.detach()),
+            _lib.check(_lib.fn("ossid_conv3x3_c1_fwd")(x.data_ptr(), B, H, W, C, wc.data_ptr(), dptr(None if bias is None else bias.detach()),
                                                        out.data_ptr(), _lib.stream()), "ossid_conv3x3_c1_fwd")
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -1215,13 +1232,7 @@ class Conv3x3C1(torch.autograd.Function):
             if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
                 dwb = grad_home(w, _grad_taken_unread(w))
                 dbb = torch.empty(1, dtype=torch.float32, device=dev)
-                nbytes = _lib.fn("ossid_conv3x3_c1_wgrad_workspace_bytes")()
-
-                def run():
-                    ws = _scratch("c1_wgrad", nbytes, dev)
-                    _lib.check(_lib.fn("ossid_conv3x3_c1_wgrad")(x.data_ptr(), g.data_ptr(), B, H, W, C, ws.data_ptr(), nbytes,
-                                                                 dwb.data_ptr(), dbb.data_ptr(), _lib.stream()), "ossid_conv3x3_c1_wgrad")
-                _wgrad_async([x, g, dwb, dbb], run, dev, weights=(w,))
+                _wgrad_async(lambda: conv3x3_c1_wgrad_raw(x, g, B, H, W, C, dwb, dbb), dev, weights=(w,))
                 # (fresh tensor objects on the same memory: AccumulateGrad takes a gradient over unread only when nothing else
                 # refers to the tensor OBJECT, and clones it -- i.e. reads it -- otherwise)
                 dw, db = _alias(dwb), (_alias(dbb) if ctx.has_bias else None)
@@ -1249,7 +1260,7 @@ class Conv1x1C1(torch.autograd.Function):
         wf = w.detach().reshape(-1).contiguous()
         out = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
         with _lib.on_device(x.device):
-            _lib.check(_lib.fn("ossid_conv1x1_c1_fwd")(x.data_ptr(), B * H * W, C, wf.data_ptr(), _p(None if bias is None else bias.detach()),
+            _lib.check(_lib.fn("ossid_conv1x1_c1_fwd")(x.data_ptr(), B * H * W, C, wf.data_ptr(), dptr(None if bias is None else bias.detach()),
                                                        0, out.data_ptr(), _lib.stream()), "ossid_conv1x1_c1_fwd")
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -1267,7 +1278,7 @@ class Conv1x1C1(torch.autograd.Function):
         ws = _scratch("c1x1_bwd", _lib.fn("ossid_conv1x1_c1_bwd_workspace_floats")(rows, C) * 4, dev)
         dwb = torch.empty(C + 1, dtype=torch.float32, device=dev)
         with _lib.on_device(dev):
-            _lib.check(_lib.fn("ossid_conv1x1_c1_bwd")(x.data_ptr(), g.data_ptr(), rows, C, wf.data_ptr(), ws.data_ptr(), _p(dx),
+            _lib.check(_lib.fn("ossid_conv1x1_c1_bwd")(x.data_ptr(), g.data_ptr(), rows, C, wf.data_ptr(), ws.data_ptr(), dptr(dx),
                                                        dwb.data_ptr(), _lib.stream()), "ossid_conv1x1_c1_bwd")
         return dx, dwb[:C].reshape(w.shape), (dwb[C:] if ctx.has_bias else None)
 
@@ -1282,6 +1293,14 @@ def bn_act_train(x, bn, relu=False):
     B, C, H, W = x.shape
     scale, shift = bn_fold(ColStats.apply(x), B * H * W, bn)
     return AffineAct.apply(x, scale, shift, bool(relu))
+
+
+def stem_wgrad_raw(img, g, B, Cin, H, W, Cout, k, dwb):
+    """ossid_stem_conv_wgrad (stride 2, padding 3): dwb [Cout,Cin,k,k] from the NCHW image and g [B][Ho][Wo][Cout]."""
+    with _lib.on_device(img.device):
+        ws = _scratch("stem_wgrad", _lib.fn("ossid_stem_conv_wgrad_workspace_bytes")(B, H, W), img.device)
+        _lib.check(_lib.fn("ossid_stem_conv_wgrad")(dptr(img), dptr(g), B, Cin, H, W, Cout, k, 2, 3, None, None, dptr(ws),
+                                                    ws.numel(), dptr(dwb), 0, _lib.stream()), "ossid_stem_conv_wgrad")
 
 
 class StemConv(torch.autograd.Function):
@@ -1301,7 +1320,7 @@ class StemConv(torch.autograd.Function):
         assert wd.is_contiguous()
         with _lib.on_device(img.device):
             _lib.check(_lib.fn("ossid_stem_conv_fwd")(img.data_ptr(), B, Cin, H, W, wd.data_ptr(), Cout, k, 2, 3,
-                                                      _p(None if bias is None else bias.detach()), None, None, out.data_ptr(),
+                                                      dptr(None if bias is None else bias.detach()), None, None, out.data_ptr(),
                                                       _lib.stream()), "ossid_stem_conv_fwd")
         ctx.save_for_backward(img, w)
         ctx.has_bias = bias is not None
@@ -1312,22 +1331,13 @@ class StemConv(torch.autograd.Function):
         img, w = ctx.saved_tensors
         B, Cin, H, W = img.shape
         Cout, k = int(w.shape[0]), int(w.shape[2])
-        dev = img.device
         g = nhwc(g)
         dw = db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = g.sum((0, 2, 3))
         if ctx.needs_input_grad[1]:
             dwb = grad_home(w, _grad_taken_unread(w))
-            nbytes = _lib.fn("ossid_stem_conv_wgrad_workspace_bytes")(B, H, W)
-
-            def run():
-                ws = _scratch("stem_wgrad", nbytes, dev)
-                _lib.check(_lib.fn("ossid_stem_conv_wgrad")(img.data_ptr(), g.data_ptr(), B, Cin, H, W, Cout, k, 2, 3, None, None,
-                                                            ws.data_ptr(), ws.numel(), dwb.data_ptr(), 0, _lib.stream()),
-                           "ossid_stem_conv_wgrad")
-            with _lib.on_device(dev):
-                _wgrad_async([img, g, dwb], run, dev, weights=(w,))
+            _wgrad_async(lambda: stem_wgrad_raw(img, g, B, Cin, H, W, Cout, k, dwb), img.device, weights=(w,))
             dw = _alias(dwb)
         return None, dw, db
 
