@@ -120,6 +120,12 @@ int ossid_pn2_score(const float* point_x, int B, int M, const ossid_pn2_weights*
                     float* dbg_feat1, int32_t* dbg_fps2, int32_t* dbg_ball2, float* dbg_feat2,
                     float* dbg_feat3, void* const* stage_events_host, void* stream);
 
+/* Workgroups in the grid of the two persistent kernels (sa1_kernel, sa2_kernel) of every later ossid_pn2_score call
+ * of the process. 0, the default and what every product path uses: one workgroup per compute unit. A test sets a few
+ * workgroups to give every wave a long slice of centres at a small batch; the results do not depend on it.
+ * OSSID_EINVAL: workgroups outside [0, 65536] (nothing changed). */
+int ossid_pn2_set_persistent_grid(int workgroups);
+
 /* Kernel order of ossid_pn2_score; with stage_events_host != NULL (an array of OSSID_PN2_NSTAGES+1 hipEvent_t made
  * by ossid_event_create) event[i] is recorded on `stream` before stage i and event[NSTAGES] after the last, so a
  * caller can time each kernel of the launch it is actually measuring (bench.py's roofline leg). */

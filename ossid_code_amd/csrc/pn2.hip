@@ -934,9 +934,96 @@ __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ p
     }
 }
 
+// ---- the order in which a persistent wave visits its centres, and the shared tile (SPEC 4.5) -------------------------
+// A ball row with d <= 48 distinct hits repeats its first hit in slots 48..63, and the pool is a max: those 16 columns
+// cannot change it. Such a row is SMALL, and it shows without a count: hits are distinct and ascending and the padding is
+// the first hit, so a row is small iff slot 48 equals slot 0. A small centre needs slots 0..47 only, a tile and a half --
+// and the last layer, run with its operands swapped, keeps the halves of a tile apart by itself: sample column c lands in
+// lane half (c >> 2) & 1 (row 8(r>>2) + 4h + (r&3) of the accumulator, see mfma4_swapped), so pool_acc returns one maximum
+// per lane half and they meet only in pool_halves. A SHARED tile S(A, B) carries slots 32..47 of small centre A in the 16
+// columns with bit 2 clear and those of small centre B in the 16 columns with bit 2 set, each column with its own centre's
+// coordinates and gather base; lane half 0 of its pool belongs to A, lane half 1 to B. Two small centres then cost three
+// tiles (A.0, S, B.0) instead of four, and every value is what it was: the same fmaf chain per column, a max over the same
+// set of values.
+//
+// The schedule is wave-uniform and lives in scalar registers. A wave's slice [first, end) is cut into groups of 32
+// consecutive centres from its start (the last one partial). Per group, lanes 0..31 load slot 0 and slot 48 of their
+// centre's row -- a group ahead, there is no partner wave to cover the latency -- and a ballot of their equality is the
+// group's mask of small centres. The wave visits the group's large centres in ascending order, then its small ones in
+// ascending order in pairs (1st with 2nd, 3rd with 4th, ...); an odd last one runs as an ordinary two-tile centre. A pair
+// may straddle a hypothesis boundary: its two centres carry a hypothesis each. (sa2_kernel walks this way; sa1_kernel
+// still visits its slice in ascending order, two tiles per centre.)
+enum { T_FIRST = 0, T_SECOND = 1, T_SHARED = 2, T_LAST = 3 };   // slots 0..31 of a | 32..63 of a | S(a, b) | 0..31 of b
+
+struct CentreWalk {
+    const int* ball;
+    int end, np, c;                // the slice's end, centres per hypothesis, lane & 31
+    int g0, gh, gr;                // the group's first centre, its hypothesis and its place in it
+    unsigned large, small;         // the group's centres not yet visited (bit j = centre g0 + j)
+    int n0, n48;                   // slots 0 and 48 of the NEXT group's rows (lane j and 32 + j: centre g0 + 32 + j)
+    int a, b, ha, hb;              // the centre(s) being visited and their hypotheses; a == b unless paired
+    int kind;                      // sa2_kernel walks tile by tile
+
+    __device__ __forceinline__ void load_rows(int g) {
+        const int ce = min(g + c, end - 1);
+        n0 = ball[(size_t)ce * 64], n48 = ball[(size_t)ce * 64 + 48];
+    }
+    __device__ __forceinline__ void open_group(int g) {
+        g0 = g;
+        const int left = __builtin_amdgcn_readfirstlane(end - g);
+        const unsigned valid = left >= 32 ? ~0u : (1u << left) - 1u;
+        const unsigned sm = __builtin_amdgcn_readfirstlane((unsigned)__builtin_amdgcn_ballot_w64(n0 == n48));
+        small = sm & valid, large = ~sm & valid;
+        load_rows(min(g + 32, end - 1));
+    }
+    __device__ __forceinline__ void start(const int* ball_, int first, int end_, int np_, int c_) {
+        ball = ball_, end = end_, np = np_, c = c_;
+        gh = first / np, gr = first % np;
+        load_rows(first);
+        open_group(first);
+        next_centre();
+        kind = T_FIRST;
+    }
+    __device__ __forceinline__ int hyp(int ce) const {
+        int h = gh, r = gr + (ce - g0);
+        while (r >= np) r -= np, ++h;
+        return h;
+    }
+    // the next centre, or pair of small centres, of the schedule; false (and nothing changed) when the slice is done
+    __device__ __forceinline__ bool next_centre() {
+        if (!(large | small)) {
+            if (g0 + 32 >= end) return false;
+            gr += 32;
+            while (gr >= np) gr -= np, ++gh;
+            open_group(g0 + 32);
+        }
+        if (large) {
+            a = b = g0 + __builtin_ctz(large), large &= large - 1;
+        } else {
+            a = b = g0 + __builtin_ctz(small), small &= small - 1;
+            if (small) b = g0 + __builtin_ctz(small), small &= small - 1;
+        }
+        ha = hyp(a), hb = hyp(b);
+        return true;
+    }
+    // the next TILE: a two-tile centre is FIRST, SECOND; a pair is FIRST (of a), SHARED, LAST (of b)
+    __device__ __forceinline__ bool next_tile() {
+        if (kind == T_FIRST) {
+            kind = a != b ? T_SHARED : T_SECOND;
+        } else if (kind == T_SHARED) {
+            a = b, ha = hb, kind = T_LAST;
+        } else {
+            if (!next_centre()) return false;
+            kind = T_FIRST;
+        }
+        return true;
+    }
+};
+
 // ---- SA2: (P gather + xyz columns) -> relu -> 128 -> 256 -> max over 64 samples ----------------------
 // Persistent like sa1_kernel: one 4-wave workgroup per CU, one wave per SIMD, every wave walking a contiguous slice of the
-// B * np2 centres, a centre's two 32-sample column tiles one after the other. What sa1 measured holds here: the kernel's
+// B * np2 centres in the order of CentreWalk above, tile by tile: a centre's two 32-sample column tiles one after the other,
+// or three tiles for a pair of small centres. What sa1 measured holds here: the kernel's
 // loss is its count of vector / LDS / memory instructions, so the design keeps operands where an MFMA reads them in place.
 //   middle layer 128 -> 128: its 64 weight quads are loaded once per wave and pinned to the AGPR half (256 registers): no
 //     LDS ring, no LDS-DMA, no barrier after the prologue -- the four waves run free of each other;
@@ -988,22 +1075,27 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
         a_z[kt] = h ? 0.0f : z;
     }
 
-    // Tiles are numbered 2 * centre + t. The gather of tile it + 1 is issued a tile ahead, in two steps (there is no
-    // partner wave to cover a memory latency): its sample index and centre under tile it's first layers, its 16 P quads and
-    // the sample's xyz under tile it's last layer. (hn, cn) = hypothesis and centre of the NEXT tile, kept by counting.
-    const int it_end = 2 * end;
-    int cn = first, hn = first / np2, rn = first % np2;
+    // The gather of the next tile of the walk is issued a tile ahead, in two steps (there is no partner wave to cover a
+    // memory latency): its sample index and centre under this tile's first layers, its 16 P quads and the sample's xyz under
+    // this tile's last layer. Centre, hypothesis and slot are per column: in a shared tile the columns with bit 2 set
+    // belong to centre b (in every other tile a == b).
+    CentreWalk nx;                     // the NEXT tile
+    nx.start(ball, first, end, np2, c);
+    const bool colb = (c >> 2) & 1;
+    const int slot16 = 32 + ((c & 3) | ((c >> 3) << 2));   // a shared tile's slot of column c: 32..47 in each half-set
     int inext;
     float s_xy, s_z, c_xy, c_z;        // sample and centre coordinates: half 0 holds (x, z), half 1 (y, -)
     v16f X1[4];
-    auto fetch_index = [&](int t) {
-        inext = ball[(size_t)cn * 64 + t * 32 + c];
-        c_xy = cxyz[(size_t)cn * 3 + h], c_z = cxyz[(size_t)cn * 3 + 2];
+    auto fetch_index = [&]() {
+        const int ce = colb && nx.kind == T_SHARED ? nx.b : nx.a;
+        const int slot = nx.kind == T_SHARED ? slot16 : nx.kind == T_SECOND ? c + 32 : c;
+        inext = ball[(size_t)ce * 64 + slot];
+        c_xy = cxyz[(size_t)ce * 3 + h], c_z = cxyz[(size_t)ce * 3 + 2];
     };
     auto fetch_rows = [&]() {
         int i0 = inext;
         asm volatile("" : "+v"(i0));   // consumed HERE, not behind its load (see sa1_kernel)
-        const size_t pt = (size_t)hn * np1 + i0;
+        const size_t pt = (size_t)(colb && nx.kind == T_SHARED ? nx.hb : nx.ha) * np1 + i0;
         s_xy = xyz1[pt * 3 + h], s_z = xyz1[pt * 3 + 2];
         const float* r = P + pt * 128 + 4 * h;
 #pragma unroll
@@ -1017,7 +1109,7 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
                 X1[kt][4 * q + 3] = v.w;
             }
     };
-    fetch_index(0);
+    fetch_index();
     fetch_rows();
     constexpr int G = 4;               // W3 quads per LDS read group: 16 MFMAs = 1024 pipe cycles cover the next group's reads
     float4 cur[G], nxt[G];
@@ -1042,23 +1134,15 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) kp[mt] = 0;
 #pragma unroll 1
-    for (int it = 2 * first; it < it_end; ++it) {
+    for (;;) {
         const float* w = wl + opaque_zero();      // keeps the LDS reads of this iteration inside it
-        const int t = it & 1;
+        const int centre = nx.a, kind = nx.kind;  // this tile: what it pools into and which centre it completes
         const float d_xy = s_xy - c_xy, d_z = h ? 0.0f : s_z - c_z;
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) X1[kt] = relu16(mfma(a_z[kt], d_z, mfma(a_xy[kt], d_xy, X1[kt])));
-        // the next tile: the other half of this centre, or the first half of the next one (the last tile prefetches itself)
-        int tn = 1;
-        if (it + 1 < it_end) {
-            tn = t ^ 1;
-            if (t) {
-                ++cn;
-                if (++rn == np2) rn = 0, ++hn;
-            }
-        }
+        const bool more = nx.next_tile();         // (the last tile prefetches itself: harmless)
         __builtin_amdgcn_sched_barrier(0);
-        fetch_index(tn);
+        fetch_index();
         __builtin_amdgcn_sched_barrier(0);
         v16f Y2[4];
         v16f bt = bias_tile(w + SA2_B2, 0, h);
@@ -1078,6 +1162,8 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
         // last layer, operands swapped (see mfma4_swapped); the read of the group after the last wraps to quad 0, which is
         // the next tile's first
         const float4* w3 = (const float4*)(w + SA2_W3) + lane;
+        float* out = feat + (size_t)centre * 256 + lane;
+        int fprev = 0;
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) {
             v16f acc = bs;
@@ -1103,19 +1189,31 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
 #pragma unroll
                 for (int i = 0; i < G; ++i) cur[i] = nxt[i];
             }
-            // the kept maximum of the centre's first tile (or the 0 of a fresh centre, which is the ReLU) starts the chain;
-            // the lane halves are merged once per centre, below
-            kp[mt] = pool_acc(acc, kp[mt]);
+            if (kind == T_SHARED) {
+                // lane half 0 of the tile's maxima completes centre a, whose first tile waits in kp; lane half 1 starts the
+                // chain of centre b, whose own tile comes next
+                const int p = pool_acc(acc, 0);
+                const int fa = max(kp[mt], h ? 0 : p);
+                kp[mt] = h ? p : 0;
+                if (mt & 1)
+                    out[(mt - 1) * 32] = pool_halves(fprev, fa);
+                else
+                    fprev = fa;
+            } else {
+                // the kept maximum of the centre's earlier tiles (or the 0 of a fresh centre, which is the ReLU) starts the
+                // chain; the lane halves are merged once per centre, below
+                kp[mt] = pool_acc(acc, kp[mt]);
+            }
         }
-        if (t) {
+        if (kind == T_SECOND || kind == T_LAST) {
             // after the merge both lane halves hold every tile's 32 maxima, so one full-wave store writes two m-tiles
             // (lane = 32 h + c)
-            float* out = feat + (size_t)(it >> 1) * 256 + lane;
 #pragma unroll
             for (int mt = 0; mt < 8; mt += 2) out[mt * 32] = pool_halves(kp[mt], kp[mt + 1]);
 #pragma unroll
             for (int mt = 0; mt < 8; ++mt) kp[mt] = 0;
         }
+        if (!more) break;
     }
 }
 
@@ -1433,8 +1531,11 @@ int pn2_ball1(const Pn2Call& c) { return launch_ball(c.point_x, 8, c.B, c.M, c.w
 int pn2_fps2(const Pn2Call& c) { return launch_fps(c.ws.xyz1, 3, c.B, c.np1, c.np2, c.ws.fps2, c.ws.xyz2, c.s); }
 int pn2_ball2(const Pn2Call& c) { return launch_ball(c.ws.xyz1, 3, c.B, c.np1, c.ws.xyz2, c.np2, c.w->radius2, c.ws.ball2, c.s); }
 
-// persistent grid of sa1_kernel and sa2_kernel: one 4-wave workgroup per CU (one wave per SIMD), cached per device
+// persistent grid of sa1_kernel and sa2_kernel: one 4-wave workgroup per CU (one wave per SIMD), cached per device --
+// unless ossid_pn2_set_persistent_grid chose a size (tests: few workgroups make a wave's slice long at a small batch)
+int g_persistent_workgroups = 0;
 int persistent_grid() {
+    if (g_persistent_workgroups) return g_persistent_workgroups;
     static int cache[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -1486,6 +1587,12 @@ int pn2_fc(const Pn2Call& c, float* scores) {
 }  // namespace
 
 extern "C" {
+
+int ossid_pn2_set_persistent_grid(int workgroups) {
+    if (workgroups < 0 || workgroups > 65536) return OSSID_EINVAL;
+    g_persistent_workgroups = workgroups;
+    return OSSID_OK;
+}
 
 int ossid_pn2_score(const float* point_x, int B, int M, const ossid_pn2_weights* w, void* workspace,
                     size_t workspace_bytes, float* scores, int32_t* dbg_fps1, int32_t* dbg_ball1, float* dbg_feat1,
