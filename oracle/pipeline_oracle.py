@@ -76,12 +76,17 @@ def heatmap_gaussian(h, w, cx, cy, sigma):
 def render_depth_points(T, pts, K, H, W, radius):
     T, p = T.astype(np.float32), pts.astype(np.float32)
     fx, fy, cx, cy = (np.float32(K[0, 0]), np.float32(K[1, 1]), np.float32(K[0, 2]), np.float32(K[1, 2]))
-    cam = np.stack([((T[i, 0] * p[:, 0] + T[i, 1] * p[:, 1]) + T[i, 2] * p[:, 2]) + T[i, 3] for i in range(3)], 1)
+    with np.errstate(invalid="ignore"):                        # a non-finite point: NaN here, dropped below
+        cam = np.stack([((T[i, 0] * p[:, 0] + T[i, 1] * p[:, 1]) + T[i, 2] * p[:, 2]) + T[i, 3] for i in range(3)], 1)
     depth = np.full((H, W), np.inf, np.float32)
     for X, Y, Z in cam:
         if not Z > np.float32(1e-6):
             continue
-        u, v = int(np.floor((X / Z) * fx + cx)), int(np.floor((Y / Z) * fy + cy))
+        with np.errstate(all="ignore"):
+            uf, vf = (X / Z) * fx + cx, (Y / Z) * fy + cy
+        if not (np.abs(uf) < np.float32(1e9) and np.abs(vf) < np.float32(1e9)):   # NaN, inf, or no int32 pixel: dropped
+            continue
+        u, v = int(np.floor(uf)), int(np.floor(vf))
         for vv in range(max(v - radius, 0), min(v + radius, H - 1) + 1):
             for uu in range(max(u - radius, 0), min(u + radius, W - 1) + 1):
                 depth[vv, uu] = min(depth[vv, uu], Z)
@@ -94,6 +99,7 @@ def visib_and_iou(d_obs, d_pred, gt, gt_visib, delta):
     d_obs, d_pred = d_obs.astype(np.float32), d_pred.astype(np.float32)
     pm = d_pred > 0
     vm = np.logical_and(np.logical_or((d_pred - d_obs) <= np.float32(delta), d_obs == 0), pm)
-    iou = np.logical_and(pm, gt).sum() / float(np.logical_or(pm, gt).sum())
-    iou_v = np.logical_and(vm, gt_visib).sum() / float(np.logical_or(vm, gt_visib).sum())
+    with np.errstate(invalid="ignore"):                        # an empty union: nan, as the reference's 0 / 0.0
+        iou = np.logical_and(pm, gt).sum() / np.float64(np.logical_or(pm, gt).sum())
+        iou_v = np.logical_and(vm, gt_visib).sum() / np.float64(np.logical_or(vm, gt_visib).sum())
     return pm, vm, iou, iou_v

@@ -68,7 +68,10 @@ static inline int ossid_ensure_dyn_lds(const void* fn, size_t bytes, OssidLdsAtt
     if (hipGetDevice(&dev) != hipSuccess) return OSSID_ELAUNCH;
     dev &= 15;
     if (__atomic_load_n(&st.done[dev], __ATOMIC_ACQUIRE)) return OSSID_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return OSSID_ELAUNCH;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+        (void)hipGetLastError();   // reported through the return value; not left behind for the caller's next HIP call
+        return OSSID_ELAUNCH;
+    }
     __atomic_store_n(&st.done[dev], 1, __ATOMIC_RELEASE);
     return OSSID_OK;
 }

@@ -186,9 +186,9 @@ int ossid_dtoid_prep_sample(const uint8_t* img, const float* depth, const float*
 int ossid_mask_bbox_heatmap(const float* mask, int H, int W, int heat_h, int heat_w, double heat_scale, double sigma,
                             int32_t* bbox5, double* heatmap, void* stream) {
     if (!mask || !bbox5 || H <= 0 || W <= 0) return OSSID_EINVAL;
+    if (heatmap && (heat_h <= 0 || heat_w <= 0)) return OSSID_EINVAL;   // refused without launching: the box stays untouched
     hipLaunchKernelGGL(mask_bbox_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, mask, H, W, bbox5);
     if (heatmap) {
-        if (heat_h <= 0 || heat_w <= 0) return OSSID_EINVAL;
         hipLaunchKernelGGL(heatmap_kernel, dim3((heat_h * heat_w + 255) / 256), dim3(256), 0, (hipStream_t)stream, bbox5,
                            heat_scale, sigma, heat_h, heat_w, heatmap);
     }
@@ -197,7 +197,8 @@ int ossid_mask_bbox_heatmap(const float* mask, int H, int W, int heat_h, int hea
 
 int ossid_render_depth_points(const float* transform, const float* points, int M, float fx, float fy, float cx, float cy,
                               int H, int W, int radius, void* zbuf_workspace, float* depth_out, void* stream) {
-    if (!transform || !points || !zbuf_workspace || !depth_out || M < 0 || H <= 0 || W <= 0 || radius < 0 || radius > 8) return OSSID_EINVAL;
+    if (!transform || !zbuf_workspace || !depth_out || M < 0 || H <= 0 || W <= 0 || radius < 0 || radius > 8) return OSSID_EINVAL;
+    if (!points && M > 0) return OSSID_EINVAL;   // an empty cloud has no buffer: it renders the all-zero image
     const int n = H * W;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(splat_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (unsigned*)zbuf_workspace, n);

@@ -388,6 +388,9 @@ int ossid_zephyr_featurize(const float* rgbd, int H, int W, const float* transfo
 // (BOP definitions: ADD = mean_i |(R p_i + t) - (R_gt p_i + t_gt)|, ADI = mean_i min_j |(R p_i + t) - (R_gt p_j + t_gt)|).
 // float64 like the numpy reference. One workgroup per hypothesis; the ground-truth cloud is transformed once per
 // workgroup into LDS for ADI (M^2 distance evaluations per hypothesis), sums by wave butterfly + LDS combine.
+// All LDS is dynamic: hipFuncSetAttribute refuses the 160 KiB limit for a function that also declares static LDS, so a
+// static `red[4]` made every ADI above 2048 points fail to launch. The four wave sums reuse the start of the buffer once
+// the cloud is no longer read; the launch passes max(M * 24, 32) bytes (ADD: 32).
 namespace {
 
 __device__ __forceinline__ void xform(const double* __restrict__ T, double x, double y, double z, double& ox, double& oy,
@@ -403,7 +406,7 @@ __global__ __launch_bounds__(256) void pose_error_kernel(const double* __restric
                                                          double* __restrict__ err) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* gt = (double*)smem_raw;   // [M][3] ground-truth points (ADI only)
-    __shared__ double red[4];
+    double* red = (double*)smem_raw;  // [4] wave sums, after the last read of gt
     const double* Tn = T + 16 * (size_t)blockIdx.x;
     if (SYM) {
         for (int j = threadIdx.x; j < M; j += 256)
@@ -429,6 +432,7 @@ __global__ __launch_bounds__(256) void pose_error_kernel(const double* __restric
         }
     }
     s = wave_sum_f64(s);
+    if (SYM) __syncthreads();         // every wave is done with gt
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) err[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) / (double)M;
@@ -442,13 +446,13 @@ extern "C" int ossid_pose_errors(const double* transforms, const double* transfo
     if (N == 0) return OSSID_OK;
     if (!transforms || !transform_gt || !points || !err) return OSSID_EINVAL;
     if (symmetric) {
-        const size_t lds = (size_t)M * 24;
-        if (lds > 150 * 1024) return OSSID_EINVAL;
+        if ((size_t)M * 24 > 150 * 1024) return OSSID_EINVAL;
+        const size_t lds = (size_t)M * 24 < 32 ? 32 : (size_t)M * 24;
         OSSID_ENSURE_LDS(pose_error_kernel<true>, lds);
         hipLaunchKernelGGL(pose_error_kernel<true>, dim3(N), dim3(256), lds, (hipStream_t)stream, transforms, transform_gt,
                            points, M, err);
     } else {
-        hipLaunchKernelGGL(pose_error_kernel<false>, dim3(N), dim3(256), 0, (hipStream_t)stream, transforms, transform_gt,
+        hipLaunchKernelGGL(pose_error_kernel<false>, dim3(N), dim3(256), 32, (hipStream_t)stream, transforms, transform_gt,
                            points, M, err);
     }
     return ossid_launch_status();

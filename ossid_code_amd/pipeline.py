@@ -20,16 +20,43 @@ from . import _lib
 from .zephyr.score_dataset import _dev, _f32
 
 HEATMAP_SIGMA = float(np.sqrt(1.5))   # dtoid_bop_dataset.py:286
+SPLAT_MAX_RADIUS = 8                  # ossid_render_depth_points refuses a larger square
+
+
+def _shape(x):
+    """Shape of a numpy / torch / nested-list argument without moving it."""
+    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+
+
+def _need(ok, what):
+    if not ok:
+        raise ValueError(what)
+
+
+def _need_hw(name, hw):
+    _need(len(hw) == 2 and int(hw[0]) > 0 and int(hw[1]) > 0, "%s must be two positive sizes, got %r" % (name, tuple(hw)))
+
+
+def _need_cam(cam_K):
+    _need(_shape(cam_K) == (3, 3), "cam_K must be [3,3], got %s" % (_shape(cam_K),))
 
 
 def make_dtoid_sample(img, depth, mask, cam_K, out_hw=None, heatmap_hw=(29, 39)):
     """img uint8 [Ho,Wo,3], depth [Ho,Wo] (m), mask [Ho,Wo] (non-zero = object; uint8 0/255 or float 0..1), cam_K [3,3]
     -> dict of device tensors with the reference's keys and layouts: img [3,H,W] in [0,1], xyz [3,H,W], mask [1,H,W],
     bbox_gt [1,5] (x1,y1,x2,y2,label), heatmap [1,hh,hw] float64. out_hw None keeps the input size (BOP frames)."""
-    dev = _dev()
     img = torch.as_tensor(np.ascontiguousarray(img)) if not torch.is_tensor(img) else img
     if img.dtype != torch.uint8:
         raise ValueError("img must be uint8 (utils/data.py:22)")
+    hw_in = _shape(depth)                                      # every buffer is checked against the depth's size before a launch
+    _need(len(hw_in) == 2 and min(hw_in) > 0, "depth must be [Ho,Wo], got %s" % (hw_in,))
+    _need(_shape(img) == hw_in + (3,), "img must be [Ho,Wo,3] = %s like depth, got %s" % (hw_in + (3,), _shape(img)))
+    _need(_shape(mask) == hw_in, "mask must be [Ho,Wo] = %s like depth, got %s" % (hw_in, _shape(mask)))
+    _need_cam(cam_K)
+    if out_hw is not None:
+        _need_hw("out_hw", out_hw)
+    _need_hw("heatmap_hw", heatmap_hw)
+    dev = _dev()
     img = img.to(dev).contiguous()
     depth = _f32(depth, dev)
     mask = _f32(mask, dev)
@@ -66,6 +93,12 @@ def collate(samples):
 def render_depth_points(pose, model_points, cam_K, hw, radius=1):
     """Depth image [H,W] (m, 0 = background) of the model cloud at `pose`: every point splats a (2r+1)^2 square into a
     z-buffer. Stands in for the mesh renderer of online_learning.py:485 when only the silhouette/depth is needed."""
+    _need(_shape(pose) == (4, 4), "pose must be [4,4], got %s" % (_shape(pose),))
+    _need(len(_shape(model_points)) == 2 and _shape(model_points)[1] == 3,
+          "model_points must be [M,3], got %s" % (_shape(model_points),))
+    _need_cam(cam_K)
+    _need_hw("hw", hw)
+    _need(0 <= int(radius) <= SPLAT_MAX_RADIUS, "radius must be in [0, %d], got %r" % (SPLAT_MAX_RADIUS, radius))
     dev = _dev()
     T = _f32(np.asarray(pose, dtype=np.float64).reshape(4, 4), dev)
     P = _f32(model_points, dev)
@@ -138,10 +171,16 @@ def icpRefinement(depth, uv, pose, cam_K, model_points, inpaint_depth=False, icp
 
 def visibility_and_iou(depth_obs, depth_pred, gt_mask=None, gt_mask_visib=None, delta=15 / 1000.0):
     """-> pred_mask, pred_mask_visib (bool [H,W] on the device), iou, iou_visib (python floats; nan without a gt mask)."""
+    hw = _shape(depth_obs)                                     # the kernel reads H*W elements of every buffer
+    _need(len(hw) == 2 and min(hw) > 0, "depth_obs must be [H,W], got %s" % (hw,))
+    _need(_shape(depth_pred) == hw, "depth_pred must be [H,W] = %s like depth_obs, got %s" % (hw, _shape(depth_pred)))
+    for name, m in (("gt_mask", gt_mask), ("gt_mask_visib", gt_mask_visib)):
+        _need(m is None or _shape(m) == hw, "%s must be [H,W] = %s like depth_obs, got %s" % (name, hw, m is None or _shape(m)))
     dev = _dev()
     dob, dpr = _f32(depth_obs, dev), _f32(depth_pred, dev)
     H, W = int(dob.shape[0]), int(dob.shape[1])
-    u8 = lambda m: None if m is None else torch.as_tensor(np.ascontiguousarray(np.asarray(m) > 0).astype(np.uint8)).to(dev)  # noqa: E731
+    u8 = lambda m: None if m is None else ((m > 0).to(dev, torch.uint8).contiguous() if torch.is_tensor(m) else  # noqa: E731
+                                           torch.as_tensor(np.ascontiguousarray(np.asarray(m) > 0).astype(np.uint8)).to(dev))
     g, gv = u8(gt_mask), u8(gt_mask_visib)
     pm = torch.empty(H, W, dtype=torch.uint8, device=dev)
     vm = torch.empty(H, W, dtype=torch.uint8, device=dev)

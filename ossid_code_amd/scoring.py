@@ -18,8 +18,25 @@ from .zephyr import score_dataset as _sd
 _MODEL_KEYS = ("model_points", "model_colors", "model_normals")
 
 
+ADI_MAX_POINTS = 150 * 1024 // 24    # ossid_pose_errors: 24 bytes of LDS per ground-truth point, 150 KiB at the most
+
+
 def _as_tensor(a):
     return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+
+
+def _shape(x):
+    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+
+
+def _need_points(p):
+    if len(_shape(p)) != 2 or _shape(p)[1] != 3:
+        raise ValueError("model_points must be [M,3], got %s" % (_shape(p),))
+
+
+def _need_poses(name, T):
+    if len(_shape(T)) < 2 or _shape(T)[-2:] != (4, 4):
+        raise ValueError("%s must be [...,4,4], got %s" % (name, _shape(T)))
 
 
 def networkInference(model, dataset, data, return_time=False):
@@ -83,18 +100,18 @@ def networkInferenceMany(model, dataset, frames, streams=2, return_time=False):
 
 def filterHypoByMask(model_points, meta_data, pose_hypos, mask, th=0.5):
     """Boolean [N]: hypotheses whose model points land inside `mask` (h x w, {0,1}) for more than a fraction th."""
+    _need_points(model_points)
+    _need_poses("pose_hypos", pose_hypos)
+    if len(_shape(mask)) != 2 or min(_shape(mask)) <= 0:
+        raise ValueError("mask must be [h,w], got %s" % (_shape(mask),))
     dev = _sd._dev()
     T = _sd._f32(pose_hypos, dev).reshape(-1, 4, 4)
     P = _sd._f32(model_points, dev)
     N, M = int(T.shape[0]), int(P.shape[0])
     if N == 0 or M == 0:
         return np.zeros(N, dtype=bool)
-    uv = torch.empty(N, M, 2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _sd._lib.fn("ossid_zephyr_project_uv")(T.data_ptr(), P.data_ptr(), N, M, *_sd._cam(meta_data),
-                                                    uv.data_ptr(), _sd._lib.stream())
-    _sd._lib.check(rc, "ossid_zephyr_project_uv")
-    m = _as_tensor(np.asarray(mask)).to(dev)
+    uv = _sd.project_uv(T, P, _sd._cam(meta_data))
+    m = (mask if torch.is_tensor(mask) else _as_tensor(np.asarray(mask))).to(dev)
     h, w = m.shape
     x, y = uv[..., 0].long(), uv[..., 1].long()
     inside = (x >= 0) & (x < w) & (y >= 0) & (y < h)
@@ -105,6 +122,15 @@ def filterHypoByMask(model_points, meta_data, pose_hypos, mask, th=0.5):
 def pose_errors(pose_hypos, pose_gt, model_points, symmetric=False):
     """ADD (symmetric=False) or ADI (True) of every hypothesis against the ground-truth pose, float64 numpy [N]:
     the device-side form of online_learning.py:452's per-hypothesis Python loop over zephyr.utils.metrics.add / adi."""
+    _need_poses("pose_hypos", pose_hypos)
+    if _shape(pose_gt) != (4, 4):
+        raise ValueError("pose_gt must be [4,4], got %s" % (_shape(pose_gt),))
+    _need_points(model_points)
+    if _shape(model_points)[0] < 1:
+        raise ValueError("model_points must hold at least one point")
+    if symmetric and _shape(model_points)[0] > ADI_MAX_POINTS:
+        raise ValueError("ADI takes at most %d model_points (the ground-truth cloud is kept in LDS), got %d"
+                         % (ADI_MAX_POINTS, _shape(model_points)[0]))
     dev = _sd._dev()
     T = _as_tensor(np.asarray(pose_hypos, dtype=np.float64)).to(dev).reshape(-1, 4, 4).contiguous()
     G = _as_tensor(np.asarray(pose_gt, dtype=np.float64)).to(dev).reshape(4, 4).contiguous()

@@ -110,20 +110,31 @@ def featurize(rgbd, transforms, tab, cam, sel=None, interp=0, want_uv=True):
     return px, uv
 
 
+PROJECT_MAX_HYPOS = 65535  # ossid_zephyr_project_uv puts the hypotheses on grid.y
+
+
+def project_uv(T, P, cam):
+    """T f32 [N,4,4], P f32 [M,3] on one device, cam = (fx, fy, cx, cy) -> uv int32 [N,M,2] on that device; any N: the
+    entry point is called on at most PROJECT_MAX_HYPOS hypotheses at a time."""
+    N, M = int(T.shape[0]), int(P.shape[0])
+    uv = torch.empty(N, M, 2, dtype=torch.int32, device=T.device)
+    if N and M:
+        with torch.cuda.device(T.device):
+            for n0 in range(0, N, PROJECT_MAX_HYPOS):
+                n = min(PROJECT_MAX_HYPOS, N - n0)
+                rc = _lib.fn("ossid_zephyr_project_uv")(T[n0:n0 + n].data_ptr(), P.data_ptr(), n, M, *cam,
+                                                        uv[n0:n0 + n].data_ptr(), _lib.stream())
+                _lib.check(rc, "ossid_zephyr_project_uv")
+    return uv
+
+
 def projectPointsUv(pose_hypos, model_points, meta_data):
     """zephyr.utils.projectPointsUv: (N,4,4), (M,3), camera dict -> integer pixel coordinates [N, M, 2]
     (numpy int64, [..., 0] = x / column, [..., 1] = y / row), as utils/zephyr_utils.py:58-65 consumes them."""
     dev = _dev()
     T = _f32(pose_hypos, dev).reshape(-1, 4, 4)
     P = _f32(model_points, dev)
-    N, M = int(T.shape[0]), int(P.shape[0])
-    uv = torch.empty(N, M, 2, dtype=torch.int32, device=dev)
-    if N and M:
-        with torch.cuda.device(dev):
-            rc = _lib.fn("ossid_zephyr_project_uv")(T.data_ptr(), P.data_ptr(), N, M, *_cam(meta_data), uv.data_ptr(),
-                                                    _lib.stream())
-        _lib.check(rc, "ossid_zephyr_project_uv")
-    return uv.cpu().numpy().astype(np.int64)
+    return project_uv(T, P, _cam(meta_data)).cpu().numpy().astype(np.int64)
 
 
 class ScoreDataset:
