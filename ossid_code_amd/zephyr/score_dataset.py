@@ -47,22 +47,66 @@ class FrameCache:
         self.rgbd, self.tab, self.H, self.W, self.M = rgbd, tab, H, W, M
 
 
-def stage_frame(img, depth, dev=None, blur=False):
-    """img: uint8 [H,W,3] (blurred on the GPU when blur) or float [H,W,3] in [0,1]; depth [H,W] metres."""
+def _need(ok, what):
+    if not ok:
+        raise ValueError(what)
+
+
+def _check(t, name, shape, dtype=torch.float32, dev=None):
+    """t is a contiguous tensor of `dtype` whose shape matches `shape` (None: any extent) on `dev` (None: any device).
+    Host-side only: nothing is launched and nothing is read back."""
+    _need(torch.is_tensor(t), "%s: a torch tensor is required, got %s" % (name, type(t).__name__))
+    want = "[%s]" % ",".join("*" if d is None else str(d) for d in shape)
+    _need(t.dim() == len(shape) and all(d is None or int(s) == d for s, d in zip(t.shape, shape)),
+          "%s: shape %s required, got %s" % (name, want, list(t.shape)))
+    _need(t.dtype == dtype, "%s: %s required, got %s" % (name, dtype, t.dtype))
+    _need(t.is_contiguous(), "%s: a contiguous tensor is required (strides %s)" % (name, list(t.stride())))
+    _need(dev is None or t.device == dev, "%s: on %s, the other operands on %s" % (name, t.device, dev))
+    return t
+
+
+def _check_scene(rgbd, transforms, tab):
+    """the operands inconst_count and featurize share -> (H, W, N, M)"""
+    _check(rgbd, "rgbd", (None, None, 4))
+    _need(rgbd.is_cuda, "rgbd: a staged frame on the GPU is required, got one on %s" % rgbd.device)
+    H, W = int(rgbd.shape[0]), int(rgbd.shape[1])
+    _need(H >= 1 and W >= 1, "rgbd: an empty frame %s" % list(rgbd.shape))
+    _check(transforms, "transforms", (None, 4, 4), dev=rgbd.device)
+    _check(tab, "tab", (None, 12), dev=rgbd.device)
+    _need(int(tab.shape[0]) >= 1, "tab: at least one model point is required")
+    return H, W, int(transforms.shape[0]), int(tab.shape[0])
+
+
+def _as_tensor(x):
+    return torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+
+
+def stage_frame(img, depth, dev=None, blur=False, out=None):
+    """img: uint8 [H,W,3] (blurred on the GPU when blur) or float [H,W,3] in [0,1]; depth [H,W] metres (numpy or torch,
+    any float dtype, any device: converted). -> rgbd [H,W,4] float32 on dev (`out` if given). Everything is validated
+    before the first launch; a ValueError leaves `out` untouched."""
     dev = _dev(dev)
-    if isinstance(img, np.ndarray):
-        img = torch.from_numpy(np.ascontiguousarray(img))
+    img, depth = _as_tensor(img), _as_tensor(depth)
+    _need(torch.is_tensor(img) and img.dim() == 3 and int(img.shape[2]) == 3,
+          "img: [H,W,3] required, got %s" % (list(img.shape) if torch.is_tensor(img) else type(img).__name__))
     H, W = int(img.shape[0]), int(img.shape[1])
+    _need(H >= 1 and W >= 1, "img: an empty image %s" % list(img.shape))
+    _need(img.dtype == torch.uint8 or img.dtype.is_floating_point, "img: uint8 or a float type required, got %s" % img.dtype)
+    _need(torch.is_tensor(depth) and tuple(depth.shape) == (H, W),
+          "depth: [%d,%d] required to match img, got %s" % (H, W, list(depth.shape) if torch.is_tensor(depth) else None))
+    _need(depth.dtype.is_floating_point, "depth: a float type required, got %s" % depth.dtype)
+    _need(img.dtype == torch.uint8 or not blur,
+          "blur is defined on the uint8 image (cv2.GaussianBlur, zephyr_utils.py:13)")
+    if out is not None:
+        _check(out, "out", (H, W, 4), dev=dev)
     depth = _f32(depth, dev)
-    rgbd = torch.empty(H, W, 4, dtype=torch.float32, device=dev)
+    rgbd = torch.empty(H, W, 4, dtype=torch.float32, device=dev) if out is None else out
     with torch.cuda.device(dev):
         if img.dtype == torch.uint8:
             img = img.to(dev).contiguous()
             rc = _lib.fn("ossid_zephyr_prep_frame_u8")(img.data_ptr(), depth.data_ptr(), H, W, int(bool(blur)),
                                                        rgbd.data_ptr(), _lib.stream())
         else:
-            if blur:
-                raise ValueError("blur is defined on the uint8 image (cv2.GaussianBlur, zephyr_utils.py:13)")
             img = _f32(img, dev)
             rc = _lib.fn("ossid_zephyr_prep_frame_f32")(img.data_ptr(), depth.data_ptr(), H, W, rgbd.data_ptr(),
                                                         _lib.stream())
@@ -70,11 +114,22 @@ def stage_frame(img, depth, dev=None, blur=False):
     return rgbd
 
 
-def stage_model(points, normals, colors, dev=None):
+def stage_model(points, normals, colors, dev=None, out=None):
+    """points, normals, colors [M,3] (numpy or torch, any float dtype, any device: converted), M >= 1 -> the model table
+    [M,12] float32 on dev (`out` if given). Validated before the first launch; a ValueError leaves `out` untouched."""
     dev = _dev(dev)
+    points, normals, colors = _as_tensor(points), _as_tensor(normals), _as_tensor(colors)
+    _need(torch.is_tensor(points) and points.dim() == 2 and int(points.shape[1]) == 3 and int(points.shape[0]) >= 1,
+          "points: [M,3] with M >= 1 required, got %s" % (list(points.shape) if torch.is_tensor(points) else None))
+    M = int(points.shape[0])
+    for name, t in (("points", points), ("normals", normals), ("colors", colors)):
+        _need(torch.is_tensor(t) and tuple(t.shape) == (M, 3),
+              "%s: [%d,3] required to match points, got %s" % (name, M, list(t.shape) if torch.is_tensor(t) else None))
+        _need(t.dtype.is_floating_point, "%s: a float type required, got %s" % (name, t.dtype))
+    if out is not None:
+        _check(out, "out", (M, 12), dev=dev)
     p, n, c = _f32(points, dev), _f32(normals, dev), _f32(colors, dev)
-    M = int(p.shape[0])
-    tab = torch.empty(M, 12, dtype=torch.float32, device=dev)
+    tab = torch.empty(M, 12, dtype=torch.float32, device=dev) if out is None else out
     with torch.cuda.device(dev):
         rc = _lib.fn("ossid_zephyr_prep_model")(p.data_ptr(), n.data_ptr(), c.data_ptr(), M, tab.data_ptr(),
                                                 _lib.stream())
@@ -82,10 +137,15 @@ def stage_model(points, normals, colors, dev=None):
     return tab
 
 
-def inconst_count(rgbd, transforms, tab, cam, margin=INCONST_MARGIN):
-    H, W = rgbd.shape[:2]
-    N, M = transforms.shape[0], tab.shape[0]
-    cnt = torch.empty(N, dtype=torch.int32, device=rgbd.device)
+def inconst_count(rgbd, transforms, tab, cam, margin=INCONST_MARGIN, out=None):
+    """rgbd [H,W,4], transforms [N,4,4], tab [M,12]: float32, contiguous, on one GPU -> free-space-violation counts [N]
+    int32 (`out` if given). The kernel reads raw pointers, so anything else is refused with a ValueError before the
+    launch."""
+    H, W, N, M = _check_scene(rgbd, transforms, tab)
+    _need(len(cam) == 4, "cam: (fx, fy, cx, cy) required")
+    if out is not None:
+        _check(out, "out", (N,), torch.int32, rgbd.device)
+    cnt = torch.empty(N, dtype=torch.int32, device=rgbd.device) if out is None else out
     with torch.cuda.device(rgbd.device):
         rc = _lib.fn("ossid_zephyr_inconst_count")(rgbd.data_ptr(), H, W, transforms.data_ptr(), N, tab.data_ptr(), M,
                                                    *cam, float(margin), cnt.data_ptr(), _lib.stream())
@@ -93,14 +153,33 @@ def inconst_count(rgbd, transforms, tab, cam, margin=INCONST_MARGIN):
     return cnt
 
 
-def featurize(rgbd, transforms, tab, cam, sel=None, interp=0, want_uv=True):
-    """-> point_x [N', M, 8] float32, uv_original [N', M, 2] int32 (or None)."""
-    H, W = rgbd.shape[:2]
-    M = tab.shape[0]
-    n = int(sel.shape[0]) if sel is not None else int(transforms.shape[0])
+def featurize(rgbd, transforms, tab, cam, sel=None, interp=0, want_uv=True, out_px=None, out_uv=None):
+    """-> point_x [N', M, 8] float32, uv_original [N', M, 2] int32 (or None); into out_px / out_uv if given.
+    rgbd [H,W,4], transforms [N,4,4], tab [M,12]: float32, contiguous, on one GPU. sel: None (all hypotheses, N' = N) or a
+    one-dimensional contiguous integer tensor on that GPU; the kernel reads int32, an int64 selection (what
+    torch.nonzero returns) is CONVERTED to int32, any other dtype is refused. The values of sel (0 <= sel < N) are the
+    caller's responsibility: checking them would need a read-back. interp: 0 nearest pixel, 1 bilinear. Everything is
+    validated before the first launch; a ValueError leaves out_px / out_uv untouched."""
+    H, W, N, M = _check_scene(rgbd, transforms, tab)
+    _need(len(cam) == 4, "cam: (fx, fy, cx, cy) required")
+    _need(interp in (0, 1), "interp: 0 (nearest pixel) or 1 (bilinear) required, got %r" % (interp,))
     dev = rgbd.device
-    px = torch.empty(n, M, DIM_POINT, dtype=torch.float32, device=dev)
-    uv = torch.empty(n, M, 2, dtype=torch.int32, device=dev) if want_uv else None
+    if sel is not None:
+        _need(torch.is_tensor(sel) and sel.dtype in (torch.int32, torch.int64),
+              "sel: an int32 (or int64, converted) tensor required, got %s" % (sel.dtype if torch.is_tensor(sel) else
+                                                                               type(sel).__name__))
+        _check(sel, "sel", (None,), sel.dtype, dev)
+        _need(N >= 1 or int(sel.shape[0]) == 0, "sel: selects from no hypotheses")
+    n = int(sel.shape[0]) if sel is not None else N
+    if out_px is not None:
+        _check(out_px, "out_px", (n, M, DIM_POINT), dev=dev)
+    if out_uv is not None:
+        _need(want_uv, "out_uv given but want_uv is False")
+        _check(out_uv, "out_uv", (n, M, 2), torch.int32, dev)
+    if sel is not None and sel.dtype == torch.int64:
+        sel = sel.to(torch.int32)
+    px = torch.empty(n, M, DIM_POINT, dtype=torch.float32, device=dev) if out_px is None else out_px
+    uv = (torch.empty(n, M, 2, dtype=torch.int32, device=dev) if out_uv is None else out_uv) if want_uv else None
     with torch.cuda.device(dev):
         rc = _lib.fn("ossid_zephyr_featurize")(rgbd.data_ptr(), H, W, transforms.data_ptr(),
                                                None if sel is None else sel.data_ptr(), n, tab.data_ptr(), M, *cam,
