@@ -144,17 +144,6 @@ __global__ __launch_bounds__(256) void bop_inf_kernel(unsigned long long* __rest
     if (i < N) a[i] = DINF, b[i] = DINF;
 }
 
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double w = __shfl_xor(v, m);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ bool fin(double v) { return fabs(v) < INFINITY; }     // false for NaN and +-inf
-
 __global__ __launch_bounds__(256) void bop_mssd_mspd_kernel(const float* __restrict__ vertices, int V,
                                                             const double* __restrict__ syms, int S,
                                                             const double* __restrict__ pose_est,

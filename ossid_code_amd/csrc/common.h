@@ -104,6 +104,14 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     return v;
 }
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double w = __shfl_xor(v, m);
+        v = w > v ? w : v;
+    }
+    return v;
+}
 __device__ __forceinline__ int wave_min_i32(int v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
@@ -114,3 +122,8 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
     return v;
 }
+
+__device__ __forceinline__ bool fin(double v) { return fabs(v) < INFINITY; }     // false for NaN and +-inf
+
+// a device-side element count whose producer reports overflow by leaving it above the capacity: nothing is processed then
+__device__ __forceinline__ int count_or_0(const int32_t* count, int cap) { return count[0] <= cap ? count[0] : 0; }

@@ -28,7 +28,7 @@
 // No kernel waits on another workgroup. Everything lives in caller-owned memory; launches only, nothing read back.
 #include <cmath>
 
-#include "common.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -97,59 +97,6 @@ __global__ __launch_bounds__(256) void det_n_easy_kernel(const int32_t* __restri
     if (c >= 0 && c < C && !(difficult && difficult[g])) atomicAdd(n_easy + c, 1);
 }
 
-// 64-lane inclusive scans (lane i ends with op over lanes 0..i, or i..63 for the suffix form)
-template <class T, class Op>
-__device__ __forceinline__ T wave_scan_up(T v, Op op, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T w = __shfl_up(v, d);
-        if (lane >= d) v = op(w, v);
-    }
-    return v;
-}
-template <class T, class Op>
-__device__ __forceinline__ T wave_scan_down(T v, Op op, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T w = __shfl_down(v, d);
-        if (lane + d < 64) v = op(v, w);
-    }
-    return v;
-}
-// Workgroup scans of one value per thread, NW waves. `lds` holds NW values. Return the EXCLUSIVE result (op over the threads
-// before / after this one, `id` for none) and set `total`. Two barriers: lds may be reused after the call.
-template <int NW, class T, class Op>
-__device__ __forceinline__ T block_scan_excl(T v, Op op, T id, T* lds, T& total, bool reverse) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const T inc = reverse ? wave_scan_down(v, op, lane) : wave_scan_up(v, op, lane);
-    if (lane == (reverse ? 0 : 63)) lds[wv] = inc;
-    __syncthreads();
-    T before = id, all = id;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const T x = lds[w];
-        all = op(all, x);
-        if (reverse ? w > wv : w < wv) before = op(before, x);
-    }
-    __syncthreads();
-    total = all;
-    const T nb = reverse ? __shfl_down(inc, 1) : __shfl_up(inc, 1);           // the neighbour's inclusive value
-    const bool edge = reverse ? lane == 63 : lane == 0;
-    return edge ? before : op(before, nb);
-}
-struct AddU64 {
-    __device__ u64 operator()(u64 a, u64 b) const { return a + b; }
-};
-struct AddI32 {
-    __device__ int operator()(int a, int b) const { return a + b; }
-};
-struct MaxU64 {
-    __device__ u64 operator()(u64 a, u64 b) const { return a > b ? a : b; }
-};
-struct MaxU32 {
-    __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
-};
-
 // tile_offset[c] = tiles before class c, c = 0..C: one workgroup, C <= 4096 = 4 per thread
 __global__ __launch_bounds__(1024) void det_tile_offset_kernel(const int32_t* __restrict__ class_offset, int C, int N,
                                                                int32_t* __restrict__ tile_offset) {
@@ -166,7 +113,7 @@ __global__ __launch_bounds__(1024) void det_tile_offset_kernel(const int32_t* __
         own += cnt[j];
     }
     int total;
-    int run = block_scan_excl<16>(own, AddI32(), 0, lds, total, false);
+    int run = block_scan_excl<16>(own, OpAdd(), 0, lds, total, false);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = 4 * (int)threadIdx.x + j;
@@ -299,7 +246,7 @@ __global__ __launch_bounds__(256) void det_curve_kernel(const uint8_t* __restric
         own += v[j];
     }
     int total;
-    int run = block_scan_excl<4>(own, AddI32(), 0, lds, total, false);
+    int run = block_scan_excl<4>(own, OpAdd(), 0, lds, total, false);
     const u64 pre = tpre[(size_t)k * NT + tile], cls0 = tpre[(size_t)k * NT + tile_offset[t.c]];
     const int tp0 = (int)(uint32_t)(pre >> 32) - (int)(uint32_t)(cls0 >> 32);
     const int fp0 = (int)(uint32_t)pre - (int)(uint32_t)cls0;
@@ -373,7 +320,7 @@ __global__ __launch_bounds__(256) void det_env_kernel(const uint8_t* __restrict_
     p[1] = p[2] > p[1] ? p[2] : p[1];
     p[0] = p[1] > p[0] ? p[1] : p[0];
     uint32_t total;
-    uint32_t after = block_scan_excl<4>(p[0], MaxU32(), 0u, lds, total, true);
+    uint32_t after = block_scan_excl<4>(p[0], OpMax(), 0u, lds, total, true);
     const u64 carry = tcarry[(size_t)k * NT + tile];
     if ((uint32_t)(carry >> 32) == 0xFFFFFFFFu - (uint32_t)t.c) after = (uint32_t)carry > after ? (uint32_t)carry : after;
     double sum = 0.0;
@@ -506,10 +453,10 @@ int ossid_det_match(const int32_t* best_gt, const float* best_iou, const int32_t
         hipLaunchKernelGGL(det_status_kernel, flat, dim3(256), 0, s, best_gt, best_iou, order, N, gt_difficult, G, thr, winner, status,
                            status_r);
         hipLaunchKernelGGL(det_tile_sum_kernel, tiles, dim3(256), 0, s, status_r, class_offset, tile_offset, C, N, L.NT, tsum);
-        hipLaunchKernelGGL(det_tile_scan_kernel<AddU64>, dim3((unsigned)T), dim3(1024), 0, s, tsum, tile_offset, C, L.NT, false);
+        hipLaunchKernelGGL(det_tile_scan_kernel<OpAdd>, dim3((unsigned)T), dim3(1024), 0, s, tsum, tile_offset, C, L.NT, false);
         hipLaunchKernelGGL(det_curve_kernel, tiles, dim3(256), 0, s, status_r, class_offset, tile_offset, C, N, L.NT, tsum, n_easy, rt,
                            prec_ws, tkey, (uint32_t*)p11, ctp, cfp, prec, rec);
-        hipLaunchKernelGGL(det_tile_scan_kernel<MaxU64>, dim3((unsigned)T), dim3(1024), 0, s, tkey, tile_offset, C, L.NT, true);
+        hipLaunchKernelGGL(det_tile_scan_kernel<OpMax>, dim3((unsigned)T), dim3(1024), 0, s, tkey, tile_offset, C, L.NT, true);
         hipLaunchKernelGGL(det_env_kernel, tiles, dim3(256), 0, s, status_r, prec_ws, class_offset, tile_offset, C, N, L.NT, tkey, partial,
                            env);
     }

@@ -7,7 +7,7 @@
 //   - the AMSGrad-Adam update of online_learning.py:258-263 as ONE launch over a flat parameter buffer.
 // All of them are HBM-bound elementwise / stencil / reduction kernels: coalesced 4-byte lanes over rows, LDS halo
 // tiles for the stencil, wave reductions for the kernel-gradient sums.
-#include "common.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -598,18 +598,8 @@ __device__ int topk_find_bin(const int* __restrict__ hist, int nbins, int& rem, 
     for (int j = 0; j < per; ++j) seg += hist[nbins - 1 - (t * per + j)];      // thread t owns the t-th segment FROM THE TOP
     // inclusive scan of the 256 segment sums (round 3 walked them with one thread: 256 dependent LDS reads, ~8 us per call
     // and six calls per top-k); the one segment whose range (excl, incl] holds `rem` reports itself
-    const int lane = t & 63, wave = t >> 6;
-    int incl = seg;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) incl += lds[w];
-    const int excl = incl - seg;
-    __syncthreads();
+    int total;
+    const int excl = block_scan_excl<4>(seg, OpAdd(), 0, lds, total, false), incl = excl + seg;
     if (excl < rem && rem <= incl) lds[256] = t, lds[0] = excl;   // (keys above the segment)
     __syncthreads();
     const int segi = lds[256];
@@ -720,7 +710,8 @@ __global__ __launch_bounds__(256) void topk_gather_kernel(const float* __restric
     if (!write && threadIdx.x == 0) counts[2 * blockIdx.x] = run_gt, counts[2 * blockIdx.x + 1] = run_eq;
 }
 
-// one workgroup: bitonic sort of the k (<= 2048) selected (value, index) pairs, value descending, index ascending
+// one workgroup: bitonic sort of the k (<= 2048) selected (value, index) pairs, value descending, index ascending (the
+// ascending sort of the complemented value key over the index)
 // boxes != NULL: also decode + clip the box of every survivor (anchors [A][4], deltas [rows][A][4], element i = row i / A):
 // the arithmetic of decode_clip_kernel on k boxes instead of all of them.
 __global__ __launch_bounds__(1024) void topk_sort_kernel(const float* __restrict__ sel_val, const int* __restrict__ sel_idx, int k,
@@ -729,23 +720,15 @@ __global__ __launch_bounds__(1024) void topk_sort_kernel(const float* __restrict
                                                          float img_w, float img_h, float4* __restrict__ boxes) {
     __shared__ unsigned long long keys[2048];
     for (int i = threadIdx.x; i < 2048; i += 1024)
-        keys[i] = i < k ? (((unsigned long long)topk_key(sel_val[i]) << 32) | (unsigned)(~sel_idx[i])) : 0ull;
+        keys[i] = i < k ? (((unsigned long long)~topk_key(sel_val[i]) << 32) | (unsigned)sel_idx[i]) : ~0ull;
     __syncthreads();
-    for (int size = 2; size <= 2048; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const int t = threadIdx.x;                      // 1024 compare-exchange pairs per step
-            const int i = ((t / stride) * stride * 2) + (t % stride), j = i + stride;
-            const bool desc = ((i & size) == 0);
-            const unsigned long long a = keys[i], b = keys[j];
-            if ((a < b) == desc) keys[i] = b, keys[j] = a;
-            __syncthreads();
-        }
+    wg_bitonic_sort(keys, 2048);
     for (int i = threadIdx.x; i < k; i += 1024) {
         const unsigned long long kk = keys[i];
-        const unsigned hi = (unsigned)(kk >> 32);
+        const unsigned hi = ~(unsigned)(kk >> 32);
         const unsigned u = (hi & 0x80000000u) ? (hi & 0x7FFFFFFFu) : ~hi;
         out_val[i] = __uint_as_float(u);
-        const unsigned id = ~(unsigned)(kk & 0xFFFFFFFFu);
+        const unsigned id = (unsigned)(kk & 0xFFFFFFFFu);
         out_idx[i] = (long long)id;
         if (boxes) boxes[i] = decode_clip_one(anchors[id % A], deltas[id], img_w, img_h);
     }

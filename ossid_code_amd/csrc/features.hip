@@ -16,7 +16,7 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -144,8 +144,6 @@ __global__ void feat_down_kernel(const int32_t* __restrict__ in, int Wi, int H, 
 }
 
 // ---- detect -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int feat_n(const int32_t* count, int cap) { return count[0] <= cap ? count[0] : 0; }
-
 __device__ bool is_keypoint(const Pyr& P, const int32_t* __restrict__ pyr, long long f, const float* __restrict__ depth,
                             const uint8_t* __restrict__ mask, int contrast) {
     int o = 0;
@@ -218,27 +216,9 @@ __global__ __launch_bounds__(DNT) void feat_flag_kernel(Pyr P, const int32_t* __
 
 // exclusive scan of the block counts in place, count[0] = the total, count[1] = 1 iff it is over the cap
 __global__ __launch_bounds__(1024) void feat_scan_kernel(int32_t* __restrict__ bcount, int nb, int cap, int32_t* __restrict__ count) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int a = min(nb, tid * per), b = min(nb, a + per);
-    int sum = 0;
-    for (int i = a; i < b; ++i) sum += bcount[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - sum;
-    for (int i = a; i < b; ++i) {
-        const int v = bcount[i];
-        bcount[i] = run;
-        run += v;
-    }
-    if (tid == 1023) count[0] = part[1023], count[1] = part[1023] > cap ? 1 : 0;
+    __shared__ int lds[16];
+    const int total = wg_scan_range<16>(bcount, nb, lds, [&](int i, int run) { bcount[i] = run; });
+    if (threadIdx.x == 0) count[0] = total, count[1] = total > cap ? 1 : 0;
 }
 
 __global__ __launch_bounds__(DNT) void feat_compact_kernel(Pyr P, const uint8_t* __restrict__ flags,
@@ -331,7 +311,7 @@ __global__ __launch_bounds__(64) void feat_describe_kernel(Pyr P, FeatTables T, 
                                                            double* __restrict__ frames, uint8_t* __restrict__ ok) {
     __shared__ DescShared sh;
     const int kp = blockIdx.x, lane = threadIdx.x;
-    if (kp >= feat_n(count, cap)) return;
+    if (kp >= count_or_0(count, cap)) return;
     const int o = kps[4 * kp], s = kps[4 * kp + 1], y = kps[4 * kp + 2], x = kps[4 * kp + 3];
     const int H = P.H[o], W = P.W[o];
     const int32_t* L = pyr + P.off[o] + (long long)s * H * W;
@@ -499,7 +479,7 @@ __global__ __launch_bounds__(256) void feat_match_kernel(const uint8_t* __restri
                                                          unsigned long long* __restrict__ keys) {
     __shared__ __attribute__((aligned(16))) unsigned char rows[MT_ROWS * MT_STRIDE];
     __shared__ int norms[MT_ROWS];
-    const int n = feat_n(count, cap);
+    const int n = count_or_0(count, cap);
     const int sbase = blockIdx.x * S_TILE;
     if (sbase >= n) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, half = lane >> 5;
@@ -556,7 +536,7 @@ __global__ __launch_bounds__(256) void feat_match_kernel(const uint8_t* __restri
 __global__ void feat_match_finish_kernel(const unsigned long long* __restrict__ keys, const int32_t* __restrict__ count, int cap,
                                          int32_t* __restrict__ match) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= feat_n(count, cap)) return;
+    if (i >= count_or_0(count, cap)) return;
     const unsigned long long k = keys[i];
     int j = -1, d2 = 0, w = 0;
     if (k != ~0ull) {
@@ -571,7 +551,7 @@ __global__ void feat_hypotheses_kernel(const int32_t* __restrict__ match, const 
                                        const int32_t* __restrict__ count, int cap, const double* __restrict__ Fm, int Nm,
                                        int32_t* __restrict__ peaks, double* __restrict__ cand) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= feat_n(count, cap)) return;
+    if (i >= count_or_0(count, cap)) return;
     const int j = match[3 * i], w = match[3 * i + 2];
     double* T = cand + 16 * (size_t)i;
     if (w <= 0 || j < 0 || j >= Nm) {

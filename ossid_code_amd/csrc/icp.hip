@@ -14,7 +14,8 @@
 
 #include <cmath>
 
-#include "common.h"
+#include "cell_grid.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -32,41 +33,18 @@ struct IcpShared {
     double pose[16], mom[NMOM];
     float bb[NW][6];
     int wsum[NW];
-    float lo[3], inv_h;
-    int n[3], go;
+    CellGrid grid;
+    int go;
 };
 
-// f32 cell coordinate of one axis; float rounding stays far below the cell margin (see icp_grid)
-__device__ __forceinline__ float cell_coord(float x, float lo, float inv_h) { return floorf((x - lo) * inv_h); }
-
-// Cell edge and extent: h >= max_dist * (1 + 1/16) + maxabs * 2^-14, so for any pair accepted by SPEC 5's f32 test the
-// two f32 cell coordinates of each axis differ by less than 1 and the pair lies in adjacent cells. Grown by 5/4 until
-// the grid fits MAX_CELLS (a larger cell keeps the 27-cell probe exact).
-__device__ void icp_grid(IcpShared& sh, const float* mn, const float* mx, float max_dist) {
-    float maxabs = 0.0f;
-    for (int a = 0; a < 3; ++a) maxabs = fmaxf(maxabs, fmaxf(fabsf(mn[a]), fabsf(mx[a])));
-    float h = max_dist * (1.0f + 1.0f / 16.0f) + maxabs * (1.0f / 16384.0f);
-    float nf[3];
-    for (int guard = 0; guard < 256; ++guard) {
-        double cells = 1.0;
-        for (int a = 0; a < 3; ++a) {
-            nf[a] = floorf((mx[a] - mn[a]) / h) + 1.0f;
-            cells *= (double)nf[a];
-        }
-        if (cells <= (double)MAX_CELLS) break;
-        h *= 1.25f;
+// the grid's storage for cell_probe: cell[c] = END of cell c, sorted points in LDS
+struct IcpCells {
+    const IcpShared& sh;
+    __device__ __forceinline__ void run(int first, int last, int& b, int& e) const {
+        b = first == 0 ? 0 : sh.cell[first - 1], e = sh.cell[last];
     }
-    float inv_h = 1.0f / h;
-    if (!(nf[0] * nf[1] * nf[2] <= (float)MAX_CELLS)) {   // growth did not get there (|coords| near FLT_MAX): one cell,
-        nf[0] = nf[1] = nf[2] = 1.0f;                      // every coordinate maps to it, the probe is the brute force
-        inv_h = 0.0f;
-    }
-    for (int a = 0; a < 3; ++a) {
-        sh.lo[a] = mn[a];
-        sh.n[a] = (int)nf[a];
-    }
-    sh.inv_h = inv_h;
-}
+    __device__ __forceinline__ float4 point(int p) const { return sh.q[p]; }
+};
 
 // One Jacobi rotation of the symmetric 4x4 A (row-major) in the (p, q) plane, accumulated into V. Called with constant
 // p, q from fully unrolled loops, so A and V stay in registers.
@@ -206,25 +184,15 @@ __global__ __launch_bounds__(NT) void icp_refine_kernel(const float* __restrict_
             mx[0] = fmaxf(mx[0], qx[i]), mx[1] = fmaxf(mx[1], qy[i]), mx[2] = fmaxf(mx[2], qz[i]);
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        for (int m = 32; m >= 1; m >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], m));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], m));
-        }
-    if (lane == 0)
-        for (int a = 0; a < 3; ++a) sh.bb[wv][a] = mn[a], sh.bb[wv][3 + a] = mx[a];
-    __syncthreads();
+    wg_bbox3<NW>(mn, mx, sh.bb);
     if (tid == 0) {
-        for (int w = 1; w < NW; ++w)
-            for (int a = 0; a < 3; ++a) mn[a] = fminf(mn[a], sh.bb[w][a]), mx[a] = fmaxf(mx[a], sh.bb[w][3 + a]);
         if (!(mn[0] <= mx[0]))                         // empty Q: a one-cell grid that nothing lands in
             for (int a = 0; a < 3; ++a) mn[a] = mx[a] = 0.0f;
-        icp_grid(sh, mn, mx, max_dist);
+        sh.grid = cell_grid_size(mn, mx, max_dist, MAX_CELLS);
     }
     __syncthreads();
-    const float lo0 = sh.lo[0], lo1 = sh.lo[1], lo2 = sh.lo[2], inv_h = sh.inv_h;
-    const int nx = sh.n[0], ny = sh.n[1], nz = sh.n[2], ncell = nx * ny * nz;
+    const CellGrid G = sh.grid;
+    const int ncell = G.n[0] * G.n[1] * G.n[2];
 
     // ---- grid: count, scan, place --------------------------------------------------------------------------------
     for (int c = tid; c < ncell; c += NT) sh.cell[c] = 0;
@@ -232,10 +200,7 @@ __global__ __launch_bounds__(NT) void icp_refine_kernel(const float* __restrict_
     int qc[PPT];
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
-        const int cx_ = min(max((int)cell_coord(qx[i], lo0, inv_h), 0), nx - 1);
-        const int cy_ = min(max((int)cell_coord(qy[i], lo1, inv_h), 0), ny - 1);
-        const int cz_ = min(max((int)cell_coord(qz[i], lo2, inv_h), 0), nz - 1);
-        qc[i] = (cz_ * ny + cy_) * nx + cx_;
+        qc[i] = cell_of(G, qx[i], qy[i], qz[i]);
         if (qok[i]) atomicAdd(&sh.cell[qc[i]], 1);
     }
     __syncthreads();
@@ -248,16 +213,8 @@ __global__ __launch_bounds__(NT) void icp_refine_kernel(const float* __restrict_
             v[i] = c < ncell ? sh.cell[c] : 0;
             s += v[i];
         }
-        int incl = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) sh.wsum[wv] = incl;
-        __syncthreads();
-        int base = incl - s;
-        for (int w = 0; w < wv; ++w) base += sh.wsum[w];
+        int total;
+        int base = block_scan_excl<NW>(s, OpAdd(), 0, sh.wsum, total, false);
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
             const int c = tid * CPT + i;
@@ -276,7 +233,7 @@ __global__ __launch_bounds__(NT) void icp_refine_kernel(const float* __restrict_
 
     // ---- iterate ---------------------------------------------------------------------------------------------------
     const float md2 = max_dist * max_dist;
-    const double c0[3] = {(double)lo0, (double)lo1, (double)lo2};   // moments are taken about Q's box corner
+    const double c0[3] = {(double)G.lo[0], (double)G.lo[1], (double)G.lo[2]};   // moments are taken about Q's box corner
     double prev_fit = 0.0, prev_rmse = 0.0;
     int it = 0;
     for (;;) {
@@ -292,39 +249,13 @@ __global__ __launch_bounds__(NT) void icp_refine_kernel(const float* __restrict_
             const float sx = ((T[0] * px[i] + T[1] * py[i]) + T[2] * pz[i]) + T[3];
             const float sy = ((T[4] * px[i] + T[5] * py[i]) + T[6] * pz[i]) + T[7];
             const float sz = ((T[8] * px[i] + T[9] * py[i]) + T[10] * pz[i]) + T[11];
-            // probe range per axis, clamped; a NaN or far-away coordinate gives an empty range
-            int r0[3], r1[3];
-            const float sv[3] = {sx, sy, sz}, lov[3] = {lo0, lo1, lo2};
-            const int nv[3] = {nx, ny, nz};
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                float f = cell_coord(sv[a], lov[a], inv_h);
-                f = f >= -2.0f ? fminf(f, (float)nv[a] + 1.0f) : -2.0f;
-                const int c = (int)f;
-                r0[a] = max(c - 1, 0), r1[a] = min(c + 1, nv[a] - 1);
-            }
-            float best = INFINITY;
-            int bj = INT_MAX;
-            float bx = 0.0f, by = 0.0f, bz = 0.0f;
-            for (int cz_ = r0[2]; cz_ <= r1[2]; ++cz_)
-                for (int cy_ = r0[1]; cy_ <= r1[1]; ++cy_) {
-                    const int row = (cz_ * ny + cy_) * nx;
-                    const int c_first = row + r0[0], c_last = row + r1[0];
-                    if (c_first > c_last) continue;
-                    const int b = c_first == 0 ? 0 : sh.cell[c_first - 1], e = sh.cell[c_last];
-                    for (int p = b; p < e; ++p) {
-                        const float4 q = sh.q[p];
-                        const float dx = sx - q.x, dy = sy - q.y, dz = sz - q.z;
-                        const float d2 = (dx * dx + dy * dy) + dz * dz;
-                        const int j = __float_as_int(q.w);
-                        if (d2 < best || (d2 == best && j < bj)) best = d2, bj = j, bx = q.x, by = q.y, bz = q.z;
-                    }
-                }
-            if (bj != INT_MAX && best <= md2) {
+            const CellHit hit = cell_probe(G, IcpCells{sh}, sx, sy, sz, INFINITY);
+            if (hit.j != INT_MAX && hit.d2 <= md2) {
+                const float4 bq = sh.q[hit.pos];
                 const double s[3] = {(double)sx - c0[0], (double)sy - c0[1], (double)sz - c0[2]};
-                const double q[3] = {(double)bx - c0[0], (double)by - c0[1], (double)bz - c0[2]};
+                const double q[3] = {(double)bq.x - c0[0], (double)bq.y - c0[1], (double)bq.z - c0[2]};
                 mom[0] += 1.0;
-                mom[1] += (double)best;
+                mom[1] += (double)hit.d2;
 #pragma unroll
                 for (int a = 0; a < 3; ++a) mom[2 + a] += s[a], mom[5 + a] += q[a];
 #pragma unroll
@@ -356,7 +287,7 @@ __global__ __launch_bounds__(NT) void icp_refine_kernel(const float* __restrict_
                 iterations[k] = it;
                 sh.go = 0;
             } else {
-                icp_update(sh.pose, sh.mom, sh.lo);
+                icp_update(sh.pose, sh.mom, sh.grid.lo);
                 ++it;
                 sh.go = 1;
             }

@@ -22,7 +22,7 @@
 // ossid_mesh_diameter (9.6)     all pairs in tiles of 256 x 1024, f64, the upper triangle of tiles only, atomicMax on the bits.
 #include <cmath>
 
-#include "common.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -30,8 +30,6 @@ constexpr int SCAN_ITEMS = 16;                        // faces per thread of the
 constexpr int SCAN_BLOCK = 256 * SCAN_ITEMS;          // faces per workgroup: OSSID_RASTER_MAX_FACES / 4096 = 1024 totals
 constexpr int FPS_THREADS = 1024;
 constexpr int DIAM_TJ = 1024;
-
-__device__ __forceinline__ bool fin(double v) { return fabs(v) < INFINITY; }     // false for NaN and +-inf
 
 struct Tri {
     double p[3][3];
@@ -146,7 +144,7 @@ template <bool FINAL>
 __global__ __launch_bounds__(256) void cloud_scan_kernel(const unsigned long long* __restrict__ w, int F,
                                                          unsigned long long* __restrict__ totals,
                                                          unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long sh[256];
+    __shared__ unsigned long long sh[4];
     const size_t base = (size_t)blockIdx.x * SCAN_BLOCK + (size_t)threadIdx.x * SCAN_ITEMS;
     unsigned long long v[SCAN_ITEMS], sum = 0ull;
 #pragma unroll
@@ -154,19 +152,13 @@ __global__ __launch_bounds__(256) void cloud_scan_kernel(const unsigned long lon
         v[k] = base + k < (size_t)F ? w[base + k] : 0ull;
         sum += v[k];
     }
-    sh[threadIdx.x] = sum;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {                // Hillis-Steele over the threads' sums
-        const unsigned long long o = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0ull;
-        __syncthreads();
-        sh[threadIdx.x] += o;
-        __syncthreads();
-    }
+    unsigned long long total;
+    const unsigned long long before = block_scan_excl<4>(sum, OpAdd(), 0ull, sh, total, false);
     if (!FINAL) {
-        if (threadIdx.x == 255) totals[blockIdx.x] = sh[255];
+        if (threadIdx.x == 0) totals[blockIdx.x] = total;
         return;
     }
-    unsigned long long run = totals[blockIdx.x] + (threadIdx.x ? sh[threadIdx.x - 1] : 0ull);
+    unsigned long long run = totals[blockIdx.x] + before;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         run += v[k];
@@ -176,17 +168,10 @@ __global__ __launch_bounds__(256) void cloud_scan_kernel(const unsigned long lon
 
 // exclusive sums of at most 1024 totals, in place, one workgroup
 __global__ __launch_bounds__(1024) void cloud_scan_totals_kernel(unsigned long long* __restrict__ totals, int n) {
-    __shared__ unsigned long long sh[1024];
-    const unsigned long long mine = (int)threadIdx.x < n ? totals[threadIdx.x] : 0ull;
-    sh[threadIdx.x] = mine;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned long long o = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0ull;
-        __syncthreads();
-        sh[threadIdx.x] += o;
-        __syncthreads();
-    }
-    if ((int)threadIdx.x < n) totals[threadIdx.x] = sh[threadIdx.x] - mine;
+    __shared__ unsigned long long sh[16];
+    unsigned long long total;
+    const unsigned long long before = block_scan_excl<16>((int)threadIdx.x < n ? totals[threadIdx.x] : 0ull, OpAdd(), 0ull, sh, total, false);
+    if ((int)threadIdx.x < n) totals[threadIdx.x] = before;
 }
 
 // ---- 9.4 candidates --------------------------------------------------------------------------------------------------------------

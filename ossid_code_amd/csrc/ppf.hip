@@ -18,7 +18,7 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -175,15 +175,8 @@ __global__ __launch_bounds__(1024) void ppf_bounds_kernel(Src s, float rel, floa
         if (!load_point(s, i, p)) continue;
         for (int a = 0; a < 3; ++a) mn[a] = fminf(mn[a], p[a]), mx[a] = fmaxf(mx[a], p[a]);
     }
-    for (int a = 0; a < 3; ++a)
-        for (int m = 32; m >= 1; m >>= 1) mn[a] = fminf(mn[a], __shfl_xor(mn[a], m)), mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], m));
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int a = 0; a < 3; ++a) red[wv][a] = mn[a], red[wv][3 + a] = mx[a];
-    __syncthreads();
+    wg_bbox3<16>(mn, mx, red);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w)
-            for (int a = 0; a < 3; ++a) mn[a] = fminf(mn[a], red[w][a]), mx[a] = fmaxf(mx[a], red[w][3 + a]);
         if (!(mn[0] <= mx[0]))                         // no valid point: an empty sample
             for (int a = 0; a < 3; ++a) mn[a] = mx[a] = 0.0f;
         const float ex = mx[0] - mn[0], ey = mx[1] - mn[1], ez = mx[2] - mn[2];
@@ -239,26 +232,6 @@ __device__ __forceinline__ bool is_rep(const Src& s, const float* stats, const u
     return false;
 }
 
-__device__ __forceinline__ int block_excl_scan(int v, int* wsum, int& total) {   // SNT threads
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-    for (int w = 0; w < nw; ++w) {
-        if (w < wv) base += wsum[w];
-        total += wsum[w];
-    }
-    __syncthreads();
-    return base + incl - v;
-}
-
 __global__ __launch_bounds__(SNT) void ppf_rep_count_kernel(Src s, const float* __restrict__ stats,
                                                             const uint32_t* __restrict__ table, uint32_t tmask,
                                                             int* __restrict__ block_counts) {
@@ -266,7 +239,7 @@ __global__ __launch_bounds__(SNT) void ppf_rep_count_kernel(Src s, const float* 
     float p[3];
     const int f = is_rep(s, stats, table, tmask, blockIdx.x * SNT + threadIdx.x, p) ? 1 : 0;
     int total;
-    block_excl_scan(f, wsum, total);
+    block_scan_excl<SNT / 64>(f, OpAdd(), 0, wsum, total, false);
     if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
 }
 
@@ -289,7 +262,7 @@ __global__ __launch_bounds__(SNT) void ppf_compact_kernel(Src s, const float* __
     float p[3];
     const bool rep = is_rep(s, stats, table, tmask, i, p);
     int total;
-    const int pos = base + block_excl_scan(rep ? 1 : 0, wsum, total);
+    const int pos = base + block_scan_excl<SNT / 64>(rep ? 1 : 0, OpAdd(), 0, wsum, total, false);
     if (rep && pos < max_out) {
         idx_out[pos] = i;
         pts_out[3 * pos] = p[0], pts_out[3 * pos + 1] = p[1], pts_out[3 * pos + 2] = p[2];
@@ -325,25 +298,8 @@ __global__ __launch_bounds__(256) void ppf_model_pairs_kernel(const float* __res
 __global__ __launch_bounds__(1024) void ppf_scan_kernel(const uint32_t* counts, int64_t L,   // counts may alias cursor
                                                         uint32_t* __restrict__ offsets, uint32_t* cursor) {
     __shared__ uint32_t wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t per = (L + 1023) / 1024, b0 = tid * per, b1 = b0 + per < L ? b0 + per : L;
-    uint32_t s = 0;
-    for (int64_t j = b0; j < b1; ++j) s += counts[j];
-    uint32_t incl = s;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    uint32_t base = incl - s;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    for (int64_t j = b0; j < b1; ++j) {
-        const uint32_t c = counts[j];
-        offsets[j] = base, cursor[j] = base;
-        base += c;
-    }
-    if (tid == 1023) offsets[L] = base;
+    const uint32_t total = wg_scan_range<16>(counts, L, wsum, [&](int64_t j, uint32_t base) { offsets[j] = base, cursor[j] = base; });
+    if (threadIdx.x == 0) offsets[L] = total;
 }
 
 // ---- scene normals ----------------------------------------------------------------------------------------------------
@@ -433,8 +389,6 @@ struct VoteShared {
     int bi[VNT / 64];
 };
 
-__device__ __forceinline__ int scene_n(const int32_t* count, int cap) { return count[0] <= cap ? count[0] : 0; }
-
 __global__ __launch_bounds__(VNT) void ppf_vote_kernel(const float* __restrict__ S, const float* __restrict__ Sn,
                                                        const uint8_t* __restrict__ Sok, const int32_t* __restrict__ count,
                                                        int cap, int ref_step, const uint32_t* __restrict__ offsets,
@@ -443,7 +397,7 @@ __global__ __launch_bounds__(VNT) void ppf_vote_kernel(const float* __restrict__
     __shared__ VoteShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int slot = blockIdx.x, chunk = blockIdx.y, r = slot * ref_step;
-    const int n = scene_n(count, cap);
+    const int n = count_or_0(count, cap);
     uint2* out = peaks + (size_t)slot * nch + chunk;
     if (r >= n || !Sok[r]) {
         if (tid == 0) *out = make_uint2(0u, 0u);
@@ -466,7 +420,7 @@ __global__ __launch_bounds__(VNT) void ppf_vote_kernel(const float* __restrict__
             }
         }
         int total;
-        const int pre = block_excl_scan(len, sh.wsum, total);
+        const int pre = block_scan_excl<VNT / 64>(len, OpAdd(), 0, sh.wsum, total, false);
         sh.pre[tid] = pre, sh.start[tid] = st, sh.bin[tid] = bn;
         __syncthreads();
         for (int e = tid; e < total; e += VNT) {
@@ -509,7 +463,7 @@ __global__ __launch_bounds__(256) void ppf_peak_pose_kernel(const float* __restr
                                                             double* __restrict__ cand_pose) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= max_ref) return;
-    const int n = scene_n(count, cap), r = j * ref_step;
+    const int n = count_or_0(count, cap), r = j * ref_step;
     uint32_t bc = 0u, bi = 0u;
     if (r < n)
         for (int c = 0; c < nch; ++c) {
@@ -556,21 +510,6 @@ struct ClusterShared {
     int ncand, nseed, first;
 };
 
-__device__ void bitonic(unsigned long long* key, int n) {      // ascending, n a power of two, CNT threads
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n; i += CNT) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long a = key[i], b = key[l];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) key[i] = b, key[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-}
-
 __global__ __launch_bounds__(CNT) void ppf_cluster_kernel(const int32_t* __restrict__ peak, const double* __restrict__ cand_pose,
                                                           const int32_t* __restrict__ count, int cap, int ref_step,
                                                           int max_ref, double thr2, double cos_thr, int Ms, int num_result,
@@ -578,7 +517,7 @@ __global__ __launch_bounds__(CNT) void ppf_cluster_kernel(const int32_t* __restr
                                                           int32_t* __restrict__ info) {
     __shared__ ClusterShared sh;
     const int tid = threadIdx.x;
-    const int n = scene_n(count, cap);
+    const int n = count_or_0(count, cap);
     const int nref = min((n + ref_step - 1) / ref_step, max_ref);
     int np2 = 2;
     while (np2 < nref) np2 <<= 1;
@@ -590,7 +529,7 @@ __global__ __launch_bounds__(CNT) void ppf_cluster_kernel(const int32_t* __restr
         if (v > 0u) atomicAdd(&sh.ncand, 1);
     }
     __syncthreads();
-    bitonic(sh.key, np2);
+    wg_bitonic_sort(sh.key, np2);
     const int ncand = sh.ncand;
     for (int c = 0; c < ncand; ++c) {
         const int j = (int)(sh.key[c] & 0xffffffffu);
@@ -626,7 +565,7 @@ __global__ __launch_bounds__(CNT) void ppf_cluster_kernel(const int32_t* __restr
     for (int s = tid; s < np3; s += CNT)
         sh.key[s] = s < nseed ? ((unsigned long long)(~sh.sum[s]) << 32) | (unsigned)s : ~0ull;
     __syncthreads();
-    bitonic(sh.key, np3);
+    wg_bitonic_sort(sh.key, np3);
     const int nres = min(nseed, num_result);
     for (int k = tid; k < num_result; k += CNT) {
         double sc = 0.0;

@@ -3,7 +3,7 @@
 //
 //   model grid   once per model: for each distinct distance threshold of the step schedule a uniform grid over the
 //                refinement model points in the model frame (counting sort in global memory by one workgroup per level);
-//                the cell edge follows icp.hip's exactness argument, so the 27-cell probe keeping the lexicographic
+//                the cell edge follows cell_grid.h's exactness argument, so the 27-cell probe keeping the lexicographic
 //                minimum of (d2, model index) equals SPEC 6.9's brute force for every pair it accepts.
 //   per frame    one launch chain, the hypothesis count stays on the device (info[0] of ossid_ppf_cluster):
 //                init (pose copies, f32 inverses), then per step one workgroup per (hypothesis, chunk of 1024 scene
@@ -15,7 +15,8 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.h"
+#include "cell_grid.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -31,8 +32,8 @@ constexpr int MAX_RESULTS = 4096;            // sort in LDS
 constexpr int GNT = 1024;                    // grid build workgroup
 
 struct Level {
-    float lo[3], inv_h;
-    int n[3], ncell;
+    CellGrid g;
+    int ncell;
 };
 
 struct GridHeader {                          // at the start of the grid buffer, written by the setup kernel
@@ -93,8 +94,7 @@ struct Thr {
     float t[MAX_LEVELS];
 };
 
-// one workgroup: bounds of the model points, every level's cell edge (h >= thr (1 + 1/16) + maxabs 2^-14, grown by 5/4
-// until the grid fits MAX_CELLS), float4 copies of the points and normals
+// one workgroup: bounds of the model points, every level's grid (cell_grid_size), float4 copies of the points and normals
 __global__ __launch_bounds__(GNT) void refine_grid_setup_kernel(const float* __restrict__ P, const float* __restrict__ N, int Mr,
                                                                 int nlev, Thr thr, void* __restrict__ grid) {
     __shared__ float red[GNT / 64][6];
@@ -109,51 +109,11 @@ __global__ __launch_bounds__(GNT) void refine_grid_setup_kernel(const float* __r
         mn[0] = fminf(mn[0], x), mn[1] = fminf(mn[1], y), mn[2] = fminf(mn[2], z);
         mx[0] = fmaxf(mx[0], x), mx[1] = fmaxf(mx[1], y), mx[2] = fmaxf(mx[2], z);
     }
-    for (int a = 0; a < 3; ++a)
-        for (int m = 32; m >= 1; m >>= 1) mn[a] = fminf(mn[a], __shfl_xor(mn[a], m)), mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], m));
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int a = 0; a < 3; ++a) red[wv][a] = mn[a], red[wv][3 + a] = mx[a];
-    __syncthreads();
-    if (threadIdx.x >= nlev) return;
-    for (int w = 0; w < GNT / 64; ++w)
-        for (int a = 0; a < 3; ++a) mn[a] = fminf(mn[a], red[w][a]), mx[a] = fmaxf(mx[a], red[w][3 + a]);
-    float maxabs = 0.0f;
-    for (int a = 0; a < 3; ++a) maxabs = fmaxf(maxabs, fmaxf(fabsf(mn[a]), fabsf(mx[a])));
-    float h = thr.t[threadIdx.x] * (1.0f + 1.0f / 16.0f) + maxabs * (1.0f / 16384.0f);
-    float nf[3];
-    for (int guard = 0; guard < 256; ++guard) {
-        double cells = 1.0;
-        for (int a = 0; a < 3; ++a) {
-            nf[a] = floorf((mx[a] - mn[a]) / h) + 1.0f;
-            cells *= (double)nf[a];
-        }
-        if (cells <= (double)MAX_CELLS) break;
-        h *= 1.25f;
-    }
-    float inv_h = 1.0f / h;
-    if (!(nf[0] * nf[1] * nf[2] <= (float)MAX_CELLS)) {   // one cell: the probe is the brute force
-        nf[0] = nf[1] = nf[2] = 1.0f;
-        inv_h = 0.0f;
-    }
+    wg_bbox3<GNT / 64>(mn, mx, red);
+    if (threadIdx.x >= nlev) return;                    // nlev <= MAX_LEVELS: wave 0
     Level& L = hdr->lev[threadIdx.x];
-    for (int a = 0; a < 3; ++a) L.lo[a] = mn[a], L.n[a] = (int)nf[a];
-    L.inv_h = inv_h;
-    L.ncell = L.n[0] * L.n[1] * L.n[2];
-}
-
-__device__ __forceinline__ int cell_axis(float x, float lo, float inv_h, int n) {
-    const float c = floorf((x - lo) * inv_h);
-    return (int)fminf(fmaxf(c, -2.0f), (float)(n + 1));   // outside the box by more than one cell: no cell in reach
-}
-
-// a model point's cell: its coordinate is >= 0 (lo is the minimum); rounding of (hi - lo) * inv_h can reach n, which
-// stays within one cell of every query that can accept the point, so it is clamped to n - 1
-__device__ __forceinline__ int model_cell(const float4& p, const Level& L) {
-    const int cx = min(max(cell_axis(p.x, L.lo[0], L.inv_h, L.n[0]), 0), L.n[0] - 1);
-    const int cy = min(max(cell_axis(p.y, L.lo[1], L.inv_h, L.n[1]), 0), L.n[1] - 1);
-    const int cz = min(max(cell_axis(p.z, L.lo[2], L.inv_h, L.n[2]), 0), L.n[2] - 1);
-    return (cz * L.n[1] + cy) * L.n[0] + cx;
+    L.g = cell_grid_size(mn, mx, thr.t[threadIdx.x], MAX_CELLS);
+    L.ncell = L.g.n[0] * L.g.n[1] * L.g.n[2];
 }
 
 // one workgroup per level: counting sort of the model points into the level's cells (order inside a cell is free: the
@@ -171,36 +131,18 @@ __global__ __launch_bounds__(GNT) void refine_grid_sort_kernel(int Mr, void* __r
     __threadfence();
     __syncthreads();
     for (int i = threadIdx.x; i < Mr; i += GNT) {
-        atomicAdd(&cursor[model_cell(pts[i], L)], 1);
+        const float4 p = pts[i];
+        atomicAdd(&cursor[cell_of(L.g, p.x, p.y, p.z)], 1);
     }
     __threadfence();
     __syncthreads();
-    // exclusive scan: each thread a contiguous segment of cells, then the segments' totals across the workgroup
-    const int per = (L.ncell + GNT - 1) / GNT, c0 = threadIdx.x * per, c1 = min(c0 + per, L.ncell);
-    int s = 0;
-    for (int c = c0; c < c1; ++c) s += cursor[c];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int incl = s;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int base = incl - s;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    for (int c = c0; c < c1; ++c) {
-        const int v = cursor[c];
-        start[c] = base;
-        cursor[c] = base;
-        base += v;
-    }
+    wg_scan_range<GNT / 64>(cursor, L.ncell, wsum, [&](int c, int base) { start[c] = base, cursor[c] = base; });
     if (threadIdx.x == 0) start[L.ncell] = Mr;
     __threadfence();
     __syncthreads();
     for (int i = threadIdx.x; i < Mr; i += GNT) {
         const float4 p = pts[i];
-        const int pos = atomicAdd(&cursor[model_cell(p, L)], 1);
+        const int pos = atomicAdd(&cursor[cell_of(L.g, p.x, p.y, p.z)], 1);
         sorted[pos] = make_float4(p.x, p.y, p.z, __int_as_float(i));
     }
 }
@@ -264,29 +206,19 @@ __global__ __launch_bounds__(256) void refine_init_kernel(const double* __restri
     w.done[h] = 0;
 }
 
+// a level's storage for cell_probe: start[c] = first position of cell c (start[ncell] = Mr), sorted points in global memory
+struct LevelCells {
+    const int* start;
+    const float4* srt;
+    __device__ __forceinline__ void run(int first, int last, int& b, int& e) const { b = start[first], e = start[last + 1]; }
+    __device__ __forceinline__ float4 point(int p) const { return srt[p]; }
+};
+
 // nearest refinement model point of x within the level's grid, ties to the lowest index -> index (or -1 when none
 // within thr2)
 __device__ __forceinline__ int probe(const GridView& g, int lev, const float* x, float thr2) {
-    const Level& L = g.hdr->lev[lev];
-    const int* start = g.start(lev);
-    const float4* srt = g.sorted(lev);
-    const int cx = cell_axis(x[0], L.lo[0], L.inv_h, L.n[0]), cy = cell_axis(x[1], L.lo[1], L.inv_h, L.n[1]),
-              cz = cell_axis(x[2], L.lo[2], L.inv_h, L.n[2]);
-    float best = FLT_MAX;
-    int bj = 0x7fffffff;
-    for (int z = max(cz - 1, 0); z <= min(cz + 1, L.n[2] - 1); ++z)
-        for (int y = max(cy - 1, 0); y <= min(cy + 1, L.n[1] - 1); ++y) {
-            const int row = (z * L.n[1] + y) * L.n[0];
-            const int b = start[row + max(cx - 1, 0)], e = start[row + min(cx + 1, L.n[0] - 1) + 1];
-            for (int q = b; q < e; ++q) {             // the cells of one x-run are contiguous in the sorted array
-                const float4 m = srt[q];
-                const float dx = x[0] - m.x, dy = x[1] - m.y, dz = x[2] - m.z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                const int j = __float_as_int(m.w);
-                if (d2 < best || (d2 == best && j < bj)) best = d2, bj = j;
-            }
-        }
-    return (bj != 0x7fffffff && best <= thr2) ? bj : -1;
+    const CellHit h = cell_probe(g.hdr->lev[lev].g, LevelCells{g.start(lev), g.sorted(lev)}, x[0], x[1], x[2], FLT_MAX);
+    return (h.j != INT_MAX && h.d2 <= thr2) ? h.j : -1;
 }
 
 // MODE 0: moments of one step for active hypotheses; 1: pair count at the final pose for every hypothesis; 2: the
@@ -458,18 +390,7 @@ __global__ __launch_bounds__(1024) void refine_final_kernel(const int32_t* __res
         key[h] = k;
     }
     __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < np2; i += 1024) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long a = key[i], b = key[l];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) key[i] = b, key[l] = a;
-                }
-            }
-            __syncthreads();
-        }
+    wg_bitonic_sort(key, np2);
     for (int r = threadIdx.x; r < NR; r += 1024) {
         if (r < n) {
             const int h = (int)(key[r] & 0xffffffffu);

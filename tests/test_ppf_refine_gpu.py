@@ -1,6 +1,8 @@
 """Dense pose refinement of PPF hypotheses on the device (csrc/ppf_refine.hip, SPEC.md 6.9) against the numpy restatement
 tests/ref_ppf_refine.py: samplings, correspondence sets (grid cell edges and exact ties included), poses after one step and
 after the full run, scores and order, reproducibility, both call forms, the caps and bad arguments, and the stream."""
+import types
+
 import numpy as np
 import pytest
 import torch
@@ -144,6 +146,55 @@ def test_correspondences_on_a_lattice_with_ties(hiplib):
         assert np.array_equal(got, want), step
     ties = _ref_match(I[0], S[:300], rm, thr[0])
     assert np.all(ties >= 0)
+
+
+def _grown_grid_case(shift):
+    """The lattice model and a scene at the acceptance edges of thresholds 0.2, 0.1, 0.08 (D = 2.0, smaller than the
+    extent 9, so every level's own cell edge needs more than 32768 cells and is grown) -> (L, S, D, h, thr)."""
+    g = np.arange(10, dtype=np.float32)
+    off = np.array([2.0 + shift, 2.0, 2.0], dtype=np.float32)
+    L = (np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3) + off).astype(np.float32)
+    D = np.float32(2.0)
+    h = rr.refine_step_h(rr.REFINE_SAMPLING_REL, D)
+    thr = rr.thresholds(D, h, steps=3)
+    assert [float(t) for t in thr] == [float(np.float32(v)) for v in (0.2, 0.1, 0.08)]
+    rng = np.random.default_rng(11)
+    dirs = np.array([[1.0, 0.0, 0.0], [0.0, -1.0, 0.0], [1.0, 1.0, 0.0], [0.0, 1.0, -1.0], [1.0, 1.0, 1.0], [-1.0, 1.0, -1.0]])
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    M = L[rng.integers(0, 1000, 8)].astype(np.float64)
+    edge = [m + float(t) * f * u for t in thr for f in (1.0 - 1e-6, 1.0, 1.0 + 1e-6) for u in dirs for m in M]
+    mid = L[rng.integers(0, 1000, 100)] + np.float32(0.5) * np.eye(3, dtype=np.float32)[rng.integers(0, 3, 100)]
+    far = off + np.array([[-50.0, 3.0, 3.0], [5.0, 5.0, 400.0], [9.0 + float(thr[0]), 4.0, 4.0], [4.0, -1e6, 4.0]], dtype=np.float32)
+    S = np.concatenate([np.asarray(edge), mid, L[rng.integers(0, 1000, 60)], far]).astype(np.float32)
+    return L, S, D, h, thr
+
+
+@pytest.mark.parametrize("shift", [0.0, 3000.0], ids=["margin", "maxabs"])
+def test_grown_levels_and_cell_edges_keep_the_brute_force_pairs(hiplib, shift):
+    """Grid growth and the cell-edge margin of the refinement's levels, through ossid_ppf_refine_model_grid and
+    ossid_ppf_refine_match at the C ABI: scene points at thr (1 - 1e-6, 1, 1 + 1e-6) from a model point along an axis, a
+    face diagonal and the space diagonal, at midpoints (exact ties), on lattice points and far outside; shifted by 3000 the
+    maxabs 2^-14 term dominates the cell edge. Every step's rows equal the brute force."""
+    L, S, D, h, thr = _grown_grid_case(np.float32(shift))
+    Mr = len(L)
+    N = np.tile(np.array([[0.0, 0.0, 1.0]], dtype=np.float32), (Mr, 1))
+    gb = int(_lib.fn("ossid_ppf_refine_grid_bytes")(Mr, 3, float(D), float(h)))
+    assert gb > 0
+    grid = torch.empty(gb, dtype=torch.uint8, device="cuda")
+    pts, nrm = torch.from_numpy(L).cuda(), torch.from_numpy(N).cuda()
+    assert _lib.fn("ossid_ppf_refine_model_grid")(pts.data_ptr(), nrm.data_ptr(), Mr, 3, float(D), float(h), grid.data_ptr(),
+                                                  gb, None) == 0
+    dev = types.SimpleNamespace(D=D, refine={"grid": grid, "Mr": Mr, "steps": 3, "h": h})
+    model = types.SimpleNamespace(P=L)
+    I = np.eye(4)
+    d = (S[:, None, :] - L[None, :, :]).astype(np.float32)
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    n_ties = int(np.sum(np.sum(d2 == d2.min(axis=1, keepdims=True), axis=1) > 1))
+    for step in range(3):
+        want = _ref_match(I, S, model, thr[step])
+        assert n_ties > 0 and np.any(want >= 0) and np.any(want < 0), step
+        got = _match(dev, S, len(S), I[None], step, cap=2048)[0]
+        assert np.array_equal(got, want), (step, np.flatnonzero(got != want)[:8])
 
 
 def test_one_step_and_full_run_equal_the_restatement(obj, scenes):
