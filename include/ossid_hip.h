@@ -941,6 +941,36 @@ int ossid_raster_color(const float* vertices, int V, const int32_t* faces, int F
 int ossid_template_reduce(const uint8_t* color, const float* depth, int N, int T, int s, float* img_out, float* mask_out,
                           void* stream);
 
+/* 8f-3d  texture-mapped meshes: BOP models whose .ply carries `comment TextureFile NAME` and per-vertex (u, v), the colour
+ * living in the image. Build-defined, SPEC.md 7.15-7.17 (csrc/texture.hip, csrc/texture.h, csrc/raster.hip): the reference
+ * renders such models with Blender / pyrender, neither in its tree.
+ * ossid_texture_mips: image u8 [Ht][Wt][3] (RGB, row 0 the top row of the image file), 1 <= Ht, Wt <=
+ * OSSID_TEXTURE_MAX_SIDE -> the mip chain in the caller's buffer `mips` (4-byte aligned, ossid_texture_mip_bytes(Ht, Wt)
+ * bytes, 0 = bad sizes). Layout: 4 bytes per texel (R, G, B, 0); level 0 is the image, h_0 x w_0 = Ht x Wt; level l + 1
+ * has h_{l+1} x w_{l+1} = ((h_l + 1) >> 1) x ((w_l + 1) >> 1) texels, down to 1 x 1 (ossid_texture_levels(Ht, Wt) levels,
+ * 0 = bad sizes); level l starts at BYTE offset 4 * sum_{k<l} h_k w_k and is row-major. A texel of level l + 1 is, per
+ * channel, (a + b + c + d + 2) / 4 (integer division) over rows 2y, 2y + 1 and columns 2x, 2x + 1 of level l, the odd ones
+ * clamped to the last row / column: every level is made from the one before it. One launch per level.
+ * ossid_raster_textured: ossid_raster_color with `colors` replaced by uvs f32 [V][2] = (u, v), v upwards, and the mip
+ * chain of an Ht x Wt texture; the same workspace (ossid_raster_color_workspace_bytes) and the same first two launches, so
+ * depth_out, face_id_out and stats are ossid_raster_color's bit for bit. The resolve interpolates (u, v)
+ * perspective-correctly at the sample and at the samples of pixels (x + 1, y) and (x, y + 1), takes rho = the largest of
+ * the four |differences| in level-0 texels, the level = the smallest l with rho <= 2^l (the top level when a neighbour's
+ * denominator is <= 0 or a value is not finite), and fetches bilinearly with clamp-to-edge addressing at
+ * s = u w_l - 0.5, t = (1 - v) h_l - 0.5. -> color_out u8 [N][H][W][3], lod_out int32 [N][H][W] (may be NULL; -1 where
+ * nothing is drawn). UVs outside [0, 1] are legal; the caller refuses non-finite ones (the kernel then draws 0 and never
+ * reads outside the chain). Three launches, nothing read back, capturable.
+ * OSSID_EINVAL before any launch: what ossid_raster_color refuses, Ht or Wt outside [1, OSSID_TEXTURE_MAX_SIDE], a NULL
+ * or misaligned mip buffer, mip_bytes below ossid_texture_mip_bytes(Ht, Wt). */
+#define OSSID_TEXTURE_MAX_SIDE 8192
+size_t ossid_texture_mip_bytes(int Ht, int Wt);
+int ossid_texture_levels(int Ht, int Wt);
+int ossid_texture_mips(const uint8_t* image, int Ht, int Wt, void* mips, size_t mip_bytes, void* stream);
+int ossid_raster_textured(const float* vertices, int V, const int32_t* faces, int F, const float* uvs, const void* mips,
+                          size_t mip_bytes, int Ht, int Wt, const float* transforms, int N, const float* intrinsics, int H, int W,
+                          float pixel_offset, float z_near, void* workspace, size_t workspace_bytes, uint8_t* color_out,
+                          float* depth_out, int32_t* face_id_out, int32_t* lod_out, int32_t* stats, void* stream);
+
 /* 8f-4  the BOP-19 pose errors the reference's run ends with (scripts/online_learning.py:603-608:
  * saveResultsBop(..., run_eval_script=True); utils/bop_utils.py:51-53 shells out to bop_toolkit's scripts/eval_bop19.py
  * --renderer_type=cpp, which is not part of the reference tree). SPEC.md section 8 (csrc/bop_eval.hip): this build's own
@@ -987,6 +1017,11 @@ int ossid_bop_mssd_mspd(const float* vertices, int V, const double* symmetries, 
  * [K][3], normals f32 [K][3], colors f32 [K][3] (in [0, 1]), face int32 [K] (-1 and zeros everywhere when Wt = 0). A face
  * that got more votes from its back is read as (p0, p2, p1): the cloud does not depend on how the mesh is wound.
  *
+ * ossid_cloud_candidates_textured (9.4.1): the same candidates of a texture-mapped mesh -- points, normals and face are
+ * ossid_cloud_candidates' bit for bit -- with colors_out = the bilinear fetch (7.17) at level lod in [0, top] of the mip
+ * chain (ossid_texture_mips) at the affinely interpolated (u, v); uvs f32 [V][2]. OSSID_EINVAL also for Ht or Wt outside
+ * [1, OSSID_TEXTURE_MAX_SIDE], a mip buffer that is NULL, misaligned or too small, lod outside [0, top].
+ *
  * ossid_cloud_fps (9.5, online_learning.py:303-311): farthest-point sampling of M of K arbitrary FINITE f32 points
  * [K][3], from point 0, lowest index among equal maxima -> selection int32 [M] in pick order, radius f32 [M] (the
  * largest distance^2 to the earlier picks when pick j was chosen; radius[0] = +inf). One workgroup of 1024 threads.
@@ -1008,6 +1043,10 @@ int ossid_cloud_weights(const float* vertices, int V, const int32_t* faces, int 
 int ossid_cloud_candidates(const float* vertices, int V, const int32_t* faces, int F, const uint8_t* colors,
                            const int32_t* votes, const uint64_t* prefix, const float* normals, int K, float* points_out,
                            float* normals_out, float* colors_out, int32_t* face_out, void* stream);
+int ossid_cloud_candidates_textured(const float* vertices, int V, const int32_t* faces, int F, const float* uvs, const void* mips,
+                                    size_t mip_bytes, int Ht, int Wt, int lod, const int32_t* votes, const uint64_t* prefix,
+                                    const float* normals, int K, float* points_out, float* normals_out, float* colors_out,
+                                    int32_t* face_out, void* stream);
 int ossid_cloud_fps(const float* points, int K, int M, int32_t* selection, float* radius, void* stream);
 int ossid_mesh_diameter(const float* vertices, int V, double* out, void* stream);
 

@@ -12,6 +12,7 @@
 //                               launches (4096 faces per workgroup, at most 1024 workgroups, one workgroup scans the totals).
 // ossid_cloud_candidates (9.4)  one thread per candidate: stratified position in the prefix sums, binary search, barycentric
 //                               coordinates from the integer R2 sequence, all in f64.
+// ossid_cloud_candidates_textured (9.4.1)  the same kernel with the colour taken from a UV texture at one mip level.
 // ossid_cloud_fps (9.5)         ONE workgroup of 1024 threads. Lane t owns candidates t, t + 1024, ...: at most 32, their
 //                               coordinates in registers (96 VGPRs of the 128 a wave has at 4 waves per SIMD), their running
 //                               minimum distances in LDS (128 KiB of the CU's 160: registers cannot hold both), conflict-free
@@ -22,6 +23,7 @@
 // ossid_mesh_diameter (9.6)     all pairs in tiles of 256 x 1024, f64, the upper triangle of tiles only, atomicMax on the bits.
 #include <cmath>
 
+#include "texture.h"
 #include "workgroup.h"
 
 namespace {
@@ -175,9 +177,14 @@ __global__ __launch_bounds__(1024) void cloud_scan_totals_kernel(unsigned long l
 }
 
 // ---- 9.4 candidates --------------------------------------------------------------------------------------------------------------
+// TEX = false: colors u8 [V][3], interpolated (9.4). TEX = true: uvs f32 [V][2] interpolated the same way, then one bilinear
+// fetch at level lod of the mip chain (9.4.1; the sampler is texture.h's, shared with the textured rasteriser).
+template <bool TEX>
 __global__ __launch_bounds__(256) void cloud_candidates_kernel(const float* __restrict__ vertices, int V,
                                                                const int32_t* __restrict__ faces, int F,
                                                                const uint8_t* __restrict__ colors,
+                                                               const float* __restrict__ uvs,
+                                                               const unsigned* __restrict__ mips, int tex_h, int tex_w, int lod,
                                                                const int32_t* __restrict__ votes,
                                                                const unsigned long long* __restrict__ prefix,
                                                                const float* __restrict__ normals, int K,
@@ -210,12 +217,24 @@ __global__ __launch_bounds__(256) void cloud_candidates_kernel(const float* __re
                 const double a0 = (double)vertices[3 * (size_t)i0 + c], a1 = (double)vertices[3 * (size_t)i1 + c],
                              a2 = (double)vertices[3 * (size_t)i2 + c];
                 P[c] = (float)((w0 * a0 + u * a1) + v * a2);
-                const double c0 = (double)colors[3 * (size_t)i0 + c], c1 = (double)colors[3 * (size_t)i1 + c],
-                             c2 = (double)colors[3 * (size_t)i2 + c];
-                double a = rint((w0 * c0 + u * c1) + v * c2);
-                a = a < 0.0 ? 0.0 : (a > 255.0 ? 255.0 : a);
-                C[c] = (float)a / 255.0f;
+                if constexpr (!TEX) {
+                    const double c0 = (double)colors[3 * (size_t)i0 + c], c1 = (double)colors[3 * (size_t)i1 + c],
+                                 c2 = (double)colors[3 * (size_t)i2 + c];
+                    double a = rint((w0 * c0 + u * c1) + v * c2);
+                    a = a < 0.0 ? 0.0 : (a > 255.0 ? 255.0 : a);
+                    C[c] = (float)a / 255.0f;
+                }
                 N[c] = normals[3 * (size_t)f + c];
+            }
+            if constexpr (TEX) {
+                double t[2], q[3];
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+                    t[c] = (w0 * (double)uvs[2 * (size_t)i0 + c] + u * (double)uvs[2 * (size_t)i1 + c]) +
+                           v * (double)uvs[2 * (size_t)i2 + c];
+                tex_bilinear(tex_level(mips, tex_h, tex_w, lod), t[0], t[1], q);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) C[c] = (float)tex_round_u8(q[c]) / 255.0f;
             }
         }
     }
@@ -393,9 +412,24 @@ int ossid_cloud_candidates(const float* vertices, int V, const int32_t* faces, i
     if (!vertices || !faces || !colors || !votes || !prefix || !normals || !points_out || !normals_out || !colors_out ||
         !face_out || V < 1 || F < 1 || F > OSSID_RASTER_MAX_FACES || K < 1 || K > OSSID_CLOUD_MAX_CANDIDATES)
         return OSSID_EINVAL;
-    hipLaunchKernelGGL(cloud_candidates_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vertices,
-                       V, faces, F, colors, votes, (const unsigned long long*)prefix, normals, K, points_out, normals_out,
-                       colors_out, face_out);
+    hipLaunchKernelGGL(cloud_candidates_kernel<false>, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       vertices, V, faces, F, colors, (const float*)nullptr, (const unsigned*)nullptr, 1, 1, 0, votes,
+                       (const unsigned long long*)prefix, normals, K, points_out, normals_out, colors_out, face_out);
+    return ossid_launch_status();
+}
+
+int ossid_cloud_candidates_textured(const float* vertices, int V, const int32_t* faces, int F, const float* uvs, const void* mips,
+                                    size_t mip_bytes, int Ht, int Wt, int lod, const int32_t* votes, const uint64_t* prefix,
+                                    const float* normals, int K, float* points_out, float* normals_out, float* colors_out,
+                                    int32_t* face_out, void* stream) {
+    const size_t tex = ossid_texture_mip_bytes(Ht, Wt);
+    if (!vertices || !faces || !uvs || !mips || !votes || !prefix || !normals || !points_out || !normals_out || !colors_out ||
+        !face_out || V < 1 || F < 1 || F > OSSID_RASTER_MAX_FACES || K < 1 || K > OSSID_CLOUD_MAX_CANDIDATES || tex == 0 ||
+        mip_bytes < tex || ((uintptr_t)mips & 3) != 0 || lod < 0 || lod > tex_top_level(Ht, Wt))
+        return OSSID_EINVAL;
+    hipLaunchKernelGGL(cloud_candidates_kernel<true>, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       vertices, V, faces, F, (const uint8_t*)nullptr, uvs, (const unsigned*)mips, Ht, Wt, lod, votes,
+                       (const unsigned long long*)prefix, normals, K, points_out, normals_out, colors_out, face_out);
     return ossid_launch_status();
 }
 

@@ -23,11 +23,17 @@
 // redoes the winner's setup per pixel, recomputes the exact edge functions and interpolates the vertex colours
 // perspective-correctly. ossid_template_reduce (7.13) is the s x s box filter that makes a template of such a render.
 //
+// ossid_raster_textured (SPEC 7.16-7.17; BOP models whose colour lives in a UV texture) is ossid_raster_color with another
+// resolve: the same prepare and triangle launches, then per covered pixel the perspective-correct (u, v) at the sample and
+// at its right and lower neighbour, a mip level from their largest difference, and one bilinear fetch (texture.h) from the
+// chain csrc/texture.hip built.
+//
 // The arithmetic of a sample (vertex stage, setup, edge functions, depth, colour) lives in raster_common.h, shared with
 // csrc/scene.hip.
 #include <cmath>
 
 #include "raster_common.h"
+#include "texture.h"
 
 namespace {
 
@@ -197,6 +203,76 @@ __global__ __launch_bounds__(256) void raster_resolve_color_kernel(const unsigne
     }
 }
 
+// (u, v) of triangle a b d (after the swap; UVs uv0 uv1 uv2 travel with them) at the fixed-point sample (px, py), SPEC
+// 7.16: the edge functions are affine, so the integers are exact outside the triangle too. Returns the denominator.
+__device__ __forceinline__ double uv_at(const VRec& a, const VRec& b, const VRec& d, const float* __restrict__ uv0,
+                                        const float* __restrict__ uv1, const float* __restrict__ uv2, int px, int py, double& u,
+                                        double& v) {
+    long long w0, w1, w2;
+    edge_in(a.sx, a.sy, b.sx, b.sy, px, py, w2);
+    edge_in(b.sx, b.sy, d.sx, d.sy, px, py, w0);
+    edge_in(d.sx, d.sy, a.sx, a.sy, px, py, w1);
+    const double b0 = (double)w0 * a.rz, b1 = (double)w1 * b.rz, b2 = (double)w2 * d.rz;
+    const double den = (b0 + b1) + b2;
+    u = ((b0 * (double)uv0[0] + b1 * (double)uv1[0]) + b2 * (double)uv2[0]) / den;
+    v = ((b0 * (double)uv0[1] + b1 * (double)uv1[1]) + b2 * (double)uv2[1]) / den;
+    return den;
+}
+
+// SPEC 7.16-7.17, one thread per (pose, pixel): the winner's setup again as sample_color does it (the UVs swap with the
+// vertices), (u, v) at the sample and at the samples of the right and lower neighbour, the level by comparison with
+// powers of two, the bilinear fetch of texture.h.
+__global__ __launch_bounds__(256) void raster_resolve_textured_kernel(
+    const unsigned long long* __restrict__ keys, const int32_t* __restrict__ faces, int V, const VRec* __restrict__ rec,
+    const float* __restrict__ uvs, const unsigned* __restrict__ mips, int Ht, int Wt, int H, int W, int o, size_t npix,
+    unsigned char* __restrict__ color_out, float* __restrict__ depth_out, int32_t* __restrict__ face_out,
+    int32_t* __restrict__ lod_out) {
+    const size_t hw = (size_t)H * W;
+    const int top = tex_top_level(Ht, Wt);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
+        const unsigned long long key = keys[i];
+        float z = 0.0f;
+        int face = -1, lod = -1, c[3] = {0, 0, 0};
+        if (key != KFAR) {
+            const int pose = (int)(i / hw);
+            const int pix = (int)(i - (size_t)pose * hw), y = pix / W, x = pix - y * W;
+            face = (int)(unsigned)key;                   // written by a usable triangle: its indices lie in [0, V)
+            z = __uint_as_float((unsigned)(key >> 32));
+            const size_t f = (size_t)face;
+            const VRec* vr = rec + (size_t)pose * V;
+            int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+            VRec a = vr[i0], b = vr[i1], d = vr[i2];
+            const long long A = (long long)(b.sx - a.sx) * (long long)(d.sy - a.sy) - (long long)(b.sy - a.sy) * (long long)(d.sx - a.sx);
+            if (A < 0) {
+                const VRec s = b;
+                b = d, d = s;
+                const int j = i1;
+                i1 = i2, i2 = j;
+            }
+            const float *uv0 = uvs + 2 * (size_t)i0, *uv1 = uvs + 2 * (size_t)i1, *uv2 = uvs + 2 * (size_t)i2;
+            const int px = 256 * x + o, py = 256 * y + o;
+            double u, v, ux, vx, uy, vy;
+            uv_at(a, b, d, uv0, uv1, uv2, px, py, u, v);
+            const double denx = uv_at(a, b, d, uv0, uv1, uv2, px + 256, py, ux, vx);
+            const double deny = uv_at(a, b, d, uv0, uv1, uv2, px, py + 256, uy, vy);
+            const double dsx = fabs((ux - u) * (double)Wt), dtx = fabs((vx - v) * (double)Ht);
+            const double dsy = fabs((uy - u) * (double)Wt), dty = fabs((vy - v) * (double)Ht);
+            lod = top;
+            if (denx > 0.0 && deny > 0.0 && fin(dsx) && fin(dtx) && fin(dsy) && fin(dty)) {
+                const double m0 = dsx > dtx ? dsx : dtx, m1 = dsy > dty ? dsy : dty;
+                lod = tex_select_level(m0 > m1 ? m0 : m1, top);
+            }
+            double q[3];
+            tex_bilinear(tex_level(mips, Ht, Wt, lod), u, v, q);
+            c[0] = tex_round_u8(q[0]), c[1] = tex_round_u8(q[1]), c[2] = tex_round_u8(q[2]);
+        }
+        depth_out[i] = z;
+        color_out[3 * i] = (unsigned char)c[0], color_out[3 * i + 1] = (unsigned char)c[1], color_out[3 * i + 2] = (unsigned char)c[2];
+        if (face_out) face_out[i] = face;
+        if (lod_out) lod_out[i] = lod;
+    }
+}
+
 // SPEC 7.13, one thread per output pixel: the s x s box over a supersampled render, uncovered samples count as 0.
 __global__ __launch_bounds__(256) void template_reduce_kernel(const unsigned char* __restrict__ color,
                                                               const float* __restrict__ depth, int N, int T, int s,
@@ -298,6 +374,29 @@ int ossid_raster_color(const float* vertices, int V, const int32_t* faces, int F
     if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, keys, stats, s);
     hipLaunchKernelGGL(raster_resolve_color_kernel, dim3(grid_for(npix)), dim3(256), 0, s, keys, faces, V, rec, colors, H, W, o,
                        npix, color_out, depth_out, face_id_out);
+    return ossid_launch_status();
+}
+
+int ossid_raster_textured(const float* vertices, int V, const int32_t* faces, int F, const float* uvs, const void* mips,
+                          size_t mip_bytes, int Ht, int Wt, const float* transforms, int N, const float* intrinsics, int H, int W,
+                          float pixel_offset, float z_near, void* workspace, size_t workspace_bytes, uint8_t* color_out,
+                          float* depth_out, int32_t* face_id_out, int32_t* lod_out, int32_t* stats, void* stream) {
+    const size_t need = ossid_raster_color_workspace_bytes(V, F, N, H, W), tex = ossid_texture_mip_bytes(Ht, Wt);
+    if (need == 0 || tex == 0 || !vertices || (F > 0 && !faces) || !uvs || !mips || mip_bytes < tex ||
+        ((uintptr_t)mips & 3) != 0 || !transforms || !intrinsics || !workspace || workspace_bytes < need || !color_out ||
+        !depth_out || ((uintptr_t)workspace & 15) != 0 || !frame_ok(H, W, pixel_offset, z_near))
+        return OSSID_EINVAL;
+    const int o = (int)std::nearbyint((double)pixel_offset * 256.0);
+    const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
+    hipStream_t s = (hipStream_t)stream;
+    VRec* rec = (VRec*)workspace;
+    unsigned long long* keys = (unsigned long long*)((char*)workspace + nv * sizeof(VRec));
+    // the prepare and triangle stages are ossid_raster_color's: key, depth, face and statistics are 7.11's
+    hipLaunchKernelGGL(raster_prepare_color_kernel, dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0, s, vertices, V,
+                       transforms, N, intrinsics, z_near, rec, keys, npix, stats);
+    if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, keys, stats, s);
+    hipLaunchKernelGGL(raster_resolve_textured_kernel, dim3(grid_for(npix)), dim3(256), 0, s, keys, faces, V, rec, uvs,
+                       (const unsigned*)mips, Ht, Wt, H, W, o, npix, color_out, depth_out, face_id_out, lod_out);
     return ossid_launch_status();
 }
 

@@ -154,24 +154,23 @@ class FeatureModel:
 
     # ---- building -------------------------------------------------------------------------------------------------------
     def construct(self, obj_id, obj_path, dataset_camera, mm2m=True, **kwargs):
-        """The reference's call (:74): a BOP .ply with vertex colours (millimetres; mm2m scales it to metres, the unit of
+        """The reference's call (:74): a BOP .ply with vertex colours or a texture (millimetres; mm2m scales it to metres, the unit of
         the scene depth, SPEC 7.1), dataset_camera["K"] the camera the scenes are taken with."""
         from . import render
-        V, F, C = render.read_ply_mesh(obj_path, with_colors=True)
-        mesh = render.Mesh(V, F, scale=0.001 if mm2m else 1.0, colors=C)
+        mesh = render.load_mesh(obj_path, scale=0.001 if mm2m else 1.0)
         self.obj_id = obj_id
         return self._build(mesh, np.asarray(dataset_camera["K"], dtype=np.float64), **kwargs)
 
     @classmethod
     def from_mesh(cls, mesh, cam_K, **kwargs):
-        """From a vertex-coloured render.Mesh (already in the scene's units) -> FeatureModel."""
+        """From a vertex-coloured or texture-mapped render.Mesh (already in the scene's units) -> FeatureModel."""
         return cls()._build(mesh, np.asarray(cam_K, dtype=np.float64), **kwargs)
 
     def _build(self, mesh, cam_K, level=2, view_size=256, distance=0.8, contrast=CONTRAST, pad=1.1, z_near=0.05,
                rotations=None, views_per_call=16):
         from . import render
-        if getattr(mesh, "colors", None) is None:
-            raise ValueError("FeatureModel: the mesh has no vertex colours")
+        if getattr(mesh, "colors", None) is None and not render._has_texture(mesh):
+            raise ValueError("FeatureModel: the mesh has no vertex colours and no texture")
         R = render.view_grid(level=level, inplane=1) if rotations is None else np.asarray(rotations, dtype=np.float64)
         S, n = int(view_size), len(R)
         cams, _tz = render._frame_views(mesh.vertices, R, float(distance), cam_K, S, S, float(pad), float(z_near))

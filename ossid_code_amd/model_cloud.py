@@ -4,9 +4,10 @@ scripts/online_learning.py loads from a file that neither tree can make:
     model_data_path = os.path.join(args.zephyr_model_data, "model_cloud_{:02d}.npz")   scripts/online_learning.py:303-311
     model_points, model_colors, model_normals = data["model_points"], data["model_colors"], data["model_normals"]
 
-sample_model_cloud takes a vertex-coloured render.Mesh and returns a ModelCloud: points on the surface that is visible from
-outside, flat normals turned outwards by what the rasteriser saw, colours interpolated from the vertices, evenly spread and
-ordered so that every prefix is itself an even sample. The definition is this build's own (parity with zephyr's clouds is
+sample_model_cloud takes a vertex-coloured or texture-mapped render.Mesh and returns a ModelCloud: points on the surface that
+is visible from outside, flat normals turned outwards by what the rasteriser saw, colours interpolated from the vertices (or
+fetched from the texture at one mip level, SPEC 9.4.1), evenly spread and ordered so that every prefix is itself an even
+sample. The definition is this build's own (parity with zephyr's clouds is
 unpinned); every stage is bit-equal to the numpy restatement tests/ref_model_cloud.py.
 
 The cloud is in the MESH's frame and units. A BOP .ply is in the BOP frame: a YCB-V run that takes these clouds must not
@@ -79,15 +80,54 @@ def face_weights(mesh, votes):
     return weights, prefix, normals
 
 
-def face_candidates(mesh, votes, prefix, normals, K):
+def default_texture_lod(mesh, n_points):
+    """SPEC 9.4.1's host rule, f64: the smallest mip level whose texel on the surface is at least half the cloud's nominal
+    spacing sqrt(total area / n_points). The texel of level l measures 2^l x the median over the faces with positive UV
+    area of sqrt(area_3d / area_uv_texels), area_uv_texels the face's UV area times Ht Wt. At most the top level; 0 when
+    no face has a positive UV area."""
+    P = mesh.vertices.cpu().numpy().astype(np.float64)
+    uv = mesh.uvs.cpu().numpy().astype(np.float64)
+    Fc = mesh.faces.cpu().numpy().astype(np.int64)
+    Ht, Wt = mesh.texture_hw
+    g = np.cross(P[Fc[:, 1]] - P[Fc[:, 0]], P[Fc[:, 2]] - P[Fc[:, 0]])
+    a3 = 0.5 * np.sqrt((g * g).sum(1))
+    e1, e2 = uv[Fc[:, 1]] - uv[Fc[:, 0]], uv[Fc[:, 2]] - uv[Fc[:, 0]]
+    at = 0.5 * np.abs(e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]) * float(Wt) * float(Ht)
+    pos = np.isfinite(at) & (at > 0.0) & np.isfinite(a3)
+    if not pos.any():
+        return 0
+    texel = float(np.median(np.sqrt(a3[pos] / at[pos])))
+    spacing = float(np.sqrt(a3[np.isfinite(a3)].sum() / float(n_points)))
+    lod, top = 0, mesh.texture_levels - 1
+    while lod < top and texel < 0.5 * spacing:         # exact doublings: no logarithm
+        texel, lod = 2.0 * texel, lod + 1
+    return lod
+
+
+def face_candidates(mesh, votes, prefix, normals, K, use_texture=False, texture_lod=0):
     """SPEC 9.4: K stratified samples of the weighted faces -> dict of device tensors: points f32 [K,3], normals f32 [K,3],
-    colors f32 [K,3] in [0, 1], face int32 [K]."""
+    colors f32 [K,3] in [0, 1], face int32 [K]. The colours come from the vertex colours, or (a mesh with only a texture,
+    or use_texture=True) from the texture at mip level texture_lod (SPEC 9.4.1)."""
     _refuse_cpu(mesh.device)
     dev, F, K = mesh.device, mesh.n_faces, int(K)
     if not 1 <= K <= _lib.CLOUD_MAX_CANDIDATES:
         raise ValueError("K must lie in [1, %d], got %d" % (_lib.CLOUD_MAX_CANDIDATES, K))
-    if mesh.colors is None:
-        raise ValueError("face_candidates: the mesh has no vertex colours")
+    if mesh.colors is None and not _render._has_texture(mesh):
+        raise ValueError("face_candidates: the mesh has no vertex colours and no texture")
+    if _render._textured(mesh, use_texture):
+        lod = int(texture_lod)
+        if not 0 <= lod < mesh.texture_levels:
+            raise ValueError("texture_lod must lie in [0, %d], got %r" % (mesh.texture_levels - 1, texture_lod))
+        out = {"points": torch.empty(K, 3, dtype=torch.float32, device=dev), "normals": torch.empty(K, 3, dtype=torch.float32, device=dev),
+               "colors": torch.empty(K, 3, dtype=torch.float32, device=dev), "face": torch.empty(K, dtype=torch.int32, device=dev)}
+        with _lib.on_device(dev):
+            rc = _lib.fn("ossid_cloud_candidates_textured")(
+                mesh.vertices.data_ptr(), mesh.n_vertices, mesh.faces.data_ptr(), F, mesh.uvs.data_ptr(), mesh.mips.data_ptr(),
+                mesh.mips.numel(), mesh.texture_hw[0], mesh.texture_hw[1], lod, votes.contiguous().data_ptr(), prefix.data_ptr(),
+                normals.data_ptr(), K, out["points"].data_ptr(), out["normals"].data_ptr(), out["colors"].data_ptr(),
+                out["face"].data_ptr(), _lib.stream())
+        _lib.check(rc, "ossid_cloud_candidates_textured")
+        return out
     out = {"points": torch.empty(K, 3, dtype=torch.float32, device=dev), "normals": torch.empty(K, 3, dtype=torch.float32, device=dev),
            "colors": torch.empty(K, 3, dtype=torch.float32, device=dev), "face": torch.empty(K, dtype=torch.int32, device=dev)}
     with _lib.on_device(dev):
@@ -173,7 +213,7 @@ class ModelCloud:
                  model_normals=self.model_normals.cpu().numpy().astype(np.float64), diameter=np.float64(self.diameter))
 
 
-def _check_caps(mesh, n_points, oversample, level, view_size, views_per_call):
+def _check_caps(mesh, n_points, oversample, level, view_size, views_per_call, use_texture=False, texture_lod=None):
     """SPEC 9.1, before any launch -> (M, K, level, S, views per call)."""
     M, over, level, S, per = int(n_points), int(oversample), int(level), int(view_size), int(views_per_call)
     if not 1 <= M <= _lib.CLOUD_MAX_POINTS:
@@ -186,9 +226,11 @@ def _check_caps(mesh, n_points, oversample, level, view_size, views_per_call):
         raise ValueError("view_size must lie in [16, 1024], got %r" % (view_size,))
     if not 1 <= per <= _lib.RASTER_MAX_POSES:
         raise ValueError("views_per_call must lie in [1, %d], got %r" % (_lib.RASTER_MAX_POSES, views_per_call))
-    if not isinstance(mesh, _render.Mesh) or getattr(mesh, "colors", None) is None:
-        raise ValueError("sample_model_cloud: needs a render.Mesh with vertex colours (Mesh(..., colors=...), "
-                         "read_ply_mesh(path, with_colors=True))")
+    if not isinstance(mesh, _render.Mesh) or (getattr(mesh, "colors", None) is None and not _render._has_texture(mesh)):
+        raise ValueError("sample_model_cloud: needs a render.Mesh with vertex colours or a texture (Mesh(..., colors=...), "
+                         "Mesh(..., uvs=..., texture=...), load_mesh(path))")
+    if _render._textured(mesh, use_texture) and texture_lod is not None and not 0 <= int(texture_lod) < mesh.texture_levels:
+        raise ValueError("texture_lod must lie in [0, %d], got %r" % (mesh.texture_levels - 1, texture_lod))
     if mesh.n_faces < 1:
         raise ValueError("sample_model_cloud: the mesh has no faces")
     if not bool(torch.isfinite(mesh.vertices).all()):
@@ -196,18 +238,22 @@ def _check_caps(mesh, n_points, oversample, level, view_size, views_per_call):
     return M, over * M, level, S, per
 
 
-def sample_model_cloud(mesh, n_points=2048, oversample=16, level=2, view_size=512, views_per_call=32, return_info=False):
-    """SPEC section 9: a vertex-coloured render.Mesh -> ModelCloud of n_points points (with return_info also the dict
-    below). The mesh is rendered from the view_grid(level) viewpoints at view_size^2; a face takes part iff some sample
+def sample_model_cloud(mesh, n_points=2048, oversample=16, level=2, view_size=512, views_per_call=32, return_info=False,
+                       use_texture=False, texture_lod=None):
+    """SPEC section 9: a vertex-coloured or texture-mapped render.Mesh -> ModelCloud of n_points points (with return_info
+    also the dict below). A mesh with only a texture, or any textured one under use_texture=True, takes its colours from
+    the texture at mip level texture_lod (None: default_texture_lod's rule, SPEC 9.4.1; info["texture_lod"] tells). The mesh is rendered from the view_grid(level) viewpoints at view_size^2; a face takes part iff some sample
     shows it, its normal points to the side it was seen from, K = oversample * n_points candidates are spread over the
     faces by area, and farthest-point sampling keeps n_points of them, in pick order.
 
     info: "votes" int32 [F,2], "weights" / "prefix" int64 [F], "face_normals" f32 [F,3], "candidates" {points, normals,
     colors, face}, "selection" int32 [M], "radius" f32 [M] (device tensors); "rotations" f64 [n,3,3], "intrinsics" f32
     [n,4] (fx, fy, cx, cy of the virtual cameras), "distance", "z_near" (floats), "centres" f64 [n,3] (numpy)."""
-    M, K, level, S, per = _check_caps(mesh, n_points, oversample, level, view_size, views_per_call)
+    M, K, level, S, per = _check_caps(mesh, n_points, oversample, level, view_size, views_per_call, use_texture, texture_lod)
     _refuse_cpu(mesh.device)
     dev = mesh.device
+    textured = _render._textured(mesh, use_texture)
+    lod = None if not textured else (default_texture_lod(mesh, M) if texture_lod is None else int(texture_lod))
     P = mesh.vertices.cpu().numpy().astype(np.float64)
     r = float(np.sqrt((P * P).sum(1).max()))
     if not r > 0.0:
@@ -224,12 +270,12 @@ def sample_model_cloud(mesh, n_points=2048, oversample=16, level=2, view_size=51
     for a in range(0, len(R), per):
         b = min(len(R), a + per)
         _c, _d, face_id = _render.render_color(mesh, poses[a:b], None, (S, S), 0.5, z_near, intrinsics=cams[a:b],
-                                               return_face_id=True)
+                                               return_face_id=True, use_texture=use_texture)
         face_votes(mesh, face_id, centres[a:b], votes)
     weights, prefix, normals = face_weights(mesh, votes)
     if int(prefix[-1]) == 0:
         raise ValueError("sample_model_cloud: no usable face (none was seen, or every face that was seen has no area)")
-    cand = face_candidates(mesh, votes, prefix, normals, K)
+    cand = face_candidates(mesh, votes, prefix, normals, K, use_texture=use_texture, texture_lod=lod or 0)
     selection, radius = fps(cand["points"], M)
     idx = selection.long()
     # 9.6 has a cap of its own: a larger mesh still gets its cloud, without a diameter
@@ -239,5 +285,5 @@ def sample_model_cloud(mesh, n_points=2048, oversample=16, level=2, view_size=51
         return cloud
     info = {"votes": votes, "weights": weights, "prefix": prefix, "face_normals": normals, "candidates": cand,
             "selection": selection, "radius": radius, "rotations": R, "intrinsics": cams, "distance": distance,
-            "z_near": z_near, "centres": centres}
+            "z_near": z_near, "centres": centres, "texture_lod": lod}
     return cloud, info

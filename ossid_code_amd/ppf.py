@@ -50,10 +50,12 @@ def _call(name, *args):
     _lib.check(rc, name)
 
 
-def _ply_walk(path, lists_of=None):
-    """The header / body walk shared by read_ply and render.read_ply_mesh -> (vertex columns {name: f64 [V]} or None,
-    {property name: list of int arrays, one per row} of the list properties of element `lists_of`, or None when that
-    element is absent / not asked for). Elements and properties nobody asked for are skipped."""
+def _ply_walk(path, lists_of=None, comments=None):
+    """The header / body walk shared by read_ply, render.read_ply_mesh and render.load_mesh -> (vertex columns
+    {name: f64 [V]} or None, {property name: list of arrays, one per row -- int64, or f64 for a list of floats} of the list
+    properties of element `lists_of`, or None when that element is absent / not asked for). Elements and properties nobody
+    asked for are skipped. The text of every `comment` line of the header is appended to `comments` when a list is passed
+    (BOP names a model's texture in `comment TextureFile NAME`)."""
     types = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
              "double": "f8", "float64": "f8"}
@@ -67,6 +69,8 @@ def _ply_walk(path, lists_of=None):
                 raise ValueError("%s: PLY header without end_header" % path)
             tok = line.decode("ascii", "replace").split()
             if not tok or tok[0] in ("comment", "obj_info"):
+                if tok and tok[0] == "comment" and comments is not None:
+                    comments.append(line.decode("ascii", "replace").strip()[len("comment"):].strip())
                 continue
             if tok[0] == "format":
                 fmt = tok[1]
@@ -105,7 +109,10 @@ def _ply_walk(path, lists_of=None):
                     for pn, t in props:
                         if isinstance(t, tuple):
                             cnt = int(r[k])
-                            lists[pn].append(np.array([int(float(q)) for q in r[k + 1:k + 1 + cnt]], dtype=np.int64))
+                            if t[2] in ("f4", "f8"):
+                                lists[pn].append(np.array([float(q) for q in r[k + 1:k + 1 + cnt]], dtype=np.float64))
+                            else:
+                                lists[pn].append(np.array([int(float(q)) for q in r[k + 1:k + 1 + cnt]], dtype=np.int64))
                             k += 1 + cnt
                         else:
                             k += 1
@@ -130,7 +137,8 @@ def _ply_walk(path, lists_of=None):
                             cnt = np.frombuffer(body, dtype="<" + t[1], count=1, offset=pos)[0]
                             pos += np.dtype(t[1]).itemsize
                             if keep:
-                                lists[pn].append(np.frombuffer(body, dtype="<" + t[2], count=int(cnt), offset=pos).astype(np.int64))
+                                lists[pn].append(np.frombuffer(body, dtype="<" + t[2], count=int(cnt), offset=pos)
+                                                 .astype(np.float64 if t[2] in ("f4", "f8") else np.int64))
                             pos += int(cnt) * np.dtype(t[2]).itemsize
                         else:
                             pos += np.dtype(t).itemsize

@@ -9,10 +9,14 @@ OpenGL rasterisation that scripts/online_learning.py reaches through zephyr.util
 Renderer is the drop-in (host arrays out); render_depth is the device form that OnlineStream uses: a batch of poses in,
 a device tensor out, three launches on the current stream and no host copy or synchronisation.
 
-render_color is the same rasteriser with vertex colours (SPEC 7.11-7.12), and render_templates makes the detector's
-templates out of it (SPEC 7.13-7.14): what the reference renders offline with Blender, cuts out in
-datasets/render_dataset.py:251-331 and loads in datasets/template_dataset.py:60-117. view_grid is the set of viewpoints.
+render_color is the same rasteriser with vertex colours (SPEC 7.11-7.12) or, for a mesh that carries UV coordinates and a
+texture, with a mip-mapped bilinear texture fetch (SPEC 7.15-7.17), and render_templates makes the detector's templates out
+of it (SPEC 7.13-7.14): what the reference renders offline with Blender, cuts out in datasets/render_dataset.py:251-331 and
+loads in datasets/template_dataset.py:60-117. view_grid is the set of viewpoints. load_mesh reads a BOP .ply with whatever
+it carries: vertex colours, a texture, or both.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -62,6 +66,74 @@ def read_ply_mesh(path, with_colors=False):
     raise ValueError("%s: the vertex element has no red green blue (or diffuse_red ...) properties" % path)
 
 
+def load_mesh(path, scale=1.0, device=None):
+    """A BOP .ply -> Mesh with whatever it carries (read_ply_textured): vertex colours, a texture, or both. Every refusal
+    is a ValueError naming the file, before any device work."""
+    m = read_ply_textured(path)
+    return Mesh(m["vertices"], m["faces"], scale=scale, device=device, colors=m["colors"], uvs=m["uvs"], texture=m["texture"])
+
+
+def read_ply_textured(path):
+    """A BOP .ply -> {"vertices" f64 [V,3], "faces" int32 [F,3], "colors" u8 [V,3] or None, "uvs" f64 [V,2] or None,
+    "texture" u8 [Ht,Wt,3] or None} on the host: vertex colours (read_ply_mesh's properties), a texture, or both.
+    A texture is the image named by the header's `comment TextureFile NAME`, resolved beside the .ply and read as RGB, with
+    per-vertex coordinates texture_u texture_v (or s t), or else a face-element list `texcoord` of six floats (u0 v0 u1 v1
+    u2 v2, triangles only): vertices are then split, one per distinct (index, u, v) in first-seen order, the faces
+    remapped, and the vertex cap checked after the split. Every refusal is a ValueError naming the file."""
+    V, F = read_ply_mesh(path)
+    comments = []
+    vert, lists = _ply_walk(path, lists_of="face", comments=comments)
+    C = None
+    if all(k in vert for k in ("red", "green", "blue")) or all(k in vert for k in ("diffuse_red", "diffuse_green", "diffuse_blue")):
+        C = read_ply_mesh(path, with_colors=True)[2]
+    name = None
+    for c in comments:
+        tok = c.split(None, 1)
+        if len(tok) == 2 and tok[0] == "TextureFile":
+            name = tok[1].strip()
+    U = None
+    for ku, kv in (("texture_u", "texture_v"), ("s", "t")):
+        if U is None and ku in vert and kv in vert:
+            U = np.stack([vert[ku], vert[kv]], 1)
+    rows = None if U is not None else lists.get("texcoord")
+    if name is None or (U is None and rows is None):
+        if C is None:
+            raise ValueError("%s: the mesh has neither vertex colours nor a texture (comment TextureFile NAME with "
+                             "texture_u texture_v, s t, or a face texcoord list)" % path)
+        return {"vertices": V, "faces": F, "colors": C, "uvs": None, "texture": None}
+    if rows is not None:
+        idx = lists.get("vertex_indices", lists.get("vertex_index"))
+        first, order, Fn = {}, [], np.empty((len(idx), 3), dtype=np.int32)
+        for k, (r, tc) in enumerate(zip(idx, rows)):
+            if len(r) != 3 or len(tc) != 6:
+                raise ValueError("%s: face %d has %d vertices and a texcoord list of %d: a textured face is a triangle "
+                                 "with six floats" % (path, k, len(r), len(tc)))
+            for j in range(3):
+                key = (int(r[j]), float(tc[2 * j]), float(tc[2 * j + 1]))
+                if key not in first:
+                    first[key] = len(order)
+                    order.append(key)
+                Fn[k, j] = first[key]
+        if len(order) > _lib.RASTER_MAX_VERTICES:
+            raise ValueError("%s: %d vertices after the split by texture coordinate, at most %d"
+                             % (path, len(order), _lib.RASTER_MAX_VERTICES))
+        src = np.array([k[0] for k in order], dtype=np.int64)
+        U = np.array([k[1:] for k in order], dtype=np.float64).reshape(-1, 2)
+        V, F, C = V[src], Fn, (None if C is None else C[src])
+    if not np.isfinite(U).all():
+        raise ValueError("%s: a texture coordinate is not finite" % path)
+    image_path = os.path.join(os.path.dirname(os.path.abspath(path)), name)
+    if not os.path.isfile(image_path):
+        raise ValueError("%s: its texture %s is missing (looked for %s)" % (path, name, image_path))
+    from PIL import Image
+    with Image.open(image_path) as im:
+        if max(im.size) > _lib.TEXTURE_MAX_SIDE:
+            raise ValueError("%s: its texture %s is %d x %d, at most %d a side"
+                             % (path, name, im.size[1], im.size[0], _lib.TEXTURE_MAX_SIDE))
+        I = np.array(im.convert("RGB"), dtype=np.uint8)
+    return {"vertices": V, "faces": F, "colors": C, "uvs": U, "texture": I}
+
+
 def _check_mesh(vertices, faces):
     V = np.asarray(vertices, dtype=np.float64)
     if V.ndim != 2 or V.shape[1] != 3 or len(V) < 1:
@@ -94,16 +166,44 @@ def _check_colors(colors, n_vertices):
     return np.rint(255.0 * C).astype(np.uint8)
 
 
+def _check_uvs(uvs, n_vertices):
+    """f32 [V,2] = (u, v), v upwards; finite (values outside [0, 1] are legal: addressing clamps to the edge)."""
+    U = np.asarray(uvs)
+    if U.shape != (n_vertices, 2) or not (np.issubdtype(U.dtype, np.floating) or np.issubdtype(U.dtype, np.integer)):
+        raise ValueError("uvs must be numbers [V,2] = [%d,2], got %s %s" % (n_vertices, U.dtype, U.shape))
+    U = np.ascontiguousarray(U, dtype=np.float32)
+    if not np.isfinite(U).all():
+        raise ValueError("uvs must be finite")
+    return U
+
+
+def _check_texture(texture, what="texture"):
+    """u8 [Ht,Wt,3] RGB, row 0 the top row of the image, sides in [1, TEXTURE_MAX_SIDE]."""
+    I = np.asarray(texture)
+    if I.ndim != 3 or I.shape[2] != 3 or I.dtype != np.uint8:
+        raise ValueError("%s must be uint8 [Ht,Wt,3], got %s %s" % (what, I.dtype, I.shape))
+    if not (1 <= I.shape[0] <= _lib.TEXTURE_MAX_SIDE and 1 <= I.shape[1] <= _lib.TEXTURE_MAX_SIDE):
+        raise ValueError("%s: %d x %d is outside [1, %d] a side" % (what, I.shape[0], I.shape[1], _lib.TEXTURE_MAX_SIDE))
+    return np.ascontiguousarray(I)
+
+
 class Mesh:
     """A triangle mesh resident on the device: vertices f32(v * scale) (the product in float64), faces int32, optional
-    vertex colours u8 [V,3], and the rasteriser's workspaces, grown on demand. scale = 0.001 is the Renderer's mm2m."""
+    vertex colours u8 [V,3], optional UV coordinates f32 [V,2] with a texture u8 [Ht,Wt,3] (both or neither; the mip chain
+    of SPEC 7.15 is built once, here, and kept on the device as `mips`), and the rasteriser's workspaces, grown on demand.
+    scale = 0.001 is the Renderer's mm2m."""
 
-    colors = None
+    colors = uvs = mips = None
+    texture_hw = None
     _ws = _ws_color = None
 
-    def __init__(self, vertices, faces, scale=1.0, device=None, colors=None):
+    def __init__(self, vertices, faces, scale=1.0, device=None, colors=None, uvs=None, texture=None):
         V, F = _check_mesh(vertices, faces)
         C = None if colors is None else _check_colors(colors, len(V))
+        if (uvs is None) != (texture is None):
+            raise ValueError("a textured mesh needs both uvs and texture")
+        U = None if uvs is None else _check_uvs(uvs, len(V))
+        I = None if texture is None else _check_texture(texture)
         self.scale = float(scale)
         self.n_vertices, self.n_faces = len(V), len(F)
         self.device = torch.device(device) if device is not None else _dev()
@@ -111,6 +211,24 @@ class Mesh:
         self.faces = torch.from_numpy(F).to(self.device).contiguous()
         self.colors = None if C is None else torch.from_numpy(C).to(self.device).contiguous()
         self._ws = self._ws_color = None
+        self.uvs = self.mips = self.texture_hw = None
+        if I is not None:
+            if self.device.type != "cuda":
+                raise RuntimeError("a textured Mesh builds its mip chain on the GPU (got device %s)" % (self.device,))
+            self.uvs =torch.from_numpy(U).to(self.device).contiguous()
+            self.texture_hw = (int(I.shape[0]), int(I.shape[1]))
+            image = torch.from_numpy(I).to(self.device).contiguous()
+            need = int(_lib.fn("ossid_texture_mip_bytes")(*self.texture_hw))
+            self.mips = torch.empty(need, dtype=torch.uint8, device=self.device)
+            with _lib.on_device(self.device):
+                rc = _lib.fn("ossid_texture_mips")(image.data_ptr(), self.texture_hw[0], self.texture_hw[1],
+                                                   self.mips.data_ptr(), need, _lib.stream())
+            _lib.check(rc, "ossid_texture_mips")
+
+    @property
+    def texture_levels(self):
+        """Levels of the mip chain (the top level is texture_levels - 1); 0 without a texture."""
+        return 0 if self.texture_hw is None else int(_lib.fn("ossid_texture_levels")(*self.texture_hw))
 
     def workspace(self, n_poses):
         need = int(_lib.fn("ossid_raster_workspace_bytes")(self.n_vertices, self.n_faces, int(n_poses)))
@@ -180,16 +298,34 @@ def render_depth(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, return_s
     return (depth, stats) if return_stats else depth
 
 
+def _has_texture(mesh):
+    return getattr(mesh, "mips", None) is not None and getattr(mesh, "uvs", None) is not None
+
+
+def _textured(mesh, use_texture):
+    """Which resolve a colour render of `mesh` takes: vertex colours when it has them, unless use_texture asks for the
+    texture; the texture when that is all it has."""
+    if use_texture and not _has_texture(mesh):
+        raise ValueError("use_texture=True: the mesh has no texture (Mesh(..., uvs=..., texture=...), load_mesh(path))")
+    return _has_texture(mesh) and (use_texture or getattr(mesh, "colors", None) is None)
+
+
 def render_color(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, intrinsics=None, return_face_id=False,
-                 return_stats=False):
-    """Colour and depth of a vertex-coloured `mesh` at every pose (SPEC 7.11-7.12): poses as render_depth ->
-    device tensors (color u8 [N,H,W,3], depth f32 [N,H,W][, face_id int32 [N,H,W]][, stats int32 [N,4]]); a single [4,4]
-    pose drops the leading axis. Colours are interpolated perspective-correctly and unlit; face_id is the index in the
-    mesh's faces of the triangle seen, -1 where nothing is drawn. `intrinsics` [N,4] (fx, fy, cx, cy per pose) replaces
-    cam_K, which may then be None. The depth equals render_depth's bit for bit. Nothing is copied to the host."""
-    if getattr(mesh, "colors", None) is None:
-        raise ValueError("render_color: the mesh has no vertex colours (Mesh(..., colors=...), "
-                         "read_ply_mesh(path, with_colors=True))")
+                 return_stats=False, use_texture=False, return_lod=False):
+    """Colour and depth of a vertex-coloured or texture-mapped `mesh` at every pose (SPEC 7.11-7.12, 7.15-7.17): poses as
+    render_depth -> device tensors (color u8 [N,H,W,3], depth f32 [N,H,W][, face_id int32 [N,H,W]][, stats int32 [N,4]]
+    [, lod int32 [N,H,W]]); a single [4,4] pose drops the leading axis. Colours are interpolated perspective-correctly and
+    unlit; face_id is the index in the mesh's faces of the triangle seen, -1 where nothing is drawn. `intrinsics` [N,4]
+    (fx, fy, cx, cy per pose) replaces cam_K, which may then be None. The depth equals render_depth's bit for bit. Nothing
+    is copied to the host. A mesh with vertex colours is rendered from them; one with only a texture, or any textured one
+    under use_texture=True, by a mip-mapped bilinear fetch at the perspective-correct (u, v). return_lod (textured
+    renders only) adds the mip level each pixel was fetched at, -1 where nothing is drawn."""
+    if getattr(mesh, "colors", None) is None and not _has_texture(mesh):
+        raise ValueError("render_color: the mesh has no vertex colours and no texture (Mesh(..., colors=...) or "
+                         "Mesh(..., uvs=..., texture=...), load_mesh(path))")
+    textured = _textured(mesh, use_texture)
+    if return_lod and not textured:
+        raise ValueError("return_lod: the render is not textured (the mesh's vertex colours are used unless use_texture=True)")
     T, single, N, H, W = _check_call("render_color", poses, hw, pixel_offset, z_near)
     dev = mesh.device
     if intrinsics is None:
@@ -216,15 +352,26 @@ def render_color(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, intrinsi
     depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
     face = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_face_id else None
     stats = torch.empty(N, 4, dtype=torch.int32, device=dev) if return_stats else None
+    lod = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_lod else None
     with _lib.on_device(dev):
-        rc = _lib.fn("ossid_raster_color")(mesh.vertices.data_ptr(), mesh.n_vertices,
-                                           mesh.faces.data_ptr() if mesh.n_faces else None, mesh.n_faces,
-                                           mesh.colors.data_ptr(), T.data_ptr(), N, cams.data_ptr(), H, W, float(pixel_offset),
-                                           float(z_near), ws.data_ptr(), ws.numel(), color.data_ptr(), depth.data_ptr(),
-                                           None if face is None else face.data_ptr(),
-                                           None if stats is None else stats.data_ptr(), _lib.stream())
-    _lib.check(rc, "ossid_raster_color")
-    out = [color, depth] + ([face] if return_face_id else []) + ([stats] if return_stats else [])
+        if textured:
+            what = "ossid_raster_textured"
+            rc = _lib.fn(what)(mesh.vertices.data_ptr(), mesh.n_vertices, mesh.faces.data_ptr() if mesh.n_faces else None,
+                               mesh.n_faces, mesh.uvs.data_ptr(), mesh.mips.data_ptr(), mesh.mips.numel(), mesh.texture_hw[0],
+                               mesh.texture_hw[1], T.data_ptr(), N, cams.data_ptr(), H, W, float(pixel_offset), float(z_near),
+                               ws.data_ptr(), ws.numel(), color.data_ptr(), depth.data_ptr(),
+                               None if face is None else face.data_ptr(), None if lod is None else lod.data_ptr(),
+                               None if stats is None else stats.data_ptr(), _lib.stream())
+        else:
+            what = "ossid_raster_color"
+            rc = _lib.fn(what)(mesh.vertices.data_ptr(), mesh.n_vertices, mesh.faces.data_ptr() if mesh.n_faces else None,
+                               mesh.n_faces, mesh.colors.data_ptr(), T.data_ptr(), N, cams.data_ptr(), H, W,
+                               float(pixel_offset), float(z_near), ws.data_ptr(), ws.numel(), color.data_ptr(),
+                               depth.data_ptr(), None if face is None else face.data_ptr(),
+                               None if stats is None else stats.data_ptr(), _lib.stream())
+    _lib.check(rc, what)
+    out = [color, depth] + ([face] if return_face_id else []) + ([stats] if return_stats else []) + \
+          ([lod] if return_lod else [])
     return tuple(t[0] for t in out) if single else tuple(out)
 
 
@@ -307,16 +454,17 @@ def _frame_views(vertices, rotations, distance, cam_K, S, T, pad, z_near):
 
 
 def render_templates(mesh, rotations=None, size=124, supersample=4, distance=0.8, cam_K=None, pad=1.1, z_near=0.05,
-                     views_per_call=32):
-    """The detector's templates of a vertex-coloured mesh (SPEC 7.13-7.14) -> (img f32 [n,3,T,T] in [0, 1],
+                     views_per_call=32, use_texture=False):
+    """The detector's templates of a vertex-coloured or texture-mapped mesh (render_color's choice; SPEC 7.13-7.14) -> (img f32 [n,3,T,T] in [0, 1],
     mask f32 [n,1,T,T], info) on the mesh's device, T = size. View v shows the mesh under rotations[v] (default
     view_grid()) at `distance` on the optical axis, through a virtual camera derived from cam_K that frames the object
     with the margin `pad`, rendered at supersample x T and reduced by the exact box filter. info: "rotations" f64
     [n,3,3], "quats" f64 [n,4] (xyzw), "intrinsics" f32 [n,4] of the virtual cameras, "template_z" f64 [n], the value
     DtoidNet.forwardTestTime's z filter takes. views_per_call bounds the memory: 8 bytes x (supersample T)^2 per view."""
-    if getattr(mesh, "colors", None) is None:
-        raise ValueError("render_templates: the mesh has no vertex colours (Mesh(..., colors=...), "
-                         "read_ply_mesh(path, with_colors=True))")
+    if getattr(mesh, "colors", None) is None and not _has_texture(mesh):
+        raise ValueError("render_templates: the mesh has no vertex colours and no texture (Mesh(..., colors=...) or "
+                         "Mesh(..., uvs=..., texture=...), load_mesh(path))")
+    _textured(mesh, use_texture)
     if cam_K is None:
         raise ValueError("render_templates: cam_K is required (the camera the templates will be matched under)")
     K = np.asarray(cam_K, dtype=np.float64)
@@ -348,7 +496,7 @@ def render_templates(mesh, rotations=None, size=124, supersample=4, distance=0.8
     mask = torch.empty(n, 1, T, T, dtype=torch.float32, device=dev)
     for a in range(0, n, per):
         b = min(n, a + per)
-        color, depth = render_color(mesh, poses[a:b], None, (S, S), 0.5, z_near, intrinsics=cams[a:b])
+        color, depth = render_color(mesh, poses[a:b], None, (S, S), 0.5, z_near, intrinsics=cams[a:b], use_texture=use_texture)
         with _lib.on_device(dev):
             rc = _lib.fn("ossid_template_reduce")(color.data_ptr(), depth.data_ptr(), b - a, T, s, img[a:b].data_ptr(),
                                                   mask[a:b].data_ptr(), _lib.stream())

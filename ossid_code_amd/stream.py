@@ -90,7 +90,7 @@ class OnlineStream:
     meshes (None = off): dict obj_id -> render.Mesh in metres; the pseudo-label step then renders the mesh of
     frame["obj_id"] at the chosen pose (render.render_depth, pixel_offset = mesh_pixel_offset: 0 is this package's pixel
     convention, under which the render lines up with the observed depth) instead of splatting the model points. A frame
-    WITHOUT "model_points" whose object's mesh has vertex colours is scored with the mesh's own cloud
+    WITHOUT "model_points" whose object's mesh has vertex colours or a texture is scored with the mesh's own cloud
     (model_cloud.sample_model_cloud(mesh), SPEC.md section 9), built at the object's first frame and kept;
     a frame that carries its cloud is processed exactly as without meshes."""
 
@@ -123,9 +123,9 @@ class OnlineStream:
             return frame
         obj = int(frame["obj_id"])
         mesh = None if self.meshes is None else self.meshes.get(obj)
-        if mesh is None or getattr(mesh, "colors", None) is None:
+        if mesh is None or (getattr(mesh, "colors", None) is None and getattr(mesh, "mips", None) is None):
             raise KeyError("frame of object %d has no model_points, and OnlineStream(meshes=...) holds no vertex-coloured "
-                           "mesh of it to sample them from" % obj)
+                           "or textured mesh of it to sample them from" % obj)
         if obj not in self._clouds:
             cloud = model_cloud.sample_model_cloud(mesh)
             # host arrays, as the frames of a stream carry them (pose_errors and the ICP take numpy)

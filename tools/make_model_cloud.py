@@ -3,7 +3,7 @@
     python3 tools/make_model_cloud.py MODELS_DIR OUT_DIR [--n_points 2048] [--oversample 16] [--level 2] [--view_size 512]
                                       [--no-mm2m]
 
-Every MODELS_DIR/obj_XXXXXX.ply (vertex-coloured; millimetres, as BOP stores them, scaled to metres unless --no-mm2m)
+Every MODELS_DIR/obj_XXXXXX.ply (vertex-coloured, or texture-mapped with its image beside it; millimetres, as BOP stores them, scaled to metres unless --no-mm2m)
 becomes OUT_DIR/model_cloud_XX.npz with model_points / model_colors / model_normals as float64 [n_points,3] and `diameter`.
 model_cloud.sample_model_cloud (SPEC.md section 9) does the work. The clouds are in the BOP frame of the .ply: a YCB-V
 run that uses them must not also apply modelPointsShiftYcbv2Bop. Parity with zephyr's own clouds is unpinned.
@@ -40,8 +40,7 @@ def main():
     os.makedirs(a.out_dir, exist_ok=True)
     for p in paths:
         obj = int(os.path.basename(p)[4:10])
-        V, F, C = render.read_ply_mesh(p, with_colors=True)
-        mesh = render.Mesh(V, F, scale=1.0 if a.no_mm2m else 0.001, colors=C)
+        mesh = render.load_mesh(p, scale=1.0 if a.no_mm2m else 0.001)
         cloud = model_cloud.sample_model_cloud(mesh, n_points=a.n_points, oversample=a.oversample, level=a.level,
                                                view_size=a.view_size)
         out = os.path.join(a.out_dir, "model_cloud_{:02d}.npz".format(obj))

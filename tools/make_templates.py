@@ -1,10 +1,11 @@
-"""Templates of an object from its vertex-coloured PLY model -> an .npz the detector's TemplateBank can be filled from:
+"""Templates of an object from its vertex-coloured or texture-mapped PLY model -> an .npz the detector's TemplateBank can be filled from:
 
     python3 tools/make_templates.py obj_000001.ply obj_000001_templates.npz [--mm2m] [--level 2] [--inplane 1]
                                     [--size 124] [--supersample 4] [--distance 0.8] [--fx 572.4 --fy 573.6 --cx 325.3 --cy 242.0]
 
 The file holds numeric arrays only: img f32 [n,3,T,T], mask f32 [n,1,T,T], rotations f64 [n,3,3], quats f64 [n,4] (xyzw),
-template_z f64 [n], intrinsics f32 [n,4]. render.render_templates (SPEC.md 7.13-7.14) does the work;
+template_z f64 [n], intrinsics f32 [n,4]. render.load_mesh reads the model (vertex colours, or the texture its header names,
+looked for beside the .ply; a model with both is rendered from its vertex colours); render.render_templates (SPEC.md 7.13-7.14) does the work;
 `TemplateBank.add(obj_id, z["img"], z["mask"], z["quats"])` takes the result, and `TemplateBank.add_mesh` skips the file.
 """
 import argparse
@@ -36,8 +37,7 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("make_templates.py renders on the GPU: there is no CPU path")
-    V, F, C = render.read_ply_mesh(a.ply, with_colors=True)
-    mesh = render.Mesh(V, F, scale=0.001 if a.mm2m else 1.0, colors=C)
+    mesh = render.load_mesh(a.ply, scale=0.001 if a.mm2m else 1.0)
     K = np.array([[a.fx, 0.0, a.cx], [0.0, a.fy, a.cy], [0.0, 0.0, 1.0]])
     img, mask, info = render.render_templates(mesh, rotations=render.view_grid(a.level, a.inplane), size=a.size,
                                               supersample=a.supersample, distance=a.distance, cam_K=K,
