@@ -835,7 +835,9 @@ int ossid_icp_refine(const float* depth, int H, int W, const int32_t* uv, const 
  * z > 0), or a depth image f32 [H][W] + mask u8 [H][W] (pixel i valid iff mask && depth > 0, back-projected as SPEC 5.2,
  * input index = row-major pixel index). Voxel edge h = rel * (diam > 0 ? diam : this cloud's own diameter D). Outputs:
  * idx_out int32 [max_out] (input indices, ascending), pts_out f32 [max_out][3], count[0] = the number of voxels, which
- * may exceed max_out (then only max_out rows are written), stats f32 [8] = lo[3], hi[3], D, h. */
+ * may exceed max_out (then only max_out rows are written; rows past min(count, max_out) are never written), stats f32 [8] =
+ * lo[3], hi[3], D, h. Without a valid point lo = hi = 0, D = 0 and count = 0. With h = 0 (diam <= 0 and a cloud whose box is
+ * a single point, so D = 0) nothing is kept: count = 0, stats still holds the box. */
 #define OSSID_PPF_MAX_MODEL_POINTS 4096
 #define OSSID_PPF_MAX_SCENE_SAMPLES 8192
 size_t ossid_ppf_sample_workspace_bytes(int n_in);

@@ -5,6 +5,7 @@
 //                voxels keeping the lowest input index (atomicCAS / atomicMin: the result does not depend on the order the
 //                atomics run in), per-block representative counts, an ordered compaction (each block sums the counts of
 //                the blocks before it: our own scan). Input is an f32 cloud or a depth image + mask (row-major pixels).
+//                h = 0 (no diameter given and all valid points in one place, D = 0) keeps nothing: count = 0.
 //   model table  one thread per ordered model pair: key and rotation bin, counting sort into a dense [key][chunk] offset
 //                table (global atomics count, one workgroup scans, global atomics place) of u32 entries m_r * 32 + bin_m.
 //   normals      per sampled scene point: brute-force neighbours in index order, f64 covariance, Jacobi in registers.

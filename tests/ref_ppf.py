@@ -149,6 +149,34 @@ class Model:
         self.keys, self.entries = keys[order], ents[order]
         self.nkeys = self.tab["nd"] * NA ** 3
 
+    @classmethod
+    def from_sampled(cls, P, N, h, D):
+        """The model of already-sampled points P f32 [Ms,3], unit normals N f32 [Ms,3] and free h, D (what the C ABI
+        takes). The keyed pairs are found first by 6.4's own distance test, then `feature` runs on those pairs alone, in
+        (r, i) order: the same entries in the same order as __init__'s loop over all pairs."""
+        self = cls.__new__(cls)
+        self.P, self.N = np.ascontiguousarray(P, dtype=F32).reshape(-1, 3), np.ascontiguousarray(N, dtype=F32).reshape(-1, 3)
+        self.h, self.D = F32(h), F32(D)
+        Ms = len(self.P)
+        self.idx, self.lo = np.arange(Ms), None
+        self.e1, self.e2 = basis(self.N)
+        self.tab = tables(self.h, self.D)
+        rr, ii = [], []
+        for r0 in range(0, Ms, 256):
+            d = (self.P[None, :, :] - self.P[r0:r0 + 256, None, :]).astype(F32)
+            s2 = _dot(d, d)
+            r, i = np.nonzero((s2 > 0) & (s2 <= self.tab["d2max"]))
+            keep = (r + r0) != i
+            rr.append(r[keep] + r0)
+            ii.append(i[keep])
+        r, i = np.concatenate(rr), np.concatenate(ii)
+        okp, key, bn = feature(self.P[r], self.N[r], self.e1[r], self.e2[r], self.P[i], self.N[i], self.tab)
+        assert okp.all()
+        order = np.argsort(key, kind="stable")
+        self.keys, self.entries = key[order], (r * 32 + bn).astype(np.uint32)[order]
+        self.nkeys = self.tab["nd"] * NA ** 3
+        return self
+
     def key_entries(self, key):
         a, b = np.searchsorted(self.keys, [key, key + 1])
         return np.sort(self.entries[a:b])
@@ -163,7 +191,12 @@ def smallest_eigvec(C):
 
 def scene_normals(S, h, rel=NORMAL_RADIUS_REL):
     """-> (normals f32 [n,3], ok bool [n]) of the sampled scene S f32 [n,3]."""
-    r = float(F32(F32(rel) * F32(h)))
+    return scene_normals_radius(S, F32(F32(rel) * F32(h)))
+
+
+def scene_normals_radius(S, radius):
+    """scene_normals with the f32 radius r given (what the C ABI takes)."""
+    r = float(F32(radius))
     r2 = F32(r * r)
     n = len(S)
     out, ok = np.zeros((n, 3), dtype=F32), np.zeros(n, dtype=bool)
@@ -205,29 +238,37 @@ def pose(model, m_r, alpha, s, ns):
     return T
 
 
+def vote_acc(model, S, Sn, Sok, r, basis_s=None):
+    """The accumulator acc[m_r * 30 + alpha] of reference r (int64 [Ms * 30]), or None when r is dropped or no pair of
+    its has a key with entries. Also returns the range lengths of its keyed partners (for the cases' premises)."""
+    e1, e2 = basis(Sn) if basis_s is None else basis_s
+    if not Sok[r]:
+        return None, np.zeros(0, dtype=np.int64)
+    okp, key, bs = feature(S[r], Sn[r], e1[r], e2[r], S, Sn, model.tab)
+    okp &= np.asarray(Sok, dtype=bool)
+    okp[r] = False
+    key, bs = key[okp], bs[okp]
+    a = np.searchsorted(model.keys, key)
+    b = np.searchsorted(model.keys, key + 1)
+    ln = b - a
+    if ln.sum() == 0:
+        return None, ln
+    rep = np.repeat(np.arange(len(key)), ln)
+    pos = np.arange(ln.sum()) - np.repeat(np.cumsum(ln) - ln, ln) + np.repeat(a, ln)
+    e = model.entries[pos].astype(np.int64)
+    alpha = ((e & 31) - bs[rep]) % NALPHA
+    return np.bincount((e >> 5) * NALPHA + alpha, minlength=len(model.idx) * NALPHA), ln
+
+
 def vote(model, S, Sn, Sok, ref_step):
     """-> list over reference indices 0, k, 2k, ... of (ref, m_r, alpha, count) (count 0: no candidate)."""
-    e1, e2 = basis(Sn)
+    bs = basis(Sn)
     out = []
     for r in range(0, len(S), ref_step):
-        if not Sok[r]:
+        acc, _ln = vote_acc(model, S, Sn, Sok, r, bs)
+        if acc is None:
             out.append((r, 0, 0, 0))
             continue
-        okp, key, bs = feature(S[r], Sn[r], e1[r], e2[r], S, Sn, model.tab)
-        okp &= Sok
-        okp[r] = False
-        key, bs = key[okp], bs[okp]
-        a = np.searchsorted(model.keys, key)
-        b = np.searchsorted(model.keys, key + 1)
-        ln = b - a
-        if ln.sum() == 0:
-            out.append((r, 0, 0, 0))
-            continue
-        rep = np.repeat(np.arange(len(key)), ln)
-        pos = np.arange(ln.sum()) - np.repeat(np.cumsum(ln) - ln, ln) + np.repeat(a, ln)
-        e = model.entries[pos].astype(np.int64)
-        alpha = ((e & 31) - bs[rep]) % NALPHA
-        acc = np.bincount((e >> 5) * NALPHA + alpha, minlength=len(model.idx) * NALPHA)
         best = int(acc.argmax())
         out.append((r, best // NALPHA, best % NALPHA, int(acc[best])))
     return out
@@ -259,6 +300,83 @@ def cluster(model, cands, S, Sn, dist_rel=0.1, num_result=100):
     order = sorted(range(len(seeds)), key=lambda j: (-sums[j], j))[:num_result]
     poses = np.array([seeds[j] for j in order]).reshape(-1, 4, 4)
     return poses, np.array([sums[j] / len(model.idx) for j in order], dtype=np.float64)
+
+
+def cluster_arrays(votes, poses, thr, Ms, num_result=100):
+    """SPEC 6.6 over given candidates: votes int [nref] (0: no candidate), poses f64 [nref,4,4], thr = f32(dist_rel) * D as
+    f64 -> (poses f64 [k,4,4], scores f64 [k], ncand, nseed). The plain greedy loop in f64, each candidate tested against
+    the seeds so far (one numpy expression over the seeds, the sums in 6.6's written order)."""
+    votes = np.asarray(votes, dtype=np.int64)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    cs = sorted((j for j in range(len(votes)) if votes[j] > 0), key=lambda j: (-votes[j], j))
+    thr2 = float(thr) * float(thr)
+    seedT = np.zeros((max(len(cs), 1), 4, 4))
+    seeds, sums = [], []
+    for j in cs:
+        T, ns = poses[j], len(seeds)
+        hit = -1
+        if ns:
+            Ts = seedT[:ns]
+            dt = T[None, :3, 3] - Ts[:, :3, 3]
+            near = ((dt[:, 0] * dt[:, 0] + dt[:, 1] * dt[:, 1]) + dt[:, 2] * dt[:, 2]) <= thr2
+            tr = np.zeros(ns)
+            for a in range(3):
+                for b in range(3):
+                    tr = tr + T[a, b] * Ts[:, a, b]
+            ok = near & ((tr - 1.0) / 2.0 >= CLUSTER_COS)
+            if ok.any():
+                hit = int(np.argmax(ok))
+        if hit >= 0:
+            sums[hit] += int(votes[j])
+        else:
+            seedT[ns] = T
+            seeds.append(j)
+            sums.append(int(votes[j]))
+    order = sorted(range(len(seeds)), key=lambda s_: (-sums[s_], s_))[:num_result]
+    out = np.array([poses[seeds[s_]] for s_ in order]).reshape(-1, 4, 4)
+    return out, np.array([sums[s_] / Ms for s_ in order], dtype=np.float64), len(cs), len(seeds)
+
+
+# ---- 6.4 a second time: geometry in float64, no sign tests --------------------------------------------------------------
+def basis64(n):
+    """Duff et al.'s basis of the f32 normals, evaluated in float64."""
+    n = np.asarray(n, dtype=np.float64)
+    nx, ny, nz = n[..., 0], n[..., 1], n[..., 2]
+    sign = np.copysign(1.0, nz)
+    a = -1.0 / (sign + nz)
+    b = nx * ny * a
+    return (np.stack([1.0 + sign * nx * nx * a, sign * b, -sign * nx], -1), np.stack([b, sign + ny * ny * a, -ny], -1))
+
+
+def feature_geometric(pr, nr, pi, ni, h, D, ang_margin=1e-5, dist_margin=1e-6):
+    """SPEC 6.4 stated by its geometry, in float64 from the f32 inputs: the three angles by arccos, the rotation angle by
+    arctan2 in the reference normal's basis, bins by floor(angle / 12 degrees) and floor(l / h).
+    -> (ok, key, rotation bin, safe): `safe` is False where a quantity lies within ang_margin rad of an angle bin edge or
+    within dist_margin * D of a distance edge (0, k h, D): there float32 may decide either way."""
+    pr, nr, pi, ni = (np.asarray(x, dtype=np.float64) for x in (pr, nr, pi, ni))
+    h, D = float(F32(h)), float(F32(D))
+    d = pi - pr
+    l = np.sqrt((d * d).sum(-1))
+    ok = (l > 0) & (l <= D)
+    ls = np.where(l > 0, l, 1.0)
+    step = math.pi / NA
+    nd = int(np.floor(D / h)) + 1
+    db = np.minimum(np.floor(l / h), nd - 1).astype(np.int64)
+    edge = np.minimum(np.abs(l / h - np.round(l / h)) * h, np.abs(l - D))
+    safe = edge > dist_margin * D
+    bins = []
+    for c in ((nr * d).sum(-1) / ls, (ni * d).sum(-1) / ls, (nr * ni).sum(-1)):
+        ang = np.arccos(np.clip(c, -1.0, 1.0))
+        bins.append(np.minimum(np.floor(ang / step), NA - 1).astype(np.int64))
+        safe &= np.abs(ang / step - np.round(ang / step)) * step > ang_margin
+    e1, e2 = basis64(nr)
+    u, v = (e1 * d).sum(-1), (e2 * d).sum(-1)
+    rot = np.mod(np.arctan2(v, u), 2.0 * math.pi)
+    rb = np.minimum(np.floor(rot / step), NALPHA - 1).astype(np.int64)
+    safe &= np.abs(rot / step - np.round(rot / step)) * step > ang_margin
+    safe &= np.hypot(u, v) > ang_margin * ls                  # partner on the normal's axis: no rotation angle
+    key = ((db * NA + bins[0]) * NA + bins[1]) * NA + bins[2]
+    return ok, key, rb, safe
 
 
 def find(model, cloud, rel=0.05, ref_rate=0.2, num_result=100, normals=None, trace=None):
