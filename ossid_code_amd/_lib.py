@@ -391,6 +391,11 @@ class _NullCtx:
 _NULL_CTX = _NullCtx()
 
 
+def _dev():
+    """The current GPU as a torch.device."""
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 def on_device(dev):
     """`with on_device(t.device):` -- torch.cuda.device(dev), or nothing at all when dev is already current (one process
     per GPU: always, after start-up)."""

@@ -11,6 +11,9 @@ static inline int ossid_launch_status() {
     return e == hipSuccess ? OSSID_OK : OSSID_ELAUNCH;
 }
 
+// workgroups of 256 threads for a grid-stride kernel over `work` elements
+static inline int grid_for(size_t work) { return (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192); }
+
 // ELU(alpha = 1) without libm's expm1f (~40 vector instructions per value -- 160 M of them per test-time frame in the head's
 // convolution epilogues: ~0.13 ms of vector-ALU time): a degree-7 Taylor polynomial near zero, where exp(x) - 1 would cancel,
 // and the hardware exponential elsewhere; relative error < 1e-6 (tests/test_dtoid_gpu.py holds it against torch's ELU).

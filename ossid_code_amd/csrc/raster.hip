@@ -20,16 +20,18 @@
 // ossid_raster_color (SPEC 7.11-7.12; the template renders of datasets/render_dataset.py:251-331) runs the same vertex
 // stage and the same triangle walk over a visibility buffer: one 64-bit key (bits(z) << 32 | face index) per sample in
 // the workspace, so that the minimum is the nearest depth and, among equal depths, the lowest face index. Its resolve
-// redoes the winner's setup per pixel, recomputes the exact edge functions and interpolates the vertex colours
-// perspective-correctly. ossid_template_reduce (7.13) is the s x s box filter that makes a template of such a render.
+// sets the winner up again per pixel (raster_common.h's winner_of), recomputes the exact edge functions and interpolates
+// the vertex colours perspective-correctly. ossid_template_reduce (7.13) is the s x s box filter that makes a template of
+// such a render.
 //
 // ossid_raster_textured (SPEC 7.16-7.17; BOP models whose colour lives in a UV texture) is ossid_raster_color with another
-// resolve: the same prepare and triangle launches, then per covered pixel the perspective-correct (u, v) at the sample and
-// at its right and lower neighbour, a mip level from their largest difference, and one bilinear fetch (texture.h) from the
-// chain csrc/texture.hip built.
+// resolve: the same visibility_pass (refusals, workspace, prepare and triangle launches), then per covered pixel the
+// perspective-correct (u, v) at the sample and at its right and lower neighbour, a mip level from their largest
+// difference, and one bilinear fetch (texture.h) from the chain csrc/texture.hip built.
 //
-// The arithmetic of a sample (vertex stage, setup, edge functions, depth, colour) lives in raster_common.h, shared with
-// csrc/scene.hip.
+// What csrc/scene.hip needs as well lives in raster_common.h: the arithmetic of a sample (vertex stage, setup, edge
+// functions, depth, colour), fetch_triangle, the 64-bit shade, wave_walk, the winner's setup and the frame check. This file
+// keeps what is its own: the launch geometry, the z-buffer shade, the coverage statistic and the resolves.
 #include <cmath>
 
 #include "raster_common.h"
@@ -41,52 +43,45 @@ constexpr int TARGET_WAVES = 2048;    // 256 CUs x 8: below this many full waves
 constexpr int MAX_WAVES = 16;         // waves per workgroup that share the large boxes of a call with few triangles
 constexpr int RESIDENT_WAVES = 8192;  // 256 CUs x 32: extra waves per workgroup are added only while all stay resident
 
+// Where a pose's camera comes from: the call's one camera (ossid_raster_depth), or intrinsics f32 [N][4] = fx, fy, cx, cy.
+struct Camera {
+    float fx, fy, cx, cy;
+};
+struct OneCamera {
+    Camera c;
+    __device__ Camera at(int) const { return c; }
+};
+struct CameraPerPose {
+    const float* __restrict__ k;
+    __device__ Camera at(int pose) const {
+        const float* c = k + 4 * (size_t)pose;
+        return {c[0], c[1], c[2], c[3]};
+    }
+};
+
+// ZB is unsigned (z-buffer: the float's bits, cleared to ZFAR) or unsigned long long (visibility buffer, cleared to KFAR).
+template <typename ZB, typename Cams>
 __global__ __launch_bounds__(256) void raster_prepare_kernel(const float* __restrict__ vertices, int V,
-                                                             const float* __restrict__ transforms, int N, float fx, float fy,
-                                                             float cx, float cy, float z_near, VRec* __restrict__ rec,
-                                                             unsigned* __restrict__ zbuf, size_t npix,
+                                                             const float* __restrict__ transforms, int N, Cams cams, float z_near,
+                                                             VRec* __restrict__ rec, ZB* __restrict__ zbuf, size_t npix,
                                                              int32_t* __restrict__ stats) {
     const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nthreads = (size_t)gridDim.x * 256;
-    for (size_t i = tid; i < npix; i += nthreads) zbuf[i] = ZFAR;
+    for (size_t i = tid; i < npix; i += nthreads) zbuf[i] = sizeof(ZB) == 4 ? (ZB)ZFAR : (ZB)KFAR;
     if (stats && tid < (size_t)4 * N) stats[tid] = 0;
     const size_t nv = (size_t)N * V;
     for (size_t i = tid; i < nv; i += nthreads) {
         const int pose = (int)(i / V), k = (int)(i - (size_t)pose * V);
-        rec[i] = project_vertex(vertices, k, transforms + 16 * (size_t)pose, fx, fy, cx, cy, z_near);
+        const Camera c = cams.at(pose);
+        rec[i] = project_vertex(vertices, k, transforms + 16 * (size_t)pose, c.fx, c.fy, c.cx, c.cy, z_near);
     }
 }
 
-// The same with one camera per pose (intrinsics f32 [N][4] = fx, fy, cx, cy) and the visibility buffer cleared to KFAR.
-__global__ __launch_bounds__(256) void raster_prepare_color_kernel(const float* __restrict__ vertices, int V,
-                                                                   const float* __restrict__ transforms, int N,
-                                                                   const float* __restrict__ intrinsics, float z_near,
-                                                                   VRec* __restrict__ rec, unsigned long long* __restrict__ keys,
-                                                                   size_t npix, int32_t* __restrict__ stats) {
-    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nthreads = (size_t)gridDim.x * 256;
-    for (size_t i = tid; i < npix; i += nthreads) keys[i] = KFAR;
-    if (stats && tid < (size_t)4 * N) stats[tid] = 0;
-    const size_t nv = (size_t)N * V;
-    for (size_t i = tid; i < nv; i += nthreads) {
-        const int pose = (int)(i / V), k = (int)(i - (size_t)pose * V);
-        const float* c = intrinsics + 4 * (size_t)pose;
-        rec[i] = project_vertex(vertices, k, transforms + 16 * (size_t)pose, c[0], c[1], c[2], c[3], z_near);
-    }
-}
-
-// Sample of pixel (x, y): coverage, perspective-correct depth, buffer update. Returns whether it was covered. ZB is
-// unsigned (z-buffer: the float's bits) or unsigned long long (visibility buffer: bits << 32 | face, SPEC 7.11).
-template <typename ZB>
-__device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, int o, int W, ZB* __restrict__ zb, unsigned face) {
+// The z-buffer form of raster_common.h's shade: the float's bits alone, no face.
+__device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, int o, int W, unsigned* __restrict__ zb, unsigned) {
     unsigned zbits;
     if (!sample_depth(t, area, x, y, o, zbits)) return false;
-    ZB* p = zb + (size_t)y * W + x;
-    if constexpr (sizeof(ZB) == 4) {
-        if (zbits < *p) atomicMin(p, zbits);
-    } else {
-        // one 8-byte load (never two halves of different keys); keys only fall, so a stale one costs a useless atomic
-        const unsigned long long key = ((unsigned long long)zbits << 32) | face;
-        if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
-    }
+    unsigned* p = zb + (size_t)y * W + x;
+    if (zbits < *p) atomicMin(p, zbits);
     return true;
 }
 
@@ -103,57 +98,22 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void raster_tri_kernel(const int32_
         __syncthreads();
     }
     const long long tri = (long long)blockIdx.x * tpw + lane;
-    const VRec* vr = rec + (size_t)pose * V;
     ZB* zb = zbuf + (size_t)pose * H * W;
     Tri t = {};
     long long A = 0;
-    int n_bad = 0, n_degen = 0, n_cov = 0, n_large = 0;
-    bool large = false;
-    if (lane < tpw && tri < F) {
-        const unsigned i0 = (unsigned)faces[3 * tri], i1 = (unsigned)faces[3 * tri + 1], i2 = (unsigned)faces[3 * tri + 2];
-        bool bad = i0 >= (unsigned)V || i1 >= (unsigned)V || i2 >= (unsigned)V;   // never read outside the records
-        VRec a = {}, b = {}, c = {};
-        if (!bad) {
-            a = vr[i0], b = vr[i1], c = vr[i2];
-            bad = a.sx == INT_MIN || b.sx == INT_MIN || c.sx == INT_MIN;
-        }
-        if (bad) {
-            n_bad = 1;
-        } else if (!tri_setup(a, b, c, o, H, W, t, A)) {
-            n_degen = 1;
-        } else if (t.xa <= t.xb && t.ya <= t.yb) {
-            large = (long long)(t.xb - t.xa + 1) * (t.yb - t.ya + 1) > COOP_MIN;
-            if (large) {
-                n_large = 1;
-            } else if (wv == 0) {
-                bool cov = false;
-                for (int y = t.ya; y <= t.yb; ++y)
-                    for (int x = t.xa; x <= t.xb; ++x) cov |= shade(t, (double)A, x, y, o, W, zb, (unsigned)tri);
-                n_cov = cov;
-            }
-        }
-    }
-    // large boxes: the whole wave walks each, 8 x 8 samples per step
-    unsigned long long todo = __ballot(large);
-    const int lx = lane & 7, ly = lane >> 3;
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        Tri s;
-        s.x0 = __shfl(t.x0, src), s.y0 = __shfl(t.y0, src), s.x1 = __shfl(t.x1, src), s.y1 = __shfl(t.y1, src);
-        s.x2 = __shfl(t.x2, src), s.y2 = __shfl(t.y2, src);
-        s.r0 = __shfl(t.r0, src), s.r1 = __shfl(t.r1, src), s.r2 = __shfl(t.r2, src);
-        s.xa = __shfl(t.xa, src), s.ya = __shfl(t.ya, src), s.xb = __shfl(t.xb, src), s.yb = __shfl(t.yb, src);
-        const double area = (double)__shfl(A, src);
-        const unsigned face = (unsigned)(blockIdx.x * tpw + src);
+    const TriKind kind = lane < tpw && tri < F ? fetch_triangle(faces + 3 * tri, V, rec + (size_t)pose * V, o, H, W, t, A) : TRI_EMPTY;
+    const bool large = kind == TRI_LARGE;
+    int n_bad = kind == TRI_BAD, n_degen = kind == TRI_DEGENERATE, n_cov = 0, n_large = large;
+    if (kind == TRI_SMALL && wv == 0) {
         bool cov = false;
-        for (int y0 = s.ya + 8 * wv; y0 <= s.yb; y0 += 8 * nw)
-            for (int x0 = s.xa; x0 <= s.xb; x0 += 8) {
-                const int x = x0 + lx, y = y0 + ly;
-                if (x <= s.xb && y <= s.yb) cov |= shade(s, area, x, y, o, W, zb, face);
-            }
-        if (__ballot(cov) != 0ull && lane == src) n_cov = 1;
+        for (int y = t.ya; y <= t.yb; ++y)
+            for (int x = t.xa; x <= t.xb; ++x) cov |= shade(t, (double)A, x, y, o, W, zb, (unsigned)tri);
+        n_cov = cov;
     }
+    wave_walk(t, A, large, wv, nw, [&](const Tri& s, double area, int src, int, int x, int y, bool in) {
+        const bool cov = in && shade(s, area, x, y, o, W, zb, (unsigned)(blockIdx.x * tpw + src));
+        if (__ballot(cov) != 0ull && lane == src) n_cov = 1;
+    });
     if (nw > 1) {
         if (n_cov && large) atomicOr(&cov_large, 1ull << lane);
         __syncthreads();
@@ -176,59 +136,15 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(unsigned* __restric
         if (zbuf[i] == ZFAR) zbuf[i] = 0u;
 }
 
-// SPEC 7.11-7.12, one thread per (pose, pixel): the winner's setup again (three records, area, the A < 0 swap -- the
-// colours swap with the vertices), the exact edge functions at the sample, colour in f64 with the written parenthesisation.
-__global__ __launch_bounds__(256) void raster_resolve_color_kernel(const unsigned long long* __restrict__ keys,
-                                                                   const int32_t* __restrict__ faces, int V,
-                                                                   const VRec* __restrict__ rec,
-                                                                   const unsigned char* __restrict__ colors, int H, int W, int o,
-                                                                   size_t npix, unsigned char* __restrict__ color_out,
-                                                                   float* __restrict__ depth_out, int32_t* __restrict__ face_out) {
+// One thread per (pose, pixel) of a visibility buffer: the key's decode, then depth, colour, face and the optional level.
+// shade_winner(vr, i0, i1, i2, x, y, c) colours the sample of the winning face and returns its level.
+template <typename ShadeWinner>
+__device__ __forceinline__ void resolve_pixels(const unsigned long long* __restrict__ keys, const int32_t* __restrict__ faces, int V,
+                                               const VRec* __restrict__ rec, int H, int W, size_t npix,
+                                               unsigned char* __restrict__ color_out, float* __restrict__ depth_out,
+                                               int32_t* __restrict__ face_out, int32_t* __restrict__ lod_out,
+                                               ShadeWinner shade_winner) {
     const size_t hw = (size_t)H * W;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
-        const unsigned long long key = keys[i];
-        float z = 0.0f;
-        int face = -1, c[3] = {0, 0, 0};
-        if (key != KFAR) {
-            const int pose = (int)(i / hw);
-            const int pix = (int)(i - (size_t)pose * hw), y = pix / W, x = pix - y * W;
-            face = (int)(unsigned)key;                   // written by a usable triangle: its indices lie in [0, V)
-            z = __uint_as_float((unsigned)(key >> 32));
-            const size_t f = (size_t)face;
-            sample_color(rec + (size_t)pose * V, colors, faces[3 * f], faces[3 * f + 1], faces[3 * f + 2], x, y, o, c);
-        }
-        depth_out[i] = z;
-        color_out[3 * i] = (unsigned char)c[0], color_out[3 * i + 1] = (unsigned char)c[1], color_out[3 * i + 2] = (unsigned char)c[2];
-        if (face_out) face_out[i] = face;
-    }
-}
-
-// (u, v) of triangle a b d (after the swap; UVs uv0 uv1 uv2 travel with them) at the fixed-point sample (px, py), SPEC
-// 7.16: the edge functions are affine, so the integers are exact outside the triangle too. Returns the denominator.
-__device__ __forceinline__ double uv_at(const VRec& a, const VRec& b, const VRec& d, const float* __restrict__ uv0,
-                                        const float* __restrict__ uv1, const float* __restrict__ uv2, int px, int py, double& u,
-                                        double& v) {
-    long long w0, w1, w2;
-    edge_in(a.sx, a.sy, b.sx, b.sy, px, py, w2);
-    edge_in(b.sx, b.sy, d.sx, d.sy, px, py, w0);
-    edge_in(d.sx, d.sy, a.sx, a.sy, px, py, w1);
-    const double b0 = (double)w0 * a.rz, b1 = (double)w1 * b.rz, b2 = (double)w2 * d.rz;
-    const double den = (b0 + b1) + b2;
-    u = ((b0 * (double)uv0[0] + b1 * (double)uv1[0]) + b2 * (double)uv2[0]) / den;
-    v = ((b0 * (double)uv0[1] + b1 * (double)uv1[1]) + b2 * (double)uv2[1]) / den;
-    return den;
-}
-
-// SPEC 7.16-7.17, one thread per (pose, pixel): the winner's setup again as sample_color does it (the UVs swap with the
-// vertices), (u, v) at the sample and at the samples of the right and lower neighbour, the level by comparison with
-// powers of two, the bilinear fetch of texture.h.
-__global__ __launch_bounds__(256) void raster_resolve_textured_kernel(
-    const unsigned long long* __restrict__ keys, const int32_t* __restrict__ faces, int V, const VRec* __restrict__ rec,
-    const float* __restrict__ uvs, const unsigned* __restrict__ mips, int Ht, int Wt, int H, int W, int o, size_t npix,
-    unsigned char* __restrict__ color_out, float* __restrict__ depth_out, int32_t* __restrict__ face_out,
-    int32_t* __restrict__ lod_out) {
-    const size_t hw = (size_t)H * W;
-    const int top = tex_top_level(Ht, Wt);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
         const unsigned long long key = keys[i];
         float z = 0.0f;
@@ -239,38 +155,67 @@ __global__ __launch_bounds__(256) void raster_resolve_textured_kernel(
             face = (int)(unsigned)key;                   // written by a usable triangle: its indices lie in [0, V)
             z = __uint_as_float((unsigned)(key >> 32));
             const size_t f = (size_t)face;
-            const VRec* vr = rec + (size_t)pose * V;
-            int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-            VRec a = vr[i0], b = vr[i1], d = vr[i2];
-            const long long A = (long long)(b.sx - a.sx) * (long long)(d.sy - a.sy) - (long long)(b.sy - a.sy) * (long long)(d.sx - a.sx);
-            if (A < 0) {
-                const VRec s = b;
-                b = d, d = s;
-                const int j = i1;
-                i1 = i2, i2 = j;
-            }
-            const float *uv0 = uvs + 2 * (size_t)i0, *uv1 = uvs + 2 * (size_t)i1, *uv2 = uvs + 2 * (size_t)i2;
-            const int px = 256 * x + o, py = 256 * y + o;
-            double u, v, ux, vx, uy, vy;
-            uv_at(a, b, d, uv0, uv1, uv2, px, py, u, v);
-            const double denx = uv_at(a, b, d, uv0, uv1, uv2, px + 256, py, ux, vx);
-            const double deny = uv_at(a, b, d, uv0, uv1, uv2, px, py + 256, uy, vy);
-            const double dsx = fabs((ux - u) * (double)Wt), dtx = fabs((vx - v) * (double)Ht);
-            const double dsy = fabs((uy - u) * (double)Wt), dty = fabs((vy - v) * (double)Ht);
-            lod = top;
-            if (denx > 0.0 && deny > 0.0 && fin(dsx) && fin(dtx) && fin(dsy) && fin(dty)) {
-                const double m0 = dsx > dtx ? dsx : dtx, m1 = dsy > dty ? dsy : dty;
-                lod = tex_select_level(m0 > m1 ? m0 : m1, top);
-            }
-            double q[3];
-            tex_bilinear(tex_level(mips, Ht, Wt, lod), u, v, q);
-            c[0] = tex_round_u8(q[0]), c[1] = tex_round_u8(q[1]), c[2] = tex_round_u8(q[2]);
+            lod = shade_winner(rec + (size_t)pose * V, faces[3 * f], faces[3 * f + 1], faces[3 * f + 2], x, y, c);
         }
         depth_out[i] = z;
         color_out[3 * i] = (unsigned char)c[0], color_out[3 * i + 1] = (unsigned char)c[1], color_out[3 * i + 2] = (unsigned char)c[2];
         if (face_out) face_out[i] = face;
         if (lod_out) lod_out[i] = lod;
     }
+}
+
+// SPEC 7.11-7.12: the winner's vertex colours, interpolated perspective-correctly.
+__global__ __launch_bounds__(256) void raster_resolve_color_kernel(const unsigned long long* __restrict__ keys,
+                                                                   const int32_t* __restrict__ faces, int V,
+                                                                   const VRec* __restrict__ rec,
+                                                                   const unsigned char* __restrict__ colors, int H, int W, int o,
+                                                                   size_t npix, unsigned char* __restrict__ color_out,
+                                                                   float* __restrict__ depth_out, int32_t* __restrict__ face_out) {
+    resolve_pixels(keys, faces, V, rec, H, W, npix, color_out, depth_out, face_out, nullptr,
+                   [&](const VRec* vr, int i0, int i1, int i2, int x, int y, int c[3]) {
+                       sample_color(vr, colors, i0, i1, i2, x, y, o, c);
+                       return -1;
+                   });
+}
+
+// (u, v) of the winner w at the fixed-point sample (px, py), SPEC 7.16. Returns the denominator.
+__device__ __forceinline__ double uv_at(const Winner& w, const float* __restrict__ uvs, int px, int py, double& u, double& v) {
+    double b0, b1, b2;
+    const double den = winner_weights(w, px, py, b0, b1, b2);
+    const float *uv0 = uvs + 2 * (size_t)w.i0, *uv1 = uvs + 2 * (size_t)w.i1, *uv2 = uvs + 2 * (size_t)w.i2;
+    u = ((b0 * (double)uv0[0] + b1 * (double)uv1[0]) + b2 * (double)uv2[0]) / den;
+    v = ((b0 * (double)uv0[1] + b1 * (double)uv1[1]) + b2 * (double)uv2[1]) / den;
+    return den;
+}
+
+// SPEC 7.16-7.17: (u, v) at the sample and at the samples of the right and lower neighbour, the level by comparison with
+// powers of two, the bilinear fetch of texture.h.
+__global__ __launch_bounds__(256) void raster_resolve_textured_kernel(
+    const unsigned long long* __restrict__ keys, const int32_t* __restrict__ faces, int V, const VRec* __restrict__ rec,
+    const float* __restrict__ uvs, const unsigned* __restrict__ mips, int Ht, int Wt, int H, int W, int o, size_t npix,
+    unsigned char* __restrict__ color_out, float* __restrict__ depth_out, int32_t* __restrict__ face_out,
+    int32_t* __restrict__ lod_out) {
+    const int top = tex_top_level(Ht, Wt);
+    resolve_pixels(keys, faces, V, rec, H, W, npix, color_out, depth_out, face_out, lod_out,
+                   [&](const VRec* vr, int i0, int i1, int i2, int x, int y, int c[3]) {
+                       const Winner w = winner_of(vr, i0, i1, i2);
+                       const int px = 256 * x + o, py = 256 * y + o;
+                       double u, v, ux, vx, uy, vy;
+                       uv_at(w, uvs, px, py, u, v);
+                       const double denx = uv_at(w, uvs, px + 256, py, ux, vx);
+                       const double deny = uv_at(w, uvs, px, py + 256, uy, vy);
+                       const double dsx = fabs((ux - u) * (double)Wt), dtx = fabs((vx - v) * (double)Ht);
+                       const double dsy = fabs((uy - u) * (double)Wt), dty = fabs((vy - v) * (double)Ht);
+                       int lod = top;
+                       if (denx > 0.0 && deny > 0.0 && fin(dsx) && fin(dtx) && fin(dsy) && fin(dty)) {
+                           const double m0 = dsx > dtx ? dsx : dtx, m1 = dsy > dty ? dsy : dty;
+                           lod = tex_select_level(m0 > m1 ? m0 : m1, top);
+                       }
+                       double q[3];
+                       tex_bilinear(tex_level(mips, Ht, Wt, lod), u, v, q);
+                       c[0] = tex_round_u8(q[0]), c[1] = tex_round_u8(q[1]), c[2] = tex_round_u8(q[2]);
+                       return lod;
+                   });
 }
 
 // SPEC 7.13, one thread per output pixel: the s x s box over a supersampled render, uncovered samples count as 0.
@@ -302,13 +247,6 @@ bool sizes_ok(int V, int F, int N) {
            N <= OSSID_RASTER_MAX_POSES;
 }
 
-bool frame_ok(int H, int W, float pixel_offset, float z_near) {
-    return H > 0 && W > 0 && (long long)H * W <= OSSID_RASTER_MAX_PIXELS && pixel_offset >= 0.0f && pixel_offset <= 1.0f &&
-           z_near >= 0.0f && std::isfinite(z_near);
-}
-
-int grid_for(size_t work) { return (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192); }
-
 template <typename ZB>
 void launch_triangles(const int32_t* faces, int F, int V, int N, const VRec* rec, int H, int W, int o, ZB* zbuf, int32_t* stats,
                       hipStream_t s) {
@@ -320,6 +258,27 @@ void launch_triangles(const int32_t* faces, int F, int V, int N, const VRec* rec
     nw = nw < 1 ? 1 : (nw > MAX_WAVES ? MAX_WAVES : nw);
     hipLaunchKernelGGL(raster_tri_kernel<ZB>, dim3((unsigned)groups, N), dim3(64 * (unsigned)nw), 0, s, faces, F, V, rec, H, W, o,
                        (int)tpw, zbuf, stats);
+}
+
+// The visibility pass of ossid_raster_color and ossid_raster_textured (SPEC 7.11): their common refusals, the workspace
+// cut into records and keys, the prepare and triangle launches; then the caller's resolve(keys, rec, o, npix, stream).
+template <typename Resolve>
+int visibility_pass(const float* vertices, int V, const int32_t* faces, int F, const float* transforms, int N,
+                    const float* intrinsics, int H, int W, float pixel_offset, float z_near, void* workspace,
+                    size_t workspace_bytes, uint8_t* color_out, float* depth_out, int32_t* stats, hipStream_t s, Resolve resolve) {
+    const size_t need = ossid_raster_color_workspace_bytes(V, F, N, H, W);
+    if (need == 0 || !vertices || (F > 0 && !faces) || !transforms || !intrinsics || !workspace || workspace_bytes < need ||
+        !color_out || !depth_out || ((uintptr_t)workspace & 15) != 0 || !raster_frame_ok(H, W, pixel_offset, z_near))
+        return OSSID_EINVAL;
+    const int o = snap_offset(pixel_offset);
+    const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
+    VRec* rec = (VRec*)workspace;
+    unsigned long long* keys = (unsigned long long*)((char*)workspace + nv * sizeof(VRec));
+    hipLaunchKernelGGL((raster_prepare_kernel<unsigned long long, CameraPerPose>), dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0,
+                       s, vertices, V, transforms, N, CameraPerPose{intrinsics}, z_near, rec, keys, npix, stats);
+    if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, keys, stats, s);
+    resolve(keys, rec, o, npix, s);
+    return ossid_launch_status();
 }
 
 }  // namespace
@@ -336,15 +295,15 @@ int ossid_raster_depth(const float* vertices, int V, const int32_t* faces, int F
                        size_t workspace_bytes, float* depth_out, int32_t* stats, void* stream) {
     const size_t need = ossid_raster_workspace_bytes(V, F, N);
     if (need == 0 || !vertices || (F > 0 && !faces) || !transforms || !workspace || workspace_bytes < need || !depth_out ||
-        ((uintptr_t)workspace & 15) != 0 || !frame_ok(H, W, pixel_offset, z_near))
+        ((uintptr_t)workspace & 15) != 0 || !raster_frame_ok(H, W, pixel_offset, z_near))
         return OSSID_EINVAL;
-    const int o = (int)std::nearbyint((double)pixel_offset * 256.0);       // round half to even
+    const int o = snap_offset(pixel_offset);
     const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
     hipStream_t s = (hipStream_t)stream;
     VRec* rec = (VRec*)workspace;
     unsigned* zbuf = (unsigned*)depth_out;
-    hipLaunchKernelGGL(raster_prepare_kernel, dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0, s, vertices, V, transforms, N,
-                       fx, fy, cx, cy, z_near, rec, zbuf, npix, stats);
+    hipLaunchKernelGGL((raster_prepare_kernel<unsigned, OneCamera>), dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0, s, vertices,
+                       V, transforms, N, OneCamera{{fx, fy, cx, cy}}, z_near, rec, zbuf, npix, stats);
     if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, zbuf, stats, s);
     hipLaunchKernelGGL(raster_resolve_kernel, dim3(grid_for(npix)), dim3(256), 0, s, zbuf, npix);
     return ossid_launch_status();
@@ -359,45 +318,28 @@ int ossid_raster_color(const float* vertices, int V, const int32_t* faces, int F
                        const float* transforms, int N, const float* intrinsics, int H, int W, float pixel_offset, float z_near,
                        void* workspace, size_t workspace_bytes, uint8_t* color_out, float* depth_out, int32_t* face_id_out,
                        int32_t* stats, void* stream) {
-    const size_t need = ossid_raster_color_workspace_bytes(V, F, N, H, W);
-    if (need == 0 || !vertices || (F > 0 && !faces) || !colors || !transforms || !intrinsics || !workspace ||
-        workspace_bytes < need || !color_out || !depth_out || ((uintptr_t)workspace & 15) != 0 ||
-        !frame_ok(H, W, pixel_offset, z_near))
-        return OSSID_EINVAL;
-    const int o = (int)std::nearbyint((double)pixel_offset * 256.0);
-    const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
-    hipStream_t s = (hipStream_t)stream;
-    VRec* rec = (VRec*)workspace;
-    unsigned long long* keys = (unsigned long long*)((char*)workspace + nv * sizeof(VRec));
-    hipLaunchKernelGGL(raster_prepare_color_kernel, dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0, s, vertices, V,
-                       transforms, N, intrinsics, z_near, rec, keys, npix, stats);
-    if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, keys, stats, s);
-    hipLaunchKernelGGL(raster_resolve_color_kernel, dim3(grid_for(npix)), dim3(256), 0, s, keys, faces, V, rec, colors, H, W, o,
-                       npix, color_out, depth_out, face_id_out);
-    return ossid_launch_status();
+    if (!colors) return OSSID_EINVAL;
+    return visibility_pass(vertices, V, faces, F, transforms, N, intrinsics, H, W, pixel_offset, z_near, workspace, workspace_bytes,
+                           color_out, depth_out, stats, (hipStream_t)stream,
+                           [&](const unsigned long long* keys, const VRec* rec, int o, size_t npix, hipStream_t s) {
+                               hipLaunchKernelGGL(raster_resolve_color_kernel, dim3(grid_for(npix)), dim3(256), 0, s, keys, faces, V,
+                                                  rec, colors, H, W, o, npix, color_out, depth_out, face_id_out);
+                           });
 }
 
 int ossid_raster_textured(const float* vertices, int V, const int32_t* faces, int F, const float* uvs, const void* mips,
                           size_t mip_bytes, int Ht, int Wt, const float* transforms, int N, const float* intrinsics, int H, int W,
                           float pixel_offset, float z_near, void* workspace, size_t workspace_bytes, uint8_t* color_out,
                           float* depth_out, int32_t* face_id_out, int32_t* lod_out, int32_t* stats, void* stream) {
-    const size_t need = ossid_raster_color_workspace_bytes(V, F, N, H, W), tex = ossid_texture_mip_bytes(Ht, Wt);
-    if (need == 0 || tex == 0 || !vertices || (F > 0 && !faces) || !uvs || !mips || mip_bytes < tex ||
-        ((uintptr_t)mips & 3) != 0 || !transforms || !intrinsics || !workspace || workspace_bytes < need || !color_out ||
-        !depth_out || ((uintptr_t)workspace & 15) != 0 || !frame_ok(H, W, pixel_offset, z_near))
-        return OSSID_EINVAL;
-    const int o = (int)std::nearbyint((double)pixel_offset * 256.0);
-    const size_t npix = (size_t)N * H * W, nv = (size_t)N * V;
-    hipStream_t s = (hipStream_t)stream;
-    VRec* rec = (VRec*)workspace;
-    unsigned long long* keys = (unsigned long long*)((char*)workspace + nv * sizeof(VRec));
-    // the prepare and triangle stages are ossid_raster_color's: key, depth, face and statistics are 7.11's
-    hipLaunchKernelGGL(raster_prepare_color_kernel, dim3(grid_for(npix > nv ? npix : nv)), dim3(256), 0, s, vertices, V,
-                       transforms, N, intrinsics, z_near, rec, keys, npix, stats);
-    if (F > 0) launch_triangles(faces, F, V, N, rec, H, W, o, keys, stats, s);
-    hipLaunchKernelGGL(raster_resolve_textured_kernel, dim3(grid_for(npix)), dim3(256), 0, s, keys, faces, V, rec, uvs,
-                       (const unsigned*)mips, Ht, Wt, H, W, o, npix, color_out, depth_out, face_id_out, lod_out);
-    return ossid_launch_status();
+    const size_t tex = ossid_texture_mip_bytes(Ht, Wt);
+    if (tex == 0 || !uvs || !mips || mip_bytes < tex || ((uintptr_t)mips & 3) != 0) return OSSID_EINVAL;
+    return visibility_pass(vertices, V, faces, F, transforms, N, intrinsics, H, W, pixel_offset, z_near, workspace, workspace_bytes,
+                           color_out, depth_out, stats, (hipStream_t)stream,
+                           [&](const unsigned long long* keys, const VRec* rec, int o, size_t npix, hipStream_t s) {
+                               hipLaunchKernelGGL(raster_resolve_textured_kernel, dim3(grid_for(npix)), dim3(256), 0, s, keys, faces,
+                                                  V, rec, uvs, (const unsigned*)mips, Ht, Wt, H, W, o, npix, color_out, depth_out,
+                                                  face_id_out, lod_out);
+                           });
 }
 
 int ossid_template_reduce(const uint8_t* color, const float* depth, int N, int T, int s, float* img_out, float* mask_out,

@@ -2,7 +2,8 @@
 // one frame per scene, with mutual occlusion, per-pixel instance labels, amodal masks, the numbers of BOP's
 // scene_gt_info.json and the depth corruption the reference applies to its pre-training renders
 // (utils/augmentation.py:5-26, over the BlenderProc scenes of datasets/render_dataset.py:81-189). The arithmetic of a
-// sample is csrc/raster.hip's (raster_common.h), so a scene image is, per pixel, the winner by (bits(z), instance) among
+// sample, the triangle fetch, the wave walk over large boxes and the winner's setup are raster_common.h's, the ones
+// csrc/raster.hip runs, so a scene image is, per pixel, the winner by (bits(z), instance) among
 // what ossid_raster_color renders for each instance alone, bit for bit.
 //
 // ossid_scene_render, three launches on the caller's stream, nothing read back:
@@ -12,8 +13,8 @@
 //             search of the caller's prefix sums, so a 12-face box and a 300 000-face scan both fill waves. A mesh of nf
 //             faces is cut into groups of tpw = clamp(ceil(nf / 64), 1, 64) triangles; meshes of at most 64 faces (tables,
 //             boxes: few, large triangles) get one triangle per group and SPLIT items per group that share its large box by
-//             rows of tiles. Small boxes are walked by their lane, large ones by the whole wave, 8 x 8 samples per step,
-//             as in raster.hip. Every covered sample sets its bit in the instance's amodal mask BEFORE the depth test (the
+//             rows of tiles. Small boxes are walked by their lane, large ones by the whole wave, 8 x 8 samples per step
+//             (wave_walk). Every covered sample sets its bit in the instance's amodal mask BEFORE the depth test (the
 //             wave walk ORs one byte per tile row, not one bit per sample) and then competes for the pixel's key
 //             bits(z) << 32 | local instance << 22 | face by atomicMin behind a plain load;
 //   resolve   one thread per (scene, pixel): the winner's colour, depth, global instance, face and facing, or the background.
@@ -101,17 +102,6 @@ __device__ __forceinline__ void or_bits(unsigned* p, unsigned bits) {
     if ((__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bits) != bits) atomicOr(p, bits);
 }
 
-// Sample of pixel (x, y) of triangle t of an instance: coverage, depth, the pixel's key. Returns whether it was covered.
-__device__ __forceinline__ bool shade(const Tri& t, double area, int x, int y, int o, int W, unsigned long long* __restrict__ zb,
-                                      unsigned low) {
-    unsigned zbits;
-    if (!sample_depth(t, area, x, y, o, zbits)) return false;
-    unsigned long long* p = zb + (size_t)y * W + x;
-    const unsigned long long key = ((unsigned long long)zbits << 32) | low;
-    if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
-    return true;
-}
-
 __global__ __launch_bounds__(256) void scene_tri_kernel(ossid_scene_desc d, const VRec* __restrict__ rec,
                                                         unsigned long long* __restrict__ keys, int o) {
     const int lane = threadIdx.x & 63;
@@ -131,50 +121,26 @@ __global__ __launch_bounds__(256) void scene_tri_kernel(ossid_scene_desc d, cons
     const unsigned low = (unsigned)in.local << FACE_BITS;
     Tri t = {};
     long long A = 0;
-    bool large = false;
-    if (lane < tpw && tri < in.nf) {
-        const int32_t* f = d.faces + 3 * (size_t)(in.f0 + tri);
-        const unsigned i0 = (unsigned)f[0], i1 = (unsigned)f[1], i2 = (unsigned)f[2];
-        if (i0 < (unsigned)in.nv && i1 < (unsigned)in.nv && i2 < (unsigned)in.nv) {      // never read outside the records
-            const VRec a = vr[i0], b = vr[i1], c = vr[i2];
-            if (a.sx != INT_MIN && b.sx != INT_MIN && c.sx != INT_MIN && tri_setup(a, b, c, o, d.H, d.W, t, A) &&
-                t.xa <= t.xb && t.ya <= t.yb) {
-                large = (long long)(t.xb - t.xa + 1) * (t.yb - t.ya + 1) > COOP_MIN;
-                if (!large && part == 0)
-                    for (int y = t.ya; y <= t.yb; ++y)
-                        for (int x = t.xa; x <= t.xb; ++x)
-                            if (shade(t, (double)A, x, y, o, d.W, zb, low | (unsigned)tri))
-                                or_bits(am + (size_t)y * Wd + (x >> 5), 1u << (x & 31));
-            }
-        }
-    }
-    // large boxes: the whole wave walks each, 8 x 8 samples per step; the items of a split group take every split-th row of tiles
-    unsigned long long todo = __ballot(large);
+    const TriKind kind = lane < tpw && tri < in.nf ? fetch_triangle(d.faces + 3 * (size_t)(in.f0 + tri), in.nv, vr, o, d.H, d.W, t, A)
+                                                   : TRI_EMPTY;
+    if (kind == TRI_SMALL && part == 0)
+        for (int y = t.ya; y <= t.yb; ++y)
+            for (int x = t.xa; x <= t.xb; ++x)
+                if (shade(t, (double)A, x, y, o, d.W, zb, low | (unsigned)tri))
+                    or_bits(am + (size_t)y * Wd + (x >> 5), 1u << (x & 31));
+    // the items of a split group take every split-th row of tiles
     const int lx = lane & 7, ly = lane >> 3;
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        Tri s;
-        s.x0 = __shfl(t.x0, src), s.y0 = __shfl(t.y0, src), s.x1 = __shfl(t.x1, src), s.y1 = __shfl(t.y1, src);
-        s.x2 = __shfl(t.x2, src), s.y2 = __shfl(t.y2, src);
-        s.r0 = __shfl(t.r0, src), s.r1 = __shfl(t.r1, src), s.r2 = __shfl(t.r2, src);
-        s.xa = __shfl(t.xa, src), s.ya = __shfl(t.ya, src), s.xb = __shfl(t.xb, src), s.yb = __shfl(t.yb, src);
-        const double area = (double)__shfl(A, src);
-        const unsigned key_low = low | (unsigned)(tri - lane + src);
-        for (int y0 = s.ya + 8 * part; y0 <= s.yb; y0 += 8 * split)
-            for (int x0 = s.xa; x0 <= s.xb; x0 += 8) {
-                const int x = x0 + lx, y = y0 + ly;
-                const bool cov = x <= s.xb && y <= s.yb && shade(s, area, x, y, o, d.W, zb, key_low);
-                // the tile row's 8 coverage bits in one OR by its first lane (two when the row straddles a mask word)
-                const unsigned row = (unsigned)(__ballot(cov) >> (8 * ly)) & 0xffu;
-                if (lx == 0 && row) {
-                    unsigned* p = am + (size_t)y * Wd + (x0 >> 5);
-                    const int sh = x0 & 31;
-                    or_bits(p, row << sh);
-                    if (sh > 24 && (row >> (32 - sh))) or_bits(p + 1, row >> (32 - sh));
-                }
-            }
-    }
+    wave_walk(t, A, kind == TRI_LARGE, part, split, [&](const Tri& s, double area, int src, int x0, int x, int y, bool in_box) {
+        const bool cov = in_box && shade(s, area, x, y, o, d.W, zb, low | (unsigned)(tri - lane + src));
+        // the tile row's 8 coverage bits in one OR by its first lane (two when the row straddles a mask word)
+        const unsigned row = (unsigned)(__ballot(cov) >> (8 * ly)) & 0xffu;
+        if (lx == 0 && row) {
+            unsigned* p = am + (size_t)y * Wd + (x0 >> 5);
+            const int sh = x0 & 31;
+            or_bits(p, row << sh);
+            if (sh > 24 && (row >> (32 - sh))) or_bits(p + 1, row >> (32 - sh));
+        }
+    });
 }
 
 // SPEC 13.4, one thread per (scene, pixel).
@@ -324,8 +290,6 @@ bool frame_ok(int S, int H, int W) {
     return S >= 1 && S <= OSSID_SCENE_MAX_SCENES && H > 0 && W > 0 && (long long)H * W <= OSSID_RASTER_MAX_PIXELS;
 }
 
-int grid_for(size_t work) { return (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192); }
-
 }  // namespace
 
 extern "C" {
@@ -345,14 +309,14 @@ int ossid_scene_render(const ossid_scene_desc* desc_host, void* workspace, size_
     const size_t need = ossid_scene_workspace_bytes(d.records, d.S, d.H, d.W);
     if (need == 0 || !workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) return OSSID_EINVAL;
     if (d.K < 1 || d.Vt < 1 || d.Vt > MAX_TOTAL || d.Ft < 0 || d.Ft > MAX_TOTAL || d.I < 0 ||
-        (long long)d.I > (long long)d.S * OSSID_SCENE_MAX_INSTANCES || d.work_items < 0 || d.work_items > (1 << 30) || !(d.pixel_offset >= 0.0f) ||
-        !(d.pixel_offset <= 1.0f) || !(d.z_near >= 0.0f) || !std::isfinite(d.z_near))
+        (long long)d.I > (long long)d.S * OSSID_SCENE_MAX_INSTANCES || d.work_items < 0 || d.work_items > (1 << 30) ||
+        !raster_frame_ok(d.H, d.W, d.pixel_offset, d.z_near))
         return OSSID_EINVAL;
     if (!d.vertices || !d.colors || (d.Ft > 0 && !d.faces) || !d.meshes || !d.scene_first || !d.cams || !d.offsets ||
         (d.I > 0 && (!d.instance_mesh || !d.transforms || !d.amodal_out)) || !d.color_out || !d.depth_out || !d.instance_out ||
         (d.background && d.Sb != 1 && d.Sb != d.S))
         return OSSID_EINVAL;
-    const int o = (int)std::nearbyint((double)d.pixel_offset * 256.0);       // round half to even
+    const int o = snap_offset(d.pixel_offset);
     const size_t npix = (size_t)d.S * d.H * d.W, nwords = (size_t)d.I * d.H * ((d.W + 31) / 32);
     hipStream_t s = (hipStream_t)stream;
     VRec* rec = (VRec*)workspace;

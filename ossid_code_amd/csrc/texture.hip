@@ -34,8 +34,6 @@ __global__ __launch_bounds__(256) void texture_down_kernel(const unsigned* __res
     }
 }
 
-int grid_for(size_t work) { return (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192); }
-
 }  // namespace
 
 extern "C" {

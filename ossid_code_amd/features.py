@@ -16,27 +16,17 @@ import numpy as np
 import torch
 
 from . import _lib, hostutil
+from .render import _intrinsics
 
 CONTRAST = 192                      # SPEC 11.2: |D| >= 3 grey levels (6 fractional bits)
 OCTAVES = 3
 MAX_KEYPOINTS = _lib.FEAT_MAX_KEYPOINTS
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _call(name, *args):
-    with torch.cuda.device(_dev()):
+    with torch.cuda.device(_lib._dev()):
         rc = _lib.fn(name)(*args)
     _lib.check(rc, name)
-
-
-def _intrinsics(cam_K):
-    K = np.asarray(cam_K, dtype=np.float64)
-    if K.shape != (3, 3):
-        raise ValueError("cam_K must be [3,3], got %s" % (K.shape,))
-    return tuple(float(np.float32(v)) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
 
 
 def _u8(a, dev):
@@ -50,7 +40,7 @@ def featurize(img, depth, mask, cam_K, contrast=CONTRAST, max_keypoints=None, oc
     "keypoints" int32 [cap,4] = (octave, level, y, x), "count" int32 [2] = (keypoints found, 1 iff over the cap), "ok" u8
     [cap] (0 = dropped, its rows are zero), "bins" int32 [cap], "pyramid" (int32, opaque). Rows past count[0] are
     unspecified. Nothing is copied to the host: check_count raises on a frame over the cap."""
-    dev = _dev()
+    dev = _lib._dev()
     cap = _lib.FEAT_MAX_KEYPOINTS if max_keypoints is None else int(max_keypoints)
     if not 1 <= cap <= _lib.FEAT_MAX_KEYPOINTS:
         raise ValueError("featurize: max_keypoints must lie in [1, %d], got %r" % (_lib.FEAT_MAX_KEYPOINTS, max_keypoints))
@@ -213,7 +203,7 @@ class FeatureModel:
     def load(cls, path, device=None):
         z = np.load(path)
         self = cls()
-        dev = torch.device(device) if device is not None else _dev()
+        dev = torch.device(device) if device is not None else _lib._dev()
         self.descriptors = torch.from_numpy(np.ascontiguousarray(z["descriptors"], dtype=np.uint8)).to(dev)
         self.frames = torch.from_numpy(np.ascontiguousarray(z["frames"], dtype=np.float64)).to(dev)
         self.D, self.contrast = np.float32(z["D"]), int(z["contrast"])

@@ -155,7 +155,7 @@ def fps(points, m):
     if not bool(torch.isfinite(P).all()):
         raise ValueError("fps: the points must be finite")
     if not P.is_cuda:
-        P = P.to(_render._dev())
+        P = P.to(_lib._dev())
     P = P.contiguous()
     sel = torch.empty(m, dtype=torch.int32, device=P.device)
     rad = torch.empty(m, dtype=torch.float32, device=P.device)
@@ -180,7 +180,7 @@ def mesh_diameter(mesh):
     if not P.is_cuda:
         if isinstance(mesh, _render.Mesh):
             _refuse_cpu(P.device)
-        P = P.to(_render._dev())
+        P = P.to(_lib._dev())
     P = P.to(torch.float32).contiguous()
     out = torch.empty(2, dtype=torch.float64, device=P.device)
     with _lib.on_device(P.device):

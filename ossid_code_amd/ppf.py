@@ -35,17 +35,13 @@ def dense_flag(v):
     raise ValueError("find_surface_model: DensePoseRefinement=%r is not 'true' or 'false'" % (v,))
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _f32(a, dev):
     t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
     return t.to(dev, torch.float32).contiguous()
 
 
 def _call(name, *args):
-    with torch.cuda.device(_dev()):
+    with torch.cuda.device(_lib._dev()):
         rc = _lib.fn(name)(*args)
     _lib.check(rc, name)
 
@@ -200,7 +196,7 @@ class PPFModel:
             raise ValueError("PPFModel: points and normals must both be [V,3] with V > 0")
         if not float(ModelSamplingDist) > 0.0:
             raise ValueError("PPFModel: ModelSamplingDist must be > 0")
-        dev = _dev()
+        dev = _lib._dev()
         self.device = dev
         self.sampling_dist = float(ModelSamplingDist)
         cap = _lib.PPF_MAX_MODEL_POINTS

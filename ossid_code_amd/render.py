@@ -25,10 +25,6 @@ from .hostutil import meta2K
 from .ppf import _ply_walk
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def read_ply_mesh(path, with_colors=False):
     """BOP-style PLY (ASCII or binary little-endian) -> (vertices f64 [V,3], faces int32 [F,3]). Faces come from the face
     element's list property vertex_indices (or vertex_index); polygons with more than three vertices are
@@ -206,7 +202,7 @@ class Mesh:
         I = None if texture is None else _check_texture(texture)
         self.scale = float(scale)
         self.n_vertices, self.n_faces = len(V), len(F)
-        self.device = torch.device(device) if device is not None else _dev()
+        self.device = torch.device(device) if device is not None else _lib._dev()
         self.vertices = torch.from_numpy((V * self.scale).astype(np.float32)).to(self.device).contiguous()
         self.faces = torch.from_numpy(F).to(self.device).contiguous()
         self.colors = None if C is None else torch.from_numpy(C).to(self.device).contiguous()
@@ -256,6 +252,20 @@ def _intrinsics(cam_K):
     return tuple(float(np.float32(v)) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
 
 
+def _check_frame(what, hw, pixel_offset=0.0, z_near=0.0):
+    """The frame and sampling checks of every render, scenes included -> (H, W). `what` names the caller in the frame's
+    message (None: nothing does)."""
+    H, W = int(hw[0]), int(hw[1])
+    if H <= 0 or W <= 0 or H * W > _lib.RASTER_MAX_PIXELS:
+        raise ValueError("%sframe %d x %d is outside (0, %d] pixels"
+                         % ("%s: " % what if what else "", H, W, _lib.RASTER_MAX_PIXELS))
+    if not 0.0 <= float(pixel_offset) <= 1.0:
+        raise ValueError("pixel_offset must lie in [0, 1], got %r" % (pixel_offset,))
+    if not (float(z_near) >= 0.0 and np.isfinite(z_near)):
+        raise ValueError("z_near must be finite and >= 0, got %r" % (z_near,))
+    return H, W
+
+
 def _check_call(what, poses, hw, pixel_offset, z_near):
     """The argument checks shared by render_depth and render_color -> (poses as a tensor, single, N, H, W)."""
     T = poses if torch.is_tensor(poses) else torch.from_numpy(np.asarray(poses, dtype=np.float64))
@@ -263,15 +273,9 @@ def _check_call(what, poses, hw, pixel_offset, z_near):
         raise ValueError("poses must be [4,4] or [N,4,4], got %s" % (tuple(T.shape),))
     single = T.dim() == 2
     N = 1 if single else int(T.shape[0])
-    H, W = int(hw[0]), int(hw[1])
     if not 1 <= N <= _lib.RASTER_MAX_POSES:
         raise ValueError("%s takes 1 to %d poses, got %d" % (what, _lib.RASTER_MAX_POSES, N))
-    if H <= 0 or W <= 0 or H * W > _lib.RASTER_MAX_PIXELS:
-        raise ValueError("%s: frame %d x %d is outside (0, %d] pixels" % (what, H, W, _lib.RASTER_MAX_PIXELS))
-    if not 0.0 <= float(pixel_offset) <= 1.0:
-        raise ValueError("pixel_offset must lie in [0, 1], got %r" % (pixel_offset,))
-    if not (float(z_near) >= 0.0 and np.isfinite(z_near)):
-        raise ValueError("z_near must be finite and >= 0, got %r" % (z_near,))
+    H, W = _check_frame(what, hw, pixel_offset, z_near)
     return T, single, N, H, W
 
 
@@ -353,22 +357,18 @@ def render_color(mesh, poses, cam_K, hw, pixel_offset=0.5, z_near=0.05, intrinsi
     face = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_face_id else None
     stats = torch.empty(N, 4, dtype=torch.int32, device=dev) if return_stats else None
     lod = torch.empty(N, H, W, dtype=torch.int32, device=dev) if return_lod else None
+    # the two entry points differ in the surface (colours | UVs and the mip chain) and in the textured one's lod_out
+    head = (mesh.vertices.data_ptr(), mesh.n_vertices, mesh.faces.data_ptr() if mesh.n_faces else None, mesh.n_faces)
+    frame = (T.data_ptr(), N, cams.data_ptr(), H, W, float(pixel_offset), float(z_near), ws.data_ptr(), ws.numel(),
+             color.data_ptr(), depth.data_ptr(), _lib.ptr(face))
+    if textured:
+        what = "ossid_raster_textured"
+        args = head + (mesh.uvs.data_ptr(), mesh.mips.data_ptr(), mesh.mips.numel()) + mesh.texture_hw + frame + (_lib.ptr(lod),)
+    else:
+        what = "ossid_raster_color"
+        args = head + (mesh.colors.data_ptr(),) + frame
     with _lib.on_device(dev):
-        if textured:
-            what = "ossid_raster_textured"
-            rc = _lib.fn(what)(mesh.vertices.data_ptr(), mesh.n_vertices, mesh.faces.data_ptr() if mesh.n_faces else None,
-                               mesh.n_faces, mesh.uvs.data_ptr(), mesh.mips.data_ptr(), mesh.mips.numel(), mesh.texture_hw[0],
-                               mesh.texture_hw[1], T.data_ptr(), N, cams.data_ptr(), H, W, float(pixel_offset), float(z_near),
-                               ws.data_ptr(), ws.numel(), color.data_ptr(), depth.data_ptr(),
-                               None if face is None else face.data_ptr(), None if lod is None else lod.data_ptr(),
-                               None if stats is None else stats.data_ptr(), _lib.stream())
-        else:
-            what = "ossid_raster_color"
-            rc = _lib.fn(what)(mesh.vertices.data_ptr(), mesh.n_vertices, mesh.faces.data_ptr() if mesh.n_faces else None,
-                               mesh.n_faces, mesh.colors.data_ptr(), T.data_ptr(), N, cams.data_ptr(), H, W,
-                               float(pixel_offset), float(z_near), ws.data_ptr(), ws.numel(), color.data_ptr(),
-                               depth.data_ptr(), None if face is None else face.data_ptr(),
-                               None if stats is None else stats.data_ptr(), _lib.stream())
+        rc = _lib.fn(what)(*args, _lib.ptr(stats), _lib.stream())
     _lib.check(rc, what)
     out = [color, depth] + ([face] if return_face_id else []) + ([stats] if return_stats else []) + \
           ([lod] if return_lod else [])
@@ -467,9 +467,8 @@ def render_templates(mesh, rotations=None, size=124, supersample=4, distance=0.8
     _textured(mesh, use_texture)
     if cam_K is None:
         raise ValueError("render_templates: cam_K is required (the camera the templates will be matched under)")
+    _intrinsics(cam_K)                                     # refuses what is not [3,3]
     K = np.asarray(cam_K, dtype=np.float64)
-    if K.shape != (3, 3):
-        raise ValueError("cam_K must be [3,3], got %s" % (K.shape,))
     T, s, per = int(size), int(supersample), int(views_per_call)
     if not 1 <= s <= 8:
         raise ValueError("supersample must lie in [1, 8], got %r" % (supersample,))
@@ -481,8 +480,7 @@ def render_templates(mesh, rotations=None, size=124, supersample=4, distance=0.8
         raise ValueError("distance must be finite and > 0, got %r" % (distance,))
     if not (float(pad) > 0.0 and np.isfinite(pad)):
         raise ValueError("pad must be finite and > 0, got %r" % (pad,))
-    if not (float(z_near) >= 0.0 and np.isfinite(z_near)):
-        raise ValueError("z_near must be finite and >= 0, got %r" % (z_near,))
+    _check_frame("render_templates", (s * T, s * T), 0.5, z_near)
     R = view_grid() if rotations is None else np.array(rotations, dtype=np.float64)
     if R.ndim != 3 or R.shape[1:] != (3, 3) or len(R) < 1:
         raise ValueError("rotations must be [n,3,3] with n >= 1, got %s" % (R.shape,))

@@ -138,13 +138,6 @@ class Sensor:
         return Sensor(np.zeros(n_scenes), np.zeros(n_scenes, np.int32), np.zeros((n_scenes, _lib.SCENE_MAX_RECTS, 4), np.int32))
 
 
-def _check_hw(hw):
-    H, W = int(hw[0]), int(hw[1])
-    if H <= 0 or W <= 0 or H * W > _lib.RASTER_MAX_PIXELS:
-        raise ValueError("frame %d x %d is outside (0, %d] pixels" % (H, W, _lib.RASTER_MAX_PIXELS))
-    return H, W
-
-
 def _uniform_rotation(rng):
     """Uniform over SO(3): a normalised 4-vector of normals as a quaternion (w, x, y, z)."""
     q = rng.normal(size=4)
@@ -160,7 +153,7 @@ def sample_layouts(atlas, n_scenes, objects_per_scene, cam_K, hw, rng, z_range=(
     centre has its depth uniform in z_range and its projection uniform over the frame. table=True puts the atlas's
     square first in every scene, tilted by 15 to 40 degrees so that it recedes towards the top of the image, its nearest
     edge behind the farthest possible object. The same Generator state gives the same layout."""
-    H, W = _check_hw(hw)
+    H, W = _render._check_frame(None, hw)
     S, n = int(n_scenes), int(objects_per_scene)
     if not isinstance(rng, np.random.Generator):
         raise ValueError("rng must be a numpy.random.Generator")
@@ -201,7 +194,7 @@ def sample_sensor(n_scenes, hw, rng):
     """SPEC 13.8, the distributions of utils/augmentation.py:5-26 -> Sensor: the threshold uniform in [0.2, 0.5]; 0 to 6
     rectangles, each starting at a row and column uniform over the frame with an extent uniform in [H//16, H//4) x
     [W//16, W//4), its end clipped at H-1 / W-1."""
-    H, W = _check_hw(hw)
+    H, W = _render._check_frame(None, hw)
     S = int(n_scenes)
     if not isinstance(rng, np.random.Generator):
         raise ValueError("rng must be a numpy.random.Generator")
@@ -234,15 +227,11 @@ def work_offsets(atlas, layout):
 
 
 def _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, depth_scale):
-    H, W = _check_hw(hw)
     if not isinstance(atlas, MeshAtlas) or not isinstance(layout, Layout):
         raise ValueError("render_scenes takes a MeshAtlas and a Layout")
     if layout.n_instances and (layout.instance_mesh.min() < 0 or layout.instance_mesh.max() >= atlas.n_meshes):
         raise ValueError("instance_mesh outside [0, %d)" % atlas.n_meshes)
-    if not 0.0 <= float(pixel_offset) <= 1.0:
-        raise ValueError("pixel_offset must lie in [0, 1], got %r" % (pixel_offset,))
-    if not (float(z_near) >= 0.0 and np.isfinite(z_near)):
-        raise ValueError("z_near must be finite and >= 0, got %r" % (z_near,))
+    H, W = _render._check_frame(None, hw, pixel_offset, z_near)
     if not (float(depth_scale) > 0.0 and np.isfinite(depth_scale)):
         raise ValueError("depth_scale must be finite and > 0, got %r" % (depth_scale,))
     S = layout.n_scenes

@@ -25,7 +25,7 @@ def _dev(device=None):
     if not torch.cuda.is_available():
         raise RuntimeError("the OSSID hot path needs a GPU: torch.cuda.is_available() is False and there is no "
                            "CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib._dev()
 
 
 def _f32(x, dev):
