@@ -1129,8 +1129,8 @@ int ossid_feat_match(const uint8_t* scene_descriptors, const uint8_t* scene_ok, 
 int ossid_feat_hypotheses(const int32_t* match, const double* scene_frames, const int32_t* count, int max_keypoints,
                           const double* model_frames, int Nm, int32_t* peaks, double* cand_poses, void* stream);
 
-/* 8f-8  cluttered multi-object RGB-D scenes with BOP ground truth, in place of the offline BlenderProc renders the
- * reference pre-trains on (datasets/render_dataset.py:81-189, datasets/dtoid_dataset.py:97-235) and of the depth corruption
+/* 8f-8  cluttered multi-object RGB-D scenes of vertex-coloured and texture-mapped meshes with BOP ground truth, in place
+ * of the offline BlenderProc renders the reference pre-trains on (datasets/render_dataset.py:81-189, datasets/dtoid_dataset.py:97-235) and of the depth corruption
  * it applies to them (utils/augmentation.py:5-26). SPEC.md section 13 (csrc/scene.hip): this build's own definition. Raw
  * device pointers, caller-owned memory, launches only: nothing allocates, synchronises or is read back; capturable.
  *
@@ -1152,6 +1152,18 @@ int ossid_feat_hypotheses(const int32_t* match, const double* scene_frames, cons
  * Three launches. The CONTENTS of the device arrays are the caller's to check (scenes.py does); an instance whose table
  * entries lead outside an array is not drawn.
  *
+ * ossid_scene_render_textured: ossid_scene_render for an atlas some of whose meshes are texture-mapped (SPEC 7.15-7.17,
+ * 13.3): the same descriptor, workspace and three launches, and depth, instance, face, facing and the amodal masks are
+ * ossid_scene_render's bit for bit. ossid_scene_tex adds uvs f32 [Vt][2] = (u, v), v upwards, beside the atlas's
+ * vertices (the rows of a mesh without a texture are not read); mips, the meshes' mip chains (each in ossid_texture_mips'
+ * layout) back to back, 4-byte aligned, mip_texels texels in all; tex_table int64 [K][3] = (first texel of the mesh's
+ * chain in mips, Ht, Wt), Ht = 0 for a mesh drawn from its vertex colours (its other two entries are not read); and
+ * lod_out int32 [S][H][W] (may be NULL). A pixel whose winning instance's mesh has Ht > 0 gets the colour and level
+ * ossid_raster_textured gives that instance alone, from uvs + 2 v0 and the chain at mips + 4 t0 bytes; any other pixel is
+ * coloured as by ossid_scene_render and has lod -1. desc->colors may hold anything in the rows of textured meshes. An
+ * instance whose mesh's row has Ht < 0, Ht > 0 with Ht or Wt outside [1, OSSID_TEXTURE_MAX_SIDE], t0 < 0, or a chain that
+ * ends past mip_texels is not drawn by any of the three launches: no texel outside [0, mip_texels) is addressed.
+ *
  * ossid_scene_gt_info (13.5): amodal, instance_img = instance_out, sensor_depth f32 [S][H][W] -> gt_info int32 [I][12] =
  * (px_count_all, px_count_visib, px_count_valid, bbox_obj x y w h, bbox_visib x y w h, 0); an empty box is four -1s.
  * Integer atomics only: bit-reproducible. Three launches.
@@ -1165,7 +1177,8 @@ int ossid_feat_hypotheses(const int32_t* match, const double* scene_frames, cons
  * OSSID_EINVAL before any launch: a NULL pointer that is not optional, S outside [1, OSSID_SCENE_MAX_SCENES], I outside
  * [0, S * OSSID_SCENE_MAX_INSTANCES], H W outside (0, OSSID_RASTER_MAX_PIXELS], K < 1, Vt outside [1, 2^29], Ft outside
  * [0, 2^29], work_items outside [0, 2^30], records < 0, Sb not 1 or S with a background, pixel_offset outside [0, 1], z_near negative or not finite, units or unit_inv not positive and finite, a
- * workspace that is too small or misaligned. */
+ * workspace that is too small or misaligned; for ossid_scene_render_textured also a NULL tex_host, uvs, mips or tex_table,
+ * a mips that is not 4-byte aligned, mip_texels < 1. */
 #define OSSID_SCENE_MAX_SCENES 256
 #define OSSID_SCENE_MAX_INSTANCES 1024
 #define OSSID_SCENE_MAX_RECTS 6
@@ -1189,9 +1202,18 @@ typedef struct ossid_scene_desc {
     int32_t Vt, Ft, K, I, S, H, W, Sb, work_items, records;
     float pixel_offset, z_near;
 } ossid_scene_desc;
+typedef struct ossid_scene_tex {
+    const float* uvs;         /* f32 [Vt][2] = (u, v), v upwards; rows of meshes without a texture are not read */
+    const void* mips;         /* the meshes' mip chains (ossid_texture_mips layout) back to back, 4-byte aligned */
+    const int64_t* tex_table; /* int64 [K][3] = (first texel of the mesh's chain in `mips`, Ht, Wt); Ht = 0: vertex colours */
+    int32_t* lod_out;         /* int32 [S][H][W], may be NULL: the level fetched; -1 where nothing is drawn or the winner is vertex-coloured */
+    int64_t mip_texels;       /* texels in `mips` */
+} ossid_scene_tex;
 int ossid_scene_work_items(int n_faces);
 size_t ossid_scene_workspace_bytes(int records, int S, int H, int W);
 int ossid_scene_render(const ossid_scene_desc* desc_host, void* workspace, size_t workspace_bytes, void* stream);
+int ossid_scene_render_textured(const ossid_scene_desc* desc_host, const ossid_scene_tex* tex_host, void* workspace,
+                                size_t workspace_bytes, void* stream);
 int ossid_scene_gt_info(const uint32_t* amodal, const int32_t* instance_img, const float* sensor_depth,
                         const int32_t* scene_first, int I, int S, int H, int W, int32_t* gt_info, void* stream);
 int ossid_scene_sensor(const float* depth, const float* facing, int S, int H, int W, const float* thresholds,

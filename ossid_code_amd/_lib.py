@@ -25,7 +25,8 @@ OSSID_OK = _CONSTS["OSSID_OK"]
 _STRUCT_NAMES = {"ossid_pn2_weights": "PN2Weights", "ossid_conv_desc": "ConvDesc", "ossid_wgrad_desc": "WgradDesc",
                  "ossid_chan_op_desc": "ChanOpDesc", "ossid_pack_row": "PackRow", "ossid_seq_op": "SeqOp",
                  "ossid_pn2_train_params": "PN2TrainParams", "ossid_pn2_train_grads": "PN2TrainGrads",
-                 "ossid_pn2_train_dbg": "PN2TrainDbg", "ossid_scene_desc": "SceneDesc"}
+                 "ossid_pn2_train_dbg": "PN2TrainDbg", "ossid_scene_desc": "SceneDesc",
+                 "ossid_scene_tex": "SceneTex"}
 
 
 def _structure(cname, pyname):

@@ -27,15 +27,15 @@
 // ossid_raster_textured (SPEC 7.16-7.17; BOP models whose colour lives in a UV texture) is ossid_raster_color with another
 // resolve: the same visibility_pass (refusals, workspace, prepare and triangle launches), then per covered pixel the
 // perspective-correct (u, v) at the sample and at its right and lower neighbour, a mip level from their largest
-// difference, and one bilinear fetch (texture.h) from the chain csrc/texture.hip built.
+// difference, and one bilinear fetch (texture.h) from the chain csrc/texture.hip built: raster_common.h's sample_texture,
+// the one csrc/scene.hip calls for a textured winner.
 //
 // What csrc/scene.hip needs as well lives in raster_common.h: the arithmetic of a sample (vertex stage, setup, edge
-// functions, depth, colour), fetch_triangle, the 64-bit shade, wave_walk, the winner's setup and the frame check. This file
-// keeps what is its own: the launch geometry, the z-buffer shade, the coverage statistic and the resolves.
+// functions, depth, colour, texture), fetch_triangle, the 64-bit shade, wave_walk, the winner's setup and the frame check.
+// This file keeps what is its own: the launch geometry, the z-buffer shade, the coverage statistic and the resolves.
 #include <cmath>
 
 #include "raster_common.h"
-#include "texture.h"
 
 namespace {
 
@@ -178,43 +178,15 @@ __global__ __launch_bounds__(256) void raster_resolve_color_kernel(const unsigne
                    });
 }
 
-// (u, v) of the winner w at the fixed-point sample (px, py), SPEC 7.16. Returns the denominator.
-__device__ __forceinline__ double uv_at(const Winner& w, const float* __restrict__ uvs, int px, int py, double& u, double& v) {
-    double b0, b1, b2;
-    const double den = winner_weights(w, px, py, b0, b1, b2);
-    const float *uv0 = uvs + 2 * (size_t)w.i0, *uv1 = uvs + 2 * (size_t)w.i1, *uv2 = uvs + 2 * (size_t)w.i2;
-    u = ((b0 * (double)uv0[0] + b1 * (double)uv1[0]) + b2 * (double)uv2[0]) / den;
-    v = ((b0 * (double)uv0[1] + b1 * (double)uv1[1]) + b2 * (double)uv2[1]) / den;
-    return den;
-}
-
-// SPEC 7.16-7.17: (u, v) at the sample and at the samples of the right and lower neighbour, the level by comparison with
-// powers of two, the bilinear fetch of texture.h.
+// SPEC 7.16-7.17: the winner's texture, by raster_common.h's sample_texture.
 __global__ __launch_bounds__(256) void raster_resolve_textured_kernel(
     const unsigned long long* __restrict__ keys, const int32_t* __restrict__ faces, int V, const VRec* __restrict__ rec,
     const float* __restrict__ uvs, const unsigned* __restrict__ mips, int Ht, int Wt, int H, int W, int o, size_t npix,
     unsigned char* __restrict__ color_out, float* __restrict__ depth_out, int32_t* __restrict__ face_out,
     int32_t* __restrict__ lod_out) {
-    const int top = tex_top_level(Ht, Wt);
     resolve_pixels(keys, faces, V, rec, H, W, npix, color_out, depth_out, face_out, lod_out,
                    [&](const VRec* vr, int i0, int i1, int i2, int x, int y, int c[3]) {
-                       const Winner w = winner_of(vr, i0, i1, i2);
-                       const int px = 256 * x + o, py = 256 * y + o;
-                       double u, v, ux, vx, uy, vy;
-                       uv_at(w, uvs, px, py, u, v);
-                       const double denx = uv_at(w, uvs, px + 256, py, ux, vx);
-                       const double deny = uv_at(w, uvs, px, py + 256, uy, vy);
-                       const double dsx = fabs((ux - u) * (double)Wt), dtx = fabs((vx - v) * (double)Ht);
-                       const double dsy = fabs((uy - u) * (double)Wt), dty = fabs((vy - v) * (double)Ht);
-                       int lod = top;
-                       if (denx > 0.0 && deny > 0.0 && fin(dsx) && fin(dtx) && fin(dsy) && fin(dty)) {
-                           const double m0 = dsx > dtx ? dsx : dtx, m1 = dsy > dty ? dsy : dty;
-                           lod = tex_select_level(m0 > m1 ? m0 : m1, top);
-                       }
-                       double q[3];
-                       tex_bilinear(tex_level(mips, Ht, Wt, lod), u, v, q);
-                       c[0] = tex_round_u8(q[0]), c[1] = tex_round_u8(q[1]), c[2] = tex_round_u8(q[2]);
-                       return lod;
+                       return sample_texture(vr, i0, i1, i2, uvs, mips, Ht, Wt, x, y, o, c);
                    });
 }
 

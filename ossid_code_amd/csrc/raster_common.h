@@ -2,15 +2,17 @@
 // per image) share it: the vertex stage, the snapped 1/256-pixel record, the triangle after setup and the exact edge
 // function with its ownership rule; fetch_triangle (a lane's triangle, checked, set up and classified), the 64-bit shade
 // and wave_walk (the large boxes of a wave, 8 x 8 samples per step); winner_of / winner_weights, the setup every resolve
-// redoes for the triangle that won a pixel; and the host's snap_offset and raster_frame_ok. Both files evaluate a sample
-// with these and the same written f64 expressions, which is what makes a scene image, per pixel, the bits of the winning
-// instance's own render (SPEC 13.3).
+// redoes for the triangle that won a pixel, with both of its surfaces: sample_color (vertex colours) and sample_texture
+// (UVs, level and one bilinear fetch of texture.h's chain); and the host's snap_offset and raster_frame_ok. Both files
+// evaluate a sample with these and the same written f64 expressions, which is what makes a scene image, per pixel, the
+// bits of the winning instance's own render (SPEC 13.3).
 #pragma once
 #include <limits.h>
 
 #include <cmath>
 
 #include "common.h"
+#include "texture.h"
 
 namespace {
 
@@ -203,6 +205,41 @@ __device__ __forceinline__ void sample_color(const VRec* __restrict__ vr, const 
         const double v = ((b0 * (double)c0[ch] + b1 * (double)c1[ch]) + b2 * (double)c2[ch]) / den;
         c[ch] = min(255, max(0, (int)rint(v)));
     }
+}
+
+// (u, v) of the winner w at the fixed-point sample (px, py), SPEC 7.16. Returns the denominator.
+__device__ __forceinline__ double uv_at(const Winner& w, const float* __restrict__ uvs, int px, int py, double& u, double& v) {
+    double b0, b1, b2;
+    const double den = winner_weights(w, px, py, b0, b1, b2);
+    const float *uv0 = uvs + 2 * (size_t)w.i0, *uv1 = uvs + 2 * (size_t)w.i1, *uv2 = uvs + 2 * (size_t)w.i2;
+    u = ((b0 * (double)uv0[0] + b1 * (double)uv1[0]) + b2 * (double)uv2[0]) / den;
+    v = ((b0 * (double)uv0[1] + b1 * (double)uv1[1]) + b2 * (double)uv2[1]) / den;
+    return den;
+}
+
+// Colour of the sample of pixel (x, y) of the winning triangle i0 i1 i2 (indices into rec / uvs) from the Ht x Wt chain
+// at mips, SPEC 7.16-7.17: (u, v) at the sample and at the samples of the right and lower neighbour, the level by
+// comparison with powers of two, the bilinear fetch of texture.h. Returns the level fetched.
+__device__ __forceinline__ int sample_texture(const VRec* __restrict__ vr, int i0, int i1, int i2, const float* __restrict__ uvs,
+                                              const unsigned* __restrict__ mips, int Ht, int Wt, int x, int y, int o, int c[3]) {
+    const int top = tex_top_level(Ht, Wt);
+    const Winner w = winner_of(vr, i0, i1, i2);
+    const int px = 256 * x + o, py = 256 * y + o;
+    double u, v, ux, vx, uy, vy;
+    uv_at(w, uvs, px, py, u, v);
+    const double denx = uv_at(w, uvs, px + 256, py, ux, vx);
+    const double deny = uv_at(w, uvs, px, py + 256, uy, vy);
+    const double dsx = fabs((ux - u) * (double)Wt), dtx = fabs((vx - v) * (double)Ht);
+    const double dsy = fabs((uy - u) * (double)Wt), dty = fabs((vy - v) * (double)Ht);
+    int lod = top;
+    if (denx > 0.0 && deny > 0.0 && fin(dsx) && fin(dtx) && fin(dsy) && fin(dty)) {
+        const double m0 = dsx > dtx ? dsx : dtx, m1 = dsy > dty ? dsy : dty;
+        lod = tex_select_level(m0 > m1 ? m0 : m1, top);
+    }
+    double q[3];
+    tex_bilinear(tex_level(mips, Ht, Wt, lod), u, v, q);
+    c[0] = tex_round_u8(q[0]), c[1] = tex_round_u8(q[1]), c[2] = tex_round_u8(q[2]);
+    return lod;
 }
 
 // 256 * pixel_offset as the integer the samples are taken at: round half to even.

@@ -20,6 +20,14 @@
 //   resolve   one thread per (scene, pixel): the winner's colour, depth, global instance, face and facing, or the background.
 // Minima and ORs do not depend on the order of arrival: every output is bit-reproducible whatever the schedule.
 //
+// ossid_scene_render_textured is the same three launches with an ossid_scene_tex behind the descriptor: a per-mesh
+// texture table (first texel of the mesh's mip chain, Ht, Wt; Ht = 0: vertex colours), the atlas's UV rows and the chains
+// back to back. The kernels are templates over a pack `Tex...` that is empty for ossid_scene_render -- whose
+// instantiations therefore hold no texture code and take the arguments they always took -- and one ossid_scene_tex for
+// the textured entry. There load_instance also checks the mesh's row of the table against mip_texels, so an instance
+// whose row leads outside the chains is not drawn by any of the three, and the resolve colours a winner whose mesh has
+// Ht > 0 by raster_common.h's sample_texture, the function csrc/raster.hip's textured resolve calls.
+//
 // ossid_scene_gt_info: one thread per (instance, 32-pixel mask word); popcounts, per-wave shuffles, a per-workgroup LDS
 // step, then one integer atomic per counter per workgroup. ossid_scene_sensor: one thread per pixel, no random numbers.
 #include <cmath>
@@ -60,10 +68,21 @@ struct Inst {
     bool ok;
 };
 
-__device__ __forceinline__ Inst load_instance(const ossid_scene_desc& d, int inst) {
+// The texture table's row of mesh m leads to texels inside [0, mip_texels) only (a vertex-coloured row, Ht = 0, leads
+// to none); without a table every mesh is vertex-coloured.
+__device__ __forceinline__ bool tex_row_ok(int) { return true; }
+__device__ __forceinline__ bool tex_row_ok(int m, const ossid_scene_tex& t) {
+    const int64_t t0 = t.tex_table[3 * (size_t)m], Ht = t.tex_table[3 * (size_t)m + 1], Wt = t.tex_table[3 * (size_t)m + 2];
+    if (Ht <= 0) return Ht == 0;
+    return Ht <= OSSID_TEXTURE_MAX_SIDE && Wt >= 1 && Wt <= OSSID_TEXTURE_MAX_SIDE && t0 >= 0 && t0 <= t.mip_texels &&
+           (int64_t)tex_total_texels((int)Ht, (int)Wt) <= t.mip_texels - t0;
+}
+
+template <typename... Tex>
+__device__ __forceinline__ Inst load_instance(const ossid_scene_desc& d, int inst, const Tex&... tex) {
     Inst r = {};
     const int m = d.instance_mesh[inst];
-    if (m < 0 || m >= d.K) return r;
+    if (m < 0 || m >= d.K || !tex_row_ok(m, tex...)) return r;
     r.v0 = d.meshes[4 * m], r.nv = d.meshes[4 * m + 1], r.f0 = d.meshes[4 * m + 2], r.nf = d.meshes[4 * m + 3];
     r.rec0 = d.offsets[2 * (size_t)inst + 1];
     r.scene = owner(d.scene_first, d.S, 1, inst);
@@ -74,8 +93,9 @@ __device__ __forceinline__ Inst load_instance(const ossid_scene_desc& d, int ins
     return r;
 }
 
+template <typename... Tex>
 __global__ __launch_bounds__(256) void scene_prepare_kernel(ossid_scene_desc d, VRec* __restrict__ rec,
-                                                            unsigned long long* __restrict__ keys) {
+                                                            unsigned long long* __restrict__ keys, Tex... tex) {
     const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nthreads = (size_t)gridDim.x * 256;
     const size_t npix = (size_t)d.S * d.H * d.W, nwords = (size_t)d.I * d.H * ((d.W + 31) / 32);
     for (size_t i = tid; i < npix; i += nthreads) keys[i] = KFAR;
@@ -85,7 +105,7 @@ __global__ __launch_bounds__(256) void scene_prepare_kernel(ossid_scene_desc d, 
         // the wave's 64 records mostly belong to one instance: one search for the wave, then a short walk per lane
         int inst = owner(d.offsets + 1, d.I, 2, __builtin_amdgcn_readfirstlane((int)i - lane));
         while (inst + 1 < d.I && d.offsets[2 * (size_t)(inst + 1) + 1] <= (int)i) ++inst;
-        const Inst in = load_instance(d, inst);
+        const Inst in = load_instance(d, inst, tex...);
         const int k = (int)i - in.rec0;
         VRec r;
         r.sx = INT_MIN, r.sy = 0, r.rz = 0.0;
@@ -102,13 +122,14 @@ __device__ __forceinline__ void or_bits(unsigned* p, unsigned bits) {
     if ((__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bits) != bits) atomicOr(p, bits);
 }
 
+template <typename... Tex>
 __global__ __launch_bounds__(256) void scene_tri_kernel(ossid_scene_desc d, const VRec* __restrict__ rec,
-                                                        unsigned long long* __restrict__ keys, int o) {
+                                                        unsigned long long* __restrict__ keys, int o, Tex... tex) {
     const int lane = threadIdx.x & 63;
     const int item = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (item >= d.work_items) return;                      // whole waves leave: nothing below synchronises the workgroup
     const int inst = owner(d.offsets, d.I, 2, item);
-    const Inst in = load_instance(d, inst);
+    const Inst in = load_instance(d, inst, tex...);
     if (!in.ok) return;
     const int g = item - d.offsets[2 * (size_t)inst];
     if (g < 0 || g >= items_of(in.nf)) return;
@@ -143,16 +164,36 @@ __global__ __launch_bounds__(256) void scene_tri_kernel(ossid_scene_desc d, cons
     });
 }
 
-// SPEC 13.4, one thread per (scene, pixel).
+// The surface of a winner of a textured atlas (mesh m, vertices from v0, face i0 i1 i2) at pixel (x, y): the mesh's
+// texture when its row of the table has Ht > 0, its vertex colours otherwise. Returns the level fetched, -1 for colours.
+__device__ __forceinline__ int shade_winner(const ossid_scene_desc& d, const ossid_scene_tex& t, const VRec* __restrict__ vr,
+                                            int m, int v0, int i0, int i1, int i2, int x, int y, int o, int c[3]) {
+    // the row passed tex_row_ok when the winner's key was written: the chain lies inside the buffer
+    const int Ht = (int)t.tex_table[3 * (size_t)m + 1];
+    if (Ht <= 0) {
+        sample_color(vr, d.colors + 3 * (size_t)v0, i0, i1, i2, x, y, o, c);
+        return -1;
+    }
+    return sample_texture(vr, i0, i1, i2, t.uvs + 2 * (size_t)v0, (const unsigned*)t.mips + t.tex_table[3 * (size_t)m], Ht,
+                          (int)t.tex_table[3 * (size_t)m + 2], x, y, o, c);
+}
+__device__ __forceinline__ void store_lod(size_t, int) {}
+__device__ __forceinline__ void store_lod(size_t i, int lod, const ossid_scene_tex& t) {
+    if (t.lod_out) t.lod_out[i] = lod;
+}
+
+// SPEC 13.4, one thread per (scene, pixel). TEX says whether the pack holds the textured entry's ossid_scene_tex.
+template <bool TEX, typename... Tex>
 __global__ __launch_bounds__(256) void scene_resolve_kernel(ossid_scene_desc d, const VRec* __restrict__ rec,
-                                                            const unsigned long long* __restrict__ keys, int o) {
+                                                            const unsigned long long* __restrict__ keys, int o, Tex... tex) {
+    static_assert(sizeof...(Tex) == (TEX ? 1 : 0), "one ossid_scene_tex, or none");
     const size_t hw = (size_t)d.H * d.W, npix = (size_t)d.S * hw;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
         const unsigned long long key = keys[i];
         const int scene = (int)(i / hw);
         const int pix = (int)(i - (size_t)scene * hw), y = pix / d.W, x = pix - y * d.W;
         float z = 0.0f, facing = 0.0f;
-        int face = -1, inst = -1, c[3] = {0, 0, 0};
+        int face = -1, inst = -1, lod = -1, c[3] = {0, 0, 0};
         if (key != KFAR) {
             // written by a usable triangle of a checked instance: every index below lies inside its array
             face = (int)((unsigned)key & ((1u << FACE_BITS) - 1u));
@@ -161,7 +202,11 @@ __global__ __launch_bounds__(256) void scene_resolve_kernel(ossid_scene_desc d, 
             const int m = d.instance_mesh[inst], v0 = d.meshes[4 * m], f0 = d.meshes[4 * m + 2];
             const int32_t* f = d.faces + 3 * (size_t)(f0 + face);
             const int i0 = f[0], i1 = f[1], i2 = f[2];
-            sample_color(rec + d.offsets[2 * (size_t)inst + 1], d.colors + 3 * (size_t)v0, i0, i1, i2, x, y, o, c);
+            // the untextured instantiation keeps the call it always made: its code is the one it always was
+            if constexpr (TEX)
+                lod = shade_winner(d, tex..., rec + d.offsets[2 * (size_t)inst + 1], m, v0, i0, i1, i2, x, y, o, c);
+            else
+                sample_color(rec + d.offsets[2 * (size_t)inst + 1], d.colors + 3 * (size_t)v0, i0, i1, i2, x, y, o, c);
             if (d.facing_out) {
                 const float* T = d.transforms + 16 * (size_t)inst;
                 float X0, Y0, Z0, X1, Y1, Z1, X2, Y2, Z2;
@@ -184,6 +229,7 @@ __global__ __launch_bounds__(256) void scene_resolve_kernel(ossid_scene_desc d, 
         d.color_out[3 * i + 2] = (unsigned char)c[2];
         if (d.face_out) d.face_out[i] = face;
         if (d.facing_out) d.facing_out[i] = facing;
+        store_lod(i, lod, tex...);
     }
 }
 
@@ -290,20 +336,10 @@ bool frame_ok(int S, int H, int W) {
     return S >= 1 && S <= OSSID_SCENE_MAX_SCENES && H > 0 && W > 0 && (long long)H * W <= OSSID_RASTER_MAX_PIXELS;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ossid_scene_work_items(int n_faces) {
-    return n_faces < 0 || n_faces > OSSID_RASTER_MAX_FACES ? -1 : items_of(n_faces);
-}
-
-size_t ossid_scene_workspace_bytes(int records, int S, int H, int W) {
-    if (records < 0 || !frame_ok(S, H, W)) return 0;
-    return (size_t)records * sizeof(VRec) + (size_t)S * H * W * sizeof(unsigned long long);
-}
-
-int ossid_scene_render(const ossid_scene_desc* desc_host, void* workspace, size_t workspace_bytes, void* stream) {
+// Both render entries: the refusals, the workspace cut into records and keys, and the three launches, whose kernels take
+// the pack after their own arguments.
+template <typename... Tex>
+int scene_render(const ossid_scene_desc* desc_host, void* workspace, size_t workspace_bytes, void* stream, Tex... tex) {
     if (!desc_host) return OSSID_EINVAL;
     const ossid_scene_desc d = *desc_host;
     const size_t need = ossid_scene_workspace_bytes(d.records, d.S, d.H, d.W);
@@ -323,11 +359,38 @@ int ossid_scene_render(const ossid_scene_desc* desc_host, void* workspace, size_
     unsigned long long* keys = (unsigned long long*)((char*)workspace + (size_t)d.records * sizeof(VRec));
     size_t work = npix > nwords ? npix : nwords;
     if ((size_t)d.records > work) work = (size_t)d.records;
-    hipLaunchKernelGGL(scene_prepare_kernel, dim3(grid_for(work)), dim3(256), 0, s, d, rec, keys);
+    hipLaunchKernelGGL(scene_prepare_kernel<Tex...>, dim3(grid_for(work)), dim3(256), 0, s, d, rec, keys, tex...);
     if (d.work_items > 0 && d.I > 0)
-        hipLaunchKernelGGL(scene_tri_kernel, dim3((unsigned)((d.work_items + 3) / 4)), dim3(256), 0, s, d, rec, keys, o);
-    hipLaunchKernelGGL(scene_resolve_kernel, dim3(grid_for(npix)), dim3(256), 0, s, d, rec, keys, o);
+        hipLaunchKernelGGL(scene_tri_kernel<Tex...>, dim3((unsigned)((d.work_items + 3) / 4)), dim3(256), 0, s, d, rec, keys, o,
+                           tex...);
+    hipLaunchKernelGGL((scene_resolve_kernel<sizeof...(Tex) != 0, Tex...>), dim3(grid_for(npix)), dim3(256), 0, s, d, rec, keys,
+                       o, tex...);
     return ossid_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int ossid_scene_work_items(int n_faces) {
+    return n_faces < 0 || n_faces > OSSID_RASTER_MAX_FACES ? -1 : items_of(n_faces);
+}
+
+size_t ossid_scene_workspace_bytes(int records, int S, int H, int W) {
+    if (records < 0 || !frame_ok(S, H, W)) return 0;
+    return (size_t)records * sizeof(VRec) + (size_t)S * H * W * sizeof(unsigned long long);
+}
+
+int ossid_scene_render(const ossid_scene_desc* desc_host, void* workspace, size_t workspace_bytes, void* stream) {
+    return scene_render(desc_host, workspace, workspace_bytes, stream);
+}
+
+int ossid_scene_render_textured(const ossid_scene_desc* desc_host, const ossid_scene_tex* tex_host, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    if (!tex_host || !tex_host->uvs || !tex_host->mips || !tex_host->tex_table || ((uintptr_t)tex_host->mips & 3) != 0 ||
+        tex_host->mip_texels < 1)
+        return OSSID_EINVAL;
+    return scene_render(desc_host, workspace, workspace_bytes, stream, *tex_host);
 }
 
 int ossid_scene_gt_info(const uint32_t* amodal, const int32_t* instance_img, const float* sensor_depth,

@@ -1,9 +1,10 @@
 """Cluttered multi-object RGB-D scenes with BOP ground truth, rendered on the device (csrc/scene.hip, SPEC.md section 13):
 the data the reference gets from offline BlenderProc renders (datasets/render_dataset.py:81-189,
-datasets/dtoid_dataset.py:97-235) and corrupts with utils/augmentation.py:5-26. A directory of vertex-coloured .ply models
-is enough to train the scorer, run the stream and evaluate it:
+datasets/dtoid_dataset.py:97-235) and corrupts with utils/augmentation.py:5-26. A directory of BOP .ply models, vertex-
+coloured (LM-O) or texture-mapped (YCB-V: `comment TextureFile`, UVs and a PNG beside the model), is enough to train the
+scorer, run the stream and evaluate it:
 
-    atlas = MeshAtlas({obj_id: render.Mesh(V, F, colors=C), ...})          # metres
+    atlas = MeshAtlas({obj_id: render.Mesh(V, F, colors=C), ...})          # metres; or read_models_dir(folder)
     layout = sample_layouts(atlas, 32, 12, cam_K, (480, 640), rng)
     batch = render_scenes(atlas, layout, (480, 640), sensor=sample_sensor(32, (480, 640), rng))
     batch.write_bop(root, "synth")        # bop_eval.BopFolder, tools/eval_bop19.py and read_bop_frames read it back
@@ -30,12 +31,23 @@ def _np(a):
 
 
 class MeshAtlas:
-    """Vertex-coloured meshes packed back to back (SPEC 13.1): vertices f32 [Vt,3], colors u8 [Vt,3], faces int32 [Ft,3]
-    with indices local to their mesh, table int32 [K,4] = (v0, nv, f0, nf), on the host (`*_host`) and on the device of
-    the meshes. meshes: dict obj_id (>= 1) -> render.Mesh with colours, all on one device and in one unit (metres). The
-    last mesh, obj_id TABLE_OBJ_ID, is the unit square [-1, 1]^2 in z = 0 that sample_layouts scales into a table."""
+    """Meshes packed back to back (SPEC 13.1): vertices f32 [Vt,3], colors u8 [Vt,3], faces int32 [Ft,3] with indices
+    local to their mesh, table int32 [K,4] = (v0, nv, f0, nf), on the host (`*_host`) and on the device of the meshes.
+    meshes: dict obj_id (>= 1) -> render.Mesh with vertex colours, a texture or both, all on one device and in one unit
+    (metres). The last mesh, obj_id TABLE_OBJ_ID, is the unit square [-1, 1]^2 in z = 0 that sample_layouts scales into a
+    table; it is vertex-coloured.
 
-    def __init__(self, meshes, table_color=(128, 120, 110)):
+    Each mesh is drawn from the surface render_color would take (render._textured): its vertex colours when it has them,
+    unless use_texture asks for its texture; its texture when that is all it has. use_texture=True asks for every
+    object's texture, a collection of object ids for theirs (an atlas of textured and vertex-coloured models); an object
+    it asks for that has no texture is refused. `textured` is the choice made, a bool per mesh. With a
+    textured mesh the atlas also keeps uvs f32 [Vt,2] (zero rows where unused), mips -- the chosen meshes' Mesh.mips
+    concatenated on the device -- and tex_table int64 [K,3] = (first texel of the mesh's chain, Ht, Wt), zeros for a
+    vertex-coloured mesh; all three are None when no mesh is textured. The colour rows of a texture-only mesh are zeros."""
+
+    uvs = uvs_host = mips = tex_table = tex_table_host = None
+
+    def __init__(self, meshes, table_color=(128, 120, 110), use_texture=False):
         if not isinstance(meshes, dict) or len(meshes) < 1:
             raise ValueError("MeshAtlas: meshes must be a non-empty dict obj_id -> render.Mesh")
         ids = sorted(int(k) for k in meshes)
@@ -43,17 +55,31 @@ class MeshAtlas:
             raise ValueError("MeshAtlas: object ids must be distinct integers >= 1, got %s" % (ids,))
         by_id = {int(k): m for k, m in meshes.items()}
         devices = {str(by_id[i].device) for i in ids if isinstance(by_id[i], _render.Mesh)}
+        if isinstance(use_texture, (bool, np.bool_)):
+            wanted = set(ids) if use_texture else set()
+        else:
+            wanted = {int(o) for o in use_texture}
+        if not wanted <= set(ids):
+            raise ValueError("MeshAtlas: use_texture names objects %s, which the atlas does not hold" % sorted(wanted - set(ids)))
         for i in ids:
             m = by_id[i]
-            if not isinstance(m, _render.Mesh) or m.colors is None:
-                raise ValueError("MeshAtlas: object %d is not a render.Mesh with vertex colours (Mesh(..., colors=...))" % i)
+            if not isinstance(m, _render.Mesh) or (m.colors is None and not _render._has_texture(m)):
+                raise ValueError("MeshAtlas: object %d is not a render.Mesh with vertex colours (Mesh(..., colors=...)) or a "
+                                 "texture (Mesh(..., uvs=..., texture=...), render.load_mesh(path))" % i)
+            if i in wanted and not _render._has_texture(m):
+                raise ValueError("MeshAtlas: use_texture asks for the texture of object %d, which has none" % i)
+            if _render._textured(m, i in wanted) and m.device.type != "cuda":
+                # Mesh builds mip chains on the GPU only, so a host mesh's texture is of no use to an atlas
+                raise ValueError("MeshAtlas: object %d is not a render.Mesh with vertex colours, and a texture is drawn from "
+                                 "on the GPU only (its device is %s)" % (i, m.device))
             if m.n_faces > _lib.RASTER_MAX_FACES:
                 raise ValueError("MeshAtlas: object %d has %d faces, at most %d" % (i, m.n_faces, _lib.RASTER_MAX_FACES))
         if len(devices) != 1:
             raise ValueError("MeshAtlas: the meshes live on different devices: %s" % sorted(devices))
         self.device = by_id[ids[0]].device
         V = [by_id[i].vertices.cpu().numpy() for i in ids] + [np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float32)]
-        C = [by_id[i].colors.cpu().numpy() for i in ids] + [np.tile(np.asarray(table_color, np.uint8), (4, 1))]
+        C = [np.zeros((by_id[i].n_vertices, 3), np.uint8) if by_id[i].colors is None else by_id[i].colors.cpu().numpy()
+             for i in ids] + [np.tile(np.asarray(table_color, np.uint8), (4, 1))]
         F = [by_id[i].faces.cpu().numpy().reshape(-1, 3) for i in ids] + [np.array([[0, 1, 2], [0, 2, 3]], np.int32)]
         self.obj_ids = ids + [TABLE_OBJ_ID]
         self.index_of = {o: k for k, o in enumerate(self.obj_ids)}
@@ -68,11 +94,37 @@ class MeshAtlas:
         self.vertices, self.colors, self.faces, self.table = (
             torch.from_numpy(a).to(self.device) for a in (self.vertices_host, self.colors_host, self.faces_host, self.table_host))
         self.n_meshes = len(self.obj_ids)
+        self.textured = np.array([_render._textured(by_id[i], i in wanted) for i in ids] + [False])
+        if self.textured.any():
+            chosen = [by_id[i] for i, t in zip(ids, self.textured) if t]
+            U = np.zeros((len(self.vertices_host), 2), np.float32)
+            tex = np.zeros((self.n_meshes, 3), np.int64)
+            t0 = 0
+            for k in np.nonzero(self.textured)[0]:
+                m = by_id[ids[k]]
+                U[v0[k]:v0[k] + nv[k]] = m.uvs.cpu().numpy()
+                tex[k] = (t0, m.texture_hw[0], m.texture_hw[1])
+                t0 += m.mips.numel() // 4
+            self.uvs_host, self.tex_table_host = U, tex
+            self.uvs, self.tex_table = torch.from_numpy(U).to(self.device), torch.from_numpy(tex).to(self.device)
+            self.mips = torch.cat([m.mips.reshape(-1) for m in chosen])         # device to device: nothing is rebuilt
 
     def mesh_arrays(self, obj_id):
-        """(vertices f32 [V,3], faces int32 [F,3], colors u8 [V,3]) of one object, host arrays."""
+        """(vertices f32 [V,3], faces int32 [F,3], colors u8 [V,3]) of one object, host arrays; the colours of a mesh that
+        has only a texture are zeros."""
         v0, nv, f0, nf = self.table_host[self.index_of[int(obj_id)]]
         return self.vertices_host[v0:v0 + nv], self.faces_host[f0:f0 + nf], self.colors_host[v0:v0 + nv]
+
+    def texture_arrays(self, obj_id):
+        """(uvs f32 [V,2], image u8 [Ht,Wt,3]) of an object the atlas draws from its texture, host arrays, or None for a
+        vertex-coloured one. The image is level 0 of the object's chain, read back: for the folder writer, not for a loop."""
+        k = self.index_of[int(obj_id)]
+        if not self.textured[k]:
+            return None
+        v0, nv = self.table_host[k, :2]
+        t0, Ht, Wt = (int(v) for v in self.tex_table_host[k])
+        image = self.mips[4 * t0:4 * (t0 + Ht * Wt)].reshape(Ht, Wt, 4)[..., :3].cpu().numpy()
+        return self.uvs_host[v0:v0 + nv], np.ascontiguousarray(image)
 
     def radius(self, obj_id):
         """The largest distance of a vertex from the mesh's origin."""
@@ -251,7 +303,9 @@ def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=
     (sensor=None: the clean sensor, quantisation only), the amodal masks and gt_info. pixel_offset 0 is this package's
     pixel convention, under which the render lines up with depth2xyz (as OnlineStream(mesh_pixel_offset=0.0) assumes).
     depth_scale is the BOP folder's: the 16-bit depth counts units of depth_scale millimetres (the atlas is in metres).
-    Seven launches on the current stream; nothing is read back."""
+    An atlas with a textured mesh (SPEC 13.3) takes ossid_scene_render_textured and also returns lod, the mip level each
+    pixel was fetched at (-1 where nothing is drawn or the winner is vertex-coloured). Seven launches on the current
+    stream either way; nothing is read back."""
     H, W = _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, depth_scale)
     from .model_cloud import _refuse_cpu
     _refuse_cpu(atlas.device)
@@ -293,9 +347,17 @@ def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=
         I=I, S=S, H=H, W=W, Sb=0 if bg is None else int(bg.shape[0]), work_items=items, records=records,
         pixel_offset=float(pixel_offset), z_near=float(z_near))
     units, unit_inv = 1000.0 / float(depth_scale), float(depth_scale) / 1000.0
+    lod = None
     with _lib.on_device(dev):
-        _lib.check(_lib.fn("ossid_scene_render")(ctypes.byref(desc), ws.data_ptr(), ws.numel(), _lib.stream()),
-                   "ossid_scene_render")
+        if atlas.mips is None:
+            _lib.check(_lib.fn("ossid_scene_render")(ctypes.byref(desc), ws.data_ptr(), ws.numel(), _lib.stream()),
+                       "ossid_scene_render")
+        else:
+            lod = torch.empty(S, H, W, dtype=torch.int32, device=dev)
+            tex = _lib.SceneTex(uvs=atlas.uvs.data_ptr(), mips=atlas.mips.data_ptr(), tex_table=atlas.tex_table.data_ptr(),
+                                lod_out=lod.data_ptr(), mip_texels=atlas.mips.numel() // 4)
+            _lib.check(_lib.fn("ossid_scene_render_textured")(ctypes.byref(desc), ctypes.byref(tex), ws.data_ptr(), ws.numel(),
+                                                              _lib.stream()), "ossid_scene_render_textured")
         _lib.check(_lib.fn("ossid_scene_sensor")(clean.data_ptr(), facing.data_ptr(), S, H, W, d_thr.data_ptr(), d_nr.data_ptr(),
                                                  d_rects.data_ptr(), units, unit_inv, u16.data_ptr(), depth.data_ptr(),
                                                  keep.data_ptr(), _lib.stream()), "ossid_scene_sensor")
@@ -303,7 +365,7 @@ def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=
                                                   d_first.data_ptr(), I, S, H, W, gt_info.data_ptr() if I else None,
                                                   _lib.stream()), "ossid_scene_gt_info")
     batch = SceneBatch(atlas, layout, (H, W), color, clean, depth, u16, inst, amodal, gt_info, depth_scale=depth_scale,
-                       face=face, facing=facing, keep=keep)
+                       face=face, facing=facing, keep=keep, lod=lod)
     batch.workspace_bytes = need
     return batch
 
@@ -320,16 +382,17 @@ class SceneBatch:
     color u8 [S,H,W,3]; depth_clean f32 [S,H,W] (metres, 0 = nothing drawn); depth f32 (the sensor's, metres) and
     depth_u16 (what the PNG stores: units of depth_scale millimetres); instance int32 [S,H,W] (index into the layout,
     -1 = nothing drawn); amodal int32 [I,H,ceil(W/32)] bit masks; gt_info int32 [I,12] (SPEC 13.5); optionally face,
-    facing and keep."""
+    facing and keep; lod int32 [S,H,W] (the mip level fetched, -1 where nothing is drawn or the winner is vertex-
+    coloured) from an atlas with a textured mesh, None otherwise."""
 
     workspace_bytes = None
 
     def __init__(self, atlas, layout, hw, color, depth_clean, depth, depth_u16, instance, amodal, gt_info, depth_scale=1.0,
-                 face=None, facing=None, keep=None):
+                 face=None, facing=None, keep=None, lod=None):
         self.atlas, self.layout, self.hw, self.depth_scale = atlas, layout, (int(hw[0]), int(hw[1])), float(depth_scale)
         self.color, self.depth_clean, self.depth, self.depth_u16 = color, depth_clean, depth, depth_u16
         self.instance, self.amodal, self.gt_info = instance, amodal, gt_info
-        self.face, self.facing, self.keep = face, facing, keep
+        self.face, self.facing, self.keep, self.lod = face, facing, keep, lod
         S, I, (H, W) = layout.n_scenes, layout.n_instances, self.hw
         want = {"color": (S, H, W, 3), "depth_clean": (S, H, W), "depth": (S, H, W), "depth_u16": (S, H, W),
                 "instance": (S, H, W), "amodal": (I, H, (W + 31) // 32), "gt_info": (I, 12)}
@@ -375,7 +438,9 @@ class SceneBatch:
 
     def write_bop(self, root, dataset_name, split="test", depth_scale=1.0, diameters=None):
         """The standard BOP layout under <root>/<dataset_name> (millimetres): models/ and models_eval/ (obj_%06d.ply,
-        models_info.json), test_targets_bop19.json, and per scene <split>/%06d/ with rgb/, depth/ (16-bit), mask/,
+        vertex-coloured, or for an object the atlas draws from its texture with `comment TextureFile obj_%06d.png`,
+        per-vertex texture_u texture_v and that PNG beside it; models_info.json), test_targets_bop19.json, and per scene
+        <split>/%06d/ with rgb/, depth/ (16-bit), mask/,
         mask_visib/, scene_camera.json, scene_gt.json, scene_gt_info.json; every scene holds image 0. depth_scale must be
         the one the batch was rendered with. diameters: dict obj_id -> diameter in the atlas's unit; None computes them
         on the device (model_cloud.mesh_diameter)."""
@@ -392,13 +457,17 @@ class SceneBatch:
         info = {}
         for o in objects:
             V, F, C = self.atlas.mesh_arrays(o)
+            tex = self.atlas.texture_arrays(o)
             mm = V.astype(np.float64) * 1000.0
             lo, size = mm.min(0), mm.max(0) - mm.min(0)
             info[str(o)] = {"diameter": float(diameters[o]) * 1000.0, "min_x": float(lo[0]), "min_y": float(lo[1]),
                             "min_z": float(lo[2]), "size_x": float(size[0]), "size_y": float(size[1]), "size_z": float(size[2])}
             for sub in ("models", "models_eval"):
                 os.makedirs(os.path.join(base, sub), exist_ok=True)
-                write_ply(os.path.join(base, sub, "obj_%06d.ply" % o), mm, F, C)
+                if tex is None:
+                    write_ply(os.path.join(base, sub, "obj_%06d.ply" % o), mm, F, C)
+                else:
+                    write_ply_textured(os.path.join(base, sub, "obj_%06d.ply" % o), mm, F, tex[0], tex[1])
         for sub in ("models", "models_eval"):
             with open(os.path.join(base, sub, "models_info.json"), "w") as f:
                 json.dump(info, f, indent=1)
@@ -450,6 +519,30 @@ def write_ply(path, vertices, faces, colors):
         f.write("".join("3 %d %d %d\n" % (t[0], t[1], t[2]) for t in F))
 
 
+def write_ply_textured(path, vertices, faces, uvs, image, texture_name=None):
+    """ASCII PLY with `comment TextureFile NAME`, x y z (repr of the float64) and texture_u texture_v (repr of the f32 as
+    a double: it reads back to the same f32) per vertex, and triangle faces; the image u8 [Ht,Wt,3] is written beside it
+    as the PNG NAME (default: the .ply's own name with .png). render.read_ply_textured returns the UVs (after
+    astype(float32)) and the image byte for byte."""
+    from PIL import Image
+    V, F = np.asarray(vertices, dtype=np.float64), np.asarray(faces)
+    U = np.asarray(uvs, dtype=np.float32)
+    I = _render._check_texture(image, "write_ply_textured: image")
+    if U.shape != (len(V), 2):
+        raise ValueError("write_ply_textured: uvs must be [V,2] = [%d,2], got %s" % (len(V), U.shape))
+    name = os.path.splitext(os.path.basename(path))[0] + ".png" if texture_name is None else str(texture_name)
+    if not name.lower().endswith(".png") or os.path.basename(name) != name:
+        raise ValueError("write_ply_textured: the texture is written as a PNG beside the model, got the name %r" % name)
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\ncomment TextureFile %s\nelement vertex %d\nproperty double x\nproperty double y\n"
+                "property double z\nproperty float texture_u\nproperty float texture_v\nelement face %d\n"
+                "property list uchar int vertex_indices\nend_header\n" % (name, len(V), len(F)))
+        f.write("".join("%r %r %r %r %r\n" % (float(p[0]), float(p[1]), float(p[2]), float(t[0]), float(t[1]))
+                        for p, t in zip(V, U)))
+        f.write("".join("3 %d %d %d\n" % (t[0], t[1], t[2]) for t in F))
+    Image.fromarray(I).save(os.path.join(os.path.dirname(os.path.abspath(path)), name))
+
+
 def read_bop_frames(root, dataset_name, split="test"):
     """The frames of a BOP folder as SceneBatch.frames() yields them (depth in metres, pose_gt in metres): what
     write_bop wrote comes back bit for bit -- image, sensor depth, masks -- and the pose up to the JSON's float64."""
@@ -484,7 +577,8 @@ def read_bop_frames(root, dataset_name, split="test"):
 
 def read_models_dir(models_dir, scale=0.001, device=None):
     """obj_%06d.ply (or any *.ply, numbered in sorted order from 1) of a directory -> dict obj_id -> render.Mesh with
-    colours, scaled (BOP models are in millimetres)."""
+    whatever each model carries (render.load_mesh): vertex colours, a texture named by `comment TextureFile` and found
+    beside the model, or both; scaled (BOP models are in millimetres)."""
     names = sorted(n for n in os.listdir(models_dir) if n.endswith(".ply"))
     if not names:
         raise ValueError("%s holds no .ply model" % models_dir)
@@ -492,6 +586,5 @@ def read_models_dir(models_dir, scale=0.001, device=None):
     for k, n in enumerate(names):
         digits = "".join(c for c in os.path.splitext(n)[0] if c.isdigit())
         obj_id = int(digits) if n.startswith("obj_") and digits else k + 1
-        V, F, C = _render.read_ply_mesh(os.path.join(models_dir, n), with_colors=True)
-        meshes[obj_id] = _render.Mesh(V, F, scale=scale, device=device, colors=C)
+        meshes[obj_id] = _render.load_mesh(os.path.join(models_dir, n), scale=scale, device=device)
     return meshes

@@ -11,7 +11,11 @@ depth, instance, face, the amodal masks and the amodal / visible pixel counts. T
 each route, median of `--rounds` alternating rounds after `--warmup`. Launches: the C ABI's own are counted from the
 calls made; torch's are counted as dispatched device operations (each is at least one kernel).
 
-    python3 tools/bench_scenes.py [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
+--textured draws the same four ellipsoids from a texture each instead (spherical UVs, a seeded 1024 x 1024 image, no
+vertex colours; the table stays vertex-coloured): `scene` is then ossid_scene_render_textured and `composite` renders
+every object by ossid_raster_textured; the mip level is compared as well -> profiles/scenes_textured.json.
+
+    python3 tools/bench_scenes.py [--textured] [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
     rocprofv3 --kernel-trace --stats -d out -- python3 tools/bench_scenes.py --trace       (three untimed calls of `scene`)
 """
 import argparse
@@ -34,6 +38,7 @@ from ossid_code_amd import render, scenes, synth  # noqa: E402
 
 HW = (480, 640)
 AXES = ((0.06, 0.06, 0.06), (0.09, 0.05, 0.04), (0.04, 0.08, 0.06), (0.05, 0.05, 0.10))
+TEXTURE_SIDE = 1024
 
 
 class CountOps(TorchDispatchMode):
@@ -60,11 +65,13 @@ def composite_route(meshes, atlas, layout, T_dev, cams_dev, counter=None):
     inst = torch.full((S, H, W), -1, dtype=torch.int32, device="cuda")
     face = torch.full((S, H, W), -1, dtype=torch.int32, device="cuda")
     amodal = torch.empty(I, H, W, dtype=torch.bool, device="cuda")
+    lod = torch.full((S, H, W), -1, dtype=torch.int32, device="cuda") if atlas.mips is not None else None
     for s in range(S):
         for i in range(int(layout.scene_first[s]), int(layout.scene_first[s + 1])):
             mesh = meshes[atlas.obj_ids[layout.instance_mesh[i]]]
-            c, d, f = render.render_color(mesh, T_dev[i], None, HW, pixel_offset=0.0, z_near=0.05, intrinsics=cams_dev[s:s + 1],
-                                          return_face_id=True)
+            textured = bool(atlas.textured[layout.instance_mesh[i]])
+            c, d, f, *l = render.render_color(mesh, T_dev[i], None, HW, pixel_offset=0.0, z_near=0.05,
+                                              intrinsics=cams_dev[s:s + 1], return_face_id=True, return_lod=textured)
             if counter is not None:
                 counter["c_abi"] += 3
             torch.gt(d, 0, out=amodal[i])
@@ -73,9 +80,12 @@ def composite_route(meshes, atlas, layout, T_dev, cams_dev, counter=None):
             depth[s] = torch.where(take, d, depth[s])
             face[s] = torch.where(take, f, face[s])
             inst[s].masked_fill_(take, i)
+            if lod is not None:
+                lod[s] = torch.where(take, l[0] if textured else -1, lod[s])
     px_all = amodal.sum((1, 2), dtype=torch.int32)
     px_visib = torch.bincount((inst.reshape(-1) + 1).long(), minlength=I + 1)[1:].to(torch.int32)
-    return {"color": color, "depth": depth, "instance": inst, "face": face, "amodal": amodal, "px_all": px_all, "px_visib": px_visib}
+    return {"color": color, "depth": depth, "instance": inst, "face": face, "amodal": amodal, "px_all": px_all,
+            "px_visib": px_visib, "lod": lod}
 
 
 def unpack_device(words, W):
@@ -94,7 +104,8 @@ def once_ms(fn):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scenes.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/scenes.json, or profiles/scenes_textured.json with --textured")
+    ap.add_argument("--textured", action="store_true", help="draw the objects from a 1024 x 1024 texture each")
     ap.add_argument("--scenes", type=int, default=32)
     ap.add_argument("--objects", type=int, default=11, help="objects per scene; the table is one more instance")
     ap.add_argument("--level", type=int, default=6, help="icosphere level of the objects (6: 81 920 faces)")
@@ -104,11 +115,22 @@ def main():
     ap.add_argument("--commit", default=None)
     ap.add_argument("--trace", action="store_true", help="three untimed calls of the scene route, for a kernel trace")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "scenes_textured.json" if a.textured else "scenes.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_scenes.py needs the GPU: there is nothing to time without one")
     torch.cuda.set_device(0)
     V, F = rr.icosphere(a.level)
-    meshes = {k + 1: render.Mesh(V * np.asarray(ax), F, colors=rc.axis_colors(V * np.asarray(ax))[0]) for k, ax in enumerate(AXES)}
+    if a.textured:
+        trng = np.random.default_rng(a.seed + 1)
+        n = V / np.sqrt((V * V).sum(1, keepdims=True))
+        uvs = np.stack([np.arctan2(n[:, 1], n[:, 0]) / (2.0 * np.pi) + 0.5, np.arccos(np.clip(n[:, 2], -1.0, 1.0)) / np.pi], 1)
+        meshes = {k + 1: render.Mesh(V * np.asarray(ax), F, uvs=uvs,
+                                     texture=trng.integers(0, 256, (TEXTURE_SIDE, TEXTURE_SIDE, 3)).astype(np.uint8))
+                  for k, ax in enumerate(AXES)}
+    else:
+        meshes = {k + 1: render.Mesh(V * np.asarray(ax), F, colors=rc.axis_colors(V * np.asarray(ax))[0])
+                  for k, ax in enumerate(AXES)}
     atlas = scenes.MeshAtlas(meshes)
     tv, tf, tc = atlas.mesh_arrays(scenes.TABLE_OBJ_ID)
     meshes[scenes.TABLE_OBJ_ID] = render.Mesh(tv, tf, colors=tc)           # the composite route draws the table too
@@ -133,6 +155,8 @@ def main():
             "amodal": torch.equal(unpack_device(batch.amodal, HW[1]), comp["amodal"]),
             "px_count_all": torch.equal(batch.gt_info[:, 0], comp["px_all"]),
             "px_count_visib": torch.equal(batch.gt_info[:, 1], comp["px_visib"])}
+    if a.textured:
+        same["lod"] = torch.equal(batch.lod, comp["lod"])
     print("outputs equal:", same, flush=True)
     if not all(same.values()):
         raise SystemExit("the routes disagree: %s" % same)
@@ -157,7 +181,8 @@ def main():
     H, W = HW
     I = layout.n_instances
     res = {
-        "workload": {"scenes": a.scenes, "instances": I, "instances_per_scene": a.objects + 1, "frame": list(HW),
+        "workload": {"textured": a.textured, "texture": [TEXTURE_SIDE, TEXTURE_SIDE] if a.textured else None,
+                     "scenes": a.scenes, "instances": I, "instances_per_scene": a.objects + 1, "frame": list(HW),
                      "faces_per_object": int(len(F)), "faces_drawn": int(atlas.table_host[layout.instance_mesh, 3].sum()),
                      "seed": a.seed, "visible_instances": int((g[:, 1] > 0).sum()),
                      "mean_visib_fract": float(np.mean(g[:, 1][g[:, 0] > 0] / g[:, 0][g[:, 0] > 0]))},

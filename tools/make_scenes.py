@@ -1,4 +1,5 @@
-"""Cluttered RGB-D scenes with BOP ground truth from a folder of vertex-coloured models -> a standard BOP folder:
+"""Cluttered RGB-D scenes with BOP ground truth from a folder of BOP models, vertex-coloured or texture-mapped (a .ply
+that names its texture in `comment TextureFile`, the image beside it) -> a standard BOP folder:
 
     python3 tools/make_scenes.py MODELS_DIR OUT_DIR --scenes 32 --objects 6 --seed 0 [--name synth] [--split test]
                                  [--hw 480 640] [--no-mm2m] [--clean] [--no-table] [--depth_scale 1.0]

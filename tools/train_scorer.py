@@ -5,8 +5,8 @@ loads (ckpt = torch.load(path); model.load_state_dict(ckpt['state_dict'])).
     python tools/train_scorer.py --steps 20 --hypotheses 64 --out ckpt.pt
     python tools/train_scorer.py --models MODELS_DIR --scenes 8 --objects 4 --steps 200 --out ckpt.pt
 
-With --models the frames are rendered scenes (scenes.render_scenes, SPEC.md 13) of the vertex-coloured .ply models of
-MODELS_DIR (millimetres, as BOP stores them) with the sampled depth corruption; every step takes the next (scene, object)
+With --models the frames are rendered scenes (scenes.render_scenes, SPEC.md 13) of the .ply models of MODELS_DIR,
+vertex-coloured or texture-mapped (millimetres, as BOP stores them), with the sampled depth corruption; every step takes the next (scene, object)
 frame whose object is at least --min_visib visible, scores synth.perturb_pose hypotheses around its pose_gt against the
 object's own model cloud (model_cloud.sample_model_cloud), with pp_err from scoring.pose_errors.
 
@@ -49,7 +49,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--models", default=None, help="a folder of vertex-coloured .ply models: train on rendered scenes of them")
+    ap.add_argument("--models", default=None, help="a folder of .ply models, vertex-coloured or texture-mapped: train on rendered scenes of them")
     ap.add_argument("--scenes", type=int, default=8)
     ap.add_argument("--objects", type=int, default=4, help="objects per scene (with --models)")
     ap.add_argument("--min_visib", type=float, default=0.25)
