@@ -1220,6 +1220,28 @@ int ossid_scene_sensor(const float* depth, const float* facing, int S, int H, in
                        const int32_t* n_rects, const int32_t* rects, double units, double unit_inv, uint16_t* depth_u16,
                        float* depth_out, uint8_t* keep, void* stream);
 
+/* =============================================================================================
+ * Detector pre-training on rendered scenes (SPEC.md section 15; python/ossid/train.py over
+ * datasets/dtoid_dataset.py:97-236 in the reference, which reads offline BlenderProc renders)
+ * ============================================================================================= */
+
+/* ossid_scene_dtoid_batch: T chosen targets of a rendered scene batch -> the detector's training batch, one launch, no
+ * random numbers. color u8 [S][H][W][3], instance int32 [S][H][W] and gt_info int32 [I][12] are ossid_scene_render's and
+ * ossid_scene_gt_info's outputs; targets int32 [T][2] = (scene s, instance i); jitter f32 [T][8] =
+ * (g_r, g_g, g_b, b_r, b_g, b_b, a, seed -- read as its 32 bits) or NULL (15.3).
+ *   img_out     f32 [T][3][H][W]   (float)u8 / 255.0f, the bits of ossid_dtoid_prep_sample's equal-size path; with a
+ *                                  jitter row, 15.3's steps on top, clamped to [0, 1]
+ *   mask_out    f32 [T][1][H][W]   1 where instance[s] == i, else 0
+ *   bbox_out    f32 [T][1][5]      (x, y, x+w-1, y+h-1, 1) from gt_info's bbox_visib; (2^30, 2^30, -1, -1, -1) when empty
+ *   heatmap_out f64 [T][1][heat_h][heat_w]   ossid_mask_bbox_heatmap's formula around that box's centre with
+ *                                  scale = (double)heat_h / (double)H and `sigma`; zeros for an empty box
+ * A target row with s outside [0, S) or i outside [0, I) writes zeros everywhere and the empty box and reads nothing of
+ * the inputs. Refused before a launch: a NULL buffer (jitter aside), a size or sigma that is not positive, T < 1,
+ * H*W >= 2^30, heat_h*heat_w >= 2^30. */
+int ossid_scene_dtoid_batch(const uint8_t* color, const int32_t* instance, const int32_t* gt_info, int S, int H, int W,
+                            int I, const int32_t* targets, int T, const float* jitter, int heat_h, int heat_w, double sigma,
+                            float* img_out, float* mask_out, float* bbox_out, double* heatmap_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
