@@ -17,6 +17,8 @@
 // butterfly reduce-scatter across the 32 lanes (16 shuffles per 32 channels).
 #include "common.h"
 #include "mfma.h"
+#include "slice_balance.h"
+#include "workgroup.h"
 
 namespace {
 
@@ -546,13 +548,20 @@ constexpr int BQR_WAVES = 8, BQR_THREADS = 64 * BQR_WAVES;
 constexpr int BQR_GROUP = 4;                          // chunks between two tests of the count
 constexpr int BQR_ROW = 64 * (BQR_GROUP + 1);         // ints per wave: slots < 64 + 64 * BQR_GROUP inside a group
 constexpr int BQR_MAX_N = 64 * 48;
+// centres per ball-query workgroup for a set of n points (either form), and workgroups per hypothesis
+inline int ball_cpb(int n) { return n <= BQR_MAX_N ? BQR_CPB : BQ_CPB; }
+inline int ball_parts(int n, int npoint) { return (npoint + ball_cpb(n) - 1) / ball_cpb(n); }
 
 typedef __attribute__((address_space(3))) int lds_int;
 
+// Besides the rows, the ball query can say what the SA kernel that reads them will spend (SPEC 4.5, slice_balance.h):
+// each centre's hit count, capped at 64, as a byte, and the cost of each workgroup's centres as one total. The count is
+// wave-uniform where it is made; the function returns the cost of the centres this wave answered for.
 template <int NCH, bool PLANAR>
-__device__ __forceinline__ void ball_reg_centres(const float* xs, const float* ys, const float* zs, int* row,
-                                                 const float* __restrict__ cen, int* __restrict__ out, int jbeg, int jend,
-                                                 float r2, int lane) {
+__device__ __forceinline__ int ball_reg_centres(const float* xs, const float* ys, const float* zs, int* row,
+                                                const float* __restrict__ cen, int* __restrict__ out,
+                                                unsigned char* __restrict__ hits, int sa2, int jbeg, int jend,
+                                                float r2, int lane) {
     v2f X[NCH / 2], Y[NCH / 2], Z[PLANAR ? 1 : NCH / 2];
 #pragma unroll
     for (int i = 0; i < NCH / 2; ++i) {
@@ -562,6 +571,7 @@ __device__ __forceinline__ void ball_reg_centres(const float* xs, const float* y
     }
     const unsigned row_addr = (unsigned)(size_t)(lds_int*)row;   // (LDS addresses are 32 bits)
     float cx = 0.f, cy = 0.f, cz = 0.f;
+    int cost = 0;
     if (jbeg < jend) cx = cen[3 * (size_t)jbeg], cy = cen[3 * (size_t)jbeg + 1], cz = cen[3 * (size_t)jbeg + 2];
     for (int j = jbeg; j < jend; j += BQR_WAVES) {
         const float ccx = cx, ccy = cy, ccz = cz;
@@ -599,17 +609,39 @@ __device__ __forceinline__ void ball_reg_centres(const float* xs, const float* y
         int first = __builtin_amdgcn_readfirstlane(mine);
         first = cnt > 0 ? first : 0;
         out[(size_t)j * 64 + lane] = lane < cnt ? mine : first;
+        if (hits) {
+            const int capped = min(cnt, 64);
+            if (lane == 0) hits[j] = (unsigned char)capped;
+            cost += centre_cost(capped, sa2);
+        }
+    }
+    return cost;
+}
+
+// the waves' costs, summed through LDS and written with one plain store (every thread of the workgroup calls this)
+template <int NW>
+__device__ __forceinline__ void store_cost_total(int* lds, int wave, int cost, int* __restrict__ dst) {
+    if ((threadIdx.x & 63) == 0) lds[wave] = cost;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sum = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum += lds[w];
+        *dst = sum;
     }
 }
 
 template <int NCH>
 __global__ __launch_bounds__(BQR_THREADS, NCH <= 32 ? 4 : 2) void ball_query_reg_kernel(const float* __restrict__ xyz, int stride, int n,
                                                                      const float* __restrict__ new_xyz, int npoint,
-                                                                     float r2, int* __restrict__ idx) {
+                                                                     float r2, int* __restrict__ idx,
+                                                                     unsigned char* __restrict__ hits,
+                                                                     int* __restrict__ cost_part, int sa2) {
     static_assert(NCH % BQR_GROUP == 0 && BQR_GROUP % 2 == 0, "whole groups of chunk pairs");
     constexpr int N = 64 * NCH;
     __shared__ float xs[N], ys[N], zs[N];
     __shared__ int rows[BQR_WAVES][BQR_ROW];
+    __shared__ int wave_cost[BQR_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
     const float* base = xyz + (size_t)b * n * stride;
@@ -626,10 +658,13 @@ __global__ __launch_bounds__(BQR_THREADS, NCH <= 32 ? 4 : 2) void ball_query_reg
     for (int j = jbeg + tid; j < jend; j += BQR_THREADS) offplane |= (cen[3 * (size_t)j + 2] != 0.0f);
     const bool planar = !__syncthreads_or(offplane);
     int* out = idx + (size_t)b * npoint * 64;
+    unsigned char* hb = hits ? hits + (size_t)b * npoint : nullptr;
+    int cost;
     if (planar)
-        ball_reg_centres<NCH, true>(xs, ys, zs, rows[wave], cen, out, jbeg + wave, jend, r2, lane);
+        cost = ball_reg_centres<NCH, true>(xs, ys, zs, rows[wave], cen, out, hb, sa2, jbeg + wave, jend, r2, lane);
     else
-        ball_reg_centres<NCH, false>(xs, ys, zs, rows[wave], cen, out, jbeg + wave, jend, r2, lane);
+        cost = ball_reg_centres<NCH, false>(xs, ys, zs, rows[wave], cen, out, hb, sa2, jbeg + wave, jend, r2, lane);
+    if (cost_part) store_cost_total<BQR_WAVES>(wave_cost, wave, cost, cost_part + (size_t)b * gridDim.y + blockIdx.y);
 }
 
 // ---- ball query, LDS form: the fallback for point sets over BQR_MAX_N points ----------------------------
@@ -640,9 +675,11 @@ __global__ __launch_bounds__(BQR_THREADS, NCH <= 32 ? 4 : 2) void ball_query_reg
 constexpr int BQ_THREADS = 1024;
 __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __restrict__ xyz, int stride, int n,
                                                                 const float* __restrict__ new_xyz, int npoint, float r2,
-                                                                int* __restrict__ idx) {
+                                                                int* __restrict__ idx, unsigned char* __restrict__ hits,
+                                                                int* __restrict__ cost_part, int sa2) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4* pts = (float4*)smem;
+    int* wave_cost = (int*)(pts + n);  // one int per wave behind the points (dynamic too: the kernel may be given all the LDS)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
     const float* base = xyz + (size_t)b * n * stride;
@@ -650,6 +687,7 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
         pts[k] = make_float4(base[(size_t)k * stride], base[(size_t)k * stride + 1], base[(size_t)k * stride + 2], 0.f);
     __syncthreads();
     const int jend = min((int)(blockIdx.y + 1) * BQ_CPB, npoint);
+    int cost = 0;
     for (int j = blockIdx.y * BQ_CPB + wave; j < jend; j += BQ_THREADS / 64) {
         const float* c = new_xyz + ((size_t)b * npoint + j) * 3;
         const float cx = c[0], cy = c[1], cz = c[2];
@@ -686,17 +724,24 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
         if (first < 0) first = 0;
         if (cnt > 64) cnt = 64;
         if (lane >= cnt) o[lane] = first;
+        if (hits) {
+            if (lane == 0) hits[(size_t)b * npoint + j] = (unsigned char)cnt;
+            cost += centre_cost(cnt, sa2);
+        }
     }
+    if (cost_part) store_cost_total<BQ_THREADS / 64>(wave_cost, wave, cost, cost_part + (size_t)b * gridDim.y + blockIdx.y);
 }
 
 // ---- SA1: gather (K=8) -> 64 -> 64 -> 128 -> max over the group's 64 samples -------------------------
-// One wave per centre; both 32-sample column tiles ride together. The kernel is persistent and runs ONE wave per SIMD
+// One wave per BODY of two 32-column tiles, which carry the distinct samples of one or more centres in granules of 8 columns
+// (the granule stream, below; "centre" in the figures that follow is such a body, and a centre whose 64 samples are all
+// distinct fills one). The kernel is persistent and runs ONE wave per SIMD
 // (512 registers per lane): each wave loads the three packed layers once, straight from the blob, into 50 float4 = 200
 // registers (the packed image is lane-linear: quad q of a layer is the float4 at W4[q * 64 + lane]) and the folded biases of
 // layers 1-2 as four ready-made accumulator tiles (64 registers, the C operand of each chain's first MFMA), then walks a
 // contiguous slice of the centres. All three layers are fully unrolled over their quads (16 + 128 + 256 = 400 MFMAs per
-// centre) and read no operand between MFMAs. A centre's 128 pooled values go to a row of the wave's own staging tile in LDS
-// (one ds_write2st64_b32 per centre), and once per 32 centres the wave applies the per-point part of SA2's first layer to
+// body) and read no operand between MFMAs. A centre's 128 pooled values gather in a row of the wave's own staging tile in LDS
+// (16 ds_max_i32 per body), and once per 32 centres the wave applies the per-point part of SA2's first layer to
 // that tile (sa1_p2_tile: 256 MFMAs, operands and weights read from LDS) and stores P. The layer's weights are staged in LDS
 // once per workgroup behind the kernel's only barrier, in the prologue; after it the four waves run free of each other.
 //
@@ -708,11 +753,12 @@ __global__ __launch_bounds__(BQ_THREADS) void ball_query_kernel(const float* __r
 // and pool read them in place.
 //
 // Register budget (per lane), centre loop: weights 200 + bias tiles 64 + last-layer bias 4 + x 8 + Y1 64 + Y2 64 + accumulators
-// 32 + next centre's gather 13 = 449 at the widest point (layer 2). The per-tile phase runs when the layer temporaries
+// 32 + next body's gather (map entries 2, indices 2) = 440 at the widest point (layer 2); rows 8 and centre coordinates 6 arrive
+// under the last layer. The per-tile phase runs when the layer temporaries
 // (x, Y1, Y2, accumulators: 168) are dead and needs less: the staged tile as B operand 64 + weight quads of the group in use
 // and of the next 32 + one m-tile's accumulator 16 + the next bias tile 16 = 128 beside the same 281 of weights, bias tiles
-// and gather. The build stands at 256 VGPRs + 230 AGPRs (216 before the phase was added: the allocator parks some of its
-// addressing in the AGPR half). tests/test_pn2_resources.py holds the build to zero scratch and 512 registers.
+// and gather. The build stands at 256 VGPRs + 256 AGPRs (230 before the granule stream, 216 before the phase was added: the
+// allocator parks some of its addressing in the AGPR half, 33 v_accvgpr_read per body). tests/test_pn2_resources.py holds the build to zero scratch and 512 registers.
 //
 // The weights are only ever MFMA operands, which may come from the accumulator (AGPR) half of the register file; ReLU and
 // pool are vector instructions, which may not read it. The file is compiled with the VGPR form of the MFMA (_build.py:
@@ -747,8 +793,7 @@ __device__ __forceinline__ void stage_lds(float* dst, const float* __restrict__ 
 // staging tile of SA1_ROWS centres x 128 pooled channels per wave. The row pitch of 132 floats puts the 16 lanes of a
 // ds_read_b128 lane group (same lane half, 16 different rows) on 16 different 16-byte slots of the 256-byte bank row.
 constexpr int SA1_ROWS = 32, SA1_PITCH = 132;
-constexpr int SA1_WP = 0, SA1_BP = 16384, SA1_STAGE = SA1_BP + 128,
-              SA1_LDS_FLOATS = SA1_STAGE + 4 * SA1_ROWS * SA1_PITCH;   // 64 KB | 0.5 KB | 4 x 16.5 KB = 133 632 B
+constexpr int SA1_WP = 0, SA1_BP = 16384, SA1_STAGE = SA1_BP + 128;   // 64 KB | 0.5 KB | 4 x 16.5 KB (| the maps, below)
 
 // The per-point part of SA2's first layer, p[pt][o] = chain(bias, W[:, :128] . feat1[pt]) (the grouped-xyz columns are
 // applied per sample in sa2_kernel, continuing the same chain), for the SA1_ROWS centres of a wave's staging tile: the
@@ -799,15 +844,49 @@ __device__ __forceinline__ void sa1_p2_tile(const float* w, const float* stage, 
     }
 }
 
-// After a centre's pool, lane 32h+c holds channel 32(mt-1+h)+c of m-tile pair (mt-1, mt): the 128 pooled values go to
-// row (centre - first) % SA1_ROWS of the wave's staging tile in LDS instead of to global memory, and once the tile is full
-// (or the slice ends) the wave applies SA2's per-point layer to it (sa1_p2_tile) and stores P -- what a kernel of its own
-// used to do from a feat1 written to and read back from memory. feat1 itself is written only when the caller wants the
-// debug copy (feat != nullptr). The staging tile is private to the wave and LDS operations of one wave complete in order,
-// so the hand-over from the lanes that write a row to the lanes that read it needs no barrier.
+// ---- a persistent wave's slice of the centres (SPEC 4.5, slice_balance.h) --------------------------------------------
+// The 64 lanes share the search: each sums its chunk of the ball query's cost totals into `scratch` (2 x 64 ints of LDS,
+// the wave's own; LDS operations of one wave complete in order), and the walk over the sums is uniform.
+__device__ __forceinline__ void wave_slice(const SliceCosts& sc, int gw, int nw, int* scratch, int lane, int& first, int& end) {
+    scratch[lane] = lane_part_sum(sc, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    auto lane_sums = [&](int k) { return __builtin_amdgcn_readfirstlane(scratch[k]); };
+    auto fill = [&](int p) {
+        scratch[64 + lane] = lane_centre_sum(sc, p, lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        return [=](int k) { return __builtin_amdgcn_readfirstlane(scratch[64 + k]); };
+    };
+    slice_bounds(sc, gw, nw, lane_sums, fill, first, end);
+    first = __builtin_amdgcn_readfirstlane(first), end = __builtin_amdgcn_readfirstlane(end);
+}
+
+// ---- sa1_kernel's granule stream (SPEC 4.5) ----------------------------------------------------------------------------
+// The swapped last layer puts sample column s of a tile in lane half (s >> 2) & 1, register r with r >> 2 == s >> 3: the
+// registers 0..7 and 8..15 of a lane half are two separate sets of 8 columns, and layers 1-2 treat every column on its own.
+// A tile is therefore four GRANULES of 8 columns, keyed (lane half h', j = r >> 3): columns 16 j + 8 k + 4 h' + e, and each
+// granule may carry 8 consecutive slots of a different centre. A centre with d distinct hits needs its first ceil(d / 8)
+// granules (the slots behind repeat the first hit and the pool is a max), so the wave packs the granules its centres need
+// into two-tile bodies, 8 granules each, instead of spending 8 on every centre:
+//   per group of 32 consecutive centres of the slice (one staging tile; the slice's last group may be partial) lanes 0..31
+//   take their centre's hit count, a wave scan places each centre's granules in the group's stream, and a per-wave MAP in
+//   LDS says for every granule of the stream where its first slot is in the ball array (which gives centre, hence staging
+//   row and hypothesis) and the LDS address of its owner's staging row. The stream is padded to whole bodies by repeating
+//   its last granule: the max is idempotent. The next group's map is built when a group opens, into the other buffer;
+//   granule 4 t + 2 j + h' of a body is tile t's (h', j); the gather's lane column c reads slot 4 k + e of it;
+//   the pool is one chain per (tile, j) and lane half, ending in an LDS integer max (no return) into the owner's staging
+//   row, which was zeroed when the group opened: the values are non-negative bit patterns (pool_acc), so the integer max is
+//   the float max, whichever granule of whichever body feeds a row.
+// Every column's fmaf chain and every centre's set of pooled values is what it was; sa1_p2_tile runs when the group's
+// stream is done.
+constexpr int SA1_MAP = 256;           // entries of a map: 32 centres x 8 granules at most, whole bodies
+constexpr int SA1_MAPS = SA1_STAGE + 4 * SA1_ROWS * SA1_PITCH,
+              SA1_LDS_FLOATS = SA1_MAPS + 4 * 2 * 2 * SA1_MAP;   // ... | per wave 2 buffers x (gather map, row map): 150 016 B
+
 __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ point_x, int M,
                                                      const int* __restrict__ ball, const float* __restrict__ cxyz,
-                                                     int np, int total, const float* __restrict__ W1p,
+                                                     int np, int total, const unsigned char* __restrict__ hits,
+                                                     const int* __restrict__ part, int ppb, int cpb,
+                                                     const float* __restrict__ W1p,
                                                      const float* __restrict__ b1, const float* __restrict__ W2p,
                                                      const float* __restrict__ b2, const float* __restrict__ W3p,
                                                      const float* __restrict__ b3, const float* __restrict__ Wpp,
@@ -818,14 +897,16 @@ __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ p
     stage_lds(wl + SA1_WP, Wpp, 16384);
     stage_lds(wl + SA1_BP, bp, 128);
     __syncthreads();                   // the only barrier: every wave passes it before any may leave
-    // this wave's contiguous slice of the centres (consecutive centres mostly share a hypothesis, i.e. a gather base); the
-    // wave index is made visibly uniform so that the centre walk lives in scalar registers
+    // this wave's contiguous slice of the centres, cut by work (consecutive centres mostly share a hypothesis, i.e. a gather
+    // base); the wave index is made visibly uniform so that the walk lives in scalar registers
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int gw = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
-    const int per = total / nw, rem = total % nw;
-    const int first = gw * per + min(gw, rem), end = first + per + (gw < rem ? 1 : 0);
-    if (first >= end) return;          // fewer centres than waves: nothing to do, no weights loaded
+    int* maps = (int*)(wl + SA1_MAPS) + wave * (4 * SA1_MAP);
+    int first, end;
+    wave_slice(SliceCosts{part, hits, (total / np) * ppb, ppb, cpb, np, total, 0}, gw, nw, maps, lane, first, end);
+    if (first >= end) return;          // nothing to do, no weights loaded
     float* stage = wl + SA1_STAGE + wave * (SA1_ROWS * SA1_PITCH);
+    const unsigned stage_addr = (unsigned)(size_t)(lds_int*)stage, maps_addr = (unsigned)(size_t)(lds_int*)maps;
     float4 w1[2], w2[16], w3[32];
     load_quads(w1, W1p, lane);
     load_quads(w2, W2p, lane);
@@ -836,101 +917,167 @@ __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ p
     for (int mt = 0; mt < 2; ++mt) B1[mt] = bias_tile(b1, mt, h), B2[mt] = bias_tile(b2, mt, h);
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) b3v[mt] = b3[mt * 32 + c];
-    // The gather of a centre's 64 samples is two dependent global loads (ball index -> feature row): it is issued one
-    // centre AHEAD -- the indices under the current centre's first layers, the rows under its last layer -- so that a
-    // wave never sits on ~2 memory latencies between centres (there is no partner wave to cover them).
-    int i_n[2];
+
+    // The map of the group of n centres from g0 (its hit counts in lanes 0..31 of cb), into buffer buf: returns its bodies.
+    auto build_map = [&](int buf, int g0, int n, int cb) {
+        const int gc = lane < n ? centre_cost(cb, 0) : 0;
+        const int inc = wave_scan_up(gc, OpAdd(), lane), pos = inc - gc;
+        const int G = __builtin_amdgcn_readlane(inc, 63), Gpad = (G + 7) & ~7;
+        int* gm = maps + buf * (2 * SA1_MAP);
+        int* rm = gm + SA1_MAP;
+        const int e0 = (g0 + lane) * 64, ra = (int)stage_addr + lane * (SA1_PITCH * 4);
+#pragma unroll
+        for (int g = 0; g < 8; ++g)
+            if (g < gc) gm[pos + g] = e0 + 8 * g, rm[pos + g] = ra;
+        if (lane == n - 1) {           // the filler: the stream's last granule again
+#pragma unroll
+            for (int k = 0; k < 7; ++k)
+                if (G + k < Gpad) gm[G + k] = e0 + 8 * (gc - 1), rm[G + k] = ra;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        return Gpad >> 3;
+    };
+    auto gather_map = [&](int buf, int body) { return maps_addr + (unsigned)(buf * (2 * SA1_MAP) + body * 8) * 4u; };
+
+    // The gather of a body's 64 columns is an LDS read (the column's granule) and two dependent global loads (ball index
+    // -> feature row): it is issued one body AHEAD -- the map entry at the top, the indices under the current body's second
+    // layer, the rows and the owners' centre coordinates under its last layer -- so that a wave never sits on ~2 memory
+    // latencies between bodies (there is no partner wave to cover them).
+    const int lq = 2 * (c >> 4) + ((c >> 2) & 1), slot = 4 * ((c >> 3) & 1) + (c & 3);
+    int e_n[2], i_n[2];
     float4 r_n[2];
-    float cn[3];
-    auto fetch_index = [&](int ce) {
-        i_n[0] = ball[(size_t)ce * 64 + c];
-        i_n[1] = ball[(size_t)ce * 64 + 32 + c];
-        cn[0] = cxyz[(size_t)ce * 3], cn[1] = cxyz[(size_t)ce * 3 + 1], cn[2] = cxyz[(size_t)ce * 3 + 2];
+    float cn[2][3];
+    auto read_map = [&](unsigned gm_addr) {
+        const lds_int* m = (const lds_int*)(size_t)(gm_addr + 4 * lq);
+        e_n[0] = m[0], e_n[1] = m[4];
     };
-    auto fetch_rows = [&](int ce) {
-        const size_t base = (size_t)(ce / np) * M;
-        // the indices are consumed HERE: left alone, the compiler widens them right behind their loads in fetch_index
-        // and waits for them there, a memory latency with nothing in flight
-        int i0 = i_n[0], i1 = i_n[1];
-        asm volatile("" : "+v"(i0), "+v"(i1));
-        r_n[0] = *(const float4*)(point_x + (base + i0) * 8 + 4 * h);
-        r_n[1] = *(const float4*)(point_x + (base + i1) * 8 + 4 * h);
+    auto fetch_index = [&]() {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) i_n[t] = ball[(size_t)(unsigned)(e_n[t] + slot)];
     };
-    fetch_index(first);
-    fetch_rows(first);
-    int row = 0;                       // the centre's row in the staging tile
-#pragma unroll 1
-    for (int centre = first; centre < end; ++centre) {
-        const int next = min(centre + 1, end - 1);            // (the last centre prefetches itself: harmless)
-        float4 x[2];
+    // a group of 32 straddles at most one hypothesis boundary: the granules from ball offset bound64 on gather from base_hi
+    auto fetch_rows = [&](int base_lo, int base_hi, int bound64) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            float4 r = r_n[t];
-            if (h == 0) {
-                r.x = r.x - cn[0];
-                r.y = r.y - cn[1];
-                r.z = r.z - cn[2];
-            }
-            x[t] = r;
+            // the index is consumed HERE: left alone, the compiler widens it right behind its load in fetch_index and
+            // waits for it there, a memory latency with nothing in flight
+            int i0 = i_n[t];
+            asm volatile("" : "+v"(i0));
+            const int base = e_n[t] >= bound64 ? base_hi : base_lo;
+            r_n[t] = *(const float4*)(point_x + ((size_t)base + i0) * 8 + 4 * h);
+            const float* cc = cxyz + (size_t)(unsigned)(e_n[t] >> 6) * 3;
+            cn[t][0] = cc[0], cn[t][1] = cc[1], cn[t][2] = cc[2];
         }
-        __builtin_amdgcn_sched_barrier(0);
-        fetch_index(next);
-        __builtin_amdgcn_sched_barrier(0);
-        v16f Y1[2][2], Y2[2][2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
+    };
+
+    int g0 = first, buf = 0;
+    int nb = build_map(0, first, min(32, end - first), hits[min(first + c, end - 1)]);
+    int cbn = hits[min(first + 32 + c, end - 1)];          // the NEXT group's hit counts, a group ahead
+    int base_lo = (first / np) * M, bound64 = (first / np + 1) * np * 64;
+    read_map(gather_map(0, 0));
+    fetch_index();
+    fetch_rows(base_lo, base_lo + M, bound64);
+#pragma unroll 1
+    for (;;) {
+        const int n = min(32, end - g0), g1 = g0 + 32;
+        for (int i = lane; i < SA1_ROWS * SA1_PITCH / 4; i += 64) ((float4*)stage)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        int nb1 = 0, base_lo1 = base_lo, bound641 = bound64;
+        if (g1 < end) {
+            nb1 = build_map(buf ^ 1, g1, min(32, end - g1), cbn);
+            cbn = hits[min(g1 + 32 + c, end - 1)];
+            base_lo1 = (g1 / np) * M, bound641 = (g1 / np + 1) * np * 64;
+        }
+#pragma unroll 1
+        for (int body = 0; body < nb; ++body) {
+            float4 x[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                v16f acc = mfma(w1[mt].x, x[t].x, B1[mt]);
-                acc = mfma(w1[mt].y, x[t].y, acc);
-                acc = mfma(w1[mt].z, x[t].z, acc);
-                acc = mfma(w1[mt].w, x[t].w, acc);
-                Y1[t][mt] = relu16(acc);
+                float4 r = r_n[t];
+                if (h == 0) {
+                    r.x = r.x - cn[t][0];
+                    r.y = r.y - cn[t][1];
+                    r.z = r.z - cn[t][2];
+                }
+                x[t] = r;
+            }
+            // the next body: of this group, the first of the next group, or (the slice's last) itself again: harmless
+            const bool same = body + 1 < nb, cross = !same && nb1 > 0;
+            const int nbase = cross ? base_lo1 : base_lo, nbound = cross ? bound641 : bound64;
+            __builtin_amdgcn_sched_barrier(0);
+            read_map(same ? gather_map(buf, body + 1) : cross ? gather_map(buf ^ 1, 0) : gather_map(buf, body));
+            __builtin_amdgcn_sched_barrier(0);
+            v16f Y1[2][2], Y2[2][2];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    v16f acc = mfma(w1[mt].x, x[t].x, B1[mt]);
+                    acc = mfma(w1[mt].y, x[t].y, acc);
+                    acc = mfma(w1[mt].z, x[t].z, acc);
+                    acc = mfma(w1[mt].w, x[t].w, acc);
+                    Y1[t][mt] = relu16(acc);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_index();
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                v16f acc[2] = {B2[mt], B2[mt]};
+#pragma unroll
+                for (int kq = 0; kq < 8; ++kq) {
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) acc[t] = mfma4(w2[mt * 8 + kq], Y1[t][kq / 4], 4 * (kq % 4), acc[t]);
+                }
+                Y2[0][mt] = relu16(acc[0]);
+                Y2[1][mt] = relu16(acc[1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_rows(nbase, nbase + M, nbound);
+            // the owners' staging rows: entries 4 t + 2 j + h of this body's row map, at the lane's channel
+            unsigned own[2][2];
+            {
+                const lds_int* m = (const lds_int*)(size_t)(gather_map(buf, body) + SA1_MAP * 4 + 4 * h);
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) own[t][j] = (unsigned)m[4 * t + 2 * j] + 4 * c;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // last layer, operands swapped (see mfma4_swapped): registers 0..7 and 8..15 of a tile are a granule each
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                v16f acc[2];
+                acc[0] = acc[1] = splat16(b3v[mt]);
+#pragma unroll
+                for (int kq = 0; kq < 8; ++kq) {
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) acc[t] = mfma4_swapped(Y2[t][kq / 4], 4 * (kq % 4), w3[mt * 8 + kq], acc[t]);
+                }
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        int m = 0;
+#pragma unroll
+                        for (int i = 8 * j; i < 8 * j + 8; i += 2)
+                            m = max(max(m, __float_as_int(acc[t][i])), __float_as_int(acc[t][i + 1]));
+                        __hip_atomic_fetch_max((lds_int*)(size_t)(own[t][j] + 128 * mt), m, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    }
             }
         }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            v16f acc[2] = {B2[mt], B2[mt]};
-#pragma unroll
-            for (int kq = 0; kq < 8; ++kq) {
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[t] = mfma4(w2[mt * 8 + kq], Y1[t][kq / 4], 4 * (kq % 4), acc[t]);
+        // other lanes of this wave wrote the rows a lane reads now: a wavefront-scope fence (no instruction) states it
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (feat) {                    // the debug copy of feat1 (one uniform branch per group)
+            for (int r = 0; r < n; ++r) {
+                float* o = feat + (size_t)(g0 + r) * 128 + lane;
+                o[0] = stage[r * SA1_PITCH + lane], o[64] = stage[r * SA1_PITCH + 64 + lane];
             }
-            Y2[0][mt] = relu16(acc[0]);
-            Y2[1][mt] = relu16(acc[1]);
         }
-        float* srow = stage + row * SA1_PITCH + lane;       // lane = 32 h + c: half h holds the m-tile after half 0's
-        __builtin_amdgcn_sched_barrier(0);
-        fetch_rows(next);
-        __builtin_amdgcn_sched_barrier(0);
-        // last layer, operands swapped (see mfma4_swapped). The merge of the lane halves takes two m-tiles at once, so one
-        // full-wave write puts TWO m-tiles into the staging row (half h holds tile 2j + h)
-        int pooled[4];
-        float out[2];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            v16f acc[2];
-            acc[0] = acc[1] = splat16(b3v[mt]);
-#pragma unroll
-            for (int kq = 0; kq < 8; ++kq) {
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[t] = mfma4_swapped(Y2[t][kq / 4], 4 * (kq % 4), w3[mt * 8 + kq], acc[t]);
-            }
-            pooled[mt] = pool_acc(acc[1], pool_acc(acc[0], 0));
-            if (mt & 1) srow[(mt - 1) * 32] = out[mt / 2] = pool_halves(pooled[mt - 1], pooled[mt]);
-        }
-        if (feat) {                    // the debug copy of feat1 (one uniform branch per centre)
-            float* o = feat + (size_t)centre * 128 + lane;
-            o[0] = out[0], o[64] = out[1];
-        }
-        if (row == SA1_ROWS - 1 || centre == end - 1) {
-            // other lanes of this wave wrote the rows a lane reads now: a wavefront-scope fence (no instruction) states it
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            sa1_p2_tile(wl + opaque_zero(), stage, P, centre - row, row + 1, lane);
-            row = 0;
-        } else {
-            ++row;
-        }
+        sa1_p2_tile(wl + opaque_zero(), stage, P, g0, n, lane);
+        if (!nb1) break;
+        g0 = g1, buf ^= 1, nb = nb1, base_lo = base_lo1, bound64 = bound641;
     }
 }
 
@@ -952,7 +1099,7 @@ __global__ __launch_bounds__(256, 1) void sa1_kernel(const float* __restrict__ p
 // group's mask of small centres. The wave visits the group's large centres in ascending order, then its small ones in
 // ascending order in pairs (1st with 2nd, 3rd with 4th, ...); an odd last one runs as an ordinary two-tile centre. A pair
 // may straddle a hypothesis boundary: its two centres carry a hypothesis each. (sa2_kernel walks this way; sa1_kernel
-// still visits its slice in ascending order, two tiles per centre.)
+// visits its slice in ascending order and packs granules of 8 columns instead, see its granule stream.)
 enum { T_FIRST = 0, T_SECOND = 1, T_SHARED = 2, T_LAST = 3 };   // slots 0..31 of a | 32..63 of a | S(a, b) | 0..31 of b
 
 struct CentreWalk {
@@ -1040,11 +1187,14 @@ struct CentreWalk {
 // registers under the last layer, when X1 is dead) + Y2 64 + accumulator 16 + W3 read buffers 32 + the bias tile read
 // ahead 16 + xyz weights 8 + kept maxima 8 + addressing. tests/test_pn2_resources_sa2_sa3.py holds the build to zero scratch.
 constexpr int SA2_W3 = 0, SA2_B2 = 32768, SA2_B3S = SA2_B2 + 128,
-              SA2_LDS_FLOATS = SA2_B3S + 8 * 4 * 32 * 4;   // W3p 128 KB | b2 | b3 splat tiles 16 KB = 147 968 B
+              SA2_SLICE = SA2_B3S + 8 * 4 * 32 * 4,        // W3p 128 KB | b2 | b3 splat tiles 16 KB | wave_slice's scratch
+              SA2_LDS_FLOATS = SA2_SLICE + 4 * 128;        // = 150 016 B
 
 __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P, const float* __restrict__ xyz1,
                                                      int np1, const int* __restrict__ ball,
                                                      const float* __restrict__ cxyz, int np2, int total,
+                                                     const unsigned char* __restrict__ hits,
+                                                     const int* __restrict__ part, int ppb, int cpb,
                                                      const float* __restrict__ wxyz,
                                                      const float* __restrict__ W2p, const float* __restrict__ b2,
                                                      const float* __restrict__ W3p, const float* __restrict__ b3,
@@ -1060,10 +1210,12 @@ __global__ __launch_bounds__(256, 1) void sa2_kernel(const float* __restrict__ P
             *(float4*)(wl + SA2_B3S + (((threadIdx.x >> 5) * 4 + q) * 32 + (threadIdx.x & 31)) * 4) = make_float4(v, v, v, v);
     }
     __syncthreads();                   // the only barrier: every wave passes it before any may leave
-    const int gw = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = gridDim.x * 4;
-    const int per = total / nw, rem = total % nw;
-    const int first = gw * per + min(gw, rem), end = first + per + (gw < rem ? 1 : 0);
-    if (first >= end) return;          // fewer centres than waves
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gw = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
+    int first, end;                    // the slice, cut by work in half tiles (3 for a small centre, 4 for a large one)
+    wave_slice(SliceCosts{part, hits, (total / np2) * ppb, ppb, cpb, np2, total, 1}, gw, nw, (int*)(wl + SA2_SLICE) + wave * 128,
+               lane, first, end);
+    if (first >= end) return;          // nothing to do
     float4 w2[64];
     load_quads(w2, W2p, lane);
     // A operands of the xyz step for m-tile kt: lane half 0 carries (wx, wz), half 1 (wy, 0), of channel 32 kt + c
@@ -1380,11 +1532,12 @@ struct Workspace {
     int* ball2;
     float* feat2;
     float* feat3;
+    unsigned char *hits1, *hits2;      // the centres' hit counts and the ball-query workgroups' cost totals (slice_balance.h)
+    int *part1, *part2;
     size_t bytes;
 };
 
 Workspace carve(char* base, int B, int M, int np1, int np2) {
-    (void)M;
     Workspace w;
     size_t off = 0;
     auto take = [&](size_t n) {
@@ -1402,6 +1555,10 @@ Workspace carve(char* base, int B, int M, int np1, int np2) {
     w.ball2 = (int*)take((size_t)B * np2 * 64 * 4);
     w.feat2 = (float*)take((size_t)B * np2 * 256 * 4);
     w.feat3 = (float*)take((size_t)B * 1024 * 4);
+    w.hits1 = (unsigned char*)take((size_t)B * np1);
+    w.hits2 = (unsigned char*)take((size_t)B * np2);
+    w.part1 = (int*)take((size_t)B * ball_parts(M, np1) * 4);
+    w.part2 = (int*)take((size_t)B * ball_parts(np1, np2) * 4);
     w.bytes = off;
     return w;
 }
@@ -1429,27 +1586,36 @@ int launch_fps(const float* xyz, int stride, int B, int n, int npoint, int* idx,
     return ossid_launch_status();
 }
 
+// What the ball query tells the SA kernel that reads its rows (null pointers: nothing): the centres' hit counts, the cost
+// total of each workgroup's centres in the unit of `sa2` (ball_cpb says how many centres a workgroup takes).
+struct BallCosts {
+    unsigned char* hits;
+    int* part;
+    int sa2;
+};
+
 template <int NCH>
 int launch_ball_reg(const float* xyz, int stride, int B, int n, const float* new_xyz, int npoint, float r2, int* idx,
-                    hipStream_t s) {
+                    const BallCosts& k, hipStream_t s) {
     hipLaunchKernelGGL(ball_query_reg_kernel<NCH>, dim3(B, (npoint + BQR_CPB - 1) / BQR_CPB), dim3(BQR_THREADS), 0, s, xyz,
-                       stride, n, new_xyz, npoint, r2, idx);
+                       stride, n, new_xyz, npoint, r2, idx, k.hits, k.part, k.sa2);
     return ossid_launch_status();
 }
 
 int launch_ball(const float* xyz, int stride, int B, int n, const float* new_xyz, int npoint, float radius, int* idx,
-                hipStream_t s) {
+                const BallCosts& k, hipStream_t s) {
     const float r2 = radius * radius;
-    if (n <= 64 * 8) return launch_ball_reg<8>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
-    if (n <= 64 * 16) return launch_ball_reg<16>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
-    if (n <= 64 * 32) return launch_ball_reg<32>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
-    if (n <= BQR_MAX_N) return launch_ball_reg<48>(xyz, stride, B, n, new_xyz, npoint, r2, idx, s);
+    if (n <= 64 * 8) return launch_ball_reg<8>(xyz, stride, B, n, new_xyz, npoint, r2, idx, k, s);
+    if (n <= 64 * 16) return launch_ball_reg<16>(xyz, stride, B, n, new_xyz, npoint, r2, idx, k, s);
+    if (n <= 64 * 32) return launch_ball_reg<32>(xyz, stride, B, n, new_xyz, npoint, r2, idx, k, s);
+    if (n <= BQR_MAX_N) return launch_ball_reg<48>(xyz, stride, B, n, new_xyz, npoint, r2, idx, k, s);
     // larger sets: the points stay in LDS
     size_t lds = (size_t)n * 16;
     if (lds > 160 * 1024 - 1024) return OSSID_EINVAL;
+    lds += (BQ_THREADS / 64) * 4;      // the waves' cost totals
     OSSID_ENSURE_LDS(ball_query_kernel, lds);
     hipLaunchKernelGGL(ball_query_kernel, dim3(B, (npoint + BQ_CPB - 1) / BQ_CPB), dim3(BQ_THREADS), lds, s, xyz, stride,
-                       n, new_xyz, npoint, r2, idx);
+                       n, new_xyz, npoint, r2, idx, k.hits, k.part, k.sa2);
     return ossid_launch_status();
 }
 
@@ -1470,7 +1636,7 @@ int ossid_pn2_ball_query(const float* xyz, int stride, int B, int n, const float
     if (B < 0 || n <= 0 || npoint <= 0 || stride < 3 || nsample != 64) return OSSID_EINVAL;
     if (B == 0) return OSSID_OK;
     if (!xyz || !idx || !new_xyz) return OSSID_EINVAL;
-    return launch_ball(xyz, stride, B, n, new_xyz, npoint, radius, idx, (hipStream_t)stream);
+    return launch_ball(xyz, stride, B, n, new_xyz, npoint, radius, idx, BallCosts{nullptr, nullptr, 0}, (hipStream_t)stream);
 }
 
 size_t ossid_pn2_workspace_bytes(int B, int M, int npoint1, int npoint2) {
@@ -1519,6 +1685,7 @@ int pn2_check(const float* point_x, int B, int M, const ossid_pn2_weights* w, vo
     const int np1 = w->npoint1, np2 = w->npoint2;
     if (!point_x || !workspace || !w->blob) return OSSID_EINVAL;
     if (np1 <= 0 || np2 <= 0 || np1 % 32 || np2 % 32 || M < np1 || np1 < np2) return OSSID_EINVAL;
+    if ((long long)B * np1 * 64 > 0x7fffffffLL) return OSSID_EINVAL;     // sa1_kernel's maps hold ball-array offsets as ints
     if (((uintptr_t)workspace & 255) || ((uintptr_t)point_x & 15)) return OSSID_EINVAL;
     c->ws = carve((char*)workspace, B, M, np1, np2);
     if (c->ws.bytes > workspace_bytes) return OSSID_EINVAL;
@@ -1527,9 +1694,13 @@ int pn2_check(const float* point_x, int B, int M, const ossid_pn2_weights* w, vo
 }
 
 int pn2_fps1(const Pn2Call& c) { return launch_fps(c.point_x, 8, c.B, c.M, c.np1, c.ws.fps1, c.ws.xyz1, c.s); }
-int pn2_ball1(const Pn2Call& c) { return launch_ball(c.point_x, 8, c.B, c.M, c.ws.xyz1, c.np1, c.w->radius1, c.ws.ball1, c.s); }
+int pn2_ball1(const Pn2Call& c) {
+    return launch_ball(c.point_x, 8, c.B, c.M, c.ws.xyz1, c.np1, c.w->radius1, c.ws.ball1, BallCosts{c.ws.hits1, c.ws.part1, 0}, c.s);
+}
 int pn2_fps2(const Pn2Call& c) { return launch_fps(c.ws.xyz1, 3, c.B, c.np1, c.np2, c.ws.fps2, c.ws.xyz2, c.s); }
-int pn2_ball2(const Pn2Call& c) { return launch_ball(c.ws.xyz1, 3, c.B, c.np1, c.ws.xyz2, c.np2, c.w->radius2, c.ws.ball2, c.s); }
+int pn2_ball2(const Pn2Call& c) {
+    return launch_ball(c.ws.xyz1, 3, c.B, c.np1, c.ws.xyz2, c.np2, c.w->radius2, c.ws.ball2, BallCosts{c.ws.hits2, c.ws.part2, 1}, c.s);
+}
 
 // persistent grid of sa1_kernel and sa2_kernel: one 4-wave workgroup per CU (one wave per SIMD), cached per device --
 // unless ossid_pn2_set_persistent_grid chose a size (tests: few workgroups make a wave's slice long at a small batch)
@@ -1553,7 +1724,7 @@ int pn2_sa1(const Pn2Call& c, bool want_feat1) {
     const int total = c.B * c.np1;
     OSSID_ENSURE_LDS(sa1_kernel, (size_t)SA1_LDS_FLOATS * 4);
     hipLaunchKernelGGL(sa1_kernel, dim3(persistent_grid()), dim3(256), SA1_LDS_FLOATS * 4, c.s, c.point_x, c.M, c.ws.ball1,
-                       c.ws.xyz1, c.np1, total, blob + c.w->w_off[0], blob + c.w->b_off[0], blob + c.w->w_off[1],
+                       c.ws.xyz1, c.np1, total, c.ws.hits1, c.ws.part1, ball_parts(c.M, c.np1), ball_cpb(c.M), blob + c.w->w_off[0], blob + c.w->b_off[0], blob + c.w->w_off[1],
                        blob + c.w->b_off[1], blob + c.w->w_off[2], blob + c.w->b_off[2], blob + c.w->w_off[3],
                        blob + c.w->b_off[3], want_feat1 ? c.ws.feat1 : nullptr, c.ws.p2);
     return ossid_launch_status();
@@ -1566,7 +1737,8 @@ int pn2_sa2(const Pn2Call& c) {
     const int total = c.B * c.np2;
     OSSID_ENSURE_LDS(sa2_kernel, (size_t)SA2_LDS_FLOATS * 4);
     hipLaunchKernelGGL(sa2_kernel, dim3(persistent_grid()), dim3(256), SA2_LDS_FLOATS * 4, c.s, c.ws.p2, c.ws.xyz1, c.np1, c.ws.ball2,
-                       c.ws.xyz2, c.np2, total, blob + c.w->wxyz2_off, blob + c.w->w_off[4], blob + c.w->b_off[4],
+                       c.ws.xyz2, c.np2, total, c.ws.hits2, c.ws.part2, ball_parts(c.np1, c.np2), ball_cpb(c.np1),
+                       blob + c.w->wxyz2_off, blob + c.w->w_off[4], blob + c.w->b_off[4],
                        blob + c.w->w_off[5], blob + c.w->b_off[5], c.ws.feat2);
     return ossid_launch_status();
 }
