@@ -1220,6 +1220,54 @@ int ossid_scene_sensor(const float* depth, const float* facing, int S, int H, in
                        const int32_t* n_rects, const int32_t* rects, double units, double unit_inv, uint16_t* depth_u16,
                        float* depth_out, uint8_t* keep, void* stream);
 
+/* 8f-9  light for the scenes above (SPEC.md 13.10-13.11, csrc/scene_light.hip): this build's own definition, opt-in; the
+ * render itself stays unlit. Raw device pointers, caller-owned memory, launches only; capturable. No new struct: the
+ * pass takes the render's ossid_scene_desc.
+ *
+ * ossid_mesh_vertex_normals: smooth, area-weighted unit normals of ONE mesh, vertices f32 [V][3], faces int32 [F][3] ->
+ * normals_out f32 [V][3]. Per face with all three indices in [0, V): n = (P1 - P0) x (P2 - P0) in f64 from the f32
+ * coordinates; skipped when a component is not finite; q_c = llrint(ldexp(n_c, shift)) (half to even) is added to the
+ * int64 accumulators of its three vertices by 64-bit integer atomics, so the sum does not depend on the order of
+ * arrival. Per vertex s = (double) acc, nn = (sx sx + sy sy) + sz sz, the output (float)(s_c / sqrt(nn)), or (0, 0, 0)
+ * unless nn > 0 (a vertex no face uses). shift is the caller's (scenes.normals_shift: the largest with
+ * 2 e e 2^shift <= 2^40, e the largest extent of the finite vertices' bounding box; then no accumulator of at most
+ * OSSID_RASTER_MAX_FACES terms reaches 2^63); with another shift a term outside int64 is the caller's error. Hard edges
+ * are not detected: a mesh that wants them duplicates its vertices. The workspace holds the accumulators: int64 [V][3],
+ * 8-byte aligned, ossid_mesh_vertex_normals_workspace_bytes(V) bytes (0 = V outside [1, 2^29]). Three launches: clear,
+ * accumulate (none when F = 0), finish. OSSID_EINVAL before any launch, nothing written: a NULL vertices, normals_out or
+ * workspace, NULL faces with F > 0, F outside [0, OSSID_RASTER_MAX_FACES], |shift| > 1000, a workspace that is too small
+ * or misaligned.
+ *
+ * ossid_scene_light: a deferred shading pass over a rendered batch, one launch, one thread per (scene, pixel), no
+ * workspace, no random numbers. Of desc_host it reads vertices, faces, meshes, instance_mesh, transforms, scene_first,
+ * cams, Vt, Ft, K, I, S, H, W, pixel_offset, z_near (those of the render); colors, offsets, background and the output
+ * pointers are not read and may be NULL. normals f32 [Vt][3] beside the atlas's vertices (each mesh's
+ * ossid_mesh_vertex_normals); albedo u8 [S][H][W][3], instance and face int32 [S][H][W]: the render's color_out,
+ * instance_out and face_out; lights f32 [S][OSSID_SCENE_MAX_LIGHTS][8] = (x, y, z, w, r, g, b, unused) in CAMERA space,
+ * w == 0: (x, y, z) is the direction towards the light, otherwise the position of a point light; n_lights int32 [S]
+ * (clamped to [0, OSSID_SCENE_MAX_LIGHTS]); ambient f32 [S][3]; material f32 [I][2] = (k_s, e), e truncated and clamped
+ * to [0, 10] (not > 0, NaN included: 0): the Blinn-Phong exponent is 2^e. lit_out u8 [S][H][W][3] may be the SAME
+ * buffer as albedo; normal_out f32 [S][H][W][3] (may be NULL): the unit shading normal in camera space, turned towards
+ * the camera. Per pixel, SPEC 13.11: instance < 0 -> lit = albedo, normal 0. Otherwise the winner's three vertices are
+ * projected again (7.2), its weights b0 b1 b2 and den are 7.12's, P = sum(b_j P_j) / den from the f32 camera points,
+ * N = sum(b_j R n_j) from the f32-rotated vertex normals -- the face's own normal (13.4) when that sum has no finite
+ * positive length --, lit_c = rint(albedo_c E_c + 255 (k_s Sp_c)) clamped to [0, 255] (NaN: 0) with E = ambient + sum_l
+ * I_l max(0, N.L_l) and Sp = sum_l I_l (N.H_l)^(2^e) over the lights with N.L_l > 0, all in f64 in the written order. No
+ * cast shadows, no attenuation, no light on the background; a non-uniform scale in transforms is not supported. With
+ * ambient 1 and n_lights 0, lit == albedo. A pixel whose instance is not one of its scene's ([scene_first[s],
+ * scene_first[s+1]) and < I), whose mesh entry leads outside [0, K), Vt or Ft, whose face is outside [0, nf) or has an
+ * index outside [0, nv), an unusable vertex or zero area is copied through with normal 0: nothing outside an array is
+ * addressed. OSSID_EINVAL before the launch: a NULL pointer other than normal_out (of the descriptor: vertices, meshes,
+ * scene_first, cams; faces with Ft > 0; instance_mesh and transforms with I > 0), and the limits ossid_scene_render
+ * applies to S, I, H W, K, Vt, Ft, pixel_offset and z_near. */
+#define OSSID_SCENE_MAX_LIGHTS 4
+size_t ossid_mesh_vertex_normals_workspace_bytes(int V);
+int ossid_mesh_vertex_normals(const float* vertices, const int32_t* faces, int V, int F, int shift, void* workspace,
+                              size_t workspace_bytes, float* normals_out, void* stream);
+int ossid_scene_light(const ossid_scene_desc* desc_host, const float* normals, const uint8_t* albedo, const int32_t* instance,
+                      const int32_t* face, const float* lights, const int32_t* n_lights, const float* ambient,
+                      const float* material, uint8_t* lit_out, float* normal_out, void* stream);
+
 /* =============================================================================================
  * Detector pre-training on rendered scenes (SPEC.md section 15; python/ossid/train.py over
  * datasets/dtoid_dataset.py:97-236 in the reference, which reads offline BlenderProc renders)

@@ -12,6 +12,11 @@ scorer, run the stream and evaluate it:
 
 MeshAtlas, Layout, Sensor and the folder reader and writer are host code and need no device; render_scenes needs one.
 The layout and sensor sampling are build-defined (SPEC 13.7-13.8): host numpy from the caller's Generator.
+
+The scenes are unlit unless asked otherwise (csrc/scene_light.hip, SPEC 13.10-13.12):
+
+    lights, material = sample_lights(layout, rng)                            # or a Lights of your own
+    batch = render_scenes(atlas, layout, (480, 640), lights=lights, material=material)     # .color lit, .albedo, .normal
 """
 import ctypes
 import json
@@ -45,7 +50,20 @@ class MeshAtlas:
     concatenated on the device -- and tex_table int64 [K,3] = (first texel of the mesh's chain, Ht, Wt), zeros for a
     vertex-coloured mesh; all three are None when no mesh is textured. The colour rows of a texture-only mesh are zeros."""
 
-    uvs = uvs_host = mips = tex_table = tex_table_host = None
+    uvs = uvs_host = mips = tex_table = tex_table_host = _normals = None
+
+    @property
+    def normals(self):
+        """f32 [Vt,3] on the atlas's device, row for row beside `vertices`: each mesh's smooth vertex normals (SPEC 13.10,
+        mesh_vertex_normals), built on first use -- an atlas that is never lit never pays for them. Hard edges are not
+        detected; the table's two triangles get their flat normal."""
+        if self._normals is None:
+            out = torch.empty(len(self.vertices_host), 3, dtype=torch.float32, device=self.device)
+            for v0, nv, f0, nf in self.table_host:
+                mesh_vertex_normals(self.vertices[v0:v0 + nv], self.faces[f0:f0 + nf],
+                                    normals_shift(self.vertices_host[v0:v0 + nv]), out=out[v0:v0 + nv])
+            self._normals = out
+        return self._normals
 
     def __init__(self, meshes, table_color=(128, 120, 110), use_texture=False):
         if not isinstance(meshes, dict) or len(meshes) < 1:
@@ -135,9 +153,11 @@ class MeshAtlas:
 class Layout:
     """A draw list (SPEC 13.1): instance_mesh int32 [I] (index into the atlas's table), transforms f64 [I,4,4]
     (model -> camera; rows 0-2 are used, so a scale is allowed), scene_first int32 [S+1] (the instances of a scene are
-    contiguous; an empty scene is legal), cams f32 [S,4] = fx, fy, cx, cy."""
+    contiguous; an empty scene is legal), cams f32 [S,4] = fx, fy, cx, cy. table_mesh: the atlas index of the mesh that
+    is a table, not an object (sample_layouts sets it; sample_lights gives its instances no highlight), or None."""
 
-    def __init__(self, instance_mesh, transforms, scene_first, cams):
+    def __init__(self, instance_mesh, transforms, scene_first, cams, table_mesh=None):
+        self.table_mesh = None if table_mesh is None else int(table_mesh)
         self.instance_mesh = np.ascontiguousarray(np.asarray(instance_mesh).reshape(-1), dtype=np.int32)
         self.transforms = np.ascontiguousarray(np.asarray(transforms, dtype=np.float64).reshape(-1, 4, 4))
         self.scene_first = np.ascontiguousarray(np.asarray(scene_first).reshape(-1), dtype=np.int32)
@@ -239,7 +259,8 @@ def sample_layouts(atlas, n_scenes, objects_per_scene, cam_K, hw, rng, z_range=(
             mesh.append(atlas.index_of[objects[int(k)]])
             T.append(M)
         first.append(len(mesh))
-    return Layout(mesh, np.zeros((0, 4, 4)) if not T else np.stack(T), first, np.tile([fx, fy, cx, cy], (S, 1)))
+    return Layout(mesh, np.zeros((0, 4, 4)) if not T else np.stack(T), first, np.tile([fx, fy, cx, cy], (S, 1)),
+                  table_mesh=atlas.index_of[TABLE_OBJ_ID])
 
 
 def sample_sensor(n_scenes, hw, rng):
@@ -264,6 +285,185 @@ def sample_sensor(n_scenes, hw, rng):
             c1 = min(W - 1, c0 + int(rng.integers(W // 16, W // 4)))
             rects[s, k] = (r0, r1, c0, c1)
     return Sensor(thresholds, n_rects, rects)
+
+
+def normals_shift(vertices):
+    """The fixed-point shift of SPEC 13.10 for one mesh's vertices [V,3], host arithmetic: with e the largest of the
+    three f64 extents of the bounding box of the finite vertices, the largest integer with 2 e e 2^shift <= 2^40; 0 when
+    e = 0 or no vertex is finite. Every term of a vertex's sum is then at most 2^40 in magnitude."""
+    V = np.asarray(vertices, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    V = V[np.isfinite(V).all(1)]
+    e = float((V.max(0) - V.min(0)).max()) if len(V) else 0.0
+    if not e > 0.0:
+        return 0
+    m, x = np.frexp(2.0 * e * e)                 # 2 e e = m 2^x exactly, m in [0.5, 1): m 2^(x + shift) <= 2^40
+    return int(40 - x + (1 if m == 0.5 else 0))
+
+
+def mesh_vertex_normals(vertices, faces, shift=None, out=None):
+    """SPEC 13.10 -> f32 [V,3] on the device of `vertices`: smooth area-weighted unit normals of one mesh (device tensors
+    vertices f32 [V,3], faces int32 [F,3]), bit-reproducible; (0, 0, 0) for a vertex no face uses. shift=None computes
+    normals_shift from a copy of the vertices on the host. Three launches on the current stream."""
+    from .model_cloud import _refuse_cpu
+    if not (torch.is_tensor(vertices) and vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.shape[1] == 3
+            and vertices.shape[0] >= 1):
+        raise ValueError("mesh_vertex_normals: vertices must be a float32 tensor [V,3] with V >= 1")
+    _refuse_cpu(vertices.device)
+    if not (torch.is_tensor(faces) and faces.dtype == torch.int32 and faces.device == vertices.device
+            and faces.numel() % 3 == 0):
+        raise ValueError("mesh_vertex_normals: faces must be an int32 tensor [F,3] on the vertices' device")
+    V, F = int(vertices.shape[0]), faces.numel() // 3
+    if F > _lib.RASTER_MAX_FACES:
+        raise ValueError("mesh_vertex_normals: %d faces, at most %d" % (F, _lib.RASTER_MAX_FACES))
+    shift = normals_shift(vertices.cpu().numpy()) if shift is None else int(shift)
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    if out is None:
+        out = torch.empty(V, 3, dtype=torch.float32, device=vertices.device)
+    elif not (out.dtype == torch.float32 and tuple(out.shape) == (V, 3) and out.is_contiguous() and out.device == vertices.device):
+        raise ValueError("mesh_vertex_normals: out must be a contiguous float32 [V,3] = [%d,3] on the vertices' device" % V)
+    need = int(_lib.fn("ossid_mesh_vertex_normals_workspace_bytes")(V))
+    ws = torch.empty(need // 8, dtype=torch.int64, device=vertices.device)
+    with _lib.on_device(vertices.device):
+        _lib.check(_lib.fn("ossid_mesh_vertex_normals")(vertices.data_ptr(), faces.data_ptr() if F else None, V, F, shift,
+                                                        ws.data_ptr(), need, out.data_ptr(), _lib.stream()),
+                   "ossid_mesh_vertex_normals")
+    return out
+
+
+class Lights:
+    """The lights of SPEC 13.11 per scene, host arrays: lights f32 [S,4,8] = (x, y, z, w, r, g, b, unused) in camera
+    space -- w == 0: (x, y, z) is the direction towards the light, otherwise the position of a point light --, n_lights
+    int32 [S] in [0, 4], ambient f32 [S,3]."""
+
+    def __init__(self, lights, n_lights, ambient):
+        lights, n_lights, ambient = np.asarray(lights), np.asarray(n_lights), np.asarray(ambient)
+        M = _lib.SCENE_MAX_LIGHTS
+        if lights.ndim != 3 or lights.shape[1:] != (M, 8) or lights.dtype.kind != "f":
+            raise ValueError("lights must be a float array [S,%d,8], got %s %s" % (M, lights.dtype, lights.shape))
+        S = lights.shape[0]
+        if n_lights.shape != (S,) or n_lights.dtype.kind not in "iu" or (S and (n_lights.min() < 0 or n_lights.max() > M)):
+            raise ValueError("n_lights must be an integer array [S] = [%d] with values in [0, %d], got %s %s"
+                             % (S, M, n_lights.dtype, n_lights.shape))
+        if ambient.shape != (S, 3) or ambient.dtype.kind != "f":
+            raise ValueError("ambient must be a float array [S,3] = [%d,3], got %s %s" % (S, ambient.dtype, ambient.shape))
+        self.lights = np.ascontiguousarray(lights.astype(np.float32))
+        self.n_lights = np.ascontiguousarray(n_lights.astype(np.int32))
+        self.ambient = np.ascontiguousarray(ambient.astype(np.float32))
+        if not (np.isfinite(self.lights).all() and np.isfinite(self.ambient).all()):
+            raise ValueError("lights and ambient must be finite")
+
+    @property
+    def n_scenes(self):
+        return len(self.n_lights)
+
+    @staticmethod
+    def neutral(n_scenes):
+        """Ambient 1 and no light: the lit image is the albedo, bit for bit."""
+        S = int(n_scenes)
+        return Lights(np.zeros((S, _lib.SCENE_MAX_LIGHTS, 8), np.float32), np.zeros(S, np.int32), np.ones((S, 3), np.float32))
+
+
+def sample_lights(layout, rng, strength=1.0):
+    """SPEC 13.12 (build-defined, host numpy) -> (Lights, material f32 [I,2] = (k_s, e)) for the layout's scenes and
+    instances, drawn from the caller's Generator. Per scene 1 to 3 lights, each directional or a point light with equal
+    odds, on the camera's side of the scene, and a tinted ambient term; per instance a specular weight k_s in [0, 0.3] and
+    an exponent 2^e, e in 3..7. Instances of layout.table_mesh get k_s = 0. strength in [0, 1]
+    scales the departure from Lights.neutral; 0 returns it, with a zero material, and draws nothing. The same
+    Generator state gives the same lights."""
+    if not isinstance(layout, Layout):
+        raise ValueError("sample_lights takes a Layout")
+    if not isinstance(rng, np.random.Generator):
+        raise ValueError("rng must be a numpy.random.Generator")
+    s = float(strength)
+    if not 0.0 <= s <= 1.0:
+        raise ValueError("strength must lie in [0, 1], got %r" % (strength,))
+    S, I = layout.n_scenes, layout.n_instances
+    material = np.zeros((I, 2), np.float32)
+    if s == 0.0:
+        return Lights.neutral(S), material
+    table = layout.table_mesh
+    rows = np.zeros((S, _lib.SCENE_MAX_LIGHTS, 8), np.float64)
+    count, ambient = np.zeros(S, np.int32), np.zeros((S, 3), np.float64)
+    for k in range(S):
+        n = int(rng.integers(1, 4))
+        count[k] = n
+        for l in range(n):
+            point = int(rng.integers(0, 2))
+            g = rng.normal(size=3)
+            t = rng.uniform(0.5, 3.0)                      # drawn for a directional light too: the draw count is fixed
+            base, tint = rng.uniform(0.3, 0.9), rng.uniform(-0.1, 0.1, 3)
+            g[2] = -abs(g[2])                              # the camera's side: the camera looks along +z
+            norm = np.sqrt(g @ g)
+            d = g / norm if norm > 0.0 else np.array([0.0, 0.0, -1.0])
+            rows[k, l, :3] = d * t if point else d
+            rows[k, l, 3] = float(point)
+            rows[k, l, 4:7] = s * (base / n) * (1.0 + tint)
+        a, tint = rng.uniform(0.25, 0.6), rng.uniform(-0.1, 0.1, 3)
+        ambient[k] = (1.0 - s) + s * a * (1.0 + tint)
+    for i in range(I):
+        ks, e = rng.uniform(0.0, 0.3), int(rng.integers(3, 8))
+        material[i] = (0.0 if table is not None and layout.instance_mesh[i] == table else s * ks, e)
+    return Lights(rows.astype(np.float32), count, ambient.astype(np.float32)), material
+
+
+def _check_lights(layout, lights, material):
+    """-> material f32 [I,2] (zeros for None) after the checks of a Lights and a material against a layout."""
+    if not isinstance(lights, Lights) or lights.n_scenes != layout.n_scenes:
+        raise ValueError("lights must be a Lights of the layout's %d scenes" % layout.n_scenes)
+    I = layout.n_instances
+    if material is None:
+        return np.zeros((I, 2), np.float32)
+    material = np.asarray(material)
+    if material.shape != (I, 2) or material.dtype.kind != "f" or not np.isfinite(material).all():
+        raise ValueError("material must be a finite float array [I,2] = [%d,2] of (k_s, e), got %s %s"
+                         % (I, material.dtype, material.shape))
+    return np.ascontiguousarray(material.astype(np.float32))
+
+
+def _light_pass(desc, atlas, layout, hw, albedo, instance, face, lights, material, normals, out):
+    """ossid_scene_light on the current stream over the images of a render made with `desc` -> (lit, normal)."""
+    dev, S, (H, W) = atlas.device, layout.n_scenes, hw
+    up = lambda a: torch.from_numpy(a).to(dev)
+    d_l, d_n, d_a, d_m = up(lights.lights), up(lights.n_lights), up(lights.ambient), up(material)
+    if d_m.numel() == 0:
+        d_m = torch.zeros(1, 2, dtype=torch.float32, device=dev)             # the entry refuses NULL; no row is read
+    lit = torch.empty(S, H, W, 3, dtype=torch.uint8, device=dev) if out is None else out
+    normal = torch.empty(S, H, W, 3, dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.fn("ossid_scene_light")(ctypes.byref(desc), normals.data_ptr(), albedo.data_ptr(), instance.data_ptr(),
+                                                face.data_ptr(), d_l.data_ptr(), d_n.data_ptr(), d_a.data_ptr(), d_m.data_ptr(),
+                                                lit.data_ptr(), normal.data_ptr(), _lib.stream()), "ossid_scene_light")
+    return lit, normal
+
+
+def light_scenes(atlas, layout, hw, albedo, instance, face, lights, material=None, normals=None, out=None,
+                 pixel_offset=0.0, z_near=0.05):
+    """SPEC 13.11 on images a render of (atlas, layout, hw, pixel_offset, z_near) returned -> (lit u8 [S,H,W,3], normal
+    f32 [S,H,W,3]): the deferred shading pass render_scenes(lights=...) runs, for a caller that holds the images. albedo
+    u8 [S,H,W,3], instance and face int32 [S,H,W] are device tensors (SceneBatch.color, .instance, .face); material f32
+    [I,2] = (k_s, e), None for no highlights; normals f32 [Vt,3] replaces atlas.normals; out may be albedo itself. The
+    kernel checks instance and face: a pixel whose values lead outside an array is copied through. One launch."""
+    H, W = _check_layout(atlas, layout, None, None, hw, pixel_offset, z_near, 1.0)
+    from .model_cloud import _refuse_cpu
+    _refuse_cpu(atlas.device)
+    dev, S, I = atlas.device, layout.n_scenes, layout.n_instances
+    material = _check_lights(layout, lights, material)
+    normals = atlas.normals if normals is None else normals
+    for name, t, dtype, shape in (("albedo", albedo, torch.uint8, (S, H, W, 3)), ("instance", instance, torch.int32, (S, H, W)),
+                                  ("face", face, torch.int32, (S, H, W)),
+                                  ("normals", normals, torch.float32, (len(atlas.vertices_host), 3))) + \
+            ((("out", out, torch.uint8, (S, H, W, 3)),) if out is not None else ()):
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
+            raise ValueError("light_scenes: %s must be a contiguous %s tensor %s on the atlas's device" % (name, dtype, shape))
+    up = lambda a: torch.from_numpy(a).to(dev)
+    d_mesh, d_T, d_first, d_cams = (up(layout.instance_mesh), up(layout.transforms.astype(np.float32)), up(layout.scene_first),
+                                    up(layout.cams))
+    desc = _lib.SceneDesc(
+        vertices=atlas.vertices.data_ptr(), faces=atlas.faces.data_ptr(), meshes=atlas.table.data_ptr(),
+        instance_mesh=d_mesh.data_ptr() if I else None, transforms=d_T.data_ptr() if I else None,
+        scene_first=d_first.data_ptr(), cams=d_cams.data_ptr(), Vt=len(atlas.vertices_host), Ft=len(atlas.faces_host),
+        K=atlas.n_meshes, I=I, S=S, H=H, W=W, pixel_offset=float(pixel_offset), z_near=float(z_near))
+    return _light_pass(desc, atlas, layout, (H, W), albedo, instance, face, lights, material, normals, out)
 
 
 def work_offsets(atlas, layout):
@@ -298,17 +498,29 @@ def _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, d
     return H, W
 
 
-def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=0.0, z_near=0.05, depth_scale=1.0):
+def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=0.0, z_near=0.05, depth_scale=1.0,
+                  lights=None, material=None):
     """SPEC 13.2-13.6 -> SceneBatch of device tensors: the layout's scenes drawn with mutual occlusion, the sensor's depth
     (sensor=None: the clean sensor, quantisation only), the amodal masks and gt_info. pixel_offset 0 is this package's
     pixel convention, under which the render lines up with depth2xyz (as OnlineStream(mesh_pixel_offset=0.0) assumes).
     depth_scale is the BOP folder's: the 16-bit depth counts units of depth_scale millimetres (the atlas is in metres).
     An atlas with a textured mesh (SPEC 13.3) takes ossid_scene_render_textured and also returns lod, the mip level each
     pixel was fetched at (-1 where nothing is drawn or the winner is vertex-coloured). Seven launches on the current
-    stream either way; nothing is read back."""
+    stream either way; nothing is read back.
+
+    lights: a Lights of the layout's scenes (sample_lights, or Lights.neutral) lights the drawn pixels by one more launch
+    after the render (SPEC 13.11): `color` is then the lit image, `albedo` the unlit one and `normal` f32 [S,H,W,3] the
+    shading normals; material f32 [I,2] = (k_s, e) per instance, None for no highlights. Depth, instance, face, facing,
+    the masks, gt_info and the sensor do not depend on the lights. With lights=None the function is the unlit one:
+    the same launches, the same bits, albedo and normal None."""
     H, W = _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, depth_scale)
     from .model_cloud import _refuse_cpu
     _refuse_cpu(atlas.device)
+    if lights is not None:
+        material = _check_lights(layout, lights, material)
+        normals = atlas.normals               # built here, ahead of the render's launches, on first use
+    elif material is not None:
+        raise ValueError("render_scenes: material is given without lights")
     dev = atlas.device
     S, I = layout.n_scenes, layout.n_instances
     offsets = work_offsets(atlas, layout)
@@ -364,8 +576,12 @@ def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=
         _lib.check(_lib.fn("ossid_scene_gt_info")(amodal.data_ptr() if I else None, inst.data_ptr(), depth.data_ptr(),
                                                   d_first.data_ptr(), I, S, H, W, gt_info.data_ptr() if I else None,
                                                   _lib.stream()), "ossid_scene_gt_info")
+    albedo = normal = None
+    if lights is not None:
+        albedo = color
+        color, normal = _light_pass(desc, atlas, layout, (H, W), albedo, inst, face, lights, material, normals, None)
     batch = SceneBatch(atlas, layout, (H, W), color, clean, depth, u16, inst, amodal, gt_info, depth_scale=depth_scale,
-                       face=face, facing=facing, keep=keep, lod=lod)
+                       face=face, facing=facing, keep=keep, lod=lod, albedo=albedo, normal=normal)
     batch.workspace_bytes = need
     return batch
 
@@ -383,12 +599,15 @@ class SceneBatch:
     depth_u16 (what the PNG stores: units of depth_scale millimetres); instance int32 [S,H,W] (index into the layout,
     -1 = nothing drawn); amodal int32 [I,H,ceil(W/32)] bit masks; gt_info int32 [I,12] (SPEC 13.5); optionally face,
     facing and keep; lod int32 [S,H,W] (the mip level fetched, -1 where nothing is drawn or the winner is vertex-
-    coloured) from an atlas with a textured mesh, None otherwise."""
+    coloured) from an atlas with a textured mesh, None otherwise. From a lit render (render_scenes(lights=...)) color is
+    the lit image, albedo u8 [S,H,W,3] the unlit one and normal f32 [S,H,W,3] the shading normals (SPEC 13.11); both are
+    None otherwise."""
 
     workspace_bytes = None
 
     def __init__(self, atlas, layout, hw, color, depth_clean, depth, depth_u16, instance, amodal, gt_info, depth_scale=1.0,
-                 face=None, facing=None, keep=None, lod=None):
+                 face=None, facing=None, keep=None, lod=None, albedo=None, normal=None):
+        self.albedo, self.normal = albedo, normal
         self.atlas, self.layout, self.hw, self.depth_scale = atlas, layout, (int(hw[0]), int(hw[1])), float(depth_scale)
         self.color, self.depth_clean, self.depth, self.depth_u16 = color, depth_clean, depth, depth_u16
         self.instance, self.amodal, self.gt_info = instance, amodal, gt_info

@@ -15,8 +15,15 @@ calls made; torch's are counted as dispatched device operations (each is at leas
 vertex colours; the table stays vertex-coloured): `scene` is then ossid_scene_render_textured and `composite` renders
 every object by ossid_raster_textured; the mip level is compared as well -> profiles/scenes_textured.json.
 
-    python3 tools/bench_scenes.py [--textured] [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
-    rocprofv3 --kernel-trace --stats -d out -- python3 tools/bench_scenes.py --trace       (three untimed calls of `scene`)
+--lights times the light instead (csrc/scene_light.hip, SPEC 13.10-13.11) on the same workload, the same way -- HIP events,
+alternating rounds in one call -> profiles/scenes_lit.json: `render` is the unlit scenes.render_scenes, `pass` the
+shading pass alone over the images a render left (scenes.light_scenes, one launch), `lit` render_scenes(lights=...),
+the two together; and the one-off build of the atlas's vertex normals (three launches per mesh), cold and warm. The lit
+image is checked against the pass over the unlit render, and neutral lights against the albedo, first.
+
+    python3 tools/bench_scenes.py [--textured | --lights] [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
+    rocprofv3 --kernel-trace --stats -d out -- python3 tools/bench_scenes.py --trace       (three untimed calls of `scene`;
+                                                                          with --lights: of the lit render, normals first)
 """
 import argparse
 import json
@@ -102,10 +109,82 @@ def once_ms(fn):
     return a.elapsed_time(b), out
 
 
+def stats(ms):
+    return {"ms": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}
+
+
+def bench_lit(a, atlas, layout, sensor, n_faces):
+    """The legs of --lights -> the result dict."""
+    H, W = HW
+    lights, material = scenes.sample_lights(layout, np.random.default_rng(np.random.SeedSequence(a.seed, spawn_key=(0,))))
+
+    def build_normals():
+        atlas._normals = None
+        return atlas.normals
+    cold_ms, normals = once_ms(build_normals)
+    warm = [once_ms(build_normals)[0] for _ in range(max(a.rounds, 3))]
+    render_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor)  # noqa: E731
+    lit_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor, lights=lights, material=material)  # noqa: E731
+    unlit = render_fn()
+    pass_fn = lambda: scenes.light_scenes(atlas, layout, HW, unlit.color, unlit.instance, unlit.face, lights, material)  # noqa: E731
+    batch, (lit, normal) = lit_fn(), pass_fn()
+    neutral = scenes.light_scenes(atlas, layout, HW, unlit.color, unlit.instance, unlit.face, scenes.Lights.neutral(a.scenes), material)[0]
+    same = {"albedo": torch.equal(batch.albedo, unlit.color), "lit": torch.equal(batch.color, lit),
+            "normal": torch.equal(batch.normal.view(torch.int32), normal.view(torch.int32)),
+            "neutral_is_albedo": torch.equal(neutral, unlit.color),
+            "geometry": all(torch.equal(getattr(batch, n), getattr(unlit, n)) for n in ("depth_clean", "depth_u16", "instance", "face", "gt_info"))}
+    print("outputs equal:", same, flush=True)
+    if not all(same.values()):
+        raise SystemExit("the lit and the unlit route disagree: %s" % same)
+    drawn = float((unlit.instance >= 0).float().mean())
+    changed = float((batch.color != batch.albedo).any(-1).float().mean())
+    del batch, lit, normal, neutral
+    for _ in range(a.warmup):
+        render_fn(), pass_fn(), lit_fn()
+    torch.cuda.synchronize()
+    t = {"render": [], "pass": [], "lit": []}
+    for _ in range(a.rounds):
+        for name, fn in (("render", render_fn), ("pass", pass_fn), ("lit", lit_fn)):
+            t[name].append(once_ms(fn)[0])
+    npix = a.scenes * H * W
+    res = {"workload": {"scenes": a.scenes, "instances": layout.n_instances, "instances_per_scene": a.objects + 1, "frame": list(HW),
+                        "faces_per_object": n_faces, "seed": a.seed, "drawn_pixel_fraction": drawn, "changed_pixel_fraction": changed,
+                        "lights_per_scene": [int(v) for v in lights.n_lights]},
+           "outputs_equal": same,
+           "render": dict(stats(t["render"]), c_abi_launches=7),
+           "pass": dict(stats(t["pass"]), c_abi_launches=1,
+                        # albedo, instance, face in; lit and the normal image out
+                        bytes_moved=int(npix * (3 + 4 + 4 + 3 + 12))),
+           "lit": dict(stats(t["lit"]), c_abi_launches=8),
+           "vertex_normals": {"cold_ms": float(cold_ms), "warm": stats(warm), "meshes": atlas.n_meshes,
+                              "vertices": int(len(atlas.vertices_host)), "faces": int(len(atlas.faces_host)),
+                              "c_abi_launches": 3 * atlas.n_meshes},
+           "rounds": a.rounds, "warmup": a.warmup}
+    res["ratio_pass_over_render"] = res["pass"]["ms"] / res["render"]["ms"]
+    res["ratio_lit_over_render"] = res["lit"]["ms"] / res["render"]["ms"]
+    return res
+
+
+def finish(a, res):
+    commit = a.commit
+    if commit is None:
+        try:
+            commit = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+        except Exception:
+            commit = "unknown"
+    res.update(commit=commit, box={"gpu": torch.cuda.get_device_name(0), "torch": torch.__version__, "hip": torch.version.hip})
+    print(json.dumps(res), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default: profiles/scenes.json, or profiles/scenes_textured.json with --textured")
     ap.add_argument("--textured", action="store_true", help="draw the objects from a 1024 x 1024 texture each")
+    ap.add_argument("--lights", action="store_true", help="time the shading pass and the vertex normals -> profiles/scenes_lit.json")
     ap.add_argument("--scenes", type=int, default=32)
     ap.add_argument("--objects", type=int, default=11, help="objects per scene; the table is one more instance")
     ap.add_argument("--level", type=int, default=6, help="icosphere level of the objects (6: 81 920 faces)")
@@ -115,8 +194,10 @@ def main():
     ap.add_argument("--commit", default=None)
     ap.add_argument("--trace", action="store_true", help="three untimed calls of the scene route, for a kernel trace")
     a = ap.parse_args()
+    if a.lights and a.textured:
+        raise SystemExit("--lights times the pass over the vertex-coloured workload; it does not combine with --textured")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "scenes_textured.json" if a.textured else "scenes.json")
+        a.out = os.path.join(ROOT, "profiles", "scenes_lit.json" if a.lights else ("scenes_textured.json" if a.textured else "scenes.json"))
     if not torch.cuda.is_available():
         raise SystemExit("bench_scenes.py needs the GPU: there is nothing to time without one")
     torch.cuda.set_device(0)
@@ -139,10 +220,15 @@ def main():
     sensor = scenes.sample_sensor(a.scenes, HW, rng)
     scene_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor)  # noqa: E731
     if a.trace:
+        if a.lights:                                       # the normals' three launches per mesh, then the eight of a lit render
+            lights, material = scenes.sample_lights(layout, np.random.default_rng(np.random.SeedSequence(a.seed, spawn_key=(0,))))
+            scene_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor, lights=lights, material=material)  # noqa: E731
         for _ in range(3):
             scene_fn()
         torch.cuda.synchronize()
         return
+    if a.lights:
+        return finish(a, bench_lit(a, atlas, layout, sensor, int(len(F))))
     T_dev = torch.from_numpy(layout.transforms.astype(np.float32)).cuda()
     cams_dev = torch.from_numpy(layout.cams).cuda()
     comp_fn = lambda: composite_route(meshes, atlas, layout, T_dev, cams_dev)  # noqa: E731
@@ -195,18 +281,7 @@ def main():
                       "amodal_bytes": int(I * H * W), "frames_touched": I},
         "rounds": a.rounds, "warmup": a.warmup}
     res["ratio_composite_over_scene"] = res["composite"]["ms"] / res["scene"]["ms"]
-    commit = a.commit
-    if commit is None:
-        try:
-            commit = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
-        except Exception:
-            commit = "unknown"
-    res.update(commit=commit, box={"gpu": torch.cuda.get_device_name(0), "torch": torch.__version__, "hip": torch.version.hip})
-    print(json.dumps(res), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print("wrote", a.out)
+    finish(a, res)
 
 
 if __name__ == "__main__":

@@ -4,12 +4,14 @@ scripts/online_learning.py:153-167 starts from (--dtoid_weights_path; :161-162 l
 
     python tools/pretrain_dtoid.py --models MODELS_DIR --steps N --out ckpt.pt \
         [--batch 8] [--scenes 8] [--objects 4] [--views 2] [--jitter 1.0] [--val_every K] [--resume ckpt.pt] [--seed S]
+        [--lights]
 
 MODELS_DIR holds .ply models, vertex-coloured or texture-mapped, in millimetres as BOP stores them (scenes.read_models_dir).
 Every object's templates are rendered once (TemplateBank.add_mesh, the view grid of subdivision --views: 12, 42, 162 views);
 the scenes are rendered --scenes at a time with --objects objects each, and every batch is made on the device
 (dtoid.pretrain.ScenePretrainSet). Objects are split as the reference splits them (id % 4 == 0 validates); a folder that
-leaves either side empty validates on the training objects, on scenes of another seed. One line per step.
+leaves either side empty validates on the training objects, on scenes of another seed. One line per step. --lights
+lights the scenes of both sets (scenes.sample_lights, SPEC.md 13.11-13.12); whether that helps on real frames is untested.
 """
 import argparse
 import json
@@ -21,7 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def build_sets(models_dir, batch, n_scenes, n_objects, level, jitter, seed, hw=(480, 640)):
+def build_sets(models_dir, batch, n_scenes, n_objects, level, jitter, seed, hw=(480, 640), lights=False):
     """-> (train set, validation set, the printed line about the split)."""
     from ossid_code_amd import pipeline, render, scenes, synth
     from ossid_code_amd.dtoid import pretrain
@@ -35,9 +37,10 @@ def build_sets(models_dir, batch, n_scenes, n_objects, level, jitter, seed, hw=(
     # a refresh is cut into whole batches: render enough scenes for about two batches of training targets
     per_scene = n_objects * len(train_ids) / float(len(meshes))
     n_scenes = min(256, max(n_scenes, int(-(-2 * batch // per_scene))))
-    train = pretrain.ScenePretrainSet(atlas, bank, synth.CAM_K, hw, n_objects, n_scenes, batch, seed, obj_ids=train_ids, jitter=jitter)
+    train = pretrain.ScenePretrainSet(atlas, bank, synth.CAM_K, hw, n_objects, n_scenes, batch, seed, obj_ids=train_ids, jitter=jitter,
+                                      lights=lights)
     val = pretrain.ScenePretrainSet(atlas, bank, synth.CAM_K, hw, n_objects, n_scenes, batch, seed + 1000003, obj_ids=val_ids, jitter=None,
-                                    drop_last=False)
+                                    drop_last=False, lights=lights)
     line = "%d objects, %d views each, %d scenes per refresh: train on %s, validate on %s%s" % (
         len(meshes), int(bank.img[train_ids[0]].shape[0]), n_scenes, train_ids, val_ids,
         " (the split by id %% 4 leaves one side empty: validating on the training objects, scenes of seed %d)" % (seed + 1000003)
@@ -60,6 +63,7 @@ def main():
     ap.add_argument("--resume", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--lights", action="store_true", help="light the rendered scenes (default: unlit)")
     ap.add_argument("--curve", default=None, help="also write the losses and validation numbers to this JSON file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -73,7 +77,8 @@ def main():
         trainer.load(a.resume)
         print("resumed %s at iteration %d" % (a.resume, trainer.iteration), flush=True)
     # a resumed run draws new scenes: the sets' seed moves on with the iteration it starts from
-    train, val, line = build_sets(a.models, a.batch, a.scenes, a.objects, a.views, a.jitter, a.seed + trainer.iteration)
+    train, val, line = build_sets(a.models, a.batch, a.scenes, a.objects, a.views, a.jitter, a.seed + trainer.iteration,
+                                   lights=a.lights)
     print(line, flush=True)
     trainer.train_set, trainer.val_set = train, val if a.val_every > 0 else None
     curve = {"loss": [], "val": [], "first_iteration": trainer.iteration}
