@@ -358,7 +358,8 @@ int ossid_conv3x3_wgrad(const float* x, const float* dy, int B, int H, int W, in
  * through LDS with the pixels on K: as bf16 hi/lo images read back K-major (ds_read_b64_tr_b16) for three
  * v_mfma_f32_32x32x16_bf16 per f32 product (split-bf16, ~5e-6 of the result's scale; ossid_conv_wgrad_split_bf16() != 0),
  * or as f32 for v_mfma_f32_32x32x2_f32 (every layer of a -DOSSID_WGRAD_F32 build); split-K slabs in `workspace`
- * (ossid_conv_wgrad_workspace_bytes), summed in a fixed order -- bit-reproducible, no float atomics. cin, cout % 4 == 0. */
+ * (ossid_conv_wgrad_workspace_bytes; workspace_bytes below it is OSSID_EINVAL), summed in a fixed order -- bit-reproducible,
+ * no float atomics. cin, cout % 4 == 0. */
 typedef struct ossid_wgrad_desc {
     const float* x;
     const float* dy;
@@ -705,7 +706,7 @@ int ossid_dw_add_stats_nhwc(const float* x, const float* kernels, int kernels_ba
  * position (ky * 3 + kx, uint8) of the first maximum, Ho = (H - 1) / 2 + 1.
  * Backward in two passes over m, the un-pooled gradient gm = [scale m + shift > 0] * (sum of dpooled whose maximum sat at
  * this pixel) formed on the fly both times: dm == NULL: (sum gm, sum gm * m) -> ossid_stem_pool_bwd_partials(B, H, W, C)
- * partial rows for ossid_bn_fold_bwd; partials == NULL: dm = scale gm + coef_x m + coef_1 (coefficients from that fold). */
+ * partial rows [P][2][C] floats for ossid_bn_fold_bwd; partials == NULL: dm = scale gm + coef_x m + coef_1 (coefficients from that fold). */
 int ossid_stem_pool_fwd(const float* m, const float* scale, const float* shift, int B, int H, int W, int C, float* out,
                         uint8_t* argmax, void* stream);
 int ossid_stem_pool_bwd_partials(int B, int H, int W, int C);

@@ -1513,9 +1513,8 @@ int ossid_upsample_nearest_bwd_nhwc(const float* dup, int B, int Hs, int Ws, int
 // 3x3 layers, 128 -> 32, and every other plain 3x3 layer with input channels in 128s, such as the head's) where those take
 // the shape; this file's kernels take the rest.
 
-size_t ossid_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int taps) {
-    WgradPlan p;
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !wgrad_plan(B, H, W, Cin, Cout, taps, p)) return 0;
+// what ossid_conv_wgrad_workspace_bytes answers for a shape whose plan `p` is at hand: the most any kernel the shape can be routed to needs
+static size_t wgrad_need_bytes(int B, int H, int W, int Cin, int Cout, int taps, const WgradPlan& p) {
     size_t n = (size_t)p.nsplit * p.wk * taps * Cout * Cin * sizeof(float);
     if (ossid_wgrad_fewch_takes(Cin, Cout, taps, Cin, Cout)) {
         const size_t m = ossid_wgrad_fewch_workspace_bytes(B, H, W, Cin, Cout);
@@ -1532,6 +1531,12 @@ size_t ossid_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, 
     return n;
 }
 
+size_t ossid_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int taps) {
+    WgradPlan p;
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !wgrad_plan(B, H, W, Cin, Cout, taps, p)) return 0;
+    return wgrad_need_bytes(B, H, W, Cin, Cout, taps, p);
+}
+
 int ossid_conv_wgrad_split_bf16(void) { return OSSID_WGRAD_SB; }
 
 int ossid_conv_wgrad(const ossid_wgrad_desc* d, void* stream) {
@@ -1540,6 +1545,11 @@ int ossid_conv_wgrad(const ossid_wgrad_desc* d, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % 4) || (Cout % 4)) return OSSID_EINVAL;
     if (!d->x || !d->dy || !d->dw || !d->workspace || (d->pre_scale && !d->pre_shift)) return OSSID_EINVAL;
     if (d->dy_add) return OSSID_EINVAL;                        // (only csrc/wgrad_t9.hip's 1x1 jobs, reached through the group entry)
+    // A workspace below the queried size is refused, not run on whichever kernel below still fits it: which kernel a shape
+    // gets -- and with it the rounding of the result -- must not depend on the size of the caller's buffer.
+    WgradPlan p;
+    const bool planned = wgrad_plan(B, H, W, Cin, Cout, taps, p);
+    if (planned && d->workspace_bytes < wgrad_need_bytes(B, H, W, Cin, Cout, taps, p)) return OSSID_EINVAL;
     if (ossid_wgrad_fewch_takes(Cin, Cout, taps, d->in_channel_stride > 0 ? d->in_channel_stride : Cin,
                                 d->dy_channel_stride > 0 ? d->dy_channel_stride : Cout) &&
         d->workspace_bytes >= ossid_wgrad_fewch_workspace_bytes(B, H, W, Cin, Cout) && !((uintptr_t)d->x & 15) &&
@@ -1551,9 +1561,7 @@ int ossid_conv_wgrad(const ossid_wgrad_desc* d, void* stream) {
     if (Cin <= 256 && ossid_wgrad_t9_takes(d) && !((uintptr_t)d->workspace & 15) &&
         d->workspace_bytes >= ossid_wgrad_t9_workspace_bytes(d, 1))
         return ossid_wgrad_t9_group(d, 1, d->workspace, d->workspace_bytes, stream);      // the same, split-bf16 (csrc/wgrad_t9.hip)
-    WgradPlan p;
-    if (!wgrad_plan(B, H, W, Cin, Cout, taps, p)) return OSSID_EINVAL;
-    if (d->workspace_bytes < (size_t)p.nsplit * p.wk * taps * Cout * Cin * sizeof(float)) return OSSID_EINVAL;
+    if (!planned) return OSSID_EINVAL;
     WgradArgs a;
     a.x = d->x, a.dy = d->dy, a.pre_scale = d->pre_scale, a.pre_shift = d->pre_shift, a.slabs = (float*)d->workspace;
     a.B = p.B, a.H = p.H, a.W = p.W, a.Cin = Cin, a.Cout = Cout;
