@@ -100,7 +100,11 @@ def nms(boxes, scores, iou_threshold, sorted_desc=False):
 def topk_scores(scores, k):
     """(values, indices) of the k largest entries of a 1-D score vector, in decreasing order (network.py:555,
     `torch.topk(classifications, 1000, dim=1)` on the object column). Equal scores are ordered, and at the cut chosen,
-    by increasing index. On the GPU: ossid_topk (radix select + sort of the k survivors); k > 2048 or CPU: torch."""
+    by increasing index. "Largest" is the total order of the float32 bit patterns (the kernel's radix key), which is the
+    numeric order wherever that decides and beyond it ranks -0.0 below +0.0 and a positive NaN above +inf (larger payloads
+    first; a negative NaN below -inf). Values come back as copies: NaN payloads, the sign of zero and denormals survive.
+    On the GPU: ossid_topk (radix select + sort of the k survivors); k > 2048 or CPU: torch (which leaves the order among
+    equal values, +-0.0 and NaNs open)."""
     n = int(scores.shape[0])
     if not scores.is_cuda or k > 2048 or k <= 0:
         return torch.topk(scores, k)
@@ -409,7 +413,11 @@ def gather_rows(src, idx, sigmoid=False):
 
 
 def decode_clip_boxes(anchors, deltas, img_w, img_h):
-    """anchors [1,A,4] or [A,4], deltas [R,A,4] -> clipped boxes [R,A,4] (BBoxTransform + ClipBoxes, no autograd)."""
+    """anchors [1,A,4] or [A,4], deltas [R,A,4] -> clipped boxes [R,A,4] (BBoxTransform + ClipBoxes, no autograd).
+    Row r uses anchor r % A. x1, y1 are clamped at 0 from below only and x2, y2 at the frame from above only, so a box
+    wholly left of or above the frame comes out with x2 < x1 (y2 < y1), as ClipBoxes leaves it; an exp that overflows gives
+    0 .. img_w (img_h). NaN deltas are outside the contract: the kernel clamps with fmaxf / fminf, which turn a NaN into the
+    frame bound where torch.clamp would pass it on."""
     _lib.require_cuda(anchors, deltas)
     a = anchors.reshape(-1, 4).float().contiguous()
     d = deltas.detach().float().contiguous()
