@@ -1269,6 +1269,52 @@ int ossid_scene_light(const ossid_scene_desc* desc_host, const float* normals, c
                       const int32_t* face, const float* lights, const int32_t* n_lights, const float* ambient,
                       const float* material, uint8_t* lit_out, float* normal_out, void* stream);
 
+/* 8f-10  cast shadows for the light above (SPEC.md 13.13-13.15, csrc/scene_shadow.hip and csrc/scene_light.hip): this
+ * build's own definition, opt-in; ossid_scene_light is untouched. Raw device pointers, caller-owned memory, launches only;
+ * capturable. No workspace and no size query: a triangle's vertices are projected by the thread that draws it.
+ *
+ * Shared arguments: light_views f32 [S][OSSID_SCENE_MAX_LIGHTS][16] = (R row-major 9, t 3, a, b, cx, cy), the light's view
+ * of CAMERA space: Q = R P + t in f64 from the f32 rows in the written order ((r0 Px + r1 Py) + r2 Pz) + t; a point light
+ * (lights[s][l][3] != 0) projects u = (Qx / Qz) a + cx, v = (Qy / Qz) b + cy, a directional one u = Qx a + cx, v = Qy b + cy.
+ * scenes.shadow_views places them (13.15). shadow_map u32 [S][OSSID_SCENE_MAX_LIGHTS][Hs][Ws]: the bits of the nearest f32
+ * light-space depth Qz per sample, 0x7f800000 where nothing is drawn; samples sit at pixel centres. z_near_l > 0.
+ *
+ * ossid_scene_shadow_maps: clears shadow_map and draws the draw list of desc_host (of which it reads what
+ * ossid_scene_light reads, cams aside) into it, two launches (one when n = 0 or I = 0). items int32 [n][3] =
+ * (s * OSSID_SCENE_MAX_LIGHTS + l, instance, first face): one wave per row draws the faces [first, first + 64) of the
+ * instance's mesh from light l of scene s; the caller lists each (light, instance, 64 faces) it wants once
+ * (scenes.shadow_views: every instance of the scene under every enabled light). Per face the three vertices' f32 camera
+ * points (7.2) are projected as above; a vertex is usable iff Qz > z_near_l, Q, u and v are finite and |u|, |v| < 2^20, and
+ * is snapped to rint(256 u), rint(256 v); a triangle with an unusable vertex or no area casts nothing (no clipping).
+ * Coverage is 7.4-7.6's at samples 256 x + 128; the depth of a covered sample is perspective-correct for a point light
+ * (7.7 on 1 / Qz) and ((w0 z0 + w1 z1) + w2 z2) / A in f64 for a directional one, rounded to f32, reduced by a 32-bit
+ * unsigned minimum on its bits: bit-reproducible. A row whose first entry is outside [0, 4 S), whose instance is not one
+ * of scene s, whose mesh entry leads outside [0, K), Vt or Ft or whose first face is outside [0, nf) is skipped, as is a
+ * face with an index outside [0, nv): nothing outside an array is addressed. lights is read for the w column alone.
+ * OSSID_EINVAL before any launch: a NULL pointer (items with n = 0 aside), n outside [0, 2^30], Hs or Ws outside [1, 4096],
+ * z_near_l not positive and finite, and what ossid_scene_light refuses of desc_host.
+ *
+ * ossid_scene_light_shadowed: ossid_scene_light -- the same arguments, the same steps 1-8 of SPEC 13.11, stated once in
+ * the source -- with each light's diffuse and specular term scaled by its visibility at the pixel's surface point P
+ * (13.14): enable int32 [S][OSSID_SCENE_MAX_LIGHTS] (0: the light casts no shadow), shadow_params f32 [S][2] = (beta0,
+ * beta1). For a light with N.L > 0 and enable != 0: Q, u, v of P as above; vis = 1 unless Qz > z_near_l and Q, u, v are
+ * finite; texel = Qz / a (point) or 1 / a (directional), tan = sqrt(max(1 - (N.L)^2, 0)) / N.L, bias = texel (beta0 +
+ * beta1 min(tan, 8)); k counts the taps (floor(u) + dx, floor(v) + dy), dx, dy in {-1, 0, 1}, that lie inside the map, are
+ * not 0x7f800000 and hold a depth < Qz - bias (compared in f64); vis = (double)(9 - k) / 9.0; the terms are I (N.L vis) and
+ * I ((N.H)^(2^e) vis). Ambient light is not shadowed. blocked_out u8 [S][H][W] (may be NULL): the sum of k over the
+ * pixel's lights, at most 36; 0 on the background and on a pixel that is copied through. With enable all 0, lit_out and
+ * normal_out are ossid_scene_light's byte for byte. No cube maps (a point light shadows inside its one frustum), no
+ * clipping at the light's near plane, no shadow on the background. One launch. OSSID_EINVAL before it: what
+ * ossid_scene_light refuses, a NULL shadow_map, light_views, enable or shadow_params, Hs or Ws outside [1, 4096], z_near_l
+ * not positive and finite. */
+int ossid_scene_shadow_maps(const ossid_scene_desc* desc_host, const float* lights, const float* light_views,
+                            const int32_t* items, int n, int Hs, int Ws, float z_near_l, uint32_t* shadow_map, void* stream);
+int ossid_scene_light_shadowed(const ossid_scene_desc* desc_host, const float* normals, const uint8_t* albedo,
+                               const int32_t* instance, const int32_t* face, const float* lights, const int32_t* n_lights,
+                               const float* ambient, const float* material, const uint32_t* shadow_map, const float* light_views,
+                               const int32_t* enable, int Hs, int Ws, float z_near_l, const float* shadow_params,
+                               uint8_t* lit_out, float* normal_out, uint8_t* blocked_out, void* stream);
+
 /* =============================================================================================
  * Detector pre-training on rendered scenes (SPEC.md section 15; python/ossid/train.py over
  * datasets/dtoid_dataset.py:97-236 in the reference, which reads offline BlenderProc renders)

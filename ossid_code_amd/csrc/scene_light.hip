@@ -16,13 +16,15 @@
 // scene is applied to the albedo in f64 in the written order (-ffp-contract=off; / and sqrt correctly rounded).
 // instance and face are device data the kernel does not trust: a pixel whose values lead outside an array is copied
 // through unchanged.
+//
+// ossid_scene_light_shadowed (SPEC 13.14) is the same kernel with another visibility hook: light_pixel states steps 1-8
+// once and asks `vis` how much of each light arrives; NoShadow answers 1, ShadowLookup taps the light's shadow map
+// (csrc/scene_shadow.hip draws it) nine times around the texel the surface point projects into.
 #include <cmath>
 
-#include "raster_common.h"
+#include "scene_shadow.h"
 
 namespace {
-
-constexpr int MAX_TOTAL = 1 << 29;   // atlas vertices / faces, as csrc/scene.hip: 3 * index stays inside int32
 
 // ---- vertex normals (SPEC 13.10) ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void normals_clear_kernel(long long* __restrict__ acc, size_t n) {
@@ -84,12 +86,64 @@ __device__ __forceinline__ int round_u8(double v) {
     return r >= 255.0 ? 255 : (r > 0.0 ? (int)r : 0);      // NaN fails both comparisons: 0
 }
 
+// The visibility hook of light_pixel: vis(scene * 4 + slot, the light is a point light, P, ndl, blocked) is the share of
+// the light that reaches the surface point P, in [0, 1]; it adds its blocked taps to `blocked`. ossid_scene_light's hook:
+// every light arrives whole, and x * 1.0 is x, so its bits are those of the unhooked expressions.
+struct NoShadow {
+    static constexpr bool shadowed = false;
+    __device__ __forceinline__ double operator()(int, bool, const double*, double, int&) const { return 1.0; }
+};
+
+// ossid_scene_light_shadowed's hook, SPEC 13.14: nine taps of the light's shadow map around the texel P projects into.
+struct ShadowLookup {
+    static constexpr bool shadowed = true;
+    const unsigned* map;          // [S][4][Hs][Ws], ossid_scene_shadow_maps'
+    const float* views;           // [S][4][16]
+    const int32_t* enable;        // [S][4]
+    const float* params;          // [S][2] = (beta0, beta1)
+    int Hs, Ws;
+    double z_near_l;
+
+    __device__ __forceinline__ double operator()(int ls, bool point, const double* P, double ndl, int& blocked) const {
+        if (enable[ls] == 0) return 1.0;
+        const LightView lv = load_light_view(views + 16 * (size_t)ls, point);
+        double qz, u, v;
+        if (!light_project(lv, P[0], P[1], P[2], z_near_l, qz, u, v)) return 1.0;
+        const double texel = point ? qz / lv.a : 1.0 / lv.a;
+        const double s2 = 1.0 - ndl * ndl;
+        const double tn = sqrt(s2 > 0.0 ? s2 : 0.0) / ndl;
+        const float* beta = params + 2 * (size_t)(ls / OSSID_SCENE_MAX_LIGHTS);
+        const double bias = texel * ((double)beta[0] + (double)beta[1] * (tn < 8.0 ? tn : 8.0));
+        const double thr = qz - bias;
+        // floor(u) as an integer; past either border by two texels or more no tap is inside, whatever the value
+        const double fu = floor(u), fv = floor(v);
+        const int ix = fu < -2.0 ? -2 : (fu > (double)(Ws + 1) ? Ws + 1 : (int)fu);
+        const int iy = fv < -2.0 ? -2 : (fv > (double)(Hs + 1) ? Hs + 1 : (int)fv);
+        const unsigned* zb = map + (size_t)ls * Hs * Ws;
+        int k = 0;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int x = ix + dx, y = iy + dy;
+                if (x < 0 || x >= Ws || y < 0 || y >= Hs) continue;
+                const unsigned zbits = zb[(size_t)y * Ws + x];
+                k += zbits != ZFAR && (double)__uint_as_float(zbits) < thr;      // a NaN on either side blocks nothing
+            }
+        blocked += k;
+        return (double)(9 - k) / 9.0;
+    }
+};
+
 // Steps 1-8 of SPEC 13.11 for pixel (x, y) of `scene`, whose albedo is c: false (nothing written) when inst or fc leads
-// outside an array or to a triangle the render cannot have drawn; otherwise c becomes the lit colour and nrm the normal.
+// outside an array or to a triangle the render cannot have drawn; otherwise c becomes the lit colour and nrm the normal,
+// and `blocked` grows by what vis counted. Stated once for both entries: they differ in vis alone.
+template <typename Vis>
 __device__ __forceinline__ bool light_pixel(const ossid_scene_desc& d, const float* __restrict__ normals,
                                             const float* __restrict__ lights, const int32_t* __restrict__ n_lights,
                                             const float* __restrict__ ambient, const float* __restrict__ material, int scene,
-                                            int inst, int fc, int x, int y, int o, int c[3], float nrm[3]) {
+                                            int inst, int fc, int x, int y, int o, int c[3], float nrm[3], const Vis& vis,
+                                            int& blocked) {
     if (inst < d.scene_first[scene] || inst >= d.scene_first[scene + 1] || inst >= d.I) return false;
     const int m = d.instance_mesh[inst];
     if (m < 0 || m >= d.K) return false;
@@ -168,7 +222,9 @@ __device__ __forceinline__ bool light_pixel(const ossid_scene_desc& d, const flo
         const double ndl = dot3(Nh[0], Nh[1], Nh[2], Lh[0], Lh[1], Lh[2]);
         if (!(ndl > 0.0)) continue;
         const double I[3] = {(double)L[4], (double)L[5], (double)L[6]};
-        E[0] = E[0] + I[0] * ndl, E[1] = E[1] + I[1] * ndl, E[2] = E[2] + I[2] * ndl;
+        const double vs = vis(scene * OSSID_SCENE_MAX_LIGHTS + l, L[3] != 0.0f, P, ndl, blocked);
+        const double dif = ndl * vs;
+        E[0] = E[0] + I[0] * dif, E[1] = E[1] + I[1] * dif, E[2] = E[2] + I[2] * dif;
         const double Hh[3] = {Lh[0] + Vh[0], Lh[1] + Vh[1], Lh[2] + Vh[2]};
         const double hh = dot3(Hh[0], Hh[1], Hh[2], Hh[0], Hh[1], Hh[2]);
         if (!(hh > 0.0)) continue;
@@ -177,6 +233,7 @@ __device__ __forceinline__ bool light_pixel(const ossid_scene_desc& d, const flo
         if (!(ndh > 0.0)) continue;
         double p = ndh;
         for (int k = 0; k < e; ++k) p = p * p;             // ndh^(2^e) by exact squarings
+        p = p * vs;
         Sp[0] = Sp[0] + I[0] * p, Sp[1] = Sp[1] + I[1] * p, Sp[2] = Sp[2] + I[2] * p;
     }
     // 7., 8.
@@ -189,30 +246,38 @@ __device__ __forceinline__ bool light_pixel(const ossid_scene_desc& d, const flo
     return true;
 }
 
+template <typename Vis>
 __global__ __launch_bounds__(256) void scene_light_kernel(ossid_scene_desc d, const float* __restrict__ normals,
                                                           const unsigned char* albedo, const int32_t* __restrict__ instance,
                                                           const int32_t* __restrict__ face, const float* __restrict__ lights,
                                                           const int32_t* __restrict__ n_lights, const float* __restrict__ ambient,
                                                           const float* __restrict__ material, unsigned char* lit_out,
-                                                          float* __restrict__ normal_out, int o) {
+                                                          float* __restrict__ normal_out, int o, Vis vis,
+                                                          unsigned char* __restrict__ blocked_out) {
     const size_t hw = (size_t)d.H * d.W, npix = (size_t)d.S * hw;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
         // albedo and lit_out may be one buffer (neither is __restrict__): the pixel is read whole before it is written
         int c[3] = {albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2]};
         float nrm[3] = {0.0f, 0.0f, 0.0f};
         const int inst = instance[i];
+        int blocked = 0;
         if (inst >= 0) {                                   // the background is not relit
             const int scene = (int)(i / hw);
             const int pix = (int)(i - (size_t)scene * hw), y = pix / d.W, x = pix - y * d.W;
             int lit[3] = {c[0], c[1], c[2]};
             float n[3];
-            if (light_pixel(d, normals, lights, n_lights, ambient, material, scene, inst, face[i], x, y, o, lit, n)) {
+            int k = 0;
+            if (light_pixel(d, normals, lights, n_lights, ambient, material, scene, inst, face[i], x, y, o, lit, n, vis, k)) {
                 c[0] = lit[0], c[1] = lit[1], c[2] = lit[2];
                 nrm[0] = n[0], nrm[1] = n[1], nrm[2] = n[2];
+                blocked = k;
             }
         }
         lit_out[3 * i] = (unsigned char)c[0], lit_out[3 * i + 1] = (unsigned char)c[1], lit_out[3 * i + 2] = (unsigned char)c[2];
         if (normal_out) normal_out[3 * i] = nrm[0], normal_out[3 * i + 1] = nrm[1], normal_out[3 * i + 2] = nrm[2];
+        if constexpr (Vis::shadowed) {
+            if (blocked_out) blocked_out[i] = (unsigned char)blocked;      // at most 4 lights x 9 taps
+        }
     }
 }
 
@@ -245,16 +310,27 @@ int ossid_scene_light(const ossid_scene_desc* desc_host, const float* normals, c
     if (!desc_host || !normals || !albedo || !instance || !face || !lights || !n_lights || !ambient || !material || !lit_out)
         return OSSID_EINVAL;
     const ossid_scene_desc d = *desc_host;
-    if (d.S < 1 || d.S > OSSID_SCENE_MAX_SCENES || d.K < 1 || d.Vt < 1 || d.Vt > MAX_TOTAL || d.Ft < 0 || d.Ft > MAX_TOTAL ||
-        d.I < 0 || (long long)d.I > (long long)d.S * OSSID_SCENE_MAX_INSTANCES ||
-        !raster_frame_ok(d.H, d.W, d.pixel_offset, d.z_near))
+    if (!lit_desc_ok(d)) return OSSID_EINVAL;
+    hipLaunchKernelGGL(scene_light_kernel<NoShadow>, dim3(grid_for((size_t)d.S * d.H * d.W)), dim3(256), 0, (hipStream_t)stream, d,
+                       normals, albedo, instance, face, lights, n_lights, ambient, material, lit_out, normal_out,
+                       snap_offset(d.pixel_offset), NoShadow(), (unsigned char*)nullptr);
+    return ossid_launch_status();
+}
+
+int ossid_scene_light_shadowed(const ossid_scene_desc* desc_host, const float* normals, const uint8_t* albedo,
+                               const int32_t* instance, const int32_t* face, const float* lights, const int32_t* n_lights,
+                               const float* ambient, const float* material, const uint32_t* shadow_map, const float* light_views,
+                               const int32_t* enable, int Hs, int Ws, float z_near_l, const float* shadow_params,
+                               uint8_t* lit_out, float* normal_out, uint8_t* blocked_out, void* stream) {
+    if (!desc_host || !normals || !albedo || !instance || !face || !lights || !n_lights || !ambient || !material || !lit_out ||
+        !shadow_map || !light_views || !enable || !shadow_params || !shadow_map_ok(Hs, Ws, z_near_l))
         return OSSID_EINVAL;
-    if (!d.vertices || (d.Ft > 0 && !d.faces) || !d.meshes || !d.scene_first || !d.cams ||
-        (d.I > 0 && (!d.instance_mesh || !d.transforms)))
-        return OSSID_EINVAL;
-    hipLaunchKernelGGL(scene_light_kernel, dim3(grid_for((size_t)d.S * d.H * d.W)), dim3(256), 0, (hipStream_t)stream, d, normals,
-                       albedo, instance, face, lights, n_lights, ambient, material, lit_out, normal_out,
-                       snap_offset(d.pixel_offset));
+    const ossid_scene_desc d = *desc_host;
+    if (!lit_desc_ok(d)) return OSSID_EINVAL;
+    const ShadowLookup vis = {shadow_map, light_views, enable, shadow_params, Hs, Ws, (double)z_near_l};
+    hipLaunchKernelGGL(scene_light_kernel<ShadowLookup>, dim3(grid_for((size_t)d.S * d.H * d.W)), dim3(256), 0,
+                       (hipStream_t)stream, d, normals, albedo, instance, face, lights, n_lights, ambient, material, lit_out,
+                       normal_out, snap_offset(d.pixel_offset), vis, blocked_out);
     return ossid_launch_status();
 }
 

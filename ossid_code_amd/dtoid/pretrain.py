@@ -142,13 +142,16 @@ class ScenePretrainSet:
     either way. jitter: sample_jitter's strength, 0 or None for none. background=False leaves the background black.
     lights=True lights every refresh's scenes (scenes.sample_lights, SPEC 13.11-13.12) from a Generator of its own,
     derived from (seed, refresh number), so that no other draw moves: with the same seed the batches differ from the
-    unlit set's in img alone."""
+    unlit set's in img alone. shadows=True (or a scenes.Shadows) lets those lights cast shadows (SPEC 13.13-13.15); it
+    needs lights=True and draws nothing random: again img alone differs."""
 
     def __init__(self, atlas, bank, cam_K, hw, objects_per_scene, scenes_per_refresh, batch_size, seed, obj_ids=None,
                  jitter=1.0, heatmap_hw=(29, 39), min_visib=MIN_VISIB, min_px=MIN_PX, drop_last=True, background=True,
-                 lights=False):
+                 lights=False, shadows=False):
         _need(isinstance(atlas, scenes.MeshAtlas), "atlas must be a scenes.MeshAtlas")
         self.lights = bool(lights)
+        self.shadows = shadows if isinstance(shadows, scenes.Shadows) else (scenes.Shadows() if shadows else None)
+        _need(self.shadows is None or self.lights, "shadows are cast by lights: shadows needs lights=True")
         self.atlas, self.bank, self.cam_K = atlas, bank, np.asarray(cam_K, dtype=np.float64)
         self.hw = (int(hw[0]), int(hw[1]))
         _need(self.cam_K.shape == (3, 3), "cam_K must be [3,3]")
@@ -219,7 +222,7 @@ class ScenePretrainSet:
                 lrng = np.random.default_rng(np.random.SeedSequence(self.seed, spawn_key=(self.refreshes,)))
                 lights, material = scenes.sample_lights(layout, lrng)
             batch = scenes.render_scenes(self.atlas, layout, self.hw, background=bg, sensor=sensor, lights=lights,
-                                         material=material)
+                                         material=material, shadows=self.shadows)
             self.refreshes += 1
             targets = select_targets(batch, self.obj_ids, self.min_visib, self.min_px)
             n = len(targets) // self.batch_size * self.batch_size if self.drop_last else len(targets)

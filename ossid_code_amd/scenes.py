@@ -17,6 +17,10 @@ The scenes are unlit unless asked otherwise (csrc/scene_light.hip, SPEC 13.10-13
 
     lights, material = sample_lights(layout, rng)                            # or a Lights of your own
     batch = render_scenes(atlas, layout, (480, 640), lights=lights, material=material)     # .color lit, .albedo, .normal
+
+and the lights cast no shadows unless asked (csrc/scene_shadow.hip, SPEC 13.13-13.15):
+
+    batch = render_scenes(atlas, layout, (480, 640), lights=lights, material=material, shadows=Shadows())    # .blocked
 """
 import ctypes
 import json
@@ -50,7 +54,7 @@ class MeshAtlas:
     concatenated on the device -- and tex_table int64 [K,3] = (first texel of the mesh's chain, Ht, Wt), zeros for a
     vertex-coloured mesh; all three are None when no mesh is textured. The colour rows of a texture-only mesh are zeros."""
 
-    uvs = uvs_host = mips = tex_table = tex_table_host = _normals = None
+    uvs = uvs_host = mips = tex_table = tex_table_host = _normals = _radii = None
 
     @property
     def normals(self):
@@ -145,9 +149,14 @@ class MeshAtlas:
         return self.uvs_host[v0:v0 + nv], np.ascontiguousarray(image)
 
     def radius(self, obj_id):
-        """The largest distance of a vertex from the mesh's origin."""
-        V = self.mesh_arrays(obj_id)[0].astype(np.float64)
-        return float(np.sqrt((V * V).sum(1).max()))
+        """The largest distance of a vertex from the mesh's origin. Computed once per object and kept: the atlas's
+        vertices are fixed at construction (vertices_host is not to be written into)."""
+        if self._radii is None:
+            self._radii = {}
+        if int(obj_id) not in self._radii:
+            V = self.mesh_arrays(obj_id)[0].astype(np.float64)
+            self._radii[int(obj_id)] = float(np.sqrt((V * V).sum(1).max()))
+        return self._radii[int(obj_id)]
 
 
 class Layout:
@@ -420,8 +429,186 @@ def _check_lights(layout, lights, material):
     return np.ascontiguousarray(material.astype(np.float32))
 
 
-def _light_pass(desc, atlas, layout, hw, albedo, instance, face, lights, material, normals, out):
-    """ossid_scene_light on the current stream over the images of a render made with `desc` -> (lit, normal)."""
+SHADOW_MAX_SIDE = 4096      # Hs, Ws of a shadow map (csrc/scene_shadow.h)
+SHADOW_FACES = 64           # faces per row of the shadow pass's work list: one per lane of a wave
+SHADOW_Z_NEAR = 1e-3        # z_near_l: in front of it a vertex is usable from the light
+
+
+class Shadows:
+    """Cast shadows for a lit render (SPEC 13.13-13.15): size = (Hs, Ws) of the depth map each (scene, light) gets, each
+    side in [1, 4096], and beta = (beta0, beta1), the constant and the slope-scaled depth bias in texels."""
+
+    def __init__(self, size=(512, 512), beta=(1.5, 1.5)):
+        self.size, self.beta = size, beta
+        _check_shadows(self)
+
+
+def _check_shadows(shadows, lights=True):
+    """-> ((Hs, Ws), (beta0, beta1)) of a Shadows, after the checks render_scenes makes before it touches the device."""
+    if not isinstance(shadows, Shadows):
+        raise ValueError("shadows must be a scenes.Shadows or None, got %r" % (shadows,))
+    if lights is None:
+        raise ValueError("shadows are cast by lights: shadows is given without lights")
+    try:
+        size = tuple(shadows.size)
+        ok = len(size) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in size)
+    except TypeError:
+        ok = False
+    if not ok or not all(1 <= int(v) <= SHADOW_MAX_SIDE for v in size):
+        raise ValueError("Shadows: size must be two integers (Hs, Ws) in [1, %d], got %r" % (SHADOW_MAX_SIDE, shadows.size))
+    try:
+        beta = tuple(float(v) for v in shadows.beta)
+    except (TypeError, ValueError):
+        beta = ()
+    with np.errstate(over="ignore"):                       # a beta past f32's range is refused as not finite
+        finite = len(beta) == 2 and bool(np.isfinite(np.asarray(beta, dtype=np.float64).astype(np.float32)).all())
+    if not finite:
+        raise ValueError("Shadows: beta must be two finite numbers (beta0, beta1), got %r" % (shadows.beta,))
+    return (int(size[0]), int(size[1])), beta
+
+
+def _unit(v):
+    n = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    return v / n
+
+
+def shadow_views(atlas, layout, lights, shadows):
+    """SPEC 13.15 (build-defined, host numpy in f64, rounded to f32 at the end; nothing random) -> (light_views f32
+    [S,4,16], enable int32 [S,4], items int32 [n,3], z_near_l): where each light of `lights` looks from, which lights cast
+    shadows and the work list of ossid_scene_shadow_maps.
+
+    Per scene the sphere (c, r) around its instances that are not the table (instance_mesh != the atlas's table): c the
+    mean of their centres (the translations of their transforms, rigid ones), r the largest |centre - c| +
+    atlas.radius(obj). A scene without such an instance, or with r not positive and finite, enables none of its lights;
+    slots >= n_lights[s] are never enabled. With R0 = 1.05 r, Hs x Ws the map and m = min(Hs, Ws):
+      directional light, d = (x, y, z) / |(x, y, z)| (|.| = 0: not enabled): eye e = c + R0 d, forward f = -d,
+                         a = b = 0.5 m / R0;
+      point light at p, D = |p - c| (D <= 1.1 r: not enabled -- the light sits among the objects): e = p,
+                         f = (c - p) / D, a = b = 0.5 m sqrt(D D - R0 R0) / R0: the cone that touches the sphere R0.
+    The up vector is the camera axis e_k with the smallest |e_k . f|, the lowest k on a tie; x = (up x f) / |up x f|,
+    y = f x x; R's rows are x, y, f and t = -R e. cx = Ws / 2, cy = Hs / 2. A row is (R row-major, t, a, b, cx, cy).
+    items lists, for every enabled (scene s, slot l) in ascending order, every instance i of the scene (the table
+    included) in ascending order and every first face 0, 64, 128, ... below the nf of its mesh: (4 s + l, i, first)."""
+    (Hs, Ws), _beta = _check_shadows(shadows)
+    if not isinstance(atlas, MeshAtlas) or not isinstance(layout, Layout):
+        raise ValueError("shadow_views takes a MeshAtlas and a Layout")
+    if not isinstance(lights, Lights) or lights.n_scenes != layout.n_scenes:
+        raise ValueError("lights must be a Lights of the layout's %d scenes" % layout.n_scenes)
+    S, M = layout.n_scenes, _lib.SCENE_MAX_LIGHTS
+    if layout.n_instances and (layout.instance_mesh.min() < 0 or layout.instance_mesh.max() >= atlas.n_meshes):
+        raise ValueError("instance_mesh outside [0, %d)" % atlas.n_meshes)
+    table = atlas.index_of[TABLE_OBJ_ID]
+    radius = np.array([atlas.radius(o) for o in atlas.obj_ids], dtype=np.float64)
+    views = np.zeros((S, M, 16), np.float64)
+    enable = np.zeros((S, M), np.int32)
+    m = float(min(Hs, Ws))
+    axes = np.eye(3)
+    for s in range(S):
+        i0, i1 = int(layout.scene_first[s]), int(layout.scene_first[s + 1])
+        objs = [i for i in range(i0, i1) if layout.instance_mesh[i] != table]
+        if not objs:
+            continue
+        centres = layout.transforms[objs, :3, 3]
+        c = centres.sum(0) / float(len(objs))
+        off = centres - c
+        r = float((np.sqrt((off[:, 0] * off[:, 0] + off[:, 1] * off[:, 1]) + off[:, 2] * off[:, 2])
+                   + radius[layout.instance_mesh[objs]]).max())
+        if not (r > 0.0 and np.isfinite(r)):
+            continue
+        R0 = 1.05 * r
+        for l in range(int(lights.n_lights[s])):
+            row = lights.lights[s, l].astype(np.float64)
+            g = row[:3]
+            if row[3] != 0.0:
+                v = c - g
+                D = float(np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
+                if not D > 1.1 * r:
+                    continue
+                eye, f = g, v / D
+                a = 0.5 * m * np.sqrt(D * D - R0 * R0) / R0
+            else:
+                if not (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2] > 0.0:
+                    continue
+                d = _unit(g)
+                eye, f = c + R0 * d, -d
+                a = 0.5 * m / R0
+            up = axes[int(np.argmin(np.abs(f)))]            # argmin takes the first of equal values
+            x = _unit(np.cross(up, f))
+            y = np.cross(f, x)
+            R = np.stack([x, y, f])
+            t = -np.array([(R[k, 0] * eye[0] + R[k, 1] * eye[1]) + R[k, 2] * eye[2] for k in range(3)])
+            views[s, l, :9], views[s, l, 9:12] = R.reshape(9), t
+            views[s, l, 12:] = (a, a, Ws / 2.0, Hs / 2.0)
+            enable[s, l] = 1
+    views32 = np.ascontiguousarray(views.astype(np.float32))
+    enable[~np.isfinite(views32).all(2)] = 0
+    return views32, np.ascontiguousarray(enable), _shadow_items(atlas, layout, enable), SHADOW_Z_NEAR
+
+
+def _shadow_items(atlas, layout, enable):
+    """The work list of shadow_views for the enabled (scene, slot)s, int32 [n,3], built once per layout: the rows of a
+    scene -- its instances times their groups of 64 faces, by repeats -- are the same under each of its lights, and the
+    list of a layout under one `enable` is kept on the layout (callers must not write into it)."""
+    nf = atlas.table_host[layout.instance_mesh, 3].astype(np.int64) if layout.n_instances else np.zeros(0, np.int64)
+    key = (enable.tobytes(), layout.instance_mesh.tobytes(), layout.scene_first.tobytes(), nf.tobytes())
+    kept = getattr(layout, "_shadow_items_kept", None)
+    if kept is not None and kept[0] == key:
+        return kept[1]
+    M = _lib.SCENE_MAX_LIGHTS
+    groups = (nf + SHADOW_FACES - 1) // SHADOW_FACES                          # per instance
+    first_group = np.concatenate([[0], np.cumsum(groups)])
+    inst = np.repeat(np.arange(layout.n_instances, dtype=np.int32), groups)    # per group of the draw list, in order
+    first = ((np.arange(len(inst), dtype=np.int64) - first_group[inst]) * SHADOW_FACES).astype(np.int32)
+    ls = np.nonzero(enable.reshape(-1))[0]
+    lo, hi = first_group[layout.scene_first[ls // M]], first_group[layout.scene_first[ls // M + 1]]
+    n = int((hi - lo).sum())
+    if n > 1 << 30:
+        raise ValueError("the shadow pass's work list has %d rows, at most 2^30" % n)
+    items = np.empty((n, 3), np.int32)
+    at = 0
+    for k, a, b in zip(ls, lo, hi):                                           # at most 4 S blocks, each one slice copy
+        items[at:at + b - a, 0], items[at:at + b - a, 1], items[at:at + b - a, 2] = k, inst[a:b], first[a:b]
+        at += b - a
+    layout._shadow_items_kept = (key, items)
+    return items
+
+
+class ShadowMaps:
+    """The shadow maps of one (layout, lights, Shadows), device tensors, as the shadowed pass takes them: map int32
+    [S,4,Hs,Ws] (the bits of the nearest f32 light-space depth, 0x7f800000 where nothing is drawn), views f32 [S,4,16],
+    enable int32 [S,4], params f32 [S,2] = (beta0, beta1); size = (Hs, Ws), z_near_l and n_items, the work list's rows.
+    light_scenes(shadows=...) takes one in place of a Shadows and then draws no maps of its own."""
+
+    def __init__(self, map, views, enable, params, size, z_near_l, n_items):
+        self.map, self.views, self.enable, self.params = map, views, enable, params
+        self.size, self.z_near_l, self.n_items = size, z_near_l, n_items
+
+
+def _shadow_maps(desc, atlas, layout, lights, d_lights, shadows):
+    """shadow_views on the host, then ossid_scene_shadow_maps on the current stream -> ShadowMaps."""
+    dev, S = atlas.device, layout.n_scenes
+    up = lambda a: torch.from_numpy(a).to(dev)
+    (Hs, Ws), beta = _check_shadows(shadows)
+    views, enable, items, z_near_l = shadow_views(atlas, layout, lights, shadows)
+    d_v, d_e, d_b = up(views), up(enable), up(np.tile(np.asarray(beta, np.float32), (S, 1)))
+    d_items = None
+    if len(items):                                         # the list is the layout's (_shadow_items): so is its upload
+        kept = getattr(layout, "_shadow_items_dev", None)
+        if kept is None or kept[0] is not items or kept[1].device != dev:
+            kept = layout._shadow_items_dev = (items, up(items))
+        d_items = kept[1]
+    shadow_map = torch.empty(S, _lib.SCENE_MAX_LIGHTS, Hs, Ws, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.fn("ossid_scene_shadow_maps")(ctypes.byref(desc), d_lights.data_ptr(), d_v.data_ptr(),
+                                                      None if d_items is None else d_items.data_ptr(), len(items), Hs, Ws,
+                                                      z_near_l, shadow_map.data_ptr(), _lib.stream()), "ossid_scene_shadow_maps")
+    return ShadowMaps(shadow_map, d_v, d_e, d_b, (Hs, Ws), z_near_l, len(items))
+
+
+def _light_pass(desc, atlas, layout, hw, albedo, instance, face, lights, material, normals, out, shadows=None):
+    """ossid_scene_light on the current stream over the images of a render made with `desc` -> (lit, normal, None, None);
+    with a Shadows, ossid_scene_shadow_maps and ossid_scene_light_shadowed -> (lit, normal, blocked, ShadowMaps); with a
+    ShadowMaps the shadowed pass alone."""
     dev, S, (H, W) = atlas.device, layout.n_scenes, hw
     up = lambda a: torch.from_numpy(a).to(dev)
     d_l, d_n, d_a, d_m = up(lights.lights), up(lights.n_lights), up(lights.ambient), up(material)
@@ -429,21 +616,66 @@ def _light_pass(desc, atlas, layout, hw, albedo, instance, face, lights, materia
         d_m = torch.zeros(1, 2, dtype=torch.float32, device=dev)             # the entry refuses NULL; no row is read
     lit = torch.empty(S, H, W, 3, dtype=torch.uint8, device=dev) if out is None else out
     normal = torch.empty(S, H, W, 3, dtype=torch.float32, device=dev)
+    if shadows is None:
+        with _lib.on_device(dev):
+            _lib.check(_lib.fn("ossid_scene_light")(ctypes.byref(desc), normals.data_ptr(), albedo.data_ptr(),
+                                                    instance.data_ptr(), face.data_ptr(), d_l.data_ptr(), d_n.data_ptr(),
+                                                    d_a.data_ptr(), d_m.data_ptr(), lit.data_ptr(), normal.data_ptr(),
+                                                    _lib.stream()), "ossid_scene_light")
+        return lit, normal, None, None
+    maps = shadows if isinstance(shadows, ShadowMaps) else _shadow_maps(desc, atlas, layout, lights, d_l, shadows)
+    blocked = torch.empty(S, H, W, dtype=torch.uint8, device=dev)
     with _lib.on_device(dev):
-        _lib.check(_lib.fn("ossid_scene_light")(ctypes.byref(desc), normals.data_ptr(), albedo.data_ptr(), instance.data_ptr(),
-                                                face.data_ptr(), d_l.data_ptr(), d_n.data_ptr(), d_a.data_ptr(), d_m.data_ptr(),
-                                                lit.data_ptr(), normal.data_ptr(), _lib.stream()), "ossid_scene_light")
-    return lit, normal
+        _lib.check(_lib.fn("ossid_scene_light_shadowed")(
+            ctypes.byref(desc), normals.data_ptr(), albedo.data_ptr(), instance.data_ptr(), face.data_ptr(), d_l.data_ptr(),
+            d_n.data_ptr(), d_a.data_ptr(), d_m.data_ptr(), maps.map.data_ptr(), maps.views.data_ptr(), maps.enable.data_ptr(),
+            maps.size[0], maps.size[1], maps.z_near_l, maps.params.data_ptr(), lit.data_ptr(), normal.data_ptr(),
+            blocked.data_ptr(), _lib.stream()), "ossid_scene_light_shadowed")
+    return lit, normal, blocked, maps
+
+
+def _lit_desc(atlas, layout, hw, pixel_offset, z_near):
+    """-> (the SceneDesc the shading and shadow entries read, the tensors it points into)."""
+    dev, S, I = atlas.device, layout.n_scenes, layout.n_instances
+    up = lambda a: torch.from_numpy(a).to(dev)
+    keep = (up(layout.instance_mesh), up(layout.transforms.astype(np.float32)), up(layout.scene_first), up(layout.cams))
+    d_mesh, d_T, d_first, d_cams = keep
+    desc = _lib.SceneDesc(
+        vertices=atlas.vertices.data_ptr(), faces=atlas.faces.data_ptr(), meshes=atlas.table.data_ptr(),
+        instance_mesh=d_mesh.data_ptr() if I else None, transforms=d_T.data_ptr() if I else None,
+        scene_first=d_first.data_ptr(), cams=d_cams.data_ptr(), Vt=len(atlas.vertices_host), Ft=len(atlas.faces_host),
+        K=atlas.n_meshes, I=I, S=S, H=hw[0], W=hw[1], pixel_offset=float(pixel_offset), z_near=float(z_near))
+    return desc, keep
+
+
+def shadow_maps(atlas, layout, hw, lights, shadows, pixel_offset=0.0, z_near=0.05):
+    """SPEC 13.13 and 13.15 alone -> ShadowMaps: the maps render_scenes(lights=..., shadows=...) draws, for a caller that
+    lights images of its own with light_scenes(shadows=the result), or wants the maps. Two launches."""
+    H, W = _check_layout(atlas, layout, None, None, hw, pixel_offset, z_near, 1.0)
+    _check_shadows(shadows, lights)
+    _check_lights(layout, lights, None)
+    from .model_cloud import _refuse_cpu
+    _refuse_cpu(atlas.device)
+    desc, _keep = _lit_desc(atlas, layout, (H, W), pixel_offset, z_near)
+    return _shadow_maps(desc, atlas, layout, lights, torch.from_numpy(lights.lights).to(atlas.device), shadows)
 
 
 def light_scenes(atlas, layout, hw, albedo, instance, face, lights, material=None, normals=None, out=None,
-                 pixel_offset=0.0, z_near=0.05):
+                 pixel_offset=0.0, z_near=0.05, shadows=None):
     """SPEC 13.11 on images a render of (atlas, layout, hw, pixel_offset, z_near) returned -> (lit u8 [S,H,W,3], normal
     f32 [S,H,W,3]): the deferred shading pass render_scenes(lights=...) runs, for a caller that holds the images. albedo
     u8 [S,H,W,3], instance and face int32 [S,H,W] are device tensors (SceneBatch.color, .instance, .face); material f32
     [I,2] = (k_s, e), None for no highlights; normals f32 [Vt,3] replaces atlas.normals; out may be albedo itself. The
-    kernel checks instance and face: a pixel whose values lead outside an array is copied through. One launch."""
+    kernel checks instance and face: a pixel whose values lead outside an array is copied through. One launch.
+    shadows: a Shadows casts shadows (SPEC 13.13-13.15: two launches for the maps, then the shadowed pass in place of
+    the pass) and returns (lit, normal, blocked u8 [S,H,W]) instead; a ShadowMaps (shadow_maps) does so from maps
+    already drawn, in one launch."""
     H, W = _check_layout(atlas, layout, None, None, hw, pixel_offset, z_near, 1.0)
+    if isinstance(shadows, ShadowMaps):
+        if tuple(shadows.map.shape[:2]) != (layout.n_scenes, _lib.SCENE_MAX_LIGHTS) or shadows.map.device != atlas.device:
+            raise ValueError("light_scenes: the ShadowMaps are not of this layout's %d scenes on the atlas's device" % layout.n_scenes)
+    elif shadows is not None:
+        _check_shadows(shadows, lights)
     from .model_cloud import _refuse_cpu
     _refuse_cpu(atlas.device)
     dev, S, I = atlas.device, layout.n_scenes, layout.n_instances
@@ -455,15 +687,10 @@ def light_scenes(atlas, layout, hw, albedo, instance, face, lights, material=Non
             ((("out", out, torch.uint8, (S, H, W, 3)),) if out is not None else ()):
         if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
             raise ValueError("light_scenes: %s must be a contiguous %s tensor %s on the atlas's device" % (name, dtype, shape))
-    up = lambda a: torch.from_numpy(a).to(dev)
-    d_mesh, d_T, d_first, d_cams = (up(layout.instance_mesh), up(layout.transforms.astype(np.float32)), up(layout.scene_first),
-                                    up(layout.cams))
-    desc = _lib.SceneDesc(
-        vertices=atlas.vertices.data_ptr(), faces=atlas.faces.data_ptr(), meshes=atlas.table.data_ptr(),
-        instance_mesh=d_mesh.data_ptr() if I else None, transforms=d_T.data_ptr() if I else None,
-        scene_first=d_first.data_ptr(), cams=d_cams.data_ptr(), Vt=len(atlas.vertices_host), Ft=len(atlas.faces_host),
-        K=atlas.n_meshes, I=I, S=S, H=H, W=W, pixel_offset=float(pixel_offset), z_near=float(z_near))
-    return _light_pass(desc, atlas, layout, (H, W), albedo, instance, face, lights, material, normals, out)
+    desc, _keep = _lit_desc(atlas, layout, (H, W), pixel_offset, z_near)
+    lit, normal, blocked, _map = _light_pass(desc, atlas, layout, (H, W), albedo, instance, face, lights, material, normals, out,
+                                             shadows)
+    return (lit, normal) if shadows is None else (lit, normal, blocked)
 
 
 def work_offsets(atlas, layout):
@@ -499,7 +726,7 @@ def _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, d
 
 
 def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=0.0, z_near=0.05, depth_scale=1.0,
-                  lights=None, material=None):
+                  lights=None, material=None, shadows=None):
     """SPEC 13.2-13.6 -> SceneBatch of device tensors: the layout's scenes drawn with mutual occlusion, the sensor's depth
     (sensor=None: the clean sensor, quantisation only), the amodal masks and gt_info. pixel_offset 0 is this package's
     pixel convention, under which the render lines up with depth2xyz (as OnlineStream(mesh_pixel_offset=0.0) assumes).
@@ -512,8 +739,15 @@ def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=
     after the render (SPEC 13.11): `color` is then the lit image, `albedo` the unlit one and `normal` f32 [S,H,W,3] the
     shading normals; material f32 [I,2] = (k_s, e) per instance, None for no highlights. Depth, instance, face, facing,
     the masks, gt_info and the sensor do not depend on the lights. With lights=None the function is the unlit one:
-    the same launches, the same bits, albedo and normal None."""
+    the same launches, the same bits, albedo and normal None.
+
+    shadows: a Shadows lets the lights cast shadows (SPEC 13.13-13.15): shadow_views places a view per light, two launches
+    draw a depth map per (scene, light) and the shadowed pass takes the place of the shading pass. `blocked` u8 [S,H,W]
+    then counts the blocked taps of each pixel's lights (0: fully lit) and `shadow_map` is the ShadowMaps drawn; both are
+    None otherwise. With shadows=None the launches and bits are those of the function without it."""
     H, W = _check_layout(atlas, layout, sensor, background, hw, pixel_offset, z_near, depth_scale)
+    if shadows is not None:
+        _check_shadows(shadows, lights)
     from .model_cloud import _refuse_cpu
     _refuse_cpu(atlas.device)
     if lights is not None:
@@ -576,12 +810,14 @@ def render_scenes(atlas, layout, hw, background=None, sensor=None, pixel_offset=
         _lib.check(_lib.fn("ossid_scene_gt_info")(amodal.data_ptr() if I else None, inst.data_ptr(), depth.data_ptr(),
                                                   d_first.data_ptr(), I, S, H, W, gt_info.data_ptr() if I else None,
                                                   _lib.stream()), "ossid_scene_gt_info")
-    albedo = normal = None
+    albedo = normal = blocked = shadow_map = None
     if lights is not None:
         albedo = color
-        color, normal = _light_pass(desc, atlas, layout, (H, W), albedo, inst, face, lights, material, normals, None)
+        color, normal, blocked, shadow_map = _light_pass(desc, atlas, layout, (H, W), albedo, inst, face, lights, material,
+                                                         normals, None, shadows)
     batch = SceneBatch(atlas, layout, (H, W), color, clean, depth, u16, inst, amodal, gt_info, depth_scale=depth_scale,
-                       face=face, facing=facing, keep=keep, lod=lod, albedo=albedo, normal=normal)
+                       face=face, facing=facing, keep=keep, lod=lod, albedo=albedo, normal=normal, blocked=blocked,
+                       shadow_map=shadow_map)
     batch.workspace_bytes = need
     return batch
 
@@ -601,13 +837,14 @@ class SceneBatch:
     facing and keep; lod int32 [S,H,W] (the mip level fetched, -1 where nothing is drawn or the winner is vertex-
     coloured) from an atlas with a textured mesh, None otherwise. From a lit render (render_scenes(lights=...)) color is
     the lit image, albedo u8 [S,H,W,3] the unlit one and normal f32 [S,H,W,3] the shading normals (SPEC 13.11); both are
-    None otherwise."""
+    None otherwise. With shadows (render_scenes(shadows=...)) blocked u8 [S,H,W] counts each pixel's blocked shadow-map
+    taps and shadow_map is the ShadowMaps drawn (SPEC 13.13-13.14); both are None otherwise."""
 
     workspace_bytes = None
 
     def __init__(self, atlas, layout, hw, color, depth_clean, depth, depth_u16, instance, amodal, gt_info, depth_scale=1.0,
-                 face=None, facing=None, keep=None, lod=None, albedo=None, normal=None):
-        self.albedo, self.normal = albedo, normal
+                 face=None, facing=None, keep=None, lod=None, albedo=None, normal=None, blocked=None, shadow_map=None):
+        self.albedo, self.normal, self.blocked, self.shadow_map = albedo, normal, blocked, shadow_map
         self.atlas, self.layout, self.hw, self.depth_scale = atlas, layout, (int(hw[0]), int(hw[1])), float(depth_scale)
         self.color, self.depth_clean, self.depth, self.depth_u16 = color, depth_clean, depth, depth_u16
         self.instance, self.amodal, self.gt_info = instance, amodal, gt_info

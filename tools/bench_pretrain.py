@@ -7,7 +7,10 @@
   pretrain_curve.json      tools/pretrain_dtoid.py for --steps steps on a models folder written by SceneBatch.write_bop:
                            the loss per step, validation seg_IoU and AP at the start and the end
 
-    python tools/bench_pretrain.py [--reps 20] [--steps 200] [--skip-curve]
+    python tools/bench_pretrain.py [--reps 20] [--steps 200] [--skip-curve] [--lights [--shadows]]
+
+--lights and --shadows measure the producer with lit (SPEC 13.11-13.12) and shadowed (13.13-13.15) scenes; the producer's
+file is then pretrain_producer_lit.json or pretrain_producer_shadow.json, and the curve is left alone.
 """
 import argparse
 import json
@@ -94,20 +97,25 @@ def refresh_parts(train, reps, warm=3):
     for _ in range(warm + reps):
         layout, sensor = timed("layouts_sensor", train.draw_targets)
         bg = timed("backgrounds", lambda: train._backgrounds(train.n_scenes))
-        batch = timed("render_scenes", lambda: scenes.render_scenes(train.atlas, layout, train.hw, background=bg, sensor=sensor))
+        lights = material = None
+        if train.lights:
+            lights, material = scenes.sample_lights(layout, np.random.default_rng(0))
+        batch = timed("render_scenes", lambda: scenes.render_scenes(train.atlas, layout, train.hw, background=bg, sensor=sensor,
+                                                                    lights=lights, material=material, shadows=train.shadows))
         targets = timed("select_targets", lambda: pretrain.select_targets(batch, train.obj_ids, train.min_visib, train.min_px))
         plan = timed("plan", lambda: train.plan(layout, targets))
         timed("uploads", lambda: [torch.from_numpy(a).to(train.atlas.device) for a in (plan[0], plan[1], plan[2], plan[4])])
     return {k: float(np.median(v[warm:])) for k, v in parts.items()}
 
 
-def producer(models, reps):
+def producer(models, reps, lights=False, shadows=False):
     from ossid_code_amd import dtoid, pipeline
     from ossid_code_amd.dtoid import pretrain
     from pretrain_dtoid import build_sets
-    train, _val, line = build_sets(models, 8, 8, 4, 0, 1.0, 0)
+    train, _val, line = build_sets(models, 8, 8, 4, 0, 1.0, 0, lights=lights, shadows=shadows)
     print(line, flush=True)
-    res = {"batch": 8, "hw": [480, 640], "scenes_per_refresh": 8, "objects_per_scene": 4, "reps": reps}
+    res = {"batch": 8, "hw": [480, 640], "scenes_per_refresh": 8, "objects_per_scene": 4, "reps": reps, "lights": bool(lights),
+           "shadows": None if train.shadows is None else {"size": list(train.shadows.size), "beta": list(train.shadows.beta)}}
 
     # a refresh: layouts + sensor, backgrounds, render_scenes, select_targets (one read-back of gt_info), the plan, its uploads
     def refresh():
@@ -164,18 +172,23 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--skip-curve", action="store_true")
+    ap.add_argument("--lights", action="store_true", help="light the scenes -> pretrain_producer_lit.json, no curve")
+    ap.add_argument("--shadows", action="store_true", help="with --lights: cast shadows -> pretrain_producer_shadow.json")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
+    if a.shadows and not a.lights:
+        raise SystemExit("--shadows needs --lights: shadows are cast by lights")
     if not torch.cuda.is_available():
         raise SystemExit("bench_pretrain.py measures on the GPU")
     os.makedirs(a.out, exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
         models = write_models(tmp)
-        res = producer(models, a.reps)
+        res = producer(models, a.reps, a.lights, a.shadows)
         print(json.dumps(res), flush=True)
-        with open(os.path.join(a.out, "pretrain_producer.json"), "w") as f:
+        name = "pretrain_producer_shadow.json" if a.shadows else "pretrain_producer_lit.json" if a.lights else "pretrain_producer.json"
+        with open(os.path.join(a.out, name), "w") as f:
             json.dump(res, f, indent=1)
-        if not a.skip_curve:
+        if not a.skip_curve and not a.lights:
             curve_path = os.path.join(tmp, "curve.json")
             cmd = [sys.executable, os.path.join(ROOT, "tools", "pretrain_dtoid.py"), "--models", models, "--steps", str(a.steps),
                    "--out", os.path.join(tmp, "ckpt.pt"), "--views", "1", "--val_every", str(a.steps), "--curve", curve_path]

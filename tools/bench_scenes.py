@@ -21,7 +21,13 @@ shading pass alone over the images a render left (scenes.light_scenes, one launc
 the two together; and the one-off build of the atlas's vertex normals (three launches per mesh), cold and warm. The lit
 image is checked against the pass over the unlit render, and neutral lights against the albedo, first.
 
-    python3 tools/bench_scenes.py [--textured | --lights] [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
+--lights --shadows times the cast shadows (csrc/scene_shadow.hip, SPEC 13.13-13.15) beside the lit legs, in alternation
+-> profiles/scenes_shadow.json: `lit` and `pass` as above, `maps` the shadow-map pass (scenes.shadow_maps: the host's
+views and work list, two launches), `shadowed_pass` the shadowed pass over maps drawn beforehand (one launch), `shadowed`
+render_scenes(lights=..., shadows=...). First the shadowed image is checked: the two routes agree, enable = 0 gives
+the unshadowed pass, and so does every pixel no tap blocks.
+
+    python3 tools/bench_scenes.py [--textured | --lights [--shadows]] [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
     rocprofv3 --kernel-trace --stats -d out -- python3 tools/bench_scenes.py --trace       (three untimed calls of `scene`;
                                                                           with --lights: of the lit render, normals first)
 """
@@ -165,6 +171,75 @@ def bench_lit(a, atlas, layout, sensor, n_faces):
     return res
 
 
+def bench_shadowed(a, atlas, layout, sensor, n_faces):
+    """The legs of --lights --shadows -> the result dict: the lit render, the shading pass, the shadow-map pass
+    (scenes.shadow_maps: the host's views and work list, their uploads, two launches), the shadowed pass over maps drawn
+    beforehand (one launch) and the lit, shadowed render, timed in alternation."""
+    H, W = HW
+    lights, material = scenes.sample_lights(layout, np.random.default_rng(np.random.SeedSequence(a.seed, spawn_key=(0,))))
+    sh = scenes.Shadows() if a.shadow_size is None else scenes.Shadows(size=tuple(a.shadow_size))
+    atlas.normals
+    unlit = scenes.render_scenes(atlas, layout, HW, sensor=sensor)
+    maps = scenes.shadow_maps(atlas, layout, HW, lights, sh)
+    lit_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor, lights=lights, material=material)  # noqa: E731
+    shadowed_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor, lights=lights, material=material, shadows=sh)  # noqa: E731
+    pass_fn = lambda: scenes.light_scenes(atlas, layout, HW, unlit.color, unlit.instance, unlit.face, lights, material)  # noqa: E731
+    maps_fn = lambda: scenes.shadow_maps(atlas, layout, HW, lights, sh)  # noqa: E731
+    spass_fn = lambda: scenes.light_scenes(atlas, layout, HW, unlit.color, unlit.instance, unlit.face, lights, material, shadows=maps)  # noqa: E731
+    lit, batch = lit_fn(), shadowed_fn()
+    s_lit, s_normal, s_blocked = spass_fn()
+    off = scenes.ShadowMaps(maps.map, maps.views, torch.zeros_like(maps.enable), maps.params, maps.size, maps.z_near_l, maps.n_items)
+    o_lit, o_normal, o_blocked = scenes.light_scenes(atlas, layout, HW, unlit.color, unlit.instance, unlit.face, lights, material, shadows=off)
+    free = batch.blocked == 0
+    same = {"maps": torch.equal(batch.shadow_map.map, maps.map), "lit": torch.equal(batch.color, s_lit),
+            "blocked": torch.equal(batch.blocked, s_blocked),
+            "normal": torch.equal(batch.normal.view(torch.int32), lit.normal.view(torch.int32)),
+            "enable_0_is_the_unshadowed_pass": torch.equal(o_lit, lit.color) and not bool(o_blocked.any()),
+            "unblocked_pixels_are_the_unshadowed_pass": torch.equal(batch.color[free], lit.color[free]),
+            "geometry": all(torch.equal(getattr(batch, n), getattr(unlit, n)) for n in ("depth_clean", "depth_u16", "instance", "face", "gt_info"))}
+    print("outputs equal:", same, flush=True)
+    if not all(same.values()):
+        raise SystemExit("the shadowed and the unshadowed route disagree: %s" % same)
+    drawn = unlit.instance >= 0
+    # what acne would look like: pixels with a blocked tap and no pixel a light blocks whole (nine taps) within four pixels
+    # of them -- stray taps away from any shadow --, on the table and on the objects
+    whole = torch.nn.functional.max_pool2d((batch.blocked >= 9).float()[:, None], 9, 1, 4)[:, 0] > 0
+    stray = (batch.blocked > 0) & ~whole
+    is_table = torch.from_numpy(layout.instance_mesh == layout.table_mesh).to(drawn.device)[unlit.instance.clamp(min=0).long()] & drawn
+    frac = lambda m: float((stray & m).sum()) / max(1, int(m.sum()))  # noqa: E731
+    workload = {"stray_blocked_fraction_of_table_pixels": frac(is_table), "stray_blocked_fraction_of_object_pixels": frac(drawn & ~is_table),
+                "blocked_fraction_of_table_pixels": float(((batch.blocked > 0) & is_table).sum()) / max(1, int(is_table.sum())),
+                "blocked_fraction_of_object_pixels": float(((batch.blocked > 0) & drawn & ~is_table).sum()) / max(1, int((drawn & ~is_table).sum())),
+                "table_pixel_fraction": float(is_table.float().mean())}
+    workload.update({"scenes": a.scenes, "instances": layout.n_instances, "instances_per_scene": a.objects + 1, "frame": list(HW),
+                "faces_per_object": n_faces, "seed": a.seed, "lights_per_scene": [int(v) for v in lights.n_lights],
+                "shadow_map": list(maps.size), "beta": list(sh.beta), "lights_enabled": int(maps.enable.sum()),
+                "work_list_rows": int(maps.n_items), "drawn_pixel_fraction": float(drawn.float().mean()),
+                "blocked_pixel_fraction": float((batch.blocked > 0).float().mean()),
+                "fully_blocked_by_a_light_fraction": float((batch.blocked >= 9).float().mean()),
+                "map_samples_drawn_fraction_of_enabled": float((maps.map != 0x7F800000).float().sum() / max(1, int(maps.enable.sum()) * maps.size[0] * maps.size[1]))})
+    del lit, batch, s_lit, s_normal, s_blocked, o_lit, o_normal, o_blocked
+    legs = (("lit", lit_fn), ("shadowed", shadowed_fn), ("pass", pass_fn), ("maps", maps_fn), ("shadowed_pass", spass_fn))
+    for _ in range(a.warmup):
+        for _name, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name, _fn in legs}
+    for _ in range(a.rounds):
+        for name, fn in legs:
+            t[name].append(once_ms(fn)[0])
+    res = {"workload": workload, "outputs_equal": same,
+           "lit": dict(stats(t["lit"]), c_abi_launches=8), "shadowed": dict(stats(t["shadowed"]), c_abi_launches=10),
+           "pass": dict(stats(t["pass"]), c_abi_launches=1), "maps": dict(stats(t["maps"]), c_abi_launches=2),
+           "shadowed_pass": dict(stats(t["shadowed_pass"]), c_abi_launches=1), "rounds": a.rounds, "warmup": a.warmup}
+    res["added_ms_shadowed_pass_over_pass"] = res["shadowed_pass"]["ms"] - res["pass"]["ms"]
+    res["added_ms_shadowed_over_lit"] = res["shadowed"]["ms"] - res["lit"]["ms"]
+    # the yardstick of the issue: one more scene render per enabled light, scaled by the map's share of the frame's pixels
+    per_light = res["lit"]["ms"] / a.scenes * (maps.size[0] * maps.size[1]) / float(H * W)
+    res["one_render_per_light_scaled_ms"] = per_light * workload["lights_enabled"]
+    return res
+
+
 def finish(a, res):
     commit = a.commit
     if commit is None:
@@ -185,6 +260,8 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/scenes.json, or profiles/scenes_textured.json with --textured")
     ap.add_argument("--textured", action="store_true", help="draw the objects from a 1024 x 1024 texture each")
     ap.add_argument("--lights", action="store_true", help="time the shading pass and the vertex normals -> profiles/scenes_lit.json")
+    ap.add_argument("--shadows", action="store_true", help="with --lights: time the shadow maps and the shadowed pass -> profiles/scenes_shadow.json")
+    ap.add_argument("--shadow_size", type=int, nargs=2, default=None, help="Hs Ws of the shadow maps (default: scenes.Shadows' own)")
     ap.add_argument("--scenes", type=int, default=32)
     ap.add_argument("--objects", type=int, default=11, help="objects per scene; the table is one more instance")
     ap.add_argument("--level", type=int, default=6, help="icosphere level of the objects (6: 81 920 faces)")
@@ -196,8 +273,10 @@ def main():
     a = ap.parse_args()
     if a.lights and a.textured:
         raise SystemExit("--lights times the pass over the vertex-coloured workload; it does not combine with --textured")
+    if a.shadows and not a.lights:
+        raise SystemExit("--shadows needs --lights: shadows are cast by lights")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "scenes_lit.json" if a.lights else ("scenes_textured.json" if a.textured else "scenes.json"))
+        a.out = os.path.join(ROOT, "profiles", "scenes_shadow.json" if a.shadows else "scenes_lit.json" if a.lights else ("scenes_textured.json" if a.textured else "scenes.json"))
     if not torch.cuda.is_available():
         raise SystemExit("bench_scenes.py needs the GPU: there is nothing to time without one")
     torch.cuda.set_device(0)
@@ -222,11 +301,14 @@ def main():
     if a.trace:
         if a.lights:                                       # the normals' three launches per mesh, then the eight of a lit render
             lights, material = scenes.sample_lights(layout, np.random.default_rng(np.random.SeedSequence(a.seed, spawn_key=(0,))))
-            scene_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor, lights=lights, material=material)  # noqa: E731
+            sh = scenes.Shadows() if a.shadows else None
+            scene_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor, lights=lights, material=material, shadows=sh)  # noqa: E731
         for _ in range(3):
             scene_fn()
         torch.cuda.synchronize()
         return
+    if a.shadows:
+        return finish(a, bench_shadowed(a, atlas, layout, sensor, int(len(F))))
     if a.lights:
         return finish(a, bench_lit(a, atlas, layout, sensor, int(len(F))))
     T_dev = torch.from_numpy(layout.transforms.astype(np.float32)).cuda()

@@ -2,14 +2,15 @@
 that names its texture in `comment TextureFile`, the image beside it) -> a standard BOP folder:
 
     python3 tools/make_scenes.py MODELS_DIR OUT_DIR --scenes 32 --objects 6 --seed 0 [--name synth] [--split test]
-                                 [--hw 480 640] [--no-mm2m] [--clean] [--no-table] [--depth_scale 1.0] [--lights]
+                                 [--hw 480 640] [--no-mm2m] [--clean] [--no-table] [--depth_scale 1.0] [--lights [--shadows]]
 
 Every MODELS_DIR/*.ply (obj_XXXXXX.ply keeps its id; millimetres, as BOP stores them, unless --no-mm2m) goes into one
 atlas; scenes.sample_layouts places the objects, scenes.render_scenes (csrc/scene.hip, SPEC.md section 13) draws them with
 the depth corruption of scenes.sample_sensor (--clean: quantisation only), and SceneBatch.write_bop writes
 OUT_DIR/<name>: what bop_eval.BopFolder, tools/eval_bop19.py and scenes.read_bop_frames read. The same seed gives the same
 folder. At most 256 scenes per call. --lights lights the scenes (scenes.sample_lights, SPEC.md 13.11-13.12) from a
-generator of its own: rgb/ is lit, every other file is the one written without the flag at the same seed.
+generator of its own: rgb/ is lit, every other file is the one written without the flag at the same seed. --shadows (with
+--lights) lets the lights cast shadows (scenes.Shadows, SPEC.md 13.13-13.15): again rgb/ alone differs.
 """
 import argparse
 import os
@@ -39,7 +40,10 @@ def main():
     ap.add_argument("--clean", action="store_true", help="no depth corruption: quantisation only")
     ap.add_argument("--no-table", action="store_true")
     ap.add_argument("--lights", action="store_true", help="light the scenes: sampled lights and materials (default: unlit)")
+    ap.add_argument("--shadows", action="store_true", help="let the lights cast shadows; needs --lights")
     a = ap.parse_args()
+    if a.shadows and not a.lights:
+        raise SystemExit("--shadows needs --lights: shadows are cast by lights")
     if not torch.cuda.is_available():
         raise SystemExit("make_scenes.py renders on the GPU: there is no CPU path")
     if a.scenes > 256:
@@ -53,7 +57,7 @@ def main():
     if a.lights:
         lights, material = scenes.sample_lights(layout, np.random.default_rng(np.random.SeedSequence(a.seed, spawn_key=(0,))))
     batch = scenes.render_scenes(atlas, layout, a.hw, sensor=sensor, depth_scale=a.depth_scale, lights=lights,
-                                 material=material)
+                                 material=material, shadows=scenes.Shadows() if a.shadows else None)
     base = batch.write_bop(a.out_dir, a.name, split=a.split, depth_scale=a.depth_scale)
     g = batch.gt_info.cpu().numpy()
     print("%d scenes, %d instances (%d visible) of %d objects -> %s" % (a.scenes, layout.n_instances, int((g[:, 1] > 0).sum()),

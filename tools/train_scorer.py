@@ -3,13 +3,14 @@ ScorerTrainer and prints the loss per step. --out saves {'state_dict': ...}, the
 loads (ckpt = torch.load(path); model.load_state_dict(ckpt['state_dict'])).
 
     python tools/train_scorer.py --steps 20 --hypotheses 64 --out ckpt.pt
-    python tools/train_scorer.py --models MODELS_DIR --scenes 8 --objects 4 --steps 200 --out ckpt.pt [--lights]
+    python tools/train_scorer.py --models MODELS_DIR --scenes 8 --objects 4 --steps 200 --out ckpt.pt [--lights [--shadows]]
 
 With --models the frames are rendered scenes (scenes.render_scenes, SPEC.md 13) of the .ply models of MODELS_DIR,
 vertex-coloured or texture-mapped (millimetres, as BOP stores them), with the sampled depth corruption; every step takes the next (scene, object)
 frame whose object is at least --min_visib visible, scores synth.perturb_pose hypotheses around its pose_gt against the
 object's own model cloud (model_cloud.sample_model_cloud), with pp_err from scoring.pose_errors. --lights lights the
-scenes (scenes.sample_lights, SPEC.md 13.11-13.12), so that the true pose no longer has dS = dV = 0.
+scenes (scenes.sample_lights, SPEC.md 13.11-13.12), so that the true pose no longer has dS = dV = 0; --shadows (with
+--lights) lets those lights cast shadows (scenes.Shadows, SPEC.md 13.13-13.15).
 
 The loss and the recipe are this build's own (zephyr's are in neither tree): unpinned.
 """
@@ -36,7 +37,8 @@ def scene_frames(a):
     lights = material = None
     if a.lights:                                             # a generator of its own: the layouts and the sensor do not move
         lights, material = scenes.sample_lights(layout, np.random.default_rng(np.random.SeedSequence(a.seed, spawn_key=(0,))))
-    batch = scenes.render_scenes(atlas, layout, hw, sensor=sensor, lights=lights, material=material)
+    batch = scenes.render_scenes(atlas, layout, hw, sensor=sensor, lights=lights, material=material,
+                                 shadows=scenes.Shadows() if a.shadows else None)
     frames = [f for f in batch.frames() if f["visib_fract"] >= a.min_visib]
     if not frames:
         raise SystemExit("no object is at least %g visible in the %d scenes" % (a.min_visib, a.scenes))
@@ -59,7 +61,10 @@ def main():
     ap.add_argument("--objects", type=int, default=4, help="objects per scene (with --models)")
     ap.add_argument("--min_visib", type=float, default=0.25)
     ap.add_argument("--lights", action="store_true", help="light the rendered scenes (with --models; default: unlit)")
+    ap.add_argument("--shadows", action="store_true", help="let the lights cast shadows (with --models; needs --lights)")
     a = ap.parse_args()
+    if a.shadows and not a.lights:
+        raise SystemExit("--shadows needs --lights: shadows are cast by lights")
 
     from ossid_code_amd import scoring, synth, zephyr
     from ossid_code_amd.zephyr.train import ScorerTrainer
