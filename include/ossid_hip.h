@@ -385,7 +385,9 @@ size_t ossid_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, 
 int ossid_conv_wgrad(const ossid_wgrad_desc* desc_host, void* stream);
 /* Up to 48 INDEPENDENT weight gradients (e.g. the 2 x L of one DenseNet block, each too small to fill the chip) as one
  * launch per tiling variant plus one grouped slab reduction; each descriptor's `workspace` field is ignored, the slabs
- * of all problems live in the one `workspace` of ossid_conv_wgrad_group_workspace_bytes(descs, n) bytes. */
+ * of all problems live in the one `workspace` of ossid_conv_wgrad_group_workspace_bytes(descs, n) bytes. Problems that
+ * csrc/wgrad_t9.hip takes go there in rounds -- one geometry (batch, height, width) per round, fixed by the first such
+ * problem still left -- so a group may mix geometries. */
 size_t ossid_conv_wgrad_group_workspace_bytes(const ossid_wgrad_desc* descs_host, int n);
 int ossid_conv_wgrad_group(const ossid_wgrad_desc* descs_host, int n, void* workspace, size_t workspace_bytes, void* stream);
 

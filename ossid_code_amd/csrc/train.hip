@@ -924,10 +924,36 @@ __global__ __launch_bounds__(256) void wgrad_reduce2_kernel(const float* __restr
 #else
 #define OSSID_WGRAD_SB 1
 #endif
+// The tiling variants: the template arguments of wgrad_kernel / wgrad_group_kernel, by variant number. A workgroup's tile is
+// (wm tm 32) output x (wn tn 32) input channels; 5 and 6 take all nine taps per tile (kyb = 3) and share the k-steps out
+// over wk waves. Everything else a plan says about a variant follows from its row.
+struct WgradTiling {
+    int taps, kyb, tm, tn, wm, wn, wk;
+};
+constexpr WgradTiling WGRAD_TILINGS[7] = {{9, 1, 2, 1, 2, 2, 1}, {9, 1, 1, 2, 2, 2, 1}, {9, 1, 1, 1, 1, 4, 1}, {1, 1, 2, 2, 2, 2, 1},
+                                          {1, 1, 1, 2, 2, 2, 1}, {9, 3, 1, 1, 1, 1, 4}, {9, 3, 1, 1, 1, 2, 2}};
+template <int V>
+struct WgradVariant {
+    static constexpr WgradTiling t = WGRAD_TILINGS[V];
+};
+// f(WgradVariant<variant>{}): the one place a run-time variant becomes template arguments
+template <class F>
+int with_wgrad_variant(int variant, F&& f) {
+    switch (variant) {
+        case 0: return f(WgradVariant<0>{});
+        case 1: return f(WgradVariant<1>{});
+        case 2: return f(WgradVariant<2>{});
+        case 3: return f(WgradVariant<3>{});
+        case 4: return f(WgradVariant<4>{});
+        case 5: return f(WgradVariant<5>{});
+        default: return f(WgradVariant<6>{});
+    }
+}
+
+// which wgrad_reduce2_kernel<PARTS> sums a problem's slabs
+static int wgrad_reduce_parts(int slabs) { return slabs <= 16 ? 1 : slabs <= 128 ? 4 : 32; }
+
 struct WgradPlan {
-    // variant: 0 <9,1,2,1,2,2,1> 128 co x 64 ci    1 <9,1,1,2,2,2,1> 64 x 128     2 <9,1,1,1,1,4,1> 32 x 128
-    //          3 <1,1,2,2,2,2,1> 128 x 128 (1x1)   4 <1,1,1,2,2,2,1> 64 x 128 (1x1)
-    //          5 <9,3,1,1,1,1,4> 32 x 32, all nine taps, k-steps shared out over the waves   6 <9,3,1,1,1,2,2> 32 x 64
     int variant, co_t, ci_t, kyb, wk, tiles_per_wave;
     int KT, chunks_per_row, nsplit, co_blocks, ci_blocks, ntiles, B, H, W;
     int sb;                 // 1: the split-bf16 kernel (wgrad_sb_body: KT a multiple of 16, one LDS buffer of bf16 images)
@@ -937,32 +963,26 @@ struct WgradPlan {
 
 bool wgrad_plan(int B, int H, int W, int Cin, int Cout, int taps, WgradPlan& p) {
     if ((long long)B * H * W > 0x3fffffffLL) return false;
-    p.kyb = 1, p.wk = 1;
-    int ktmax = 48;
+    if (taps != 9 && taps != 1) return false;
+    if (taps == 1) p.variant = Cout <= 64 ? 4 : 3;
+    else if (Cout <= 32) p.variant = Cin <= 32 ? 5 : (Cin <= 64 ? 6 : 2);
+    else p.variant = (Cout <= 64 || Cout == 96) ? 1 : 0;
+    const WgradTiling& t = WGRAD_TILINGS[p.variant];
+    p.co_t = t.wm * t.tm * 32, p.ci_t = t.wn * t.tn * 32, p.kyb = t.kyb, p.wk = t.wk;
+    p.tiles_per_wave = t.tm * t.tn * (taps == 9 ? 3 : 1) * t.kyb;
+    p.sb = OSSID_WGRAD_SB;
     if (taps == 9) {
-        if (Cout <= 32 && Cin <= 32) p.variant = 5, p.co_t = 32, p.ci_t = 32, p.kyb = 3, p.wk = 4, p.tiles_per_wave = 9;
-        else if (Cout <= 32 && Cin <= 64) p.variant = 6, p.co_t = 32, p.ci_t = 64, p.kyb = 3, p.wk = 2, p.tiles_per_wave = 9, ktmax = 40;
-        else if (Cout <= 32) p.variant = 2, p.co_t = 32, p.ci_t = 128, p.tiles_per_wave = 3;
-        else if (Cout <= 64 || Cout == 96) p.variant = 1, p.co_t = 64, p.ci_t = 128, p.tiles_per_wave = 6;
-        else p.variant = 0, p.co_t = 128, p.ci_t = 64, p.tiles_per_wave = 6;
         p.B = B, p.H = H, p.W = W;
-        p.sb = OSSID_WGRAD_SB;
         // split form: k-steps of 16 pixels, WK of them per chunk for the tilings whose waves share the k-steps
-        if (p.sb && p.variant == 5) ktmax = 64;
-        if (p.sb && p.variant == 6) ktmax = 32;
+        const int ktmax = p.variant == 5 ? (p.sb ? 64 : 48) : p.variant == 6 ? (p.sb ? 32 : 40) : 48;
         p.chunks_per_row = (W + ktmax - 1) / ktmax;
         p.KT = p.sb ? ((W + p.chunks_per_row - 1) / p.chunks_per_row + 15) & ~15
                     : ((W + p.chunks_per_row - 1) / p.chunks_per_row + 1) & ~1;
         if (p.sb && p.KT < 16 * p.wk) p.KT = 16 * p.wk;
-    } else if (taps == 1) {
-        if (Cout <= 64) p.variant = 4, p.co_t = 64, p.ci_t = 128, p.tiles_per_wave = 2;
-        else p.variant = 3, p.co_t = 128, p.ci_t = 128, p.tiles_per_wave = 4;
+    } else {
         p.B = 1, p.H = 1, p.W = B * H * W;          // no halo: the whole tensor is one long pixel row
-        p.sb = OSSID_WGRAD_SB;
         p.KT = 32;
         p.chunks_per_row = (p.W + p.KT - 1) / p.KT;
-    } else {
-        return false;
     }
     p.n_chunks = (long long)p.B * p.H * p.chunks_per_row;
     p.co_blocks = (Cout + p.co_t - 1) / p.co_t;
@@ -986,7 +1006,7 @@ bool wgrad_plan(int B, int H, int W, int Cin, int Cout, int taps, WgradPlan& p) 
         const double rounds = ceil(blocks / (256.0 * per_cu));
         const double chunks_pb = ceil((double)p.n_chunks / sp);
         const int slabs = sp * p.wk;
-        const double t_red = (slabs <= 16 ? slabs : slabs <= 128 ? slabs / 4.0 : slabs / 32.0) * 0.12;   // dependent L2 round trips
+        const double t_red = (double)slabs / wgrad_reduce_parts(slabs) * 0.12;   // dependent L2 round trips
         const double t = rounds * (chunks_pb * t_chunk + 4.0) + slabs * dw_bytes * 2.0 / 3.0e6 + t_red;
         if (t < best) best = t, best_s = sp;
     }
@@ -994,31 +1014,42 @@ bool wgrad_plan(int B, int H, int W, int Cin, int Cout, int taps, WgradPlan& p) 
     return true;
 }
 
-template <bool SB, int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
-int launch_wgrad_group_form(const WgradGroup& g, size_t lds, hipStream_t s) {
-    auto kern = wgrad_group_kernel<SB, TAPS, KYB, TM, TN, WM, WN, WK>;
+template <bool SB, class V>
+int launch_wgrad_group_form(V, const WgradGroup& g, size_t lds, hipStream_t s) {
+    constexpr WgradTiling t = V::t;
+    auto kern = wgrad_group_kernel<SB, t.taps, t.kyb, t.tm, t.tn, t.wm, t.wn, t.wk>;
     OSSID_ENSURE_LDS(kern, lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)g.first_block[g.n]), dim3(256), lds, s, g);
     return ossid_launch_status();
 }
-template <int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
-int launch_wgrad_group(const WgradGroup& g, size_t lds, bool sb, hipStream_t s) {
-    if (sb) return launch_wgrad_group_form<true, TAPS, KYB, TM, TN, WM, WN, WK>(g, lds, s);
-    return launch_wgrad_group_form<false, TAPS, KYB, TM, TN, WM, WN, WK>(g, lds, s);
+int launch_wgrad_group(int variant, const WgradGroup& g, size_t lds, bool sb, hipStream_t s) {
+    return with_wgrad_variant(variant, [&](auto v) {
+        return sb ? launch_wgrad_group_form<true>(v, g, lds, s) : launch_wgrad_group_form<false>(v, g, lds, s);
+    });
 }
 
-template <bool SB, int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
-int launch_wgrad_form(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
-    auto kern = wgrad_kernel<SB, TAPS, KYB, TM, TN, WM, WN, WK>;
+template <bool SB, class V>
+int launch_wgrad_form(V, const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
+    constexpr WgradTiling t = V::t;
+    auto kern = wgrad_kernel<SB, t.taps, t.kyb, t.tm, t.tn, t.wm, t.wn, t.wk>;
     OSSID_ENSURE_LDS(kern, p.lds);
     const long nwg = (long)p.nsplit * p.ntiles;
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), p.lds, s, a);
     return ossid_launch_status();
 }
-template <int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
 int launch_wgrad(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
-    if (p.sb) return launch_wgrad_form<true, TAPS, KYB, TM, TN, WM, WN, WK>(a, p, s);
-    return launch_wgrad_form<false, TAPS, KYB, TM, TN, WM, WN, WK>(a, p, s);
+    return with_wgrad_variant(p.variant, [&](auto v) {
+        return p.sb ? launch_wgrad_form<true>(v, a, p, s) : launch_wgrad_form<false>(v, a, p, s);
+    });
+}
+
+// dw (+)= the sum of a problem's slabs, by the kernel wgrad_reduce_parts names
+int launch_wgrad_reduce(const float* slabs, int nslabs, int taps, int Cout, int Cin, float* dw, int accumulate, hipStream_t s) {
+    const size_t n = (size_t)taps * Cout * Cin;
+    const int parts = wgrad_reduce_parts(nslabs), epb = 256 / parts;
+    auto kern = parts == 1 ? wgrad_reduce2_kernel<1> : parts == 4 ? wgrad_reduce2_kernel<4> : wgrad_reduce2_kernel<32>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n + epb - 1) / epb)), dim3(256), 0, s, slabs, nslabs, taps, Cout, Cin, dw, accumulate);
+    return ossid_launch_status();
 }
 
 template <int QX>
@@ -1513,22 +1544,38 @@ int ossid_upsample_nearest_bwd_nhwc(const float* dup, int B, int Hs, int Ws, int
 // 3x3 layers, 128 -> 32, and every other plain 3x3 layer with input channels in 128s, such as the head's) where those take
 // the shape; this file's kernels take the rest.
 
-// what ossid_conv_wgrad_workspace_bytes answers for a shape whose plan `p` is at hand: the most any kernel the shape can be routed to needs
+enum WgradFamily { WGRAD_FEWCH, WGRAD_T9, WGRAD_T1, WGRAD_TILED };      // (TILED: this file's kernels)
+
+static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+static size_t wgrad_slab_bytes(const WgradPlan& p, const ossid_wgrad_desc& d) {
+    return (size_t)p.nsplit * p.wk * d.taps * d.cout * d.cin * sizeof(float);
+}
+
+// Where ossid_conv_wgrad sends a problem. On a bare shape (no pointers, no strides: nothing misaligned) the answer is the one
+// family besides this file's kernels that the shape can reach.
+static WgradFamily wgrad_route(const ossid_wgrad_desc& d) {
+    if ((uintptr_t)d.workspace & 15) return WGRAD_TILED;
+    if (ossid_wgrad_fewch_takes(d.cin, d.cout, d.taps, d.in_channel_stride > 0 ? d.in_channel_stride : d.cin,
+                                d.dy_channel_stride > 0 ? d.dy_channel_stride : d.cout) &&
+        !((uintptr_t)d.x & 15) && !((uintptr_t)d.dy & 15))
+        return WGRAD_FEWCH;                                  // 2-D pixel tiles, every tap from one staged patch (csrc/wgrad_fc.hip)
+    // (measured per layer at batch 8, 29 x 39, tools/train_layers_bench.py: 256 -> 256 / 96 / 48 take 0.091 / 0.054 / 0.034 ms there
+    // against 0.104 / 0.081 / 0.054 here; 512 -> 256, 640 -> 256, 768 -> 512 are no faster there -- 0.152 / 0.196 / 0.409 against
+    // 0.143 / 0.162 / 0.421: this file's 128 x 128 tiles re-use a staged element four times -- so only up to 256 input channels)
+    if (d.cin <= 256 && ossid_wgrad_t9_takes(&d)) return WGRAD_T9;       // the same, split-bf16 (csrc/wgrad_t9.hip)
+    return WGRAD_TILED;
+}
+
+// What ossid_conv_wgrad_workspace_bytes answers for a shape whose plan `p` is at hand: the most any kernel the shape can be
+// routed to needs -- this file's, where a misaligned pointer or an odd stride sends any problem, and the bare shape's family.
 static size_t wgrad_need_bytes(int B, int H, int W, int Cin, int Cout, int taps, const WgradPlan& p) {
-    size_t n = (size_t)p.nsplit * p.wk * taps * Cout * Cin * sizeof(float);
-    if (ossid_wgrad_fewch_takes(Cin, Cout, taps, Cin, Cout)) {
-        const size_t m = ossid_wgrad_fewch_workspace_bytes(B, H, W, Cin, Cout);
-        if (m > n) n = m;
-    }
-    {                                                        // (a shape-only probe: pointers and strides are checked at the call)
-        ossid_wgrad_desc d = {};
-        d.batch = B, d.height = H, d.width = W, d.cin = Cin, d.cout = Cout, d.taps = taps;
-        if (Cin <= 256 && ossid_wgrad_t9_takes(&d)) {
-            const size_t m = ossid_wgrad_t9_workspace_bytes(&d, 1);
-            if (m > n) n = m;
-        }
-    }
-    return n;
+    ossid_wgrad_desc d = {};                                 // (the bare shape: pointers and strides are checked at the call)
+    d.batch = B, d.height = H, d.width = W, d.cin = Cin, d.cout = Cout, d.taps = taps;
+    const WgradFamily f = wgrad_route(d);
+    const size_t n = wgrad_slab_bytes(p, d);
+    const size_t m = f == WGRAD_FEWCH ? ossid_wgrad_fewch_workspace_bytes(B, H, W, Cin, Cout)
+                                      : (f == WGRAD_T9 ? ossid_wgrad_t9_workspace_bytes(&d, 1) : 0);
+    return m > n ? m : n;
 }
 
 size_t ossid_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int taps) {
@@ -1538,66 +1585,6 @@ size_t ossid_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, 
 }
 
 int ossid_conv_wgrad_split_bf16(void) { return OSSID_WGRAD_SB; }
-
-int ossid_conv_wgrad(const ossid_wgrad_desc* d, void* stream) {
-    if (!d) return OSSID_EINVAL;
-    const int B = d->batch, H = d->height, W = d->width, Cin = d->cin, Cout = d->cout, taps = d->taps;
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % 4) || (Cout % 4)) return OSSID_EINVAL;
-    if (!d->x || !d->dy || !d->dw || !d->workspace || (d->pre_scale && !d->pre_shift)) return OSSID_EINVAL;
-    if (d->dy_add) return OSSID_EINVAL;                        // (only csrc/wgrad_t9.hip's 1x1 jobs, reached through the group entry)
-    // A workspace below the queried size is refused, not run on whichever kernel below still fits it: which kernel a shape
-    // gets -- and with it the rounding of the result -- must not depend on the size of the caller's buffer.
-    WgradPlan p;
-    const bool planned = wgrad_plan(B, H, W, Cin, Cout, taps, p);
-    if (planned && d->workspace_bytes < wgrad_need_bytes(B, H, W, Cin, Cout, taps, p)) return OSSID_EINVAL;
-    if (ossid_wgrad_fewch_takes(Cin, Cout, taps, d->in_channel_stride > 0 ? d->in_channel_stride : Cin,
-                                d->dy_channel_stride > 0 ? d->dy_channel_stride : Cout) &&
-        d->workspace_bytes >= ossid_wgrad_fewch_workspace_bytes(B, H, W, Cin, Cout) && !((uintptr_t)d->x & 15) &&
-        !((uintptr_t)d->dy & 15) && !((uintptr_t)d->workspace & 15))
-        return ossid_wgrad_fewch(d, stream);                 // 2-D pixel tiles, every tap from one staged patch (csrc/wgrad_fc.hip)
-    // (measured per layer at batch 8, 29 x 39, tools/train_layers_bench.py: 256 -> 256 / 96 / 48 take 0.091 / 0.054 / 0.034 ms there
-    // against 0.104 / 0.081 / 0.054 here; 512 -> 256, 640 -> 256, 768 -> 512 are no faster there -- 0.152 / 0.196 / 0.409 against
-    // 0.143 / 0.162 / 0.421: this file's 128 x 128 tiles re-use a staged element four times -- so only up to 256 input channels)
-    if (Cin <= 256 && ossid_wgrad_t9_takes(d) && !((uintptr_t)d->workspace & 15) &&
-        d->workspace_bytes >= ossid_wgrad_t9_workspace_bytes(d, 1))
-        return ossid_wgrad_t9_group(d, 1, d->workspace, d->workspace_bytes, stream);      // the same, split-bf16 (csrc/wgrad_t9.hip)
-    if (!planned) return OSSID_EINVAL;
-    WgradArgs a;
-    a.x = d->x, a.dy = d->dy, a.pre_scale = d->pre_scale, a.pre_shift = d->pre_shift, a.slabs = (float*)d->workspace;
-    a.B = p.B, a.H = p.H, a.W = p.W, a.Cin = Cin, a.Cout = Cout;
-    a.in_cs = d->in_channel_stride > 0 ? d->in_channel_stride : Cin;
-    a.dy_cs = d->dy_channel_stride > 0 ? d->dy_channel_stride : Cout;
-    if ((a.in_cs % 4) || (a.dy_cs % 4) || a.in_cs < Cin || a.dy_cs < Cout) return OSSID_EINVAL;
-    a.Hs = d->src_height > 0 ? d->src_height : p.H, a.Ws = d->src_width > 0 ? d->src_width : p.W;
-    if ((a.Hs != p.H || a.Ws != p.W) && (taps != 9 || a.Hs > H || a.Ws > W)) return OSSID_EINVAL;
-    a.scale_h = (float)a.Hs / (float)p.H, a.scale_w = (float)a.Ws / (float)p.W;
-    a.pre_relu = d->pre_relu, a.KT = p.KT, a.chunks_per_row = p.chunks_per_row, a.nsplit = p.nsplit;
-    a.co_blocks = p.co_blocks, a.ci_blocks = p.ci_blocks, a.ntiles = p.ntiles, a.n_chunks = p.n_chunks;
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    switch (p.variant) {
-        case 0: rc = launch_wgrad<9, 1, 2, 1, 2, 2, 1>(a, p, s); break;
-        case 1: rc = launch_wgrad<9, 1, 1, 2, 2, 2, 1>(a, p, s); break;
-        case 2: rc = launch_wgrad<9, 1, 1, 1, 1, 4, 1>(a, p, s); break;
-        case 3: rc = launch_wgrad<1, 1, 2, 2, 2, 2, 1>(a, p, s); break;
-        case 4: rc = launch_wgrad<1, 1, 1, 2, 2, 2, 1>(a, p, s); break;
-        case 5: rc = launch_wgrad<9, 3, 1, 1, 1, 1, 4>(a, p, s); break;
-        default: rc = launch_wgrad<9, 3, 1, 1, 1, 2, 2>(a, p, s); break;
-    }
-    if (rc != OSSID_OK) return rc;
-    const size_t n = (size_t)taps * Cout * Cin;
-    const int slabs = p.nsplit * p.wk;
-    if (slabs <= 16)
-        hipLaunchKernelGGL(wgrad_reduce2_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)d->workspace,
-                           slabs, taps, Cout, Cin, d->dw, d->accumulate);
-    else if (slabs <= 128)
-        hipLaunchKernelGGL(wgrad_reduce2_kernel<4>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, (const float*)d->workspace,
-                           slabs, taps, Cout, Cin, d->dw, d->accumulate);
-    else
-        hipLaunchKernelGGL(wgrad_reduce2_kernel<32>, dim3((unsigned)((n + 7) / 8)), dim3(256), 0, s, (const float*)d->workspace,
-                           slabs, taps, Cout, Cin, d->dw, d->accumulate);
-    return ossid_launch_status();
-}
 
 static int fill_wgrad_args(const ossid_wgrad_desc* d, const WgradPlan& p, WgradArgs& a) {
     const int H = d->height, W = d->width, Cin = d->cin, Cout = d->cout, taps = d->taps;
@@ -1612,6 +1599,30 @@ static int fill_wgrad_args(const ossid_wgrad_desc* d, const WgradPlan& p, WgradA
     a.pre_relu = d->pre_relu, a.KT = p.KT, a.chunks_per_row = p.chunks_per_row, a.nsplit = p.nsplit;
     a.co_blocks = p.co_blocks, a.ci_blocks = p.ci_blocks, a.ntiles = p.ntiles, a.n_chunks = p.n_chunks;
     return OSSID_OK;
+}
+
+int ossid_conv_wgrad(const ossid_wgrad_desc* d, void* stream) {
+    if (!d) return OSSID_EINVAL;
+    const int B = d->batch, H = d->height, W = d->width, Cin = d->cin, Cout = d->cout, taps = d->taps;
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % 4) || (Cout % 4)) return OSSID_EINVAL;
+    if (!d->x || !d->dy || !d->dw || !d->workspace || (d->pre_scale && !d->pre_shift)) return OSSID_EINVAL;
+    if (d->dy_add) return OSSID_EINVAL;                        // (only csrc/wgrad_t9.hip's 1x1 jobs, reached through the group entry)
+    // A workspace below the queried size is refused, not run on whichever kernel below still fits it: which kernel a shape
+    // gets -- and with it the rounding of the result -- must not depend on the size of the caller's buffer.
+    WgradPlan p;
+    const bool planned = wgrad_plan(B, H, W, Cin, Cout, taps, p);
+    if (planned && d->workspace_bytes < wgrad_need_bytes(B, H, W, Cin, Cout, taps, p)) return OSSID_EINVAL;
+    switch (wgrad_route(*d)) {                               // (both check the workspace they are handed themselves)
+        case WGRAD_FEWCH: return ossid_wgrad_fewch(d, stream);
+        case WGRAD_T9: return ossid_wgrad_t9_group(d, 1, d->workspace, d->workspace_bytes, stream);
+        default: break;
+    }
+    if (!planned) return OSSID_EINVAL;
+    WgradArgs a;
+    int rc = fill_wgrad_args(d, p, a);
+    if (rc == OSSID_OK) rc = launch_wgrad(a, p, (hipStream_t)stream);
+    if (rc != OSSID_OK) return rc;
+    return launch_wgrad_reduce((const float*)d->workspace, p.nsplit * p.wk, taps, Cout, Cin, d->dw, d->accumulate, (hipStream_t)stream);
 }
 
 // How many K-splits each problem of a GROUP gets: the group shares the chip, so the target is just under two workgroups
@@ -1631,150 +1642,133 @@ static void group_splits(WgradPlan* plans, int n) {
     }
 }
 
-// The problems of a group that csrc/wgrad_t9.hip takes -- `t9`: 3x3, 128 -> 32 (the dense layers' second convolution), `t1`:
-// 1x1, c -> 128 (their first) -- provided they share one geometry; the rest stay on the kernels of this file.
-struct WgradSplit {
-    ossid_wgrad_desc t9[2 * OSSID_WGRAD_GROUP_MAX], t1[2 * OSSID_WGRAD_GROUP_MAX], rest[2 * OSSID_WGRAD_GROUP_MAX];
-    int n9, n1, nr;
+// A group as the pieces it is run in, one call or launch each, in launch order = workspace order. csrc/wgrad_t9.hip takes
+// the problems it can -- `t9`: 3x3, input channels in 128s (the dense layers' second convolution), `t1`: 1x1, c -> 128 (their
+// first) -- but one geometry, and for t9 one class, per call. So the group goes there in rounds: in each, the first t9-eligible
+// problem still left fixes (batch, height, width, class) of the round's t9 piece, the first t1-eligible one that did not go
+// to t9 the geometry of its t1 pieces (calls of at most ossid_wgrad_t1_max_jobs() jobs), input order kept; rounds go on until
+// one takes nothing. What is left then stays on this file's kernels: by variant, at most OSSID_WGRAD_GROUP_MAX per launch,
+// K-splits per launch (group_splits). Every problem's share of the workspace, and every t9 / t1 piece, is rounded up to 256 bytes.
+struct WgradPiece {
+    WgradFamily family;
+    int variant;                                             // (TILED pieces)
+    int first, count;                                        // problems d[first .. first + count)
+    size_t bytes;                                            // from off[first] on
 };
-static void split_tiled(const ossid_wgrad_desc* descs, int n, WgradSplit& S) {
-    S.n9 = S.n1 = S.nr = 0;
-    for (int i = 0; i < n; ++i) {
-        const ossid_wgrad_desc& d = descs[i];
-        auto same = [&](const ossid_wgrad_desc& o) { return d.batch == o.batch && d.height == o.height && d.width == o.width; };
-        if (ossid_wgrad_t9_takes(&d) &&
-            (S.n9 == 0 || (same(S.t9[0]) && ossid_wgrad_t9_class(&d) == ossid_wgrad_t9_class(&S.t9[0]))))
-            S.t9[S.n9++] = d;
-        else if (ossid_wgrad_t1_takes(&d) && (S.n1 == 0 || same(S.t1[0]))) S.t1[S.n1++] = d;
-        else S.rest[S.nr++] = d;
+struct WgradGroupPlan {
+    ossid_wgrad_desc d[2 * OSSID_WGRAD_GROUP_MAX];           // the problems in piece order
+    WgradPlan plan[2 * OSSID_WGRAD_GROUP_MAX];               // (TILED pieces) with the K-splits
+    size_t off[2 * OSSID_WGRAD_GROUP_MAX];                   // each problem's offset in the workspace (t9 / t1: its piece's)
+    WgradPiece piece[2 * OSSID_WGRAD_GROUP_MAX];
+    int n, npieces, first_tiled;                             // d[first_tiled .. n): the problems of the TILED pieces
+    size_t total;
+};
+
+static bool wgrad_group_plan(const ossid_wgrad_desc* descs, int n, WgradGroupPlan& P) {
+    if (!descs || n <= 0 || n > 2 * OSSID_WGRAD_GROUP_MAX) return false;
+    P.n = P.npieces = 0, P.total = 0;
+    auto add_piece = [&](WgradFamily family, int variant, int count, size_t bytes) {
+        P.piece[P.npieces++] = {family, variant, P.n, count, bytes};
+        P.n += count, P.total += bytes;
+    };
+    ossid_wgrad_desc left[2 * OSSID_WGRAD_GROUP_MAX], t1[2 * OSSID_WGRAD_GROUP_MAX];
+    int nleft = n;
+    for (int i = 0; i < n; ++i) left[i] = descs[i];
+    for (;;) {
+        ossid_wgrad_desc* t9 = P.d + P.n;                    // (the round's t9 problems go straight to their place)
+        int n9 = 0, n1 = 0, nr = 0;
+        for (int i = 0; i < nleft; ++i) {
+            const ossid_wgrad_desc d = left[i];
+            auto same = [&](const ossid_wgrad_desc& o) { return d.batch == o.batch && d.height == o.height && d.width == o.width; };
+            if (ossid_wgrad_t9_takes(&d) && (n9 == 0 || (same(t9[0]) && ossid_wgrad_t9_class(&d) == ossid_wgrad_t9_class(&t9[0]))))
+                t9[n9++] = d;
+            else if (ossid_wgrad_t1_takes(&d) && (n1 == 0 || same(t1[0]))) t1[n1++] = d;
+            else left[nr++] = d;
+        }
+        nleft = nr;
+        if (n9 + n1 == 0) break;
+        if (n9) {
+            for (int i = 0; i < n9; ++i) P.off[P.n + i] = P.total;
+            add_piece(WGRAD_T9, 0, n9, round256(ossid_wgrad_t9_workspace_bytes(t9, n9)));
+        }
+        for (int f = 0; f < n1;) {
+            int cnt = 0;
+            while (f + cnt < n1 && ossid_wgrad_t1_job_count(t1 + f, cnt + 1) <= ossid_wgrad_t1_max_jobs()) ++cnt;
+            if (cnt == 0) return false;                      // one problem with more jobs than a call takes
+            for (int i = 0; i < cnt; ++i) P.d[P.n + i] = t1[f + i], P.off[P.n + i] = P.total;
+            add_piece(WGRAD_T1, 0, cnt, round256(ossid_wgrad_t1_workspace_bytes(t1 + f, cnt)));
+            f += cnt;
+        }
     }
-}
-// the t1 list in calls of at most ossid_wgrad_t1_max_jobs() jobs: [first, first + count)
-static int t1_chunk(const ossid_wgrad_desc* t1, int n1, int first) {
-    int count = 0;
-    while (first + count < n1 && ossid_wgrad_t1_job_count(t1 + first, count + 1) <= ossid_wgrad_t1_max_jobs()) ++count;
-    return count;
+    P.first_tiled = P.n;
+    WgradPlan plans[2 * OSSID_WGRAD_GROUP_MAX];
+    for (int i = 0; i < nleft; ++i)
+        if (!wgrad_plan(left[i].batch, left[i].height, left[i].width, left[i].cin, left[i].cout, left[i].taps, plans[i])) return false;
+    for (int v = 0; v < 7; ++v)
+        for (int i = 0; i < nleft;) {
+            int cnt = 0;
+            for (; i < nleft && cnt < OSSID_WGRAD_GROUP_MAX; ++i) {
+                if (plans[i].variant != v) continue;
+                P.d[P.n + cnt] = left[i], P.plan[P.n + cnt] = plans[i];
+                ++cnt;
+            }
+            if (cnt == 0) break;
+            group_splits(P.plan + P.n, cnt);
+            size_t bytes = 0;
+            for (int j = 0; j < cnt; ++j) {
+                P.off[P.n + j] = P.total + bytes;
+                bytes += round256(wgrad_slab_bytes(P.plan[P.n + j], P.d[P.n + j]));
+            }
+            add_piece(WGRAD_TILED, v, cnt, bytes);
+        }
+    return true;
 }
 
 size_t ossid_conv_wgrad_group_workspace_bytes(const ossid_wgrad_desc* descs, int n) {
-    if (!descs || n <= 0 || n > 2 * OSSID_WGRAD_GROUP_MAX) return 0;
-    {
-        WgradSplit S;
-        split_tiled(descs, n, S);
-        if (S.n9 + S.n1 > 0) {
-            size_t total = S.n9 ? (ossid_wgrad_t9_workspace_bytes(S.t9, S.n9) + 255) & ~(size_t)255 : 0;
-            for (int f = 0; f < S.n1;) {
-                const int cnt = t1_chunk(S.t1, S.n1, f);
-                if (cnt <= 0) return 0;
-                total += (ossid_wgrad_t1_workspace_bytes(S.t1 + f, cnt) + 255) & ~(size_t)255;
-                f += cnt;
-            }
-            if (S.nr == 0) return total;
-            const size_t b = ossid_conv_wgrad_group_workspace_bytes(S.rest, S.nr);     // (nothing eligible left: one level of recursion)
-            return b ? total + b : 0;
-        }
-    }
-    WgradPlan plans[4 * OSSID_WGRAD_GROUP_MAX];
-    for (int i = 0; i < n; ++i)
-        if (!wgrad_plan(descs[i].batch, descs[i].height, descs[i].width, descs[i].cin, descs[i].cout, descs[i].taps, plans[i]))
-            return 0;
-    // splits are chosen per variant bucket, as ossid_conv_wgrad_group does
-    size_t total = 0;
-    for (int v = 0; v < 7; ++v) {
-        WgradPlan sub[4 * OSSID_WGRAD_GROUP_MAX];
-        int idx[4 * OSSID_WGRAD_GROUP_MAX], m = 0;
-        for (int i = 0; i < n; ++i)
-            if (plans[i].variant == v) sub[m] = plans[i], idx[m++] = i;
-        for (int c0 = 0; c0 < m; c0 += OSSID_WGRAD_GROUP_MAX) {
-            const int cnt = m - c0 < OSSID_WGRAD_GROUP_MAX ? m - c0 : OSSID_WGRAD_GROUP_MAX;
-            group_splits(sub + c0, cnt);
-            for (int j = 0; j < cnt; ++j) {
-                const ossid_wgrad_desc& d = descs[idx[c0 + j]];
-                total += ((size_t)sub[c0 + j].nsplit * sub[c0 + j].wk * d.taps * d.cout * d.cin * sizeof(float) + 255) & ~(size_t)255;
-            }
-        }
-    }
-    return total;
+    WgradGroupPlan P;
+    return wgrad_group_plan(descs, n, P) ? P.total : 0;
 }
 
 int ossid_conv_wgrad_group(const ossid_wgrad_desc* descs, int n, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!descs || n <= 0 || n > 2 * OSSID_WGRAD_GROUP_MAX || !workspace) return OSSID_EINVAL;
-    if (workspace_bytes < ossid_conv_wgrad_group_workspace_bytes(descs, n)) return OSSID_EINVAL;
-    {
-        WgradSplit S;
-        split_tiled(descs, n, S);
-        if (S.n9 + S.n1 > 0) {
-            char* ws = (char*)workspace;
-            if (S.n9) {
-                const size_t a = (ossid_wgrad_t9_workspace_bytes(S.t9, S.n9) + 255) & ~(size_t)255;
-                const int rc = ossid_wgrad_t9_group(S.t9, S.n9, ws, a, stream);
-                if (rc != OSSID_OK) return rc;
-                ws += a;
-            }
-            for (int f = 0; f < S.n1;) {
-                const int cnt = t1_chunk(S.t1, S.n1, f);
-                if (cnt <= 0) return OSSID_EINVAL;
-                const size_t a = (ossid_wgrad_t1_workspace_bytes(S.t1 + f, cnt) + 255) & ~(size_t)255;
-                const int rc = ossid_wgrad_t1_group(S.t1 + f, cnt, ws, a, stream);
-                if (rc != OSSID_OK) return rc;
-                ws += a, f += cnt;
-            }
-            if (S.nr == 0) return OSSID_OK;
-            return ossid_conv_wgrad_group(S.rest, S.nr, ws, workspace_bytes - (size_t)(ws - (char*)workspace), stream);
-        }
-    }
-    WgradPlan plans[4 * OSSID_WGRAD_GROUP_MAX];
-    for (int i = 0; i < n; ++i) {
-        const ossid_wgrad_desc& d = descs[i];
+    WgradGroupPlan P;
+    if (!workspace || !wgrad_group_plan(descs, n, P) || workspace_bytes < P.total) return OSSID_EINVAL;
+    for (int i = P.first_tiled; i < P.n; ++i) {              // (csrc/wgrad_t9.hip checks the problems it is handed itself)
+        const ossid_wgrad_desc& d = P.d[i];
         if (d.batch <= 0 || d.height <= 0 || d.width <= 0 || d.cin <= 0 || d.cout <= 0 || (d.cin % 4) || (d.cout % 4) || !d.x ||
             !d.dy || !d.dw || (d.pre_scale && !d.pre_shift) || d.dy_add)
             return OSSID_EINVAL;
-        if (!wgrad_plan(d.batch, d.height, d.width, d.cin, d.cout, d.taps, plans[i])) return OSSID_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
     ReduceGroup red;
     red.n = 0;
     int red_blocks = 0;
-    for (int v = 0; v < 7; ++v) {
-        int idx[4 * OSSID_WGRAD_GROUP_MAX], m = 0;
-        for (int i = 0; i < n; ++i)
-            if (plans[i].variant == v) idx[m++] = i;
-        for (int c0 = 0; c0 < m; c0 += OSSID_WGRAD_GROUP_MAX) {
-            const int cnt = m - c0 < OSSID_WGRAD_GROUP_MAX ? m - c0 : OSSID_WGRAD_GROUP_MAX;
-            WgradPlan sub[OSSID_WGRAD_GROUP_MAX];
-            for (int j = 0; j < cnt; ++j) sub[j] = plans[idx[c0 + j]];
-            group_splits(sub, cnt);
+    for (int k = 0; k < P.npieces; ++k) {
+        const WgradPiece& pc = P.piece[k];
+        ossid_wgrad_desc* d = P.d + pc.first;
+        char* ws = (char*)workspace + P.off[pc.first];
+        int rc;
+        if (pc.family != WGRAD_TILED) {
+            rc = (pc.family == WGRAD_T9 ? ossid_wgrad_t9_group : ossid_wgrad_t1_group)(d, pc.count, ws, pc.bytes, stream);
+        } else {
+            const WgradPlan* sub = P.plan + pc.first;
             WgradGroup g;
-            g.n = cnt;
+            g.n = pc.count;
             g.first_block[0] = 0;
             size_t lds = 0;
-            for (int j = 0; j < cnt; ++j) {
-                ossid_wgrad_desc d = descs[idx[c0 + j]];
-                d.workspace = ws;
-                const size_t bytes = (size_t)sub[j].nsplit * sub[j].wk * d.taps * d.cout * d.cin * sizeof(float);
-                ws += (bytes + 255) & ~(size_t)255;
-                const int rc = fill_wgrad_args(&d, sub[j], g.a[j]);
+            for (int j = 0; j < pc.count; ++j) {
+                d[j].workspace = (char*)workspace + P.off[pc.first + j];
+                rc = fill_wgrad_args(&d[j], sub[j], g.a[j]);
                 if (rc != OSSID_OK) return rc;
                 g.first_block[j + 1] = g.first_block[j] + sub[j].nsplit * sub[j].ntiles;
                 if (sub[j].lds > lds) lds = sub[j].lds;
                 ReduceRow& r = red.r[red.n++];
-                r.slabs = (const float*)d.workspace, r.dw = d.dw, r.nslabs = sub[j].nsplit * sub[j].wk, r.taps = d.taps;
-                r.Cout = d.cout, r.Cin = d.cin, r.accumulate = d.accumulate, r.first_block = red_blocks;
-                red_blocks += (int)(((size_t)d.taps * d.cout * d.cin + 63) / 64);
+                r.slabs = (const float*)d[j].workspace, r.dw = d[j].dw, r.nslabs = sub[j].nsplit * sub[j].wk, r.taps = d[j].taps;
+                r.Cout = d[j].cout, r.Cin = d[j].cin, r.accumulate = d[j].accumulate, r.first_block = red_blocks;
+                red_blocks += (int)(((size_t)d[j].taps * d[j].cout * d[j].cin + 63) / 64);
             }
-            int rc;
-            switch (v) {
-                case 0: rc = launch_wgrad_group<9, 1, 2, 1, 2, 2, 1>(g, lds, sub[0].sb != 0, s); break;
-                case 1: rc = launch_wgrad_group<9, 1, 1, 2, 2, 2, 1>(g, lds, sub[0].sb != 0, s); break;
-                case 2: rc = launch_wgrad_group<9, 1, 1, 1, 1, 4, 1>(g, lds, sub[0].sb != 0, s); break;
-                case 3: rc = launch_wgrad_group<1, 1, 2, 2, 2, 2, 1>(g, lds, sub[0].sb != 0, s); break;
-                case 4: rc = launch_wgrad_group<1, 1, 1, 2, 2, 2, 1>(g, lds, sub[0].sb != 0, s); break;
-                case 5: rc = launch_wgrad_group<9, 3, 1, 1, 1, 1, 4>(g, lds, sub[0].sb != 0, s); break;
-                default: rc = launch_wgrad_group<9, 3, 1, 1, 1, 2, 2>(g, lds, sub[0].sb != 0, s); break;
-            }
-            if (rc != OSSID_OK) return rc;
+            rc = launch_wgrad_group(pc.variant, g, lds, sub[0].sb != 0, s);
         }
+        if (rc != OSSID_OK) return rc;
     }
     if (red.n > 0) hipLaunchKernelGGL(wgrad_reduce_group_kernel, dim3((unsigned)red_blocks), dim3(256), 0, s, red);
     return ossid_launch_status();

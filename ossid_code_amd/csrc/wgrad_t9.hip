@@ -453,12 +453,6 @@ static int t9_jobs_of(const ossid_wgrad_desc& d) { return ((d.cout + 32 * t9_tm(
 static long long t9_tiles(const ossid_wgrad_desc& d) {
     return (long long)d.batch * ((d.height + T9_TH - 1) / T9_TH) * ((d.width + T9_TW - 1) / T9_TW);
 }
-static int t9_nwg(int tm, int jobs, long long ntiles) {
-    int nwg = (tm == 2 ? t9_grid<2>() : t9_grid<1>()) / jobs;
-    if (nwg < 1) nwg = 1;
-    if (nwg > ntiles) nwg = (int)ntiles;
-    return nwg;
-}
 int ossid_wgrad_t9_max_jobs(void) { return T9_MAX; }
 int ossid_wgrad_t9_class(const ossid_wgrad_desc* d) { return t9_tm(*d); }          // problems of one call share it
 int ossid_wgrad_t9_job_count(const ossid_wgrad_desc* descs, int n) {
@@ -467,30 +461,38 @@ int ossid_wgrad_t9_job_count(const ossid_wgrad_desc* descs, int n) {
     return jobs;
 }
 
-// n problems of ONE geometry (batch, height, width) and one class, all accepted by ossid_wgrad_t9_takes. A problem with more
-// jobs than a launch takes is cut over several launches here; the list as a whole may be of any length.
-size_t ossid_wgrad_t9_workspace_bytes(const ossid_wgrad_desc* descs, int n) {
-    if (n <= 0) return 0;
-    const int tm = t9_tm(descs[0]);
-    const int jobs = ossid_wgrad_t9_job_count(descs, n);
-    const int per_launch = jobs < T9_MAX ? jobs : T9_MAX;
+// How a call lays its problems out: n (> 0) problems of ONE geometry (batch, height, width) and one class, all accepted by
+// ossid_wgrad_t9_takes. A problem with more jobs than a launch takes is cut over several launches; the list as a whole may be
+// of any length.
+struct T9Layout {
+    int tm, jobs;
+    long long ntiles;
+    int nwg;                // workgroups per job
+    size_t bytes;
+};
+static T9Layout t9_layout(const ossid_wgrad_desc* descs, int n) {
+    T9Layout L;
+    L.tm = t9_tm(descs[0]), L.jobs = ossid_wgrad_t9_job_count(descs, n), L.ntiles = t9_tiles(descs[0]);
     // (every launch of the call has at most per_launch jobs, hence at least this many workgroups per job)
-    return (size_t)jobs * t9_nwg(tm, per_launch, t9_tiles(descs[0])) * t9_slab(tm) * sizeof(float);
+    const int per_launch = L.jobs < T9_MAX ? L.jobs : T9_MAX;
+    L.nwg = (L.tm == 2 ? t9_grid<2>() : t9_grid<1>()) / per_launch;
+    if (L.nwg < 1) L.nwg = 1;
+    if (L.nwg > L.ntiles) L.nwg = (int)L.ntiles;
+    L.bytes = (size_t)L.jobs * L.nwg * t9_slab(L.tm) * sizeof(float);
+    return L;
 }
+
+size_t ossid_wgrad_t9_workspace_bytes(const ossid_wgrad_desc* descs, int n) { return n > 0 ? t9_layout(descs, n).bytes : 0; }
 
 int ossid_wgrad_t9_group(const ossid_wgrad_desc* descs, int n, void* workspace, size_t workspace_bytes, void* stream) {
     if (n <= 0 || !workspace || ((uintptr_t)workspace & 15)) return OSSID_EINVAL;
-    const int tm = t9_tm(descs[0]);
-    const int jobs_all = ossid_wgrad_t9_job_count(descs, n);
-    const int per_launch = jobs_all < T9_MAX ? jobs_all : T9_MAX;
+    const T9Layout L = t9_layout(descs, n);
+    const int tm = L.tm;
+    if (L.ntiles > 0x7fffffff || workspace_bytes < L.bytes) return OSSID_EINVAL;
     T9Args a;
     a.B = descs[0].batch, a.H = descs[0].height, a.W = descs[0].width;
     a.tiles_y = (a.H + T9_TH - 1) / T9_TH, a.tiles_x = (a.W + T9_TW - 1) / T9_TW;
-    const long long nt = t9_tiles(descs[0]);
-    if (nt > 0x7fffffff) return OSSID_EINVAL;
-    a.ntiles = (int)nt;
-    a.nwg = t9_nwg(tm, per_launch, nt);
-    if (workspace_bytes < (size_t)jobs_all * a.nwg * t9_slab(tm) * sizeof(float)) return OSSID_EINVAL;
+    a.ntiles = (int)L.ntiles, a.nwg = L.nwg;
     hipStream_t s = (hipStream_t)stream;
     float* ws = (float*)workspace;
     auto flush = [&]() {
@@ -550,33 +552,37 @@ static int t1_jobs(const ossid_wgrad_desc* descs, int n) {
     for (int i = 0; i < n; ++i) jobs += (descs[i].cin + T1_CIB - 1) / T1_CIB;
     return jobs;
 }
-static int t1_nwg(int jobs, long long nstages) {
-    int nwg = t1_grid() / jobs;
-    if (nwg < 1) nwg = 1;
-    if (nwg > nstages) nwg = (int)nstages;
-    return nwg;
-}
-
-// n problems of ONE pixel count (batch * height * width), all accepted by ossid_wgrad_t1_takes, at most T1_MAX jobs
 int ossid_wgrad_t1_max_jobs(void) { return T1_MAX; }
 int ossid_wgrad_t1_job_count(const ossid_wgrad_desc* descs, int n) { return t1_jobs(descs, n); }
 
-size_t ossid_wgrad_t1_workspace_bytes(const ossid_wgrad_desc* descs, int n) {
-    const int jobs = t1_jobs(descs, n);
-    if (n <= 0 || jobs > T1_MAX) return 0;
-    const long long npx = (long long)descs[0].batch * descs[0].height * descs[0].width;
-    return (size_t)jobs * t1_nwg(jobs, (npx + T1_PXS - 1) / T1_PXS) * T1_SLAB * sizeof(float);
+// How a call lays its problems out: n problems of ONE pixel count (batch * height * width), all accepted by
+// ossid_wgrad_t1_takes, at most T1_MAX jobs (bytes = 0 otherwise)
+struct T1Layout {
+    int jobs;
+    long long npx, nstages;
+    int nwg;                // workgroups per job
+    size_t bytes;
+};
+static T1Layout t1_layout(const ossid_wgrad_desc* descs, int n) {
+    T1Layout L = {};
+    L.jobs = t1_jobs(descs, n);
+    if (n <= 0 || L.jobs <= 0 || L.jobs > T1_MAX) return L;
+    L.npx = (long long)descs[0].batch * descs[0].height * descs[0].width, L.nstages = (L.npx + T1_PXS - 1) / T1_PXS;
+    L.nwg = t1_grid() / L.jobs;
+    if (L.nwg < 1) L.nwg = 1;
+    if (L.nwg > L.nstages) L.nwg = (int)L.nstages;
+    L.bytes = (size_t)L.jobs * L.nwg * T1_SLAB * sizeof(float);
+    return L;
 }
 
+size_t ossid_wgrad_t1_workspace_bytes(const ossid_wgrad_desc* descs, int n) { return t1_layout(descs, n).bytes; }
+
 int ossid_wgrad_t1_group(const ossid_wgrad_desc* descs, int n, void* workspace, size_t workspace_bytes, void* stream) {
-    const int jobs = t1_jobs(descs, n);
-    if (n <= 0 || jobs > T1_MAX || !workspace || ((uintptr_t)workspace & 15)) return OSSID_EINVAL;
+    const T1Layout L = t1_layout(descs, n);
+    const int jobs = L.jobs;
+    if (!L.bytes || L.nstages > 0x7fffffff || workspace_bytes < L.bytes || !workspace || ((uintptr_t)workspace & 15)) return OSSID_EINVAL;
     T1Args a;
-    a.npx = (long long)descs[0].batch * descs[0].height * descs[0].width;
-    const long long ns = (a.npx + T1_PXS - 1) / T1_PXS;
-    if (ns > 0x7fffffff) return OSSID_EINVAL;
-    a.nstages = (int)ns, a.n = jobs, a.nwg = t1_nwg(jobs, ns), a.slabs = (float*)workspace;
-    if (workspace_bytes < (size_t)jobs * a.nwg * T1_SLAB * sizeof(float)) return OSSID_EINVAL;
+    a.npx = L.npx, a.nstages = (int)L.nstages, a.n = jobs, a.nwg = L.nwg, a.slabs = (float*)workspace;
     int ji = 0;
     for (int i = 0; i < n; ++i) {
         const ossid_wgrad_desc& d = descs[i];

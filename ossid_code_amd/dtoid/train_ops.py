@@ -339,19 +339,26 @@ def colsum_finalize(partials, C, sums, sums_row_stride=0):
                                                     _lib.stream()), "ossid_colsum_finalize")
 
 
+def _wgrad_desc(d, x, dy, dw, B, H, W, cin, cout, taps, pre=None, pre_relu=False, in_cs=0, dy_cs=0, src_hw=(0, 0),
+                accumulate=False, dy_add=None):
+    """Fills the ossid_wgrad_desc `d` (the workspace fields are the caller's)."""
+    d.x, d.dy, d.dw = dptr(x), dptr(dy), dptr(dw)
+    d.pre_scale, d.pre_shift = map(dptr, pre or (None, None))
+    d.batch, d.height, d.width, d.cin, d.cout, d.taps = B, H, W, cin, cout, taps
+    d.pre_relu, d.accumulate = 1 if pre_relu else 0, 1 if accumulate else 0
+    d.in_channel_stride, d.dy_channel_stride = int(in_cs), int(dy_cs)
+    d.src_height, d.src_width = int(src_hw[0]), int(src_hw[1])
+    # dy = dy + scale * add + shift while it is staged (ossid_wgrad_desc.dy_add)
+    d.dy_add, d.dy_add_scale, d.dy_add_shift = map(dptr, dy_add or (None, None, None))
+
+
 def wgrad_raw(x, dy, B, H, W, cin, cout, taps, dw, pre=None, pre_relu=False, in_cs=0, dy_cs=0, src_hw=(0, 0),
               accumulate=False):
     d = _lib.WgradDesc()
     dev = dw.device
     nbytes = _lib.fn("ossid_conv_wgrad_workspace_bytes")(B, H, W, cin, cout, taps)
-    ws = _scratch("wgrad", nbytes, dev)
-    d.x, d.dy, d.dw, d.workspace, d.workspace_bytes = dptr(x), dptr(dy), dptr(dw), dptr(ws), nbytes
-    if pre is not None:
-        d.pre_scale, d.pre_shift = dptr(pre[0]), dptr(pre[1])
-    d.batch, d.height, d.width, d.cin, d.cout, d.taps = B, H, W, cin, cout, taps
-    d.pre_relu, d.accumulate = 1 if pre_relu else 0, 1 if accumulate else 0
-    d.in_channel_stride, d.dy_channel_stride = int(in_cs), int(dy_cs)
-    d.src_height, d.src_width = int(src_hw[0]), int(src_hw[1])
+    _wgrad_desc(d, x, dy, dw, B, H, W, cin, cout, taps, pre, pre_relu, in_cs, dy_cs, src_hw, accumulate)
+    d.workspace, d.workspace_bytes = dptr(_scratch("wgrad", nbytes, dev)), nbytes
     with _lib.on_device(dev):
         _lib.check(_lib.fn("ossid_conv_wgrad")(_byref(d), _lib.stream()), "ossid_conv_wgrad")
     return dw
@@ -359,17 +366,12 @@ def wgrad_raw(x, dy, B, H, W, cin, cout, taps, dw, pre=None, pre_relu=False, in_
 
 def wgrad_group(items):
     """Several independent weight gradients in one launch per tiling variant (ossid_conv_wgrad_group). items: dicts with
-    the keyword arguments of wgrad_raw (x, dy, B, H, W, cin, cout, taps, dw, pre, pre_relu, in_cs, dy_cs)."""
+    the keyword arguments of wgrad_raw (x, dy, B, H, W, cin, cout, taps, dw, pre, pre_relu, in_cs, dy_cs) and dy_add."""
     n = len(items)
     arr = (_lib.WgradDesc * n)()
     for d, it in zip(arr, items):
-        d.x, d.dy, d.dw = dptr(it["x"]), dptr(it["dy"]), dptr(it["dw"])
-        d.pre_scale, d.pre_shift = map(dptr, it.get("pre") or (None, None))
-        d.batch, d.height, d.width, d.cin, d.cout, d.taps = it["B"], it["H"], it["W"], it["cin"], it["cout"], it["taps"]
-        d.pre_relu, d.accumulate = 1 if it.get("pre_relu") else 0, 0
-        d.in_channel_stride, d.dy_channel_stride = int(it.get("in_cs", 0)), int(it.get("dy_cs", 0))
-        # dy = dy + scale * add + shift while it is staged (ossid_wgrad_desc.dy_add)
-        d.dy_add, d.dy_add_scale, d.dy_add_shift = map(dptr, it.get("dy_add") or (None, None, None))
+        _wgrad_desc(d, it["x"], it["dy"], it["dw"], it["B"], it["H"], it["W"], it["cin"], it["cout"], it["taps"], it.get("pre"),
+                    it.get("pre_relu"), it.get("in_cs", 0), it.get("dy_cs", 0), dy_add=it.get("dy_add"))
     dev = items[0]["dw"].device
     nbytes = _lib.fn("ossid_conv_wgrad_group_workspace_bytes")(arr, n)
     if nbytes == 0:

@@ -620,6 +620,49 @@ def test_grouped_weight_gradients_of_a_dense_block_match_torch(hiplib, B, H, W, 
         assert torch.equal(it["dw"], f)
 
 
+def test_a_group_of_mixed_geometries_equals_its_parts_called_separately(hiplib):
+    """ossid_conv_wgrad_group on eight problems of two geometries and both t9 classes (tests/workspace_cases.py,
+    GROUP_SHAPES[1]), with prologues and with x / dy as channel slices of wider buffers as in the dense-block test above:
+    against float64 autograd at that test's bound, bit-reproducible, and bit-equal to what the rounds of the entry amount
+    to -- the parts MIXED_PARTS submitted as separate calls (a plan that merged or reordered parts would change the
+    K-splits, and with them the rounding). An all-f32 build routes nothing apart: there the group must equal, problem by
+    problem, the same problems in one call of another order."""
+    import workspace_cases as wc
+    g = torch.Generator().manual_seed(178)
+    items, want = [], []
+    for i, (cin, cout, taps, B, H, W) in enumerate(wc.group_probs(wc.GROUP_SHAPES[1])):
+        k = 3 if taps == 9 else 1
+        xb = torch.randn(B, cin + 32, H, W, generator=g)              # x: the first cin channels of the buffer
+        gb = torch.randn(B, cout + 32, H, W, generator=g)             # dy: its channels 32 .. 32 + cout
+        ps, pt = torch.randn(cin, generator=g), torch.randn(cin, generator=g)
+        relu = i % 3 != 2
+        px = xb[:, :cin].double() * ps.double().view(1, -1, 1, 1) + pt.double().view(1, -1, 1, 1)
+        w = torch.zeros(cout, cin, k, k, dtype=torch.float64, requires_grad=True)
+        F.conv2d(F.relu(px) if relu else px, w, padding=k // 2).backward(gb[:, 32:].double())
+        want.append(w.grad)
+        items.append(dict(x=cl(xb), dy=T.flat(cl(gb), 32), B=B, H=H, W=W, cin=cin, cout=cout, taps=taps,
+                          dw=torch.empty(cout, cin, k, k, device="cuda"), pre=(ps.cuda(), pt.cuda()), pre_relu=relu,
+                          in_cs=cin + 32, dy_cs=cout + 32))
+
+    def run(order_of_calls):
+        for it in items:
+            it["dw"].fill_(float("nan"))
+        for idx in order_of_calls:
+            T.wgrad_group([items[j] for j in idx])
+        torch.cuda.synchronize()
+        return [it["dw"].clone() for it in items]
+    whole = tuple(range(len(items)))
+    first = run([whole])
+    for it, got, w in zip(items, first, want):
+        print("mixed group %d -> %d taps %d: %.3g" % (it["cin"], it["cout"], it["taps"], rel(got, w)))
+        assert rel(got, w) < 5e-5, (it["cin"], it["cout"], rel(got, w))
+    for a, b in zip(run([whole]), first):
+        assert torch.equal(a, b)
+    other = wc.MIXED_PARTS if hiplib.fn("ossid_conv_wgrad_split_bf16")() else [(6, 4, 7, 2, 5, 1, 3, 0)]
+    for i, (a, b) in enumerate(zip(run(other), first)):
+        assert torch.equal(a, b), i
+
+
 def test_c_side_replay_of_a_dense_block_equals_the_python_loop_bit_for_bit(hiplib, monkeypatch):
     """ossid_seq_replay (csrc/seq.hip) re-issues a dense block's recorded forward and backward launches -- descriptor pointers,
     integers beyond the sixth on the stack, floats and doubles in xmm registers, the stream-order ops between the main and the

@@ -163,16 +163,33 @@ def wgrad_build(lib, s):
 
 
 # ---- D16 ossid_conv_wgrad_group ------------------------------------------------------------------------------------------------
-# shape: (B, H, W, ((Cin, Cout, taps), ...)): the 3x3 (128 -> 32) and 1x1 (c -> 128) problems of a dense block, which
-# csrc/wgrad_t9.hip takes as two tiling variants of their own, and two problems that stay on train.hip's kernels (two more
-# variants): the group's one workspace is carved four ways.
-GROUP_SHAPES = [(1, 7, 9, ((128, 32, 9), (64, 128, 1), (128, 32, 9), (96, 128, 1), (16, 16, 9), (24, 40, 9)))]
+# shape: (B, H, W, ((Cin, Cout, taps) or (Cin, Cout, taps, H, W), ...)); a problem may carry a height and width of its own.
+# Row 0: the 3x3 (128 -> 32) and 1x1 (c -> 128) problems of a dense block, which csrc/wgrad_t9.hip takes as two tiling variants
+# of their own, and two problems that stay on train.hip's kernels (two more variants): the group's one workspace is carved
+# four ways. Row 1: two geometries and both t9 classes (cout 32 / cout >= 64) in one group: csrc/wgrad_t9.hip takes one
+# geometry and one class per call, so the group goes there in rounds -- {0, 7}, {1}, {2} to t9, {3}, {4} to t1 -- and the two
+# problems left over ({5, 6}) share train.hip's grouped launches.
+GROUP_SHAPES = [(1, 7, 9, ((128, 32, 9), (64, 128, 1), (128, 32, 9), (96, 128, 1), (16, 16, 9), (24, 40, 9))),
+                (1, 7, 9, ((128, 32, 9), (128, 64, 9), (128, 32, 9, 5, 6), (64, 128, 1), (96, 128, 1, 5, 6), (24, 40, 9, 5, 6),
+                           (16, 16, 9), (128, 32, 9)))]
+MIXED_PARTS = ((0, 7), (1,), (2,), (3,), (4,), (5, 6))         # row 1 as the calls its rounds amount to (split-bf16 builds)
+
+
+def group_probs(s):
+    """The problems of a row as (Cin, Cout, taps, B, H, W)."""
+    B, H, W, probs = s
+    return [(p[0], p[1], p[2], B) + (tuple(p[3:5]) if len(p) > 3 else (H, W)) for p in probs]
+
+
+def group_sub(s, idx):
+    """The row holding the problems `idx` of row `s`, in that order."""
+    return s[:3] + (tuple(s[3][i] for i in idx),)
 
 
 def _group_descs(lib, s, ptrs=None):
-    B, H, W, probs = s
+    probs = group_probs(s)
     arr = (lib.WgradDesc * len(probs))()
-    for i, (d, (cin, cout, taps)) in enumerate(zip(arr, probs)):
+    for i, (d, (cin, cout, taps, B, H, W)) in enumerate(zip(arr, probs)):
         d.batch, d.height, d.width, d.cin, d.cout, d.taps = B, H, W, cin, cout, taps
         if ptrs is not None:
             d.x, d.dy, d.dw = ptrs[i]
@@ -185,10 +202,10 @@ def group_need(lib, s):
 
 
 def group_pred(lib, s):
-    probs = s[3]
+    probs = group_probs(s)
+    sb = bool(lib.fn("ossid_conv_wgrad_split_bf16")())
     kinds = set()
-    for cin, cout, taps in probs:
-        sb = bool(lib.fn("ossid_conv_wgrad_split_bf16")())
+    for cin, cout, taps, _, _, _ in probs:
         if sb and taps == 9 and cin % 128 == 0 and cout >= 32:
             kinds.add("t9")
         elif sb and taps == 1 and cout == 128 and cin % 32 == 0:
@@ -196,12 +213,19 @@ def group_pred(lib, s):
         else:
             kinds.add(wgrad_variant(cin, cout, taps)[0])
     assert len(probs) >= 3 and len(kinds) >= 2, kinds
-    assert group_need(lib, s)["ossid_conv_wgrad_group_workspace_bytes"] > 0
+    whole = group_need(lib, s)["ossid_conv_wgrad_group_workspace_bytes"]
+    assert whole > 0
+    if s == GROUP_SHAPES[1] and sb:
+        # the group's size is the sum of its parts queried separately, whatever the order of the problems
+        parts = [group_need(lib, group_sub(s, idx))["ossid_conv_wgrad_group_workspace_bytes"] for idx in MIXED_PARTS]
+        assert all(p > 0 for p in parts) and whole == sum(parts), (whole, parts)
+        turned = group_need(lib, group_sub(s, (6, 4, 7, 2, 5, 1, 3, 0)))["ossid_conv_wgrad_group_workspace_bytes"]
+        assert turned == whole, (turned, whole)
 
 
 def group_build(lib, s):
-    B, H, W, probs = s
-    ins = [_wgrad_inputs(B, cin, cout, H, W, taps, 11 * i + cin) for i, (cin, cout, taps) in enumerate(probs)]
+    probs = group_probs(s)
+    ins = [_wgrad_inputs(B, cin, cout, H, W, taps, 11 * i + cin) for i, (cin, cout, taps, B, H, W) in enumerate(probs)]
     need = group_need(lib, s)["ossid_conv_wgrad_group_workspace_bytes"]
 
     def run(ws, out):
@@ -209,11 +233,11 @@ def group_build(lib, s):
         return lib.fn("ossid_conv_wgrad_group")(arr, len(probs), ws["ws"].ptr, ws["ws"].nbytes, stream(lib))
 
     def anchor(out):          # the bound of test_train_ops_gpu.py::test_grouped_weight_gradients_of_a_dense_block_match_torch
-        for i, ((cin, cout, taps), (_, _, want, k)) in enumerate(zip(probs, ins)):
+        for i, ((cin, cout, taps, _, _, _), (_, _, want, k)) in enumerate(zip(probs, ins)):
             assert rel(f32(out["dw%d" % i], cout, cin, k, k), want) < 5e-5, (i, cin, cout)
-    outs = {"dw%d" % i: cout * cin * taps * 4 for i, (cin, cout, taps) in enumerate(probs)}
+    outs = {"dw%d" % i: cout * cin * taps * 4 for i, (cin, cout, taps, _, _, _) in enumerate(probs)}
     # every share of the workspace is rounded to 256 bytes and the tiled kernels' slabs are multiples of 512
-    return [Contract("conv_wgrad_group " + sid(s[:3]), {"ws": need}, outs, run, anchor, short=("ws",))]
+    return [Contract("conv_wgrad_group " + sid(s), {"ws": need}, outs, run, anchor, short=("ws",))]
 
 
 # ---- D4 ossid_stem_conv_wgrad --------------------------------------------------------------------------------------------------
