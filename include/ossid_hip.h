@@ -1001,8 +1001,35 @@ int ossid_bop_vsd(const float* depth_obs, const float* cams, int Fr, int H, int 
 int ossid_bop_mssd_mspd(const float* vertices, int V, const double* symmetries, int S, const double* pose_est,
                         const double* pose_gt, const float* cams, int Fr, const int32_t* frame_host, int N, double* mssd,
                         double* mspd, void* stream);
+/* Several instances per target (SPEC.md 8.10-8.12; csrc/bop_eval.hip): BOP-19's errors between every kept estimate and
+ * every ground-truth instance of a target, and its greedy matching per threshold. Caller-owned buffers, no workspace,
+ * launches only, nothing read back, capturable. Still this build's restatement; parity with bop_toolkit unpinned.
+ * ossid_bop_vsd_pairs (8.11): ossid_bop_vsd over a pair table. z_est f32 [Ne][H][W] and z_gt f32 [Ng][H][W] are two
+ * separate stacks of ossid_raster_depth renders (each estimate and each instance rendered once); pairs int32 [P][3] =
+ * (est_row, gt_row, frame) in DEVICE memory -> counts int32 [P][T+2], errors f64 [P][T], row p from the images the table
+ * names, by ossid_bop_vsd's own per-pixel code. A row with est_row outside [0, Ne), gt_row outside [0, Ng) or frame
+ * outside [0, Fr) is found on the device: no image is read, its counts are 0 and its errors 1.0; other rows are not
+ * affected. taus_host as ossid_bop_vsd. OSSID_EINVAL before any launch: Ne, Ng, P or Fr < 1, and what ossid_bop_vsd
+ * refuses of T, taus, diameter, delta, H W, NULL pointers.
+ * ossid_bop_match (8.12): err f64 [Ptot][T+2] = per pair the T VSD errors, MSSD, MSPD; groups int32 [Gr][5] =
+ * (pair_first, est_first, inst_first, E, G) per target: its E kept estimates in rank order are rows est_first .. of match,
+ * its G instances entries inst_first .. of valid (u8, non-zero = counts towards tp), and its pairs, [e][g] row-major, rows
+ * pair_first .. of err; thr f64 [Gr][T+2][10] the thresholds -> match int32 [Etot][T+2][10] = the instance (0 .. G-1) each
+ * estimate is matched to per error kind and threshold column, -1 for none; tp int32 [T+2][10] = the matches whose
+ * instance is valid, over all groups. Estimates in rank order; an estimate takes the not yet matched instance with
+ * err < thr (strict, NaN never) of smallest error, the lowest index among equal errors. Both outputs are overwritten
+ * (cleared by a kernel first). A group row with E outside [0, OSSID_BOP_MAX_INSTANCES], G outside [1,
+ * OSSID_BOP_MAX_INSTANCES] or a range that leaves err, match or valid is skipped on the device: its estimates stay -1.
+ * Integer atomics only: bit-reproducible. OSSID_EINVAL: Gr < 1, Itot < 1, Ptot or Etot < 0, T outside [1,
+ * OSSID_BOP_MAX_TAUS], a NULL groups, valid, thr or tp, a NULL err with Ptot > 0 or match with Etot > 0. */
+#define OSSID_BOP_MAX_INSTANCES 64
+int ossid_bop_vsd_pairs(const float* depth_obs, const float* cams, int Fr, int H, int W, const float* z_est, int Ne,
+                        const float* z_gt, int Ng, const int32_t* pairs, int P, double diameter, double delta,
+                        const double* taus_host, int T, int32_t* counts, double* errors, void* stream);
+int ossid_bop_match(const double* err, int Ptot, const int32_t* groups, int Gr, const uint8_t* valid, int Itot,
+                    const double* thr, int T, int32_t* match, int Etot, int32_t* tp, void* stream);
 
-/* 8f-6  the scorer's model cloud from the object's mesh (scripts/online_learning.py:303-311 loads model_points /
+/* 8f-6 the scorer's model cloud from the object's mesh (scripts/online_learning.py:303-311 loads model_points /
  * model_colors / model_normals from zephyr_model_data/{lmo,ycbv}/model_cloud_XX.npz, a download made by a script that is
  * in neither tree). SPEC.md section 9 (csrc/model_cloud.hip): this build's own definition, parity with zephyr's clouds
  * unpinned. Raw device pointers, caller-owned memory, launches only: nothing allocates, synchronises or is read back.

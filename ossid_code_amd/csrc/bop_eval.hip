@@ -21,6 +21,14 @@
 // minimum over the chunks by atomicMin on the 64-bit pattern of the non-negative double (it orders like the value; the
 // outputs start at +inf). Max and min do not depend on order.
 //
+// ossid_bop_vsd_pairs (8.11). ossid_bop_vsd's three launches over a pair table in device memory: row p = (estimate render,
+// ground-truth render, frame) picks the two images of vsd_tile, the device function both cost kernels share, so a group of
+// E estimates and G instances costs E + G renders and E G cost rows. The indices are checked on the device.
+//
+// ossid_bop_match (8.12). clear (match = -1, tp = 0), then one wave per (group, 64 threshold columns): each lane runs
+// BOP's greedy loop for its column with the matched set as a 64-bit mask in registers; no LDS; tp by integer atomicAdd,
+// so nothing depends on the order of arrival.
+//
 // frame[] and taus[] are host arrays (checked before any launch) and travel as kernel arguments, CHUNK estimates per launch:
 // a captured graph replays with the values they had at capture.
 #include <cmath>
@@ -45,19 +53,16 @@ __global__ __launch_bounds__(256) void bop_zero_kernel(int32_t* __restrict__ cou
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) counts[i] = 0;
 }
 
+// 8.3-8.5 over this workgroup's tile of one (estimate render ze, ground-truth render zg, observed image ob, camera cam):
+// the counts (n_U, n_I, c_0 .. c_{T-1}) of the tile's TILE pixels are added to row[0 .. T+2). Both cost kernels call it:
+// ossid_bop_vsd with the n-th image of either stack, ossid_bop_vsd_pairs with the two images a pair row names.
 template <bool VEC>
-__global__ __launch_bounds__(256) void bop_vsd_kernel(const float* __restrict__ depth_obs, const float* __restrict__ cams,
-                                                      int H, int W, const float* __restrict__ z_est,
-                                                      const float* __restrict__ z_gt, FrameIdx frames, double diameter,
-                                                      double delta, Taus taus, int T, int32_t* __restrict__ counts) {
-    const int n = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+__device__ __forceinline__ void vsd_tile(const float* __restrict__ ob, const float* __restrict__ cam, int H, int W,
+                                         const float* __restrict__ ze, const float* __restrict__ zg, double diameter,
+                                         double delta, const Taus& taus, int T, int32_t* __restrict__ row) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t hw = (size_t)H * W;
-    const int fr = frames.f[n];
-    const float* ze = z_est + (size_t)n * hw;
-    const float* zg = z_gt + (size_t)n * hw;
-    const float* ob = depth_obs + (size_t)fr * hw;
-    const double fx = (double)cams[4 * fr], fy = (double)cams[4 * fr + 1], cx = (double)cams[4 * fr + 2],
-                 cy = (double)cams[4 * fr + 3];
+    const double fx = (double)cam[0], fy = (double)cam[1], cx = (double)cam[2], cy = (double)cam[3];
     int nU = 0, nI = 0, c[OSSID_BOP_MAX_TAUS];      // wave-uniform
 #pragma unroll
     for (int k = 0; k < OSSID_BOP_MAX_TAUS; ++k) c[k] = 0;
@@ -124,8 +129,36 @@ __global__ __launch_bounds__(256) void bop_vsd_kernel(const float* __restrict__ 
     __syncthreads();
     if ((int)threadIdx.x < T + 2) {
         const int v = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-        if (v) atomicAdd(counts + (size_t)n * (T + 2) + threadIdx.x, v);
+        if (v) atomicAdd(row + threadIdx.x, v);
     }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void bop_vsd_kernel(const float* __restrict__ depth_obs, const float* __restrict__ cams,
+                                                      int H, int W, const float* __restrict__ z_est,
+                                                      const float* __restrict__ z_gt, FrameIdx frames, double diameter,
+                                                      double delta, Taus taus, int T, int32_t* __restrict__ counts) {
+    const int n = blockIdx.y, fr = frames.f[n];
+    const size_t hw = (size_t)H * W;
+    vsd_tile<VEC>(depth_obs + (size_t)fr * hw, cams + 4 * fr, H, W, z_est + (size_t)n * hw, z_gt + (size_t)n * hw, diameter, delta,
+                  taus, T, counts + (size_t)n * (T + 2));
+}
+
+// 8.11: row p of the pair table names an estimate render, a ground-truth render and a frame. The three indices are the
+// same for the whole workgroup; a row with one of them out of range reads no image and leaves its (zeroed) counts alone,
+// which finalise turns into e = 1.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bop_vsd_pairs_kernel(const float* __restrict__ depth_obs, const float* __restrict__ cams,
+                                                            int Fr, int H, int W, const float* __restrict__ z_est, int Ne,
+                                                            const float* __restrict__ z_gt, int Ng,
+                                                            const int32_t* __restrict__ pairs, double diameter, double delta,
+                                                            Taus taus, int T, int32_t* __restrict__ counts) {
+    const size_t p = blockIdx.y;
+    const int e = pairs[3 * p], g = pairs[3 * p + 1], fr = pairs[3 * p + 2];
+    if (e < 0 || e >= Ne || g < 0 || g >= Ng || fr < 0 || fr >= Fr) return;      // workgroup-uniform
+    const size_t hw = (size_t)H * W;
+    vsd_tile<VEC>(depth_obs + (size_t)fr * hw, cams + 4 * fr, H, W, z_est + (size_t)e * hw, z_gt + (size_t)g * hw, diameter, delta,
+                  taus, T, counts + p * (T + 2));
 }
 
 __global__ __launch_bounds__(256) void bop_vsd_finalize_kernel(const int32_t* __restrict__ counts, int N, int T,
@@ -223,6 +256,55 @@ __global__ __launch_bounds__(256) void bop_mssd_mspd_kernel(const float* __restr
     }
 }
 
+constexpr int MATCH_COLS = 10;        // threshold columns j of 8.12
+constexpr int PAIR_ROWS = 32768;      // pair rows per launch of the pair kernel (grid.y)
+
+// 8.12 outputs before the greedy pass: every estimate unmatched, no true positive.
+__global__ __launch_bounds__(256) void bop_match_clear_kernel(int32_t* __restrict__ match, size_t n_match,
+                                                              int32_t* __restrict__ tp, int n_tp) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_match) match[i] = -1;
+    if (i < (size_t)n_tp) tp[i] = 0;
+}
+
+// 8.12. One wave per (group, 64 columns); a lane owns column c = (k, j) of its group and walks the group's estimates in
+// rank order with the matched instances as a 64-bit mask in registers. The lanes of a wave read the same [E][G] block of
+// errors, ten neighbouring lanes the same double. A group row that does not fit the tables is skipped whole (its estimates
+// stay unmatched). Matches whose instance is valid are counted per lane and leave as one integer atomicAdd per column.
+__global__ __launch_bounds__(64) void bop_match_kernel(const double* __restrict__ err, int Ptot,
+                                                       const int32_t* __restrict__ groups, const uint8_t* __restrict__ valid,
+                                                       int Itot, const double* __restrict__ thr, int K, int Etot,
+                                                       int32_t* __restrict__ match, int32_t* __restrict__ tp) {
+    const size_t gr = blockIdx.x;
+    const int c = blockIdx.y * 64 + threadIdx.x, C = K * MATCH_COLS;
+    const int32_t* row = groups + 5 * gr;
+    const int p0 = row[0], e0 = row[1], i0 = row[2], E = row[3], G = row[4];
+    if (E < 0 || E > OSSID_BOP_MAX_INSTANCES || G < 1 || G > OSSID_BOP_MAX_INSTANCES || p0 < 0 || e0 < 0 || i0 < 0 ||
+        (long long)p0 + (long long)E * G > Ptot || (long long)e0 + E > Etot || (long long)i0 + G > Itot)
+        return;                                      // wave-uniform
+    if (c >= C) return;
+    const int k = c / MATCH_COLS;
+    const double th = thr[gr * C + c];
+    const double* er = err + (size_t)p0 * K + k;
+    unsigned long long taken = 0ull;
+    int hits = 0;
+    for (int e = 0; e < E; ++e) {
+        int best = -1;
+        double best_err = 0.0;
+        for (int g = 0; g < G; ++g) {
+            const double v = er[((size_t)e * G + g) * K];
+            // strict <: a NaN is never below; ties keep the lower g
+            if (!((taken >> g) & 1ull) && v < th && (best < 0 || v < best_err)) best = g, best_err = v;
+        }
+        if (best >= 0) {
+            taken |= 1ull << best;
+            hits += valid[i0 + best] != 0;
+        }
+        match[((size_t)e0 + e) * C + c] = best;
+    }
+    if (hits) atomicAdd(tp + c, hits);
+}
+
 bool frames_ok(const int32_t* frame_host, int N, int Fr) {
     for (int i = 0; i < N; ++i)
         if (frame_host[i] < 0 || frame_host[i] >= Fr) return false;
@@ -263,6 +345,51 @@ int ossid_bop_vsd(const float* depth_obs, const float* cams, int Fr, int H, int 
                                z_gt + (size_t)a * hw, fi, diameter, delta, taus, T, counts + (size_t)a * (T + 2));
     }
     hipLaunchKernelGGL(bop_vsd_finalize_kernel, dim3((unsigned)(((size_t)N * T + 255) / 256)), dim3(256), 0, s, counts, N, T, errors);
+    return ossid_launch_status();
+}
+
+int ossid_bop_vsd_pairs(const float* depth_obs, const float* cams, int Fr, int H, int W, const float* z_est, int Ne,
+                        const float* z_gt, int Ng, const int32_t* pairs, int P, double diameter, double delta,
+                        const double* taus_host, int T, int32_t* counts, double* errors, void* stream) {
+    if (!depth_obs || !cams || !z_est || !z_gt || !pairs || !taus_host || !counts || !errors || Fr < 1 || Ne < 1 || Ng < 1 ||
+        P < 1 || H <= 0 || W <= 0 || (long long)H * W > OSSID_RASTER_MAX_PIXELS || T < 1 || T > OSSID_BOP_MAX_TAUS ||
+        !(diameter > 0.0) || !std::isfinite(diameter) || !(delta >= 0.0) || !std::isfinite(delta))
+        return OSSID_EINVAL;
+    Taus taus = {};
+    for (int k = 0; k < T; ++k) {
+        if (!std::isfinite(taus_host[k])) return OSSID_EINVAL;
+        taus.t[k] = taus_host[k];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t hw = (size_t)H * W, ncount = (size_t)P * (T + 2);
+    const bool vec = hw % 4 == 0 && (((uintptr_t)depth_obs | (uintptr_t)z_est | (uintptr_t)z_gt) & 15) == 0;
+    hipLaunchKernelGGL(bop_zero_kernel, dim3((unsigned)((ncount + 255) / 256 < 1024 ? (ncount + 255) / 256 : 1024)), dim3(256), 0, s,
+                       counts, ncount);
+    const unsigned tiles = (unsigned)((hw + TILE - 1) / TILE);
+    for (int a = 0; a < P; a += PAIR_ROWS) {
+        const int nb = P - a < PAIR_ROWS ? P - a : PAIR_ROWS;
+        if (vec)
+            hipLaunchKernelGGL(bop_vsd_pairs_kernel<true>, dim3(tiles, nb), dim3(256), 0, s, depth_obs, cams, Fr, H, W, z_est, Ne,
+                               z_gt, Ng, pairs + 3 * (size_t)a, diameter, delta, taus, T, counts + (size_t)a * (T + 2));
+        else
+            hipLaunchKernelGGL(bop_vsd_pairs_kernel<false>, dim3(tiles, nb), dim3(256), 0, s, depth_obs, cams, Fr, H, W, z_est, Ne,
+                               z_gt, Ng, pairs + 3 * (size_t)a, diameter, delta, taus, T, counts + (size_t)a * (T + 2));
+    }
+    hipLaunchKernelGGL(bop_vsd_finalize_kernel, dim3((unsigned)(((size_t)P * T + 255) / 256)), dim3(256), 0, s, counts, P, T, errors);
+    return ossid_launch_status();
+}
+
+int ossid_bop_match(const double* err, int Ptot, const int32_t* groups, int Gr, const uint8_t* valid, int Itot,
+                    const double* thr, int T, int32_t* match, int Etot, int32_t* tp, void* stream) {
+    if (!groups || !valid || !thr || !tp || Gr < 1 || Itot < 1 || Ptot < 0 || Etot < 0 || (Ptot > 0 && !err) ||
+        (Etot > 0 && !match) || T < 1 || T > OSSID_BOP_MAX_TAUS)
+        return OSSID_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int K = T + 2, C = K * MATCH_COLS;
+    const size_t n_match = (size_t)Etot * C, n_clear = n_match > (size_t)C ? n_match : (size_t)C;
+    hipLaunchKernelGGL(bop_match_clear_kernel, dim3((unsigned)((n_clear + 255) / 256)), dim3(256), 0, s, match, n_match, tp, C);
+    hipLaunchKernelGGL(bop_match_kernel, dim3((unsigned)Gr, (unsigned)((C + 63) / 64)), dim3(64), 0, s, err, Ptot, groups, valid,
+                       Itot, thr, K, Etot, match, tp);
     return ossid_launch_status();
 }
 

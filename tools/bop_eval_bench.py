@@ -7,7 +7,12 @@
   orientation, not a target (VSD: the cost pass alone on the device's renders, and one ref_raster render; MSSD / MSPD: a few
   estimates, scaled to N).
 
+  --multi: the multi-instance leg alone -> profiles/bop_eval_multi.json: groups of 4 and of 12 estimates and instances
+  through the pair table (n + n renders, ossid_bop_vsd_pairs; SPEC 8.11) against every pair as a row of bop_eval.vsd (2 n n
+  renders, ossid_bop_vsd), the two forms' windows alternating round by round: renders, cost launches, the whole Python calls.
+
     python3 tools/bop_eval_bench.py [--out profiles/bop_eval.json] [--commit ID] [--n 64]
+    python3 tools/bop_eval_bench.py --multi [--out profiles/bop_eval_multi.json]
     rocprofv3 --kernel-trace --stats -d out -- python3 tools/bop_eval_bench.py --trace
 
 Times are device events around `reps` back-to-back calls after a warm-up, the median of `rounds` such windows.
@@ -102,9 +107,89 @@ def vsd_parts(mesh, depth, K, est, gt, trace):
     return row
 
 
+def alternating_ms(fns, reps, rounds):
+    """event_ms for several callables whose windows alternate round by round (a, b, a, b ...), so that a drift of the
+    clocks meets all of them alike."""
+    for f in fns.values():
+        f()
+    torch.cuda.synchronize()
+    out = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                f()
+            b.record()
+            b.synchronize()
+            out[k].append(a.elapsed_time(b) / reps)
+    return {k: {"ms": float(np.median(v)), "ms_min": float(min(v)), "ms_max": float(max(v)), "reps": reps, "rounds": rounds}
+            for k, v in out.items()}
+
+
+def multi_instance_leg(mesh, depth, K, T, n):
+    """A group of n kept estimates and n instances at 480 x 640 (SPEC 8.11): vsd_pairs' form -- n + n renders and one
+    ossid_bop_vsd_pairs over the n x n table -- against the only way the single-instance entry has to the same numbers, every
+    pair a row of its own: n x n + n x n renders and ossid_bop_vsd over n x n rows. Device parts on device-resident inputs
+    as in vsd_parts, then the two Python calls whole (uploads, read-back and host work included)."""
+    dev = mesh.device
+    rng = np.random.default_rng(n)
+    gt = np.stack([ri.perturb(T, rng.normal(size=3), 40.0 * rng.random(), np.array([0.12, 0.08, 0.05]) * rng.uniform(-1, 1, 3))
+                   for _ in range(n)])
+    est = np.stack([ri.perturb(g, rng.normal(size=3), 5.0 * rng.random(), rng.normal(size=3) * 0.01 * rng.random()) for g in gt])
+    pairs = np.array([(e, g, 0) for e in range(n) for g in range(n)], dtype=np.int32)
+    P = len(pairs)
+    O = torch.from_numpy(depth[None]).to(dev)
+    cams = torch.from_numpy(bop_eval._cameras(K, 1)).to(dev)
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, torch.float32)  # noqa: E731
+    Te, Tg, Tex, Tgx = f32(est), f32(gt), f32(est[pairs[:, 0]]), f32(gt[pairs[:, 1]])
+    tab = torch.from_numpy(pairs).to(dev)
+    frame, taus = np.zeros(P, dtype=np.int32), np.asarray(bop_eval.VSD_TAUS)
+    rd = lambda poses: render.render_depth(mesh, poses, K, HW, pixel_offset=0.0)  # noqa: E731
+    z_est, z_gt, z_estx, z_gtx = rd(Te), rd(Tg), rd(Tex), rd(Tgx)
+    out = {k: (torch.empty(P, 12, dtype=torch.int32, device=dev), torch.empty(P, 10, dtype=torch.float64, device=dev))
+           for k in ("pairs", "expanded")}
+    fn_p, fn_x = _lib.fn("ossid_bop_vsd_pairs"), _lib.fn("ossid_bop_vsd")
+
+    def cost_pairs():
+        rc = fn_p(O.data_ptr(), cams.data_ptr(), 1, HW[0], HW[1], z_est.data_ptr(), n, z_gt.data_ptr(), n, tab.data_ptr(), P, DIAMETER,
+                  0.015, taus.ctypes.data, 10, out["pairs"][0].data_ptr(), out["pairs"][1].data_ptr(), _lib.stream())
+        assert rc == 0, rc
+
+    def cost_expanded():
+        rc = fn_x(O.data_ptr(), cams.data_ptr(), 1, HW[0], HW[1], z_estx.data_ptr(), z_gtx.data_ptr(), frame.ctypes.data, P, DIAMETER,
+                  0.015, taus.ctypes.data, 10, out["expanded"][0].data_ptr(), out["expanded"][1].data_ptr(), _lib.stream())
+        assert rc == 0, rc
+    row = {"estimates": n, "instances": n, "pairs": P, "triangles": mesh.n_faces, "frame": list(HW),
+           "renders": {"pairs": 2 * n, "expanded": 2 * P}, "expected_render_ratio": (n + n) / (2.0 * n * n)}
+    row["render"] = alternating_ms({"pairs": lambda: (rd(Te), rd(Tg)), "expanded": lambda: (rd(Tex), rd(Tgx))}, reps=10, rounds=7)
+    row["cost"] = alternating_ms({"pairs": cost_pairs, "expanded": cost_expanded}, reps=10, rounds=7)
+    cost_pairs(), cost_expanded()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(out["pairs"], out["expanded"])), "the two forms disagree"
+    c = out["pairs"][0].cpu().numpy()
+    row["mean_n_U"], row["pairs_with_overlap"] = float(c[:, 0].mean()), int((c[:, 1] > 0).sum())
+    got = {}
+
+    def call_pairs():
+        got["pairs"] = bop_eval.vsd_pairs(mesh, DIAMETER, O, K, est, gt, pairs)
+
+    def call_expanded():
+        got["expanded"] = bop_eval.vsd(mesh, DIAMETER, O, K, est[pairs[:, 0]], gt[pairs[:, 1]], chunk=_lib.RASTER_MAX_POSES)
+    row["python_call"] = alternating_ms({"pairs": call_pairs, "expanded": call_expanded}, reps=3, rounds=7)
+    assert np.array_equal(got["pairs"], got["expanded"])
+    for part in ("render", "cost", "python_call"):
+        row[part]["ratio"] = row[part]["pairs"]["ms"] / row[part]["expanded"]["ms"]
+    dev_p, dev_x = (row["render"][k]["ms"] + row["cost"][k]["ms"] for k in ("pairs", "expanded"))
+    row["device_ms"] = {"pairs": dev_p, "expanded": dev_x, "ratio": dev_p / dev_x}
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bop_eval.json"))
+    ap.add_argument("--multi", action="store_true",
+                    help="the multi-instance leg alone (groups of 4 and 12) -> profiles/bop_eval_multi.json unless --out is given")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--n", type=int, default=64, help="estimates per VSD batch")
     ap.add_argument("--trace", action="store_true", help="a few untimed calls per workload, for a kernel trace")
@@ -115,6 +200,14 @@ def main():
     depth, K, T, _pts = ri.scene()
     V, F = rr.bump_mesh(5)
     mesh = render.Mesh(V, F)
+    args.out = args.out or os.path.join(ROOT, "profiles", "bop_eval_multi.json" if args.multi else "bop_eval.json")
+    if args.multi:
+        res = {"vsd_pairs_level5_480x640": {}}
+        for n in (4, 12):
+            res["vsd_pairs_level5_480x640"]["E%d_G%d" % (n, n)] = row = multi_instance_leg(mesh, depth, K, T, n)
+            print("vsd_pairs", n, row, flush=True)
+        write(res, args)
+        return
     res = {"vsd_level5_480x640": {}, "mssd_mspd_level5_N1024": {}}
     for n in sorted(set((1, args.n))):
         row = vsd_parts(mesh, depth, K, estimates(T, n), np.stack([T] * n), args.trace)
@@ -160,6 +253,10 @@ def main():
         print("mssd_mspd S", S, row, flush=True)
     if args.trace:
         return
+    write(res, args)
+
+
+def write(res, args):
     commit = args.commit
     if commit is None:
         try:

@@ -5,6 +5,12 @@ reference issues (utils/bop_utils.py:51-53):
 
     python3 tools/eval_bop19.py --result_filenames=method_lmo-test.csv[,more.csv] --datasets_path=/data/bop
                                 [--results_path=DIR] [--targets_filename=test_targets_bop19.json] [--renderer_type=ANY]
+                                [--multi_instance [--visib_gt_min=0.1]]
+
+--multi_instance (off by default: then every target must have one instance, as before) scores targets with inst_count > 1,
+e.g. a folder tools/make_scenes.py wrote with more objects per scene than models: the inst_count best-scored rows of a
+target against all its instances, matched greedily per threshold (SPEC 8.10-8.12). Not BOP-19 even then: no per-object
+averaging variants, no time limits.
 
 A file is `<method>_<dataset>-<split>.csv` as pipeline.save_results_bop writes it (looked up under --results_path unless
 the path exists as given). --renderer_type is accepted and ignored: there is one renderer, the device rasteriser. Prints
@@ -43,6 +49,10 @@ def main(argv=None):
     ap.add_argument("--results_path", default=os.environ.get("BOP_RESULTS_PATH") or ".", help="where the csv files are looked up")
     ap.add_argument("--targets_filename", default="test_targets_bop19.json")
     ap.add_argument("--renderer_type", default=None, help="accepted and ignored")
+    ap.add_argument("--multi_instance", action="store_true",
+                    help="targets may have inst_count > 1: pair errors and BOP's greedy matching (SPEC 8.10-8.12)")
+    ap.add_argument("--visib_gt_min", type=float, default=0.1,
+                    help="with --multi_instance: an instance counts iff its visib_fract is at least this")
     args, unknown = ap.parse_known_args(argv)
     if unknown:
         print("eval_bop19: ignoring %s" % " ".join(unknown), file=sys.stderr)
@@ -56,10 +66,15 @@ def main(argv=None):
                              "BOP_RESULTS_PATH)" % (name, os.path.abspath(args.results_path)))
         method, dataset_name, split = parse_result_name(path)
         dataset = bop_eval.BopFolder(args.datasets_path, dataset_name, split, targets_filename=args.targets_filename)
-        scores = bop_eval.evaluate(bop_eval.read_results_csv(path), dataset)
-        keep = {k: v for k, v in scores.items() if k != "rows"}
+        if args.multi_instance:
+            scores = bop_eval.evaluate(bop_eval.read_results_csv(path), dataset, multi_instance=True,
+                                       visib_gt_min=args.visib_gt_min)
+        else:
+            scores = bop_eval.evaluate(bop_eval.read_results_csv(path), dataset)
+        keep = {k: v for k, v in scores.items() if k not in ("rows", "match")}
         keep.update(method=method, dataset=dataset_name, split=split)
-        print("%s: AR_VSD %.6f  AR_MSSD %.6f  AR_MSPD %.6f  AR %.6f  (%d of %d targets have an estimate)"
+        tail = "(%d estimates kept for %d targets)" if args.multi_instance else "(%d of %d targets have an estimate)"
+        print(("%s: AR_VSD %.6f  AR_MSSD %.6f  AR_MSPD %.6f  AR %.6f  " + tail)
               % (os.path.basename(path), keep["AR_VSD"], keep["AR_MSSD"], keep["AR_MSPD"], keep["AR"], keep["estimates"],
                  keep["targets"]))
         with open(path[:-4] + "_scores.json", "w") as f:
