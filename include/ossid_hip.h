@@ -1029,6 +1029,28 @@ int ossid_bop_vsd_pairs(const float* depth_obs, const float* cams, int Fr, int H
 int ossid_bop_match(const double* err, int Ptot, const int32_t* groups, int Gr, const uint8_t* valid, int Itot,
                     const double* thr, int T, int32_t* match, int Etot, int32_t* tp, void* stream);
 
+/* Several instances per frame on the estimating side: distinct-pose selection (SPEC.md section 16;
+ * csrc/pose_select.hip), this build's own definition -- the reference's loop keeps one pose per frame
+ * (scripts/online_learning.py:466-469). Greedy non-maximum suppression over scored poses under 8.7's MSSD distance.
+ * ossid_pose_select: poses f64 [N][4][4], scores f32 [N], points f32 [M][3], symmetries f64 [S][4][4] row-major (8.6; the
+ * identity when the object has none), K picks, sep a length in the poses' unit, min_score (-inf for none) ->
+ * selected int32 [K] (indices into poses in pick order, -1 past the last pick), count int32 [1] (the number of picks),
+ * owner int32 [N] (the round whose pick suppressed the candidate, -1 = never owned). A candidate is eligible iff
+ * scores[n] >= min_score (a NaN never is). Round r picks the eligible candidate without an owner of greatest score, the
+ * lowest index among equal scores (+0 = -0), and gives it and every candidate without an owner at D(n, pick) <=
+ * sep * sep the owner r, with D = min over symmetries of max over points of 8.7's squared distance q_v between the point
+ * under poses[n] and under poses[pick] . S; no square root is taken. keys uint64 [K] is caller-owned scratch and an
+ * output: keys[r] ends as round r's pick key (order-preserving score bits in the high word, the complemented index
+ * 0xffffffff - pick in the low word), 0 for a round without a pick. All four are overwritten (cleared by a kernel first).
+ * No workspace, 1 + 2 K launches whose grids depend on (N, M, S, K) alone, nothing read back, capturable. Integer
+ * atomics, max and min only: bit-reproducible. OSSID_EINVAL before any launch, nothing written: N outside [1,
+ * OSSID_SELECT_MAX_POSES], K outside [1, OSSID_BOP_MAX_INSTANCES], S outside [1, OSSID_BOP_MAX_SYMMETRIES], M outside
+ * [1, 2^22], sep negative or not finite, a NaN min_score, a NULL pointer. */
+#define OSSID_SELECT_MAX_POSES 65536
+int ossid_pose_select(const double* poses, const float* scores, int N, const float* points, int M, const double* symmetries,
+                      int S, int K, double sep, float min_score, int32_t* selected, int32_t* count, int32_t* owner,
+                      uint64_t* keys, void* stream);
+
 /* 8f-6 the scorer's model cloud from the object's mesh (scripts/online_learning.py:303-311 loads model_points /
  * model_colors / model_normals from zephyr_model_data/{lmo,ycbv}/model_cloud_XX.npz, a download made by a script that is
  * in neither tree). SPEC.md section 9 (csrc/model_cloud.hip): this build's own definition, parity with zephyr's clouds

@@ -19,7 +19,8 @@
 // compared against the chunk's transforms held in registers (SC of them, fewer in the last chunk: S = 1 pays for one);
 // running maxima of the squared distances per lane, reduced across the wave by shuffles and across the waves in LDS; the
 // minimum over the chunks by atomicMin on the 64-bit pattern of the non-negative double (it orders like the value; the
-// outputs start at +inf). Max and min do not depend on order.
+// outputs start at +inf). Max and min do not depend on order. The composition, the transform and the squared distance are
+// csrc/bop_points.h's, shared with csrc/pose_select.hip.
 //
 // ossid_bop_vsd_pairs (8.11). ossid_bop_vsd's three launches over a pair table in device memory: row p = (estimate render,
 // ground-truth render, frame) picks the two images of vsd_tile, the device function both cost kernels share, so a group of
@@ -33,6 +34,7 @@
 // a captured graph replays with the values they had at capture.
 #include <cmath>
 
+#include "bop_points.h"
 #include "common.h"
 
 namespace {
@@ -190,12 +192,7 @@ __global__ __launch_bounds__(256) void bop_mssd_mspd_kernel(const float* __restr
     const double* Pg = pose_gt + 16 * (size_t)n;
     if (threadIdx.x < SC) {
         // slots past the end hold the last transform and are never compared (live below)
-        const double* Sm = syms + 16 * (size_t)min(s0 + (int)threadIdx.x, S - 1);
-        for (int r = 0; r < 3; ++r) {
-            const double a0 = Pg[4 * r], a1 = Pg[4 * r + 1], a2 = Pg[4 * r + 2];
-            for (int col = 0; col < 3; ++col) Gs[threadIdx.x][4 * r + col] = (a0 * Sm[col] + a1 * Sm[4 + col]) + a2 * Sm[8 + col];
-            Gs[threadIdx.x][4 * r + 3] = ((a0 * Sm[3] + a1 * Sm[7]) + a2 * Sm[11]) + Pg[4 * r + 3];
-        }
+        bop_compose(Pg, syms + 16 * (size_t)min(s0 + (int)threadIdx.x, S - 1), Gs[threadIdx.x]);
     }
     __syncthreads();
     double G[SC][12], E[12];
@@ -215,20 +212,16 @@ __global__ __launch_bounds__(256) void bop_mssd_mspd_kernel(const float* __restr
     for (int v = threadIdx.x; v < V; v += 256) {
         const double x = (double)vertices[3 * (size_t)v], y = (double)vertices[3 * (size_t)v + 1],
                      z = (double)vertices[3 * (size_t)v + 2];
-        const double Xe = ((E[0] * x + E[1] * y) + E[2] * z) + E[3];
-        const double Ye = ((E[4] * x + E[5] * y) + E[6] * z) + E[7];
-        const double Ze = ((E[8] * x + E[9] * y) + E[10] * z) + E[11];
+        double Xe, Ye, Ze;
+        bop_transform(E, x, y, z, Xe, Ye, Ze);
         const double ue = (Xe / Ze) * fx + cx, ve = (Ye / Ze) * fy + cy;
         const bool oke = Ze > 0.0 && fin(Xe) && fin(Ye) && fin(Ze) && fin(ue) && fin(ve);
 #pragma unroll
         for (int s = 0; s < SC; ++s) {
             if (s >= live) break;                    // workgroup-uniform: S = 1 pays for one transform, not SC
-            const double Xg = ((G[s][0] * x + G[s][1] * y) + G[s][2] * z) + G[s][3];
-            const double Yg = ((G[s][4] * x + G[s][5] * y) + G[s][6] * z) + G[s][7];
-            const double Zg = ((G[s][8] * x + G[s][9] * y) + G[s][10] * z) + G[s][11];
-            const double dx = Xe - Xg, dy = Ye - Yg, dz = Ze - Zg;
-            double q = (dx * dx + dy * dy) + dz * dz;
-            q = q == q ? q : (double)INFINITY;       // NaN counts as +inf
+            double Xg, Yg, Zg;
+            bop_transform(G[s], x, y, z, Xg, Yg, Zg);
+            const double q = bop_sqdist(Xe, Ye, Ze, Xg, Yg, Zg);   // NaN counts as +inf
             m3[s] = q > m3[s] ? q : m3[s];
             const double ug = (Xg / Zg) * fx + cx, vg = (Yg / Zg) * fy + cy;
             const bool ok = oke && Zg > 0.0 && fin(Xg) && fin(Yg) && fin(Zg) && fin(ug) && fin(vg);

@@ -119,6 +119,66 @@ def filterHypoByMask(model_points, meta_data, pose_hypos, mask, th=0.5):
     return (hit.sum(-1) / float(M) > th).cpu().numpy()
 
 
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def select_instances(poses, scores, model_points, max_instances, sep, symmetries=None, min_score=None):
+    """ADDITIVE API (SPEC.md section 16): from N scored poses the best `max_instances` that are different objects in space --
+    greedy non-maximum suppression under the MSSD distance of 8.7 (max over model_points, min over `symmetries`), so two
+    poses of a symmetric object related by a symmetry are one instance. poses [N,4,4], scores [N] or [N,1], model_points
+    [M,3], symmetries f64 [S,4,4] in the unit of model_points (None: the identity), sep a length in that unit: a candidate
+    within sep of a pick belongs to it. min_score (None: no bound): candidates below it are never picked.
+    Returns (selected int32 [K], count int32 [1], owner int32 [N]) as device tensors -- the picks in order (-1 past the
+    last), their number, and per candidate the round that took it (-1 = never) -- without synchronising. numpy arrays or
+    tensors. ValueError before the device is touched for what does not fit."""
+    _need_poses("poses", poses)
+    _need_points(model_points)
+    if len(_shape(poses)) != 3:
+        raise ValueError("poses must be [N,4,4], got %s" % (_shape(poses),))
+    N, M = _shape(poses)[0], _shape(model_points)[0]
+    sshape = _shape(scores)
+    if sshape not in ((N,), (N, 1)):
+        raise ValueError("scores must be [N] or [N,1] with N = %d, got %s" % (N, sshape))
+    for name, a in (("poses", poses), ("scores", scores), ("model_points", model_points)):
+        dt = str(a.dtype) if hasattr(a, "dtype") else ""
+        if "float" not in dt:
+            raise ValueError("%s must be a floating-point array, got %s" % (name, dt or type(a).__name__))
+    K = int(max_instances)
+    if K != max_instances or not 1 <= K <= _sd._lib.BOP_MAX_INSTANCES:
+        raise ValueError("max_instances must be an integer in [1, %d], got %r" % (_sd._lib.BOP_MAX_INSTANCES, max_instances))
+    if not 1 <= N <= _sd._lib.SELECT_MAX_POSES:
+        raise ValueError("select_instances takes 1 to %d poses, got %d" % (_sd._lib.SELECT_MAX_POSES, N))
+    if not 1 <= M <= 1 << 22:
+        raise ValueError("select_instances takes 1 to 2^22 model_points, got %d" % M)
+    sep = float(sep)
+    if not (np.isfinite(sep) and sep >= 0.0):
+        raise ValueError("sep must be finite and >= 0, got %r" % sep)
+    min_score = -np.inf if min_score is None else float(min_score)
+    if np.isnan(min_score):
+        raise ValueError("min_score must not be NaN")
+    if symmetries is None:
+        symmetries = np.eye(4, dtype=np.float64)[None]
+    if len(_shape(symmetries)) != 3 or _shape(symmetries)[1:] != (4, 4) or not 1 <= _shape(symmetries)[0] <= _sd._lib.BOP_MAX_SYMMETRIES:
+        raise ValueError("symmetries must be [S,4,4] with 1 <= S <= %d, got %s" % (_sd._lib.BOP_MAX_SYMMETRIES, _shape(symmetries)))
+    if not torch.is_tensor(poses) or not poses.is_cuda:                      # a device tensor is the caller's to vouch for
+        if not np.isfinite(_host(poses)).all():
+            raise ValueError("poses must be finite")
+    dev = _sd._dev()
+    T = _as_tensor(poses).to(dev, torch.float64).reshape(N, 4, 4).contiguous()
+    sc = _as_tensor(scores).to(dev, torch.float32).reshape(N).contiguous()
+    P = _as_tensor(model_points).to(dev, torch.float32).contiguous()
+    Sm = _as_tensor(symmetries).to(dev, torch.float64).contiguous()
+    out = torch.empty(K + 1 + N, dtype=torch.int32, device=dev)
+    keys = torch.empty(K, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _sd._lib.fn("ossid_pose_select")(T.data_ptr(), sc.data_ptr(), N, P.data_ptr(), M, Sm.data_ptr(), int(Sm.shape[0]), K,
+                                              sep, min_score, out.data_ptr(), out.data_ptr() + 4 * K, out.data_ptr() + 4 * (K + 1),
+                                              keys.data_ptr(), _sd._lib.stream())
+    _sd._lib.check(rc, "ossid_pose_select")
+    return out[:K], out[K:K + 1], out[K + 1:]
+
+
 def pose_errors(pose_hypos, pose_gt, model_points, symmetric=False):
     """ADD (symmetric=False) or ADI (True) of every hypothesis against the ground-truth pose, float64 numpy [N]:
     the device-side form of online_learning.py:452's per-hypothesis Python loop over zephyr.utils.metrics.add / adi."""

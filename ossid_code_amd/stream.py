@@ -6,6 +6,8 @@ scripts/online_learning.py:314-591 (SURVEY.md 8d cfg-5, 8e "full online stream")
        the keypoint-feature hypotheses of --use_sift_hypos with OnlineStream(feature_models=...), :427-437, put in
        front of the PPF ones as :437 does)
     -> per-hypothesis ADD/ADI (:452) -> Zephyr score (networkInference, :464) -> argmax (:466-469)
+       (with OnlineStream(max_instances=K > 1): the best K distinct poses instead, SPEC.md section 16 -- this build's own
+       step, the reference keeps one pose per frame -- and every step below once per pick)
     -> optional ICP refinement of the chosen pose (icpRefinement, :471-480; OnlineStream(icp_max_dist=...))
     -> predicted depth (:485-493: the mesh rasteriser of SPEC.md section 7 with OnlineStream(meshes=...), otherwise
        the point-splat stand-in) -> visibility mask (:500)
@@ -25,7 +27,7 @@ import torch
 
 from . import features, model_cloud, pipeline, ppf, render
 from .hostutil import K2meta
-from .scoring import networkInference, pose_errors
+from .scoring import networkInference, pose_errors, select_instances
 
 
 class SpeculativeWindow:
@@ -92,11 +94,31 @@ class OnlineStream:
     convention, under which the render lines up with the observed depth) instead of splatting the model points. A frame
     WITHOUT "model_points" whose object's mesh has vertex colours or a texture is scored with the mesh's own cloud
     (model_cloud.sample_model_cloud(mesh), SPEC.md section 9), built at the object's first frame and kept;
-    a frame that carries its cloud is processed exactly as without meshes."""
+    a frame that carries its cloud is processed exactly as without meshes.
+    max_instances (1 = off: no launch, number or result key changes): a frame may show several instances of its object.
+    Per frame K = min(max_instances, frame.get("inst_count", max_instances)); with K > 1 the scored hypotheses go through
+    scoring.select_instances (SPEC.md section 16: the best K that are different objects in space, timed under
+    times["select"]), the picks are refined by one icp_refine call, rendered by one render_depth call (meshes) or splat one
+    by one, and each gets its visibility mask against the observed depth -- an instance in front of another makes the
+    observed depth nearer, so the hidden part is not visible -- and, if confident, its pseudo-label. The existing result
+    keys then describe pick 0 (the argmax: bit for bit what max_instances=1 returns) and the result also carries
+    "selected" and "owner" (host int32 arrays over the scored hypotheses, as select_instances returns them) and
+    "instances", one dict per pick with pred_pose, pred_score, pred_err, confident, pred_mask_visib, sample and, with ICP,
+    icp. A frame whose K is 1 is processed as without max_instances and carries none of the three.
+    instance_sep_rel: two poses nearer than instance_sep_rel x the object's diameter (max over model points, min over
+    symmetries) are one instance. The default 0.2 is the extent of one PPF pose cluster (SPEC.md 6.6: 0.1 of the diameter
+    in translation plus 12 degrees, which move a point at radius D/2 by 0.105 D); nobody has tuned it. Thin objects that
+    stack (plates, lids: neighbours a fraction of the diameter apart) need a smaller value.
+    symmetries: dict obj_id -> f64 [S,4,4] (bop_eval.symmetry_transformations) in the unit of model_points -- BOP's
+    models_info is in millimetres, the caller converts; an object without an entry has none.
+    diameters: dict obj_id -> length in that unit; otherwise frame["diameter"], otherwise
+    model_cloud.mesh_diameter(model_points) at the object's first frame, kept.
+    frame["pose_gt"] may be [G,4,4]: pp_err and every pred_err are then the minimum over the G instances."""
 
     def __init__(self, detector, scorer, score_dataset, confident_threshold=20.0, symmetric=False, finetune_fn=None,
                  icp_max_dist=None, ppf_models=None, ppf_kwargs=None, meshes=None, mesh_pixel_offset=0.0,
-                 feature_models=None, feature_kwargs=None):
+                 feature_models=None, feature_kwargs=None, max_instances=1, instance_sep_rel=0.2, symmetries=None,
+                 diameters=None):
         self.detector, self.scorer, self.dataset = detector, scorer, score_dataset
         self.threshold, self.symmetric, self.finetune_fn = confident_threshold, symmetric, finetune_fn
         self.icp_max_dist = icp_max_dist
@@ -104,8 +126,15 @@ class OnlineStream:
         self.meshes, self.mesh_pixel_offset = meshes, float(mesh_pixel_offset)
         self.feature_models, self.feature_kwargs = feature_models, dict(feature_kwargs or {})
         self._clouds = {}
+        self.max_instances, self.instance_sep_rel = int(max_instances), float(instance_sep_rel)
+        if self.max_instances != max_instances or self.max_instances < 1:
+            raise ValueError("max_instances must be an integer >= 1, got %r" % (max_instances,))
+        if not (np.isfinite(self.instance_sep_rel) and self.instance_sep_rel >= 0.0):
+            raise ValueError("instance_sep_rel must be finite and >= 0, got %r" % (instance_sep_rel,))
+        self.symmetries, self.diameters, self._diameters = symmetries, diameters, {}
         keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ()) + \
-            (("ppf",) if ppf_models is not None else ()) + (("sift",) if feature_models is not None else ())
+            (("ppf",) if ppf_models is not None else ()) + (("sift",) if feature_models is not None else ()) + \
+            (("select",) if self.max_instances > 1 else ())
         self.times = {k: 0.0 for k in keys}
         self.n_processed = 0
 
@@ -134,7 +163,8 @@ class OnlineStream:
 
     def process(self, frame):
         """frame: dict with img uint8 [H,W,3], depth [H,W], cam_K, limg [n_t,3,124,124], lmask [n_t,1,124,124], obj_id,
-        pose_hypos [N,4,4], pose_gt [4,4], model_points/normals/colors [M,3]. Returns the per-frame result dict."""
+        pose_hypos [N,4,4], pose_gt [4,4] or [G,4,4], model_points/normals/colors [M,3]; optional inst_count, diameter.
+        Returns the per-frame result dict."""
         dev = next(self.detector.parameters()).device
         frame = self._with_cloud(frame)
         self.n_processed += 1
@@ -153,11 +183,13 @@ class OnlineStream:
                 hypos = feat if hypos is None else np.concatenate([feat, hypos], axis=0)       # :437
                 if len(hypos) == 0:
                     hypos = np.eye(4)[None]
-        pp_err = self._timed("pose_err", lambda: pose_errors(hypos, frame["pose_gt"], frame["model_points"],
-                                                             self.symmetric))
+        pp_err = self._timed("pose_err", lambda: self._pose_errors(hypos, frame))
         data = {k: frame[k] for k in ("img", "depth", "cam_K", "model_points", "model_normals", "model_colors")}
         data["pose_hypos"], data["pp_err"] = hypos, pp_err
         poses, scores, errs, uv = self._timed("score", lambda: networkInference(self.scorer, self.dataset, data))
+        K = min(self.max_instances, max(1, int(frame.get("inst_count", self.max_instances))))
+        if K > 1:
+            return self._finish_instances(frame, det, hypos, n_feat, poses, scores, errs, uv, K)
         best = int(scores.argmax())
         pred_pose, pred_score = poses[best], float(scores.max())
         H, W = frame["depth"].shape
@@ -168,7 +200,7 @@ class OnlineStream:
                 out, fit, rmse, its = pipeline.icp_refine(frame["depth"], uv[best], pred_pose, frame["cam_K"],
                                                           frame["model_points"], max_dist=self.icp_max_dist)
                 T = out[0].cpu().numpy()
-                err = pose_errors(T[None], frame["pose_gt"], frame["model_points"], self.symmetric)   # :482
+                err = self._pose_errors(T[None], frame)                                               # :482
                 return T, float(err[0]), float(fit[0]), float(rmse[0]), int(its[0])
             refined, refined_err, fit, rmse, its = self._timed("icp", refine)
             icp = {"fitness": fit, "inlier_rmse": rmse, "iterations": its, "pose_unrefined": pred_pose,
@@ -192,6 +224,82 @@ class OnlineStream:
                 "pred_mask_visib": pred_mask_visib, "sample": sample, **({"icp": icp} if icp is not None else {}),
                 **({"n_hypos": len(hypos), "ppf_hypos": hypos} if self.ppf_models is not None else {}),
                 **({"n_hypos": len(hypos), "n_feature_hypos": n_feat} if n_feat is not None else {})}
+
+    def _pose_errors(self, hypos, frame):
+        """ADD / ADI of the hypotheses against frame["pose_gt"]; against [G,4,4] the minimum over the G instances."""
+        gt = frame["pose_gt"]
+        if len(np.shape(gt)) != 3:
+            return pose_errors(hypos, gt, frame["model_points"], self.symmetric)
+        if np.shape(gt)[0] < 1:
+            raise ValueError("pose_gt must hold at least one pose, got %s" % (np.shape(gt),))
+        return np.minimum.reduce([pose_errors(hypos, g, frame["model_points"], self.symmetric) for g in gt])
+
+    def _diameter(self, frame):
+        obj = int(frame["obj_id"])
+        if self.diameters is not None and obj in self.diameters:
+            return float(self.diameters[obj])
+        if "diameter" in frame:
+            return float(frame["diameter"])
+        if obj not in self._diameters:
+            self._diameters[obj] = model_cloud.mesh_diameter(frame["model_points"])
+        return self._diameters[obj]
+
+    def _finish_instances(self, frame, det, hypos, n_feat, poses, scores, errs, uv, K):
+        """process() from the scores on for a frame with K > 1: the K best distinct poses, each refined, rendered, masked
+        and pseudo-labelled; pick 0 is the argmax and fills the single-instance keys."""
+        obj = int(frame["obj_id"])
+        syms = None if self.symmetries is None else self.symmetries.get(obj)
+        sep = self.instance_sep_rel * self._diameter(frame)
+        sel, _count, own = self._timed("select", lambda: select_instances(poses, scores, frame["model_points"], K, sep,
+                                                                          symmetries=syms))
+        selected, owner = sel.cpu().numpy(), own.cpu().numpy()
+        picks = [int(p) for p in selected if p >= 0]
+        if not picks or picks[0] != int(scores.argmax()):
+            raise ValueError("OnlineStream: the frame's scores hold a NaN; the instances cannot be ranked")
+        H, W = frame["depth"].shape
+        flat, errs = np.asarray(scores).reshape(-1), np.asarray(errs)
+        pred_poses = [poses[p] for p in picks]
+        pred_scores = [float(flat[p]) for p in picks]
+        pred_errs = [float(errs[p]) for p in picks]
+        icps = [None] * len(picks)
+        if self.icp_max_dist is not None:
+            def refine():
+                out, fit, rmse, its = pipeline.icp_refine(frame["depth"], uv[picks], np.stack(pred_poses), frame["cam_K"],
+                                                          frame["model_points"], max_dist=self.icp_max_dist)
+                T = out.cpu().numpy()
+                return T, self._pose_errors(T, frame), fit.cpu().numpy(), rmse.cpu().numpy(), its.cpu().numpy()   # :482
+            refined, refined_err, fit, rmse, its = self._timed("icp", refine)
+            for i in range(len(picks)):
+                icps[i] = {"fitness": float(fit[i]), "inlier_rmse": float(rmse[i]), "iterations": int(its[i]),
+                           "pose_unrefined": pred_poses[i], "err_unrefined": pred_errs[i]}
+                pred_poses[i], pred_errs[i] = refined[i], float(refined_err[i])
+
+        def pseudo():
+            if self.meshes is not None:
+                depths = render.render_depth(self.meshes[obj], np.stack(pred_poses), frame["cam_K"], (H, W),
+                                             pixel_offset=self.mesh_pixel_offset)
+            else:
+                depths = [pipeline.render_depth_points(T, frame["model_points"], frame["cam_K"], (H, W), radius=1)
+                          for T in pred_poses]
+            return [pipeline.visibility_and_iou(frame["depth"], d)[1] for d in depths]
+        masks = self._timed("pseudo_label", pseudo)
+        instances = []
+        for i in range(len(picks)):
+            confident = pred_scores[i] > self.threshold
+            sample = None
+            if confident:
+                sample = pipeline.make_dtoid_sample(frame["img"], frame["depth"], masks[i].float(), frame["cam_K"])
+            instances.append({"pred_pose": pred_poses[i], "pred_score": pred_scores[i], "pred_err": pred_errs[i],
+                              "confident": confident, "pred_mask_visib": masks[i], "sample": sample,
+                              **({"icp": icps[i]} if icps[i] is not None else {})})
+        first = instances[0]
+        return {"pred_pose": first["pred_pose"], "pred_score": first["pred_score"], "pred_err": first["pred_err"],
+                "confident": first["confident"], "dtoid_score": det["pred_scores"][:1], "dtoid_bbox": det["pred_bbox"][:1],
+                "pred_mask_visib": first["pred_mask_visib"], "sample": first["sample"],
+                **({"icp": first["icp"]} if "icp" in first else {}),
+                **({"n_hypos": len(hypos), "ppf_hypos": hypos} if self.ppf_models is not None else {}),
+                **({"n_hypos": len(hypos), "n_feature_hypos": n_feat} if n_feat is not None else {}),
+                "selected": selected, "owner": owner, "instances": instances}
 
     def _detection_mask(self, frame, det):
         """online_learning.py:384-405: the mask from the expanded DTOID boxes -> (depth f32 [H,W], mask u8 [H,W])."""
@@ -239,8 +347,9 @@ class OnlineStream:
             f = win.window()[0]
             r = self.process(frames[f])
             results.append(r)
-            if r["sample"] is not None:
-                samples.append((frames[f], r["sample"]))
+            for inst in r.get("instances", (r,)):              # every confident instance's pseudo-label
+                if inst["sample"] is not None:
+                    samples.append((frames[f], inst["sample"]))
             fired = win.commit([r["confident"]])
             if fired is not None and self.finetune_fn is not None:
                 self.finetune_fn(samples)

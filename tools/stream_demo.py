@@ -5,6 +5,9 @@ synthetic frames: this measures the loop, not accuracy.
 With --ppf the hypotheses come from each frame's depth (device PPF, ossid_code_amd/ppf.py) instead of perturbations of the
 ground truth, and the object is the asymmetric ellipsoid with a bump of tests/ref_icp.py (on the package's sphere every
 rotation is equally good), placed at a different pose per frame.
+With --instances K every frame carries K copies of the perturbed hypotheses, 0.15 m apart along x (--hypos in all), K ground
+truths and inst_count = K, and the stream keeps up to K distinct poses per frame (OnlineStream(max_instances=K), SPEC.md
+section 16): the `select` stage time stands beside the others, and every confident instance joins the finetune set.
 """
 import argparse
 import json
@@ -31,7 +34,10 @@ def main():
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--ppf", action="store_true", help="PPF hypotheses from the frame (asymmetric test object)")
+    ap.add_argument("--instances", type=int, default=1, help="K copies of the hypotheses per frame, inst_count = K")
     a = ap.parse_args()
+    if a.instances < 1 or a.instances > 64 or (a.instances > 1 and a.ppf):
+        ap.error("--instances takes 1 to 64, and not with --ppf (the rendered frame shows one object)")
     t_start = time.perf_counter()
     from ossid_code_amd import parallel
     from ossid_code_amd.stream import run_speculative
@@ -76,8 +82,15 @@ def main():
                            "model_colors": np.full_like(M, 0.5), "limg": limg, "lmask": lmask, "obj_id": 1,
                            "pose_gt": T})
     for f in range(0 if a.ppf else a.frames):
-        d = synth.make_scoring_inputs(a.hypos, a.points, seed=100 + f)
+        d = synth.make_scoring_inputs(max(1, a.hypos // a.instances), a.points, seed=100 + f)
         d.update(limg=limg, lmask=lmask, obj_id=1, pose_gt=d["pose_hypos"][0].copy())
+        if a.instances > 1:
+            copies = []
+            for k in range(a.instances):
+                T = d["pose_hypos"].copy()
+                T[:, 0, 3] += 0.15 * (k - 0.5 * (a.instances - 1))
+                copies.append(T)
+            d.update(pose_hypos=np.concatenate(copies), pose_gt=np.stack([T[0] for T in copies]), inst_count=a.instances)
         frames.append(d)
     ft_time, ft_steps = [0.0], [0]
 
@@ -135,7 +148,8 @@ def main():
         torch.cuda.synchronize()
         ft_time[0] += time.perf_counter() - t0
 
-    stream = OnlineStream(det, scorer, dataset, confident_threshold=-1e30, finetune_fn=finetune_fn, ppf_models=ppf_models)
+    stream = OnlineStream(det, scorer, dataset, confident_threshold=-1e30, finetune_fn=finetune_fn, ppf_models=ppf_models,
+                          max_instances=a.instances)
     note("models and %d frames ready" % len(frames))
     r0 = stream.process(frames[0])             # warm-up: graph capture, workspace allocation ...
     note("warm-up frame done")
@@ -190,7 +204,8 @@ def main():
                       "ms_per_frame_excl_finetune": 1e3 * (total - ft_time[0]) / a.frames,
                       "frames_processed_by_rank0": stream.n_processed,
                       "stage_ms_per_frame": per, "hyp_per_sec_in_stream": (a.hypos / (per["score"] * 1e-3)) if not isinstance(a.hypos, str) else None,
-                      "hypotheses": "ppf" if a.ppf else "perturbed ground truth",
+                      "hypotheses": "ppf" if a.ppf else "perturbed ground truth", "instances": a.instances,
+                      "picks_per_frame": (float(np.mean([len(r.get("instances", (r,))) for r in results])) if dist is None else None),
                       "data": "synthetic", "weights": "random-init"}))
     if dist is not None:
         dist.destroy_process_group()
