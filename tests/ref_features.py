@@ -315,6 +315,66 @@ def featurize(img, depth, mask, cam_K, contrast=CONTRAST, max_keypoints=MAX_KEYP
     return kps, bins, desc, frames, ok
 
 
+def smoothed_histogram(gx, gy, s, y, x):
+    """11.3's smoothed 36-bin histogram of a keypoint whose window lies in the image; orientation() is its first arg-max."""
+    rho = RHO[s - 1]
+    wx = gx[y - rho:y + rho + 1, x - rho:x + rho + 1]
+    wy = gy[y - rho:y + rho + 1, x - rho:x + rho + 1]
+    m = np.sqrt((wx * wx + wy * wy).astype(F32)).astype(np.int64)
+    add = (m * ori_weights(s)) >> 10
+    b = sector(wx.astype(F32), wy.astype(F32), SEC_C[1:18], SEC_S[1:18], 18)
+    h = np.zeros(36, dtype=np.int64)
+    np.add.at(h, b.ravel(), add.ravel())
+    return np.roll(h, 1) + 2 * h + np.roll(h, -1)
+
+
+def describe_rows(pyr, depth, cam_K, kps):
+    """11.3-11.5 on given keypoint rows (o, s, y, x), the per-row part of featurize: pyr a list per octave of [5,Ho,Wo]
+    -> (bins int64 [n], desc i8 [n,128], frames f64 [n,4,4], ok bool [n])."""
+    kps = np.asarray(kps, dtype=np.int64).reshape(-1, 4)
+    n = len(kps)
+    bins = np.full(n, -1, dtype=np.int64)
+    desc = np.zeros((n, 128), dtype=np.int8)
+    frames = np.zeros((n, 4, 4))
+    ok = np.zeros(n, dtype=bool)
+    grads = {}
+    for i, (o, s, y, x) in enumerate(kps.tolist()):
+        if (o, s) not in grads:
+            grads[(o, s)] = gradients(np.asarray(pyr[o][s], dtype=np.int64))
+        gx, gy = grads[(o, s)]
+        b = orientation(gx, gy, s, y, x)
+        bins[i] = b
+        if b < 0:
+            continue
+        d = descriptor(pyr[o][s], gx, gy, s, y, x, b)
+        if d is None:
+            continue
+        F = frame(depth, cam_K, o, s, y, x, b)
+        if F is None:
+            continue
+        desc[i], frames[i], ok[i] = d, F, True
+    return bins, desc, frames, ok
+
+
+def match_matrix(desc_s, ok_s, desc_m):
+    """match() in matrix form: d2 = |a|^2 + |b|^2 - 2 A B^T in int64, the first minimum per row -> (best, d2, w)."""
+    A = np.asarray(desc_s).astype(np.int64)
+    B = np.asarray(desc_m).astype(np.int64)
+    n = len(A)
+    best, d2b = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    okv = np.asarray(ok_s).astype(bool)
+    if len(B) and okv.any():
+        nb = (B * B).sum(1)
+        rows = np.flatnonzero(okv)
+        for a in range(0, len(rows), 256):                      # by blocks of scene rows: bounded memory at 65536 model rows
+            r = rows[a:a + 256]
+            d2 = (A[r] * A[r]).sum(1)[:, None] + nb[None, :] - 2 * (A[r] @ B.T)
+            j = np.argmin(d2, axis=1)
+            best[r], d2b[r] = j, d2[np.arange(len(r)), j]
+    w = np.where(best >= 0, np.maximum(0, 1024 - (d2b >> 6)), 0)
+    return best, d2b, w
+
+
 # ---- 11.6 -----------------------------------------------------------------------------------------------------------------
 def rigid_inverse(T):
     """[R | t] -> [R^T | -(R^T t)] in the written order."""
