@@ -1366,6 +1366,44 @@ int ossid_scene_light_shadowed(const ossid_scene_desc* desc_host, const float* n
                                const int32_t* enable, int Hs, int Ws, float z_near_l, const float* shadow_params,
                                uint8_t* lit_out, float* normal_out, uint8_t* blocked_out, void* stream);
 
+/* 8f-11  objects at rest on a table (SPEC.md 13.16-13.18, csrc/scene_rest.hip): this build's own definition, opt-in, in
+ * place of the physics engine BlenderProc drops the reference's objects with (datasets/render_dataset.py:81-189). Raw
+ * device pointers, caller-owned memory, one launch each, no workspace, nothing read back, no random numbers, no float
+ * atomics; capturable (ossid_scene_drop with G > 110 after one call outside a capture, which raises the kernel's LDS
+ * limit). Every result is a maximum: order-independent and bit-reproducible. No struct and no changed signature: the ABI
+ * version stays, as for 8f-8 to 8f-10.
+ *
+ * ossid_mesh_support (13.16): vertices f32 [V][3], dirs f64 [D][3] -> h_out f64 [D], h[d] the maximum over the vertices
+ * whose three coordinates are finite of ((dx x + dy y) + dz z) in f64 from the (double) f32 coordinates, written order, no
+ * contraction; a term that is NaN (a direction that is not finite) never replaces the running maximum; -inf when no
+ * vertex is finite. +0 and -0 compare equal: which of them is returned is not defined. One workgroup takes 8 directions
+ * and walks every vertex. OSSID_EINVAL before the launch: a NULL pointer, V outside [1, OSSID_RASTER_MAX_VERTICES], D
+ * outside [1, OSSID_REST_MAX_DIRS].
+ *
+ * ossid_scene_drop (13.18): vertices, faces, meshes [K][4], Vt, Ft, K: the atlas as ossid_scene_desc names it;
+ * instance_mesh int32 [I], scene_first int32 [S+1]; local f64 [I][12], a 3x4 row-major map from model to TABLE frame (z'
+ * up, the table at z' = 0): p_c = ((L_c0 x + L_c1 y) + L_c2 z) + L_c3 in f64. One workgroup per scene holds a height
+ * field H f32 [G][G] in LDS, cell (iy, ix) = [x0 + ix cell, x0 + (ix + 1) cell) x [x0 + iy cell, ...), x0 = -(G / 2)
+ * cell (G / 2 = 0.5 G, not truncated), all +0 at first, and places the scene's instances one after another in draw order. A triangle is
+ * usable iff its three indices lie in [0, nv) and its nine transformed coordinates are finite; its cells are those of its
+ * bounding box, ix in [floor((xmin - x0) / cell), floor((xmax - x0) / cell)] within [0, G - 1], likewise iy. Pass 1:
+ * zlow = min of zmin, off = max(-zlow, max over usable triangles and their in-grid cells of ((double) H[cell] - zmin)).
+ * Pass 2: H[cell] = v where v > H[cell], v = zmax + off rounded UP to f32 (v >= 0: an integer maximum on its bits).
+ * drop[i] = off, status[i] = 0, or 2 when a usable triangle has a cell of its box outside the grid (the table term -zlow
+ * holds for it all the same). An instance without a usable triangle -- or whose instance_mesh or table row leads outside
+ * [0, K), Vt or Ft -- gets status 1, drop 0 and leaves H as it was. A scene whose scene_first entries are not 0 <= first
+ * <= last <= I places nothing. height_out f32 [S][G][G] (may be NULL): the final fields. Nothing outside an array is
+ * addressed. OSSID_EINVAL before the launch: S outside [1, OSSID_SCENE_MAX_SCENES], I outside [0, S *
+ * OSSID_SCENE_MAX_INSTANCES], K < 1, Vt outside [1, 2^29], Ft outside [0, 2^29], G outside [1, OSSID_REST_MAX_GRID], cell
+ * not finite or not > 0, a NULL vertices, meshes or scene_first, NULL faces with Ft > 0, a NULL instance_mesh, local,
+ * drop or status with I > 0. */
+#define OSSID_REST_MAX_DIRS 16384
+#define OSSID_REST_MAX_GRID 128
+int ossid_mesh_support(const float* vertices, int V, const double* dirs, int D, double* h_out, void* stream);
+int ossid_scene_drop(const float* vertices, const int32_t* faces, const int32_t* meshes, int Vt, int Ft, int K,
+                     const int32_t* instance_mesh, const int32_t* scene_first, const double* local, int I, int S, int G,
+                     double cell, double* drop, int32_t* status, float* height_out, void* stream);
+
 /* =============================================================================================
  * Detector pre-training on rendered scenes (SPEC.md section 15; python/ossid/train.py over
  * datasets/dtoid_dataset.py:97-236 in the reference, which reads offline BlenderProc renders)

@@ -143,12 +143,15 @@ class ScenePretrainSet:
     lights=True lights every refresh's scenes (scenes.sample_lights, SPEC 13.11-13.12) from a Generator of its own,
     derived from (seed, refresh number), so that no other draw moves: with the same seed the batches differ from the
     unlit set's in img alone. shadows=True (or a scenes.Shadows) lets those lights cast shadows (SPEC 13.13-13.15); it
-    needs lights=True and draws nothing random: again img alone differs."""
+    needs lights=True and draws nothing random: again img alone differs. rest=True rests every refresh's objects on a
+    table (scenes.sample_layouts(placement="rest"), SPEC 13.16-13.18): other layouts from other draws, one more launch and
+    one read-back per refresh, and once per object the support pass."""
 
     def __init__(self, atlas, bank, cam_K, hw, objects_per_scene, scenes_per_refresh, batch_size, seed, obj_ids=None,
                  jitter=1.0, heatmap_hw=(29, 39), min_visib=MIN_VISIB, min_px=MIN_PX, drop_last=True, background=True,
-                 lights=False, shadows=False):
+                 lights=False, shadows=False, rest=False):
         _need(isinstance(atlas, scenes.MeshAtlas), "atlas must be a scenes.MeshAtlas")
+        self.rest = bool(rest)
         self.lights = bool(lights)
         self.shadows = shadows if isinstance(shadows, scenes.Shadows) else (scenes.Shadows() if shadows else None)
         _need(self.shadows is None or self.lights, "shadows are cast by lights: shadows needs lights=True")
@@ -194,8 +197,10 @@ class ScenePretrainSet:
         return (t * 255.0).round_().clamp_(0.0, 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
     def draw_targets(self):
-        """The first draws of a refresh, host only -> (layout, sensor). The backgrounds, then plan's draws, follow."""
-        layout = scenes.sample_layouts(self.atlas, self.n_scenes, self.n_objects, self.cam_K, self.hw, self.rng)
+        """The first draws of a refresh -> (layout, sensor), host only unless the set rests its objects (then the drop's
+        launch and read-back). The backgrounds, then plan's draws, follow."""
+        layout = scenes.sample_layouts(self.atlas, self.n_scenes, self.n_objects, self.cam_K, self.hw, self.rng,
+                                       placement="rest" if self.rest else "free")
         sensor = scenes.sample_sensor(self.n_scenes, self.hw, self.rng)
         return layout, sensor
 

@@ -21,6 +21,10 @@ The scenes are unlit unless asked otherwise (csrc/scene_light.hip, SPEC 13.10-13
 and the lights cast no shadows unless asked (csrc/scene_shadow.hip, SPEC 13.13-13.15):
 
     batch = render_scenes(atlas, layout, (480, 640), lights=lights, material=material, shadows=Shadows())    # .blocked
+
+and the objects float at free poses unless asked to rest on the table (csrc/scene_rest.hip, SPEC 13.16-13.18):
+
+    layout = sample_layouts(atlas, 32, 12, cam_K, (480, 640), rng, placement="rest")    # .table_pose, .local, .drop, .status
 """
 import ctypes
 import json
@@ -158,12 +162,45 @@ class MeshAtlas:
             self._radii[int(obj_id)] = float(np.sqrt((V * V).sum(1).max()))
         return self._radii[int(obj_id)]
 
+    _resting = None
+
+    def resting(self, obj_id, level=4):
+        """The resting orientations of one object (SPEC 13.16-13.17) -> Resting, computed once per (object, level) and
+        kept like `radius`: the support heights of the object's vertices along the icosphere directions of `level`
+        (render._icosphere_vertices: 2562 at level 4, about 2 degrees apart), one launch of ossid_mesh_support and one
+        read-back, then resting_table on the host about the surface centroid. Needs the atlas on a GPU."""
+        if self._resting is None:
+            self._resting = {}
+        key = (int(obj_id), int(level))
+        if key not in self._resting:
+            if not 0 <= key[1] <= 5:
+                raise ValueError("resting: the icosphere level must lie in [0, 5], got %r" % (level,))
+            v0, nv, _f0, _nf = self.table_host[self.index_of[key[0]]]
+            V, F, _C = self.mesh_arrays(key[0])
+            dirs = _render._icosphere_vertices(key[1])
+            h = mesh_support(self.vertices[v0:v0 + nv], dirs)
+            t = resting_table(dirs, h, surface_centroid(V, F))
+            # per resting orientation the object's extent in the table frame, the same under any yaw: how high its origin
+            # lies when it stands on the table, how far it reaches above the origin, and its horizontal radius
+            P = [V[np.isfinite(V).all(1)].astype(np.float64) @ R.T for R in t.rotations]
+            t.extent = np.array([[-p[:, 2].min(), p[:, 2].max(), np.sqrt((p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1]).max())]
+                                 if len(p) else [0.0, 0.0, 0.0] for p in P])
+            self._resting[key] = t
+        return self._resting[key]
+
 
 class Layout:
     """A draw list (SPEC 13.1): instance_mesh int32 [I] (index into the atlas's table), transforms f64 [I,4,4]
     (model -> camera; rows 0-2 are used, so a scale is allowed), scene_first int32 [S+1] (the instances of a scene are
     contiguous; an empty scene is legal), cams f32 [S,4] = fx, fy, cx, cy. table_mesh: the atlas index of the mesh that
-    is a table, not an object (sample_layouts sets it; sample_lights gives its instances no highlight), or None."""
+    is a table, not an object (sample_layouts sets it; sample_lights gives its instances no highlight), or None.
+
+    A layout of sample_layouts(placement="rest") (SPEC 13.18) also holds table_pose f64 [S,4,4] (table frame -> camera),
+    local f64 [I,3,4] (model -> table frame before the drop), drop f64 [I] and status int32 [I] (ossid_scene_drop's; 0
+    for the table's own instance): transforms[i] = table_pose[s] . translate(0, 0, drop[i]) . local[i], and grid = (G,
+    cell), the field the objects were dropped on. All five are None for any other layout."""
+
+    table_pose = local = drop = status = grid = None
 
     def __init__(self, instance_mesh, transforms, scene_first, cams, table_mesh=None):
         self.table_mesh = None if table_mesh is None else int(table_mesh)
@@ -228,12 +265,305 @@ def _uniform_rotation(rng):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def sample_layouts(atlas, n_scenes, objects_per_scene, cam_K, hw, rng, z_range=(0.5, 1.2), table=True):
+def surface_centroid(vertices, faces):
+    """SPEC 13.17 -> f64 [3]: the area-weighted centroid of a mesh's surface, sum(A_f m_f) / sum(A_f) with A_f the area and
+    m_f the mean corner of face f, over the faces whose indices are valid and whose area is finite and not zero; the mean
+    of the finite vertices when no face counts ((0, 0, 0) without one). It stands in for the centre of mass -- that of a
+    thin shell of even thickness, not of a solid -- and, unlike the solid's, is defined for an open mesh."""
+    V = np.asarray(vertices, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    F = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    F = F[((F >= 0) & (F < len(V))).all(1)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        a, b, c = V[F[:, 0]], V[F[:, 1]], V[F[:, 2]]
+        n = np.cross(b - a, c - a)
+        area = 0.5 * np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+        mid = ((a + b) + c) / 3.0
+        ok = np.isfinite(area) & (area > 0.0) & np.isfinite(mid).all(1)
+        total = float(area[ok].sum())
+        if ok.any() and np.isfinite(total) and total > 0.0:
+            return (area[ok, None] * mid[ok]).sum(0) / total
+    fin = V[np.isfinite(V).all(1)]
+    return fin.sum(0) / float(len(fin)) if len(fin) else np.zeros(3)
+
+
+def mesh_support(vertices, dirs):
+    """SPEC 13.16 -> f64 [D], host: h[d] = the largest ((dx x + dy y) + dz z) over the finite vertices of a device tensor
+    f32 [V,3], in f64; -inf when none is finite. One launch of ossid_mesh_support on the current stream and one read-back."""
+    from .model_cloud import _refuse_cpu
+    dirs = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).reshape(-1, 3))
+    if not (torch.is_tensor(vertices) and vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.shape[1] == 3
+            and 1 <= vertices.shape[0] <= _lib.RASTER_MAX_VERTICES):
+        raise ValueError("mesh_support: vertices must be a float32 tensor [V,3], 1 <= V <= %d" % _lib.RASTER_MAX_VERTICES)
+    if not 1 <= len(dirs) <= _lib.REST_MAX_DIRS:
+        raise ValueError("mesh_support: dirs must be [D,3] with 1 <= D <= %d, got %d rows" % (_lib.REST_MAX_DIRS, len(dirs)))
+    _refuse_cpu(vertices.device)
+    vertices = vertices.contiguous()
+    d_dirs = torch.from_numpy(dirs).to(vertices.device)
+    h = torch.empty(len(dirs), dtype=torch.float64, device=vertices.device)
+    with _lib.on_device(vertices.device):
+        _lib.check(_lib.fn("ossid_mesh_support")(vertices.data_ptr(), int(vertices.shape[0]), d_dirs.data_ptr(), len(dirs),
+                                                 h.data_ptr(), _lib.stream()), "ossid_mesh_support")
+    return h.cpu().numpy()
+
+
+REST_NEIGHBOURS = 6         # a direction's neighbours on the grid of directions (an icosphere vertex has 5 or 6)
+REST_WIDER = 18             # ... and the two rings around it, looked at where a walk over the neighbours stalls
+
+
+class Resting:
+    """What resting_table returns, host arrays: dirs f64 [D,3], h and potential f64 [D], centroid f64 [3], neighbours
+    int [D,k], rest_of int [D] (the fixed point each direction descends to), fixed int [n] (the fixed points, ascending:
+    the resting directions), basin int [n] (how many directions descend to each) and rotations f64 [n,3,3] (rotations[j]
+    takes dirs[fixed[j]] to the table's down, (0, 0, -1)). slot_of(d) is the j of rest_of[d], rotation_of(d) its rotation.
+    MeshAtlas.resting adds extent f64 [n,3] = (origin above the table, top above the origin, horizontal radius)."""
+
+    extent = None
+
+    def __init__(self, dirs, h, centroid, potential, neighbours, rest_of, fixed, basin, rotations):
+        self.dirs, self.h, self.centroid, self.potential, self.neighbours = dirs, h, centroid, potential, neighbours
+        self.rest_of, self.fixed, self.basin, self.rotations = rest_of, fixed, basin, rotations
+        self._slot = {int(d): j for j, d in enumerate(fixed)}
+
+    def slot_of(self, d):
+        return self._slot[int(self.rest_of[int(d)])]
+
+    def rotation_of(self, d):
+        return self.rotations[self.slot_of(d)]
+
+
+def descend(potential, neighbours, wider=None):
+    """SPEC 13.17's descent -> rest_of int [D]: from d, step to the neighbour with the lowest potential that is strictly
+    below the current one (the lowest index among equals) until there is none. Every step lowers the potential, so the
+    walk ends; a direction whose potential is NaN stays where it is. wider int [D,k2], when given, is looked at where the
+    neighbours hold nothing lower, by the same rule: the walk stops only where neither holds a lower direction."""
+    U = np.asarray(potential, dtype=np.float64).reshape(-1)
+    rings = [np.asarray(n, dtype=np.int64).reshape(len(U), -1) for n in (neighbours, wider) if n is not None]
+    step = np.arange(len(U))
+    for d in range(len(U)):
+        for N in rings:
+            best, at = U[d], d
+            for j in N[d]:
+                if U[j] < best or (U[j] == best and at != d and j < at):
+                    best, at = U[j], int(j)
+            if at != d:
+                break
+        step[d] = at
+    rest_of = step.copy()
+    for d in range(len(U)):
+        k = d
+        while step[k] != k:
+            k = step[k]
+        rest_of[d] = k
+    return rest_of
+
+
+def rotation_to_down(d):
+    """-> f64 [3,3], the rotation that takes the direction d to (0, 0, -1) by the shortest way: about the axis d x
+    (0, 0, -1) by the angle between them (Rodrigues: I + K + K K / (1 + c) with K the cross-product matrix of the axis and
+    c = -d_z, d normalised first). d = (0, 0, 1), the antipode, has no such axis: within 1e-12 of it (1 + c < 1e-12) the
+    half turn about the x axis, diag(1, -1, -1)."""
+    d = np.asarray(d, dtype=np.float64).reshape(3)
+    d = d / np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    c = -d[2]
+    if 1.0 + c < 1e-12:
+        return np.diag([1.0, -1.0, -1.0])
+    v = np.array([-d[1], d[0], 0.0])                       # d x (0, 0, -1)
+    K = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return np.eye(3) + K + (K @ K) / (1.0 + c)
+
+
+def resting_table(dirs, h, centroid):
+    """SPEC 13.17, a pure host function of (dirs f64 [D,3], h f64 [D], centroid [3]) -> Resting. A direction d means "this
+    side of the object faces down"; U[d] = h[d] - ((dx cx + dy cy) + dz cz) is the centroid's height above the support
+    plane then. A direction's neighbours are its REST_NEIGHBOURS nearest others by dot product (all the others when there
+    are fewer), ties to the lower index; `descend` follows them downhill, and its fixed points are the resting
+    orientations. Drawing d uniformly and taking rest_of[d] lands in each in proportion to its basin.
+
+    U has creases -- for a box the three great circles of the directions that balance it on an edge, valleys that lead
+    down to the faces -- and the six neighbours of a grid direction in such a valley can all lie up its walls: on them
+    alone a 1 x 2 x 3 box keeps 14 "resting" directions at level 2 and 57 at level 4, most of them on an edge. So where
+    the neighbours hold nothing lower, the walk looks once at the REST_WIDER nearest directions (two rings of the grid,
+    about 4 degrees at level 4) before it stops; with that the box rests on its six faces at levels 2 to 4."""
+    dirs = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).reshape(-1, 3))
+    h = np.asarray(h, dtype=np.float64).reshape(-1)
+    c = np.asarray(centroid, dtype=np.float64).reshape(3)
+    D = len(dirs)
+    if D < 1 or len(h) != D:
+        raise ValueError("resting_table: dirs [D,3] and h [D] must agree and D >= 1, got %d and %d" % (D, len(h)))
+    if not (np.isfinite(dirs).all() and np.isfinite(c).all()):
+        raise ValueError("resting_table: dirs and centroid must be finite")
+    U = h - ((dirs[:, 0] * c[0] + dirs[:, 1] * c[1]) + dirs[:, 2] * c[2])
+    k = min(REST_NEIGHBOURS, D - 1)
+    k2 = min(REST_WIDER, D - 1)
+    wider = np.zeros((D, k2), np.int64)
+    for d in range(D if k else 0):
+        dot = (dirs[:, 0] * dirs[d, 0] + dirs[:, 1] * dirs[d, 1]) + dirs[:, 2] * dirs[d, 2]
+        dot[d] = -np.inf
+        wider[d] = np.argsort(-dot, kind="stable")[:k2]                       # stable: equal dots keep the lower index first
+    neighbours = np.ascontiguousarray(wider[:, :k])
+    rest_of = descend(U, neighbours, wider)
+    fixed, basin = np.unique(rest_of, return_counts=True)
+    rotations = np.stack([rotation_to_down(dirs[d]) for d in fixed])
+    return Resting(dirs, h, c, U, neighbours, rest_of, fixed, basin, rotations)
+
+
+def scene_drop(atlas, instance_mesh, scene_first, local, grid, cell, height=False):
+    """SPEC 13.18 -> (drop f64 [I], status int32 [I]) and, with height=True, the final height fields f32 [S,G,G], host
+    arrays: ossid_scene_drop over the draw list (instance_mesh int32 [I], scene_first int32 [S+1]) with local f64 [I,3,4],
+    model -> table frame. One launch on the current stream, then the read-back of the results: the call's only
+    synchronisation."""
+    from .model_cloud import _refuse_cpu
+    if not isinstance(atlas, MeshAtlas):
+        raise ValueError("scene_drop takes a MeshAtlas")
+    mesh = np.ascontiguousarray(np.asarray(instance_mesh).reshape(-1), dtype=np.int32)
+    first = np.ascontiguousarray(np.asarray(scene_first).reshape(-1), dtype=np.int32)
+    I, S, G = len(mesh), len(first) - 1, int(grid)
+    local = np.ascontiguousarray(np.asarray(local, dtype=np.float64).reshape(-1, 3, 4))
+    if not 1 <= S <= _lib.SCENE_MAX_SCENES or I > S * _lib.SCENE_MAX_INSTANCES:
+        raise ValueError("scene_drop: 1 to %d scenes of at most %d instances each, got %d and %d instances"
+                         % (_lib.SCENE_MAX_SCENES, _lib.SCENE_MAX_INSTANCES, S, I))
+    if len(local) != I:
+        raise ValueError("scene_drop: local must be [I,3,4] = [%d,3,4], got %s" % (I, local.shape))
+    if not 1 <= G <= _lib.REST_MAX_GRID:
+        raise ValueError("scene_drop: grid must lie in [1, %d], got %r" % (_lib.REST_MAX_GRID, grid))
+    if not (float(cell) > 0.0 and np.isfinite(float(cell))):
+        raise ValueError("scene_drop: cell must be finite and > 0, got %r" % (cell,))
+    _refuse_cpu(atlas.device)
+    dev = atlas.device
+    up = lambda a: torch.from_numpy(a).to(dev)
+    d_mesh, d_first, d_local = up(mesh), up(first), up(local)
+    drop = torch.empty(I, dtype=torch.float64, device=dev)
+    status = torch.empty(I, dtype=torch.int32, device=dev)
+    field = torch.empty(S, G, G, dtype=torch.float32, device=dev) if height else None
+    with _lib.on_device(dev):
+        _lib.check(_lib.fn("ossid_scene_drop")(
+            atlas.vertices.data_ptr(), atlas.faces.data_ptr(), atlas.table.data_ptr(), len(atlas.vertices_host),
+            len(atlas.faces_host), atlas.n_meshes, d_mesh.data_ptr() if I else None, d_first.data_ptr(),
+            d_local.data_ptr() if I else None, I, S, G, float(cell), drop.data_ptr() if I else None,
+            status.data_ptr() if I else None, None if field is None else field.data_ptr(), _lib.stream()), "ossid_scene_drop")
+    out = (drop.cpu().numpy(), status.cpu().numpy())
+    return out + (field.cpu().numpy(),) if height else out
+
+
+REST_TRIES = 256            # positions tried per object of a rest layout before sample_layouts gives up
+
+
+def _rest_layouts(atlas, S, n, intr, hw, rng, z_range, table, elevation, rest_level, grid):
+    """sample_layouts(placement="rest"), SPEC 13.18, after the argument checks."""
+    (H, W), (fx, fy, cx, cy), (z0, z1), (e0, e1) = hw, intr, z_range, elevation
+    objects = [o for o in atlas.obj_ids if o != TABLE_OBJ_ID]
+    rest = {o: atlas.resting(o, rest_level) for o in objects} if n else {}
+    radius = {o: atlas.radius(o) for o in objects}
+    r_max = max(radius.values())
+    t_mesh = atlas.index_of[TABLE_OBJ_ID]
+    mesh, local, first, poses, is_table = [], [], [0], [], []
+    # the field is fixed before anything is drawn: no foot point lies farther from the table frame's origin than `reach`
+    # (|x'| = |u - cx| / fx z; |y'| = |z - zt| / cos e, and = |v - cy| / fy z / sin e as the foot point lies in the frame)
+    far = 1.5 * z1
+    reach = max(max(cx, W - cx) / fx * far,
+                min((far - z0) / np.cos(np.deg2rad(e1)), max(cy, H - cy) / fy * far / np.sin(np.deg2rad(e0)))) + r_max
+    cell = 2.0 * reach * 1.001 / grid                      # the grid covers every object's sphere with a margin
+    x0 = -(grid * 0.5) * cell
+    for _ in range(S):
+        e = np.deg2rad(rng.uniform(e0, e1))
+        zt = rng.uniform(z0, z1)
+        ce, se = np.cos(e), np.sin(e)
+        P = np.eye(4)                                      # columns: x', y' (away from the camera), z' (the table's up), origin
+        P[:3, 0], P[:3, 1], P[:3, 2], P[:3, 3] = (1.0, 0.0, 0.0), (0.0, -se, ce), (0.0, -ce, -se), (0.0, 0.0, zt)
+        poses.append(P)
+        picks = rng.permutation(len(objects))[:n] if n <= len(objects) else rng.integers(0, len(objects), n)
+        chosen = [objects[int(k)] for k in picks]
+        placed = []                                        # (its box of cells, a bound on the height of its top)
+        if table:
+            # the square reaches from the depth zn, where the plane leaves the frame's lower edge with a quarter to
+            # spare, 2 `half` away from the camera and `half` to either side
+            q = 1.25 * max(H - cy, 1.0) / fy
+            zn = zt * (se / ce) / (se / ce + q)
+            half = 2.0 * (z1 + r_max) * max(W / fx, H / fy, 1.0)
+            L = np.zeros((3, 4))
+            L[0, 0], L[1, 1], L[2, 2], L[1, 3] = half, half, 1.0, (zn - zt) / ce + half
+            mesh.append(t_mesh), local.append(L), is_table.append(True)
+        for o in chosen:
+            slot = rest[o].slot_of(int(rng.integers(0, len(rest[o].dirs))))
+            R, (lo, hi, rho) = rest[o].rotations[slot], rest[o].extent[slot]
+            yaw = rng.uniform(0.0, 2.0 * np.pi)
+            Rz = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
+            for _try in range(REST_TRIES):
+                u, v = rng.uniform(0.0, W), rng.uniform(0.0, H)
+                den = ce * ((v - cy) / fy) + se            # the pixel's ray meets the plane at the depth z ...
+                z = zt * se / den if den > 0.0 else np.inf
+                if not 0.5 * z0 <= z <= 1.5 * z1:          # ... or above the horizon, or too near or far to be of use
+                    continue
+                xp, yp = (u - cx) / fx * z, (z - zt) / ce
+                # the origin ends at the height `drop`: at most `lo` above the table or above the top of an earlier object
+                # whose box of cells -- that of its horizontal circle, which holds every triangle's -- meets this one's
+                box = [int(np.floor((c - x0) / cell)) for c in (xp - rho, xp + rho, yp - rho, yp + rho)]
+                under = [tb for (a0, a1, b0, b1), tb in placed if a0 <= box[1] and box[0] <= a1 and b0 <= box[3] and box[2] <= b1]
+                high = lo + max(under, default=0.0)
+                foot = P[:3, :3] @ np.array([xp, yp, 0.0]) + P[:3, 3]
+                head = foot + high * P[:3, 2]
+                inside = True
+                for p in (foot, head):                     # the centre lies between them, and the frame is convex
+                    pu, pv = (fx * p[0] / p[2] + cx, fy * p[1] / p[2] + cy) if p[2] > 0.0 else (-1.0, -1.0)
+                    inside = inside and 0.0 <= pu <= W and 0.0 <= pv <= H
+                if inside:
+                    break
+            else:
+                raise ValueError("sample_layouts: no position on the table within the frame for an object after %d tries "
+                                 "(z_range %r, elevation %r)" % (REST_TRIES, (z0, z1), (e0, e1)))
+            L = np.zeros((3, 4))
+            L[:, :3], L[0, 3], L[1, 3] = Rz @ R, xp, yp
+            placed.append((box, high + hi))
+            mesh.append(atlas.index_of[o]), local.append(L), is_table.append(False)
+        first.append(len(mesh))
+    mesh = np.asarray(mesh, dtype=np.int32)
+    local = np.stack(local) if local else np.zeros((0, 3, 4))
+    is_table = np.asarray(is_table, dtype=bool)
+    I = len(mesh)
+    drop, status = np.zeros(I), np.zeros(I, np.int32)
+    if (~is_table).any():
+        # the objects alone are dropped: the table's own square is the plane z' = 0 the field starts from
+        counts = [int((~is_table[first[s]:first[s + 1]]).sum()) for s in range(S)]
+        drop[~is_table], status[~is_table] = scene_drop(atlas, mesh[~is_table], np.concatenate([[0], np.cumsum(counts)]),
+                                                        local[~is_table], grid, cell)
+    T = np.zeros((I, 4, 4))
+    for s in range(S):
+        for i in range(first[s], first[s + 1]):
+            T[i] = rest_compose(poses[s], drop[i], local[i])
+    out = Layout(mesh, T, first, np.tile([fx, fy, cx, cy], (S, 1)), table_mesh=t_mesh)
+    out.table_pose, out.local, out.drop, out.status = np.stack(poses), local, drop, status
+    out.grid = (grid, cell)
+    return out
+
+
+def rest_compose(table_pose, drop, local):
+    """SPEC 13.18 -> f64 [4,4]: table_pose . translate(0, 0, drop) . local, local f64 [3,4] completed by the row 0 0 0 1."""
+    M, D = np.eye(4), np.eye(4)
+    M[:3] = np.asarray(local, dtype=np.float64).reshape(3, 4)
+    D[2, 3] = float(drop)
+    return np.asarray(table_pose, dtype=np.float64).reshape(4, 4) @ (D @ M)
+
+
+def sample_layouts(atlas, n_scenes, objects_per_scene, cam_K, hw, rng, z_range=(0.5, 1.2), table=True, placement="free",
+                   elevation=(25.0, 65.0), rest_level=4, grid=128):
     """SPEC 13.7 (build-defined) -> Layout of n_scenes scenes under the camera cam_K, each with objects_per_scene objects
     of the atlas: distinct ones while the atlas has enough, drawn with replacement otherwise. Rotations are uniform; a
     centre has its depth uniform in z_range and its projection uniform over the frame. table=True puts the atlas's
     square first in every scene, tilted by 15 to 40 degrees so that it recedes towards the top of the image, its nearest
-    edge behind the farthest possible object. The same Generator state gives the same layout."""
+    edge behind the farthest possible object. The same Generator state gives the same layout.
+
+    placement="free" is the above, draw for draw; elevation, rest_level and grid are not read. placement="rest" (SPEC
+    13.18, needs the atlas on a GPU) rests the objects on a table plane instead: per scene the camera's elevation above
+    the plane is uniform in `elevation` (degrees, within (0, 90)) and the plane passes through the point of the optical axis at
+    a depth uniform in z_range; table=True draws the atlas's square in it, first in the scene. Per object a uniform
+    direction index goes through MeshAtlas.resting(obj, rest_level).rest_of to a resting orientation, the yaw about the
+    table's normal is uniform, and the foot point is where the ray of a pixel uniform over the frame meets the plane,
+    redrawn while that is above the horizon or at a depth outside [z_range[0] / 2, 1.5 z_range[1]], and
+    redrawn (at most REST_TRIES times, then a ValueError) until it and the point above it at a bound on the centre's
+    height -- the radius above the table or above the earlier objects it can land on -- project inside the frame, so
+    every object centre does. One ossid_scene_drop call over all
+    scenes on a grid x grid field then stacks the objects in draw order, and ONE read-back of its results -- the call's
+    only synchronisation -- gives the transforms. The layout also carries table_pose, local, drop and status."""
     H, W = _render._check_frame(None, hw)
     S, n = int(n_scenes), int(objects_per_scene)
     if not isinstance(rng, np.random.Generator):
@@ -246,6 +576,23 @@ def sample_layouts(atlas, n_scenes, objects_per_scene, cam_K, hw, rng, z_range=(
     if not 0.0 < z0 <= z1 < np.inf:
         raise ValueError("z_range must be 0 < near <= far, got %r" % (z_range,))
     fx, fy, cx, cy = _render._intrinsics(cam_K)
+    if placement not in ("free", "rest"):
+        raise ValueError("placement must be 'free' or 'rest', got %r" % (placement,))
+    if placement == "rest":
+        try:
+            e0, e1 = (float(v) for v in elevation)
+        except (TypeError, ValueError):
+            e0 = e1 = np.nan
+        if not 0.0 < e0 <= e1 < 90.0:
+            raise ValueError("elevation must be two angles 0 < low <= high < 90 in degrees, got %r" % (elevation,))
+        if isinstance(rest_level, (bool, np.bool_)) or not isinstance(rest_level, (int, np.integer)) or not 0 <= rest_level <= 5:
+            raise ValueError("rest_level must be an integer in [0, 5], got %r" % (rest_level,))
+        if isinstance(grid, (bool, np.bool_)) or not isinstance(grid, (int, np.integer)) or not 1 <= grid <= _lib.REST_MAX_GRID:
+            raise ValueError("grid must be an integer in [1, %d], got %r" % (_lib.REST_MAX_GRID, grid))
+        from .model_cloud import _refuse_cpu
+        _refuse_cpu(atlas.device)
+        return _rest_layouts(atlas, S, n, (fx, fy, cx, cy), (H, W), rng, (z0, z1), bool(table), (e0, e1), int(rest_level),
+                             int(grid))
     objects = [o for o in atlas.obj_ids if o != TABLE_OBJ_ID]
     r_max = max(atlas.radius(o) for o in objects)
     mesh, T, first = [], [], [0]

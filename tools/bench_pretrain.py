@@ -7,10 +7,12 @@
   pretrain_curve.json      tools/pretrain_dtoid.py for --steps steps on a models folder written by SceneBatch.write_bop:
                            the loss per step, validation seg_IoU and AP at the start and the end
 
-    python tools/bench_pretrain.py [--reps 20] [--steps 200] [--skip-curve] [--lights [--shadows]]
+    python tools/bench_pretrain.py [--reps 20] [--steps 200] [--skip-curve] [--lights [--shadows]] [--rest]
 
 --lights and --shadows measure the producer with lit (SPEC 13.11-13.12) and shadowed (13.13-13.15) scenes; the producer's
-file is then pretrain_producer_lit.json or pretrain_producer_shadow.json, and the curve is left alone.
+file is then pretrain_producer_lit.json or pretrain_producer_shadow.json, and the curve is left alone. --rest rests the
+objects on a table (SPEC 13.16-13.18) -> pretrain_producer_rest.json (with the other flags: ..._rest_lit / ..._rest_shadow),
+no curve: `layouts_sensor` among the refresh's parts then holds the drop's launch and read-back.
 """
 import argparse
 import json
@@ -108,13 +110,13 @@ def refresh_parts(train, reps, warm=3):
     return {k: float(np.median(v[warm:])) for k, v in parts.items()}
 
 
-def producer(models, reps, lights=False, shadows=False):
+def producer(models, reps, lights=False, shadows=False, rest=False):
     from ossid_code_amd import dtoid, pipeline
     from ossid_code_amd.dtoid import pretrain
     from pretrain_dtoid import build_sets
-    train, _val, line = build_sets(models, 8, 8, 4, 0, 1.0, 0, lights=lights, shadows=shadows)
+    train, _val, line = build_sets(models, 8, 8, 4, 0, 1.0, 0, lights=lights, shadows=shadows, rest=rest)
     print(line, flush=True)
-    res = {"batch": 8, "hw": [480, 640], "scenes_per_refresh": 8, "objects_per_scene": 4, "reps": reps, "lights": bool(lights),
+    res = {"batch": 8, "hw": [480, 640], "scenes_per_refresh": 8, "objects_per_scene": 4, "reps": reps, "lights": bool(lights), "rest": bool(rest),
            "shadows": None if train.shadows is None else {"size": list(train.shadows.size), "beta": list(train.shadows.beta)}}
 
     # a refresh: layouts + sensor, backgrounds, render_scenes, select_targets (one read-back of gt_info), the plan, its uploads
@@ -174,6 +176,7 @@ def main():
     ap.add_argument("--skip-curve", action="store_true")
     ap.add_argument("--lights", action="store_true", help="light the scenes -> pretrain_producer_lit.json, no curve")
     ap.add_argument("--shadows", action="store_true", help="with --lights: cast shadows -> pretrain_producer_shadow.json")
+    ap.add_argument("--rest", action="store_true", help="rest the objects on a table -> pretrain_producer_rest.json, no curve")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     a = ap.parse_args()
     if a.shadows and not a.lights:
@@ -183,12 +186,12 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
         models = write_models(tmp)
-        res = producer(models, a.reps, a.lights, a.shadows)
+        res = producer(models, a.reps, a.lights, a.shadows, a.rest)
         print(json.dumps(res), flush=True)
-        name = "pretrain_producer_shadow.json" if a.shadows else "pretrain_producer_lit.json" if a.lights else "pretrain_producer.json"
+        name = "pretrain_producer%s%s.json" % ("_rest" if a.rest else "", "_shadow" if a.shadows else "_lit" if a.lights else "")
         with open(os.path.join(a.out, name), "w") as f:
             json.dump(res, f, indent=1)
-        if not a.skip_curve and not a.lights:
+        if not a.skip_curve and not a.lights and not a.rest:
             curve_path = os.path.join(tmp, "curve.json")
             cmd = [sys.executable, os.path.join(ROOT, "tools", "pretrain_dtoid.py"), "--models", models, "--steps", str(a.steps),
                    "--out", os.path.join(tmp, "ckpt.pt"), "--views", "1", "--val_every", str(a.steps), "--curve", curve_path]

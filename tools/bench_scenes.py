@@ -27,7 +27,15 @@ views and work list, two launches), `shadowed_pass` the shadowed pass over maps 
 render_scenes(lights=..., shadows=...). First the shadowed image is checked: the two routes agree, enable = 0 gives
 the unshadowed pass, and so does every pixel no tap blocks.
 
-    python3 tools/bench_scenes.py [--textured | --lights [--shadows]] [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
+--rest times the placement (csrc/scene_rest.hip, SPEC 13.16-13.18) beside the render of the same run -> profiles/
+scenes_rest.json: `support` the one-off support pass of one mesh (scenes.mesh_support at the 2562 directions of level 4:
+upload, one launch, read-back) and `resting_table` the host's descent on its heights, per mesh; `drop`
+scenes.scene_drop over every scene of a rest layout (upload, one launch, read-back), per refresh; `render` and
+`render_free` scenes.render_scenes of the rest layout (z_range --rest_z, 0.8 to 1.6 m: nearer, a table in view has no room
+for 11 such objects and sample_layouts says so) and of the free layout of the same seed. The drop is first checked
+against the layout's own.
+
+    python3 tools/bench_scenes.py [--textured | --lights [--shadows] | --rest] [--out profiles/scenes.json] [--scenes 32] [--objects 11] [--level 6]
     rocprofv3 --kernel-trace --stats -d out -- python3 tools/bench_scenes.py --trace       (three untimed calls of `scene`;
                                                                           with --lights: of the lit render, normals first)
 """
@@ -240,6 +248,70 @@ def bench_shadowed(a, atlas, layout, sensor, n_faces):
     return res
 
 
+def bench_rest(a, atlas, free_layout, sensor, n_faces):
+    """The legs of --rest -> the result dict."""
+    import time
+    objects = [o for o in atlas.obj_ids if o != scenes.TABLE_OBJ_ID]
+    dirs = render._icosphere_vertices(a.rest_level)
+    rows = {o: atlas.table_host[atlas.index_of[o]] for o in objects}
+    support_fn = lambda o: scenes.mesh_support(atlas.vertices[rows[o][0]:rows[o][0] + rows[o][1]], dirs)  # noqa: E731
+    cold_ms, h0 = once_ms(lambda: support_fn(objects[0]))
+    t_sup = [once_ms(lambda: support_fn(o))[0] for _ in range(max(a.rounds, 3)) for o in objects]
+    t0 = time.perf_counter()
+    table = scenes.resting_table(dirs, h0, scenes.surface_centroid(*atlas.mesh_arrays(objects[0])[:2]))
+    table_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    layout = scenes.sample_layouts(atlas, a.scenes, a.objects, synth.CAM_K, HW, np.random.default_rng(a.seed), placement="rest",
+                                   rest_level=a.rest_level, z_range=tuple(a.rest_z))
+    first_layout_ms = (time.perf_counter() - t0) * 1e3     # with the support pass and the table of every object
+    t_host = []
+    for k in range(3):
+        t0 = time.perf_counter()
+        scenes.sample_layouts(atlas, a.scenes, a.objects, synth.CAM_K, HW, np.random.default_rng(a.seed + 1 + k), placement="rest",
+                              rest_level=a.rest_level, z_range=tuple(a.rest_z))
+        t_host.append((time.perf_counter() - t0) * 1e3)
+    obj = layout.instance_mesh != layout.table_mesh
+    counts = [int(obj[layout.scene_first[s]:layout.scene_first[s + 1]].sum()) for s in range(a.scenes)]
+    first = np.concatenate([[0], np.cumsum(counts)])
+    G, cell = layout.grid
+    drop_fn = lambda: scenes.scene_drop(atlas, layout.instance_mesh[obj], first, layout.local[obj], G, cell)  # noqa: E731
+    d, s = drop_fn()
+    same = {"drop": bool(np.array_equal(d, layout.drop[obj])), "status": bool(np.array_equal(s, layout.status[obj])),
+            "status_all_0": bool((layout.status == 0).all())}
+    print("outputs equal:", same, flush=True)
+    if not all(same.values()):
+        raise SystemExit("the drop does not repeat the layout's own: %s" % same)
+    render_fn = lambda: scenes.render_scenes(atlas, layout, HW, sensor=sensor)  # noqa: E731
+    free_fn = lambda: scenes.render_scenes(atlas, free_layout, HW, sensor=sensor)  # noqa: E731
+    g = render_fn().gt_info.cpu().numpy()
+    legs = (("drop", drop_fn), ("render", render_fn), ("render_free", free_fn))
+    for _ in range(a.warmup):
+        for _name, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name, _fn in legs}
+    for _ in range(a.rounds):
+        for name, fn in legs:
+            t[name].append(once_ms(fn)[0])
+    res = {"workload": {"scenes": a.scenes, "instances": layout.n_instances, "instances_per_scene": a.objects + 1, "frame": list(HW),
+                        "faces_per_object": n_faces, "faces_dropped": int(atlas.table_host[layout.instance_mesh[obj], 3].sum()),
+                        "seed": a.seed, "z_range": list(a.rest_z), "rest_level": a.rest_level, "directions": int(len(dirs)), "grid": int(G), "cell_m": float(cell),
+                        "stacked_objects": int((layout.drop[obj] > 1e-9 + np.array(
+                            [-(layout.local[i][2, :3] @ atlas.mesh_arrays(atlas.obj_ids[layout.instance_mesh[i]])[0].astype(np.float64).T).min()
+                             for i in np.nonzero(obj)[0]])).sum()),
+                        "resting_orientations_of_first_object": int(len(table.fixed)),
+                        "visible_instances": int((g[:, 1] > 0).sum()), "objects_in_frame": int((g[obj, 0] > 0).sum())},
+           "outputs_equal": same,
+           "support": dict(stats(t_sup), cold_ms=float(cold_ms), c_abi_launches=1, per="mesh, once"),
+           "resting_table": {"host_ms": float(table_ms), "per": "mesh, once"},
+           "drop": dict(stats(t["drop"]), c_abi_launches=1, per="refresh"),
+           "render": dict(stats(t["render"]), c_abi_launches=7), "render_free": dict(stats(t["render_free"]), c_abi_launches=7),
+           "sample_layouts_rest_host_ms": {"first": float(first_layout_ms), "later": stats(t_host)},
+           "rounds": a.rounds, "warmup": a.warmup}
+    res["ratio_drop_over_render"] = res["drop"]["ms"] / res["render"]["ms"]
+    return res
+
+
 def finish(a, res):
     commit = a.commit
     if commit is None:
@@ -261,6 +333,10 @@ def main():
     ap.add_argument("--textured", action="store_true", help="draw the objects from a 1024 x 1024 texture each")
     ap.add_argument("--lights", action="store_true", help="time the shading pass and the vertex normals -> profiles/scenes_lit.json")
     ap.add_argument("--shadows", action="store_true", help="with --lights: time the shadow maps and the shadowed pass -> profiles/scenes_shadow.json")
+    ap.add_argument("--rest", action="store_true", help="time the support pass and the drop beside the render -> profiles/scenes_rest.json")
+    ap.add_argument("--rest_level", type=int, default=4, help="icosphere level of the resting directions (4: 2562)")
+    ap.add_argument("--rest_z", type=float, nargs=2, default=(0.8, 1.6),
+                    help="z_range of the rest layout: a table holds 11 objects of 8 to 20 cm inside the frame from about 0.7 m on")
     ap.add_argument("--shadow_size", type=int, nargs=2, default=None, help="Hs Ws of the shadow maps (default: scenes.Shadows' own)")
     ap.add_argument("--scenes", type=int, default=32)
     ap.add_argument("--objects", type=int, default=11, help="objects per scene; the table is one more instance")
@@ -275,8 +351,10 @@ def main():
         raise SystemExit("--lights times the pass over the vertex-coloured workload; it does not combine with --textured")
     if a.shadows and not a.lights:
         raise SystemExit("--shadows needs --lights: shadows are cast by lights")
+    if a.rest and (a.lights or a.textured or a.trace):
+        raise SystemExit("--rest times the placement on the vertex-coloured workload; it does not combine with other modes")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "scenes_shadow.json" if a.shadows else "scenes_lit.json" if a.lights else ("scenes_textured.json" if a.textured else "scenes.json"))
+        a.out = os.path.join(ROOT, "profiles", "scenes_rest.json" if a.rest else "scenes_shadow.json" if a.shadows else "scenes_lit.json" if a.lights else ("scenes_textured.json" if a.textured else "scenes.json"))
     if not torch.cuda.is_available():
         raise SystemExit("bench_scenes.py needs the GPU: there is nothing to time without one")
     torch.cuda.set_device(0)
@@ -307,6 +385,8 @@ def main():
             scene_fn()
         torch.cuda.synchronize()
         return
+    if a.rest:
+        return finish(a, bench_rest(a, atlas, layout, sensor, int(len(F))))
     if a.shadows:
         return finish(a, bench_shadowed(a, atlas, layout, sensor, int(len(F))))
     if a.lights:

@@ -3,6 +3,7 @@ that names its texture in `comment TextureFile`, the image beside it) -> a stand
 
     python3 tools/make_scenes.py MODELS_DIR OUT_DIR --scenes 32 --objects 6 --seed 0 [--name synth] [--split test]
                                  [--hw 480 640] [--no-mm2m] [--clean] [--no-table] [--depth_scale 1.0] [--lights [--shadows]]
+                                 [--rest]
 
 Every MODELS_DIR/*.ply (obj_XXXXXX.ply keeps its id; millimetres, as BOP stores them, unless --no-mm2m) goes into one
 atlas; scenes.sample_layouts places the objects, scenes.render_scenes (csrc/scene.hip, SPEC.md section 13) draws them with
@@ -10,7 +11,9 @@ the depth corruption of scenes.sample_sensor (--clean: quantisation only), and S
 OUT_DIR/<name>: what bop_eval.BopFolder, tools/eval_bop19.py and scenes.read_bop_frames read. The same seed gives the same
 folder. At most 256 scenes per call. --lights lights the scenes (scenes.sample_lights, SPEC.md 13.11-13.12) from a
 generator of its own: rgb/ is lit, every other file is the one written without the flag at the same seed. --shadows (with
---lights) lets the lights cast shadows (scenes.Shadows, SPEC.md 13.13-13.15): again rgb/ alone differs.
+--lights) lets the lights cast shadows (scenes.Shadows, SPEC.md 13.13-13.15): again rgb/ alone differs. --rest rests the
+objects on the table (scenes.sample_layouts(placement="rest"), SPEC.md 13.16-13.18) instead of letting them float: other
+layouts, so every file differs from the folder written without the flag.
 """
 import argparse
 import os
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--no-table", action="store_true")
     ap.add_argument("--lights", action="store_true", help="light the scenes: sampled lights and materials (default: unlit)")
     ap.add_argument("--shadows", action="store_true", help="let the lights cast shadows; needs --lights")
+    ap.add_argument("--rest", action="store_true", help="rest the objects on the table, stacked where they overlap (default: free poses)")
     a = ap.parse_args()
     if a.shadows and not a.lights:
         raise SystemExit("--shadows needs --lights: shadows are cast by lights")
@@ -51,7 +55,8 @@ def main():
     atlas = scenes.MeshAtlas(scenes.read_models_dir(a.models_dir, scale=1.0 if a.no_mm2m else 0.001))
     rng = np.random.default_rng(a.seed)
     K = synth.CAM_K * np.array([[a.hw[1] / 640.0], [a.hw[0] / 480.0], [1.0]])
-    layout = scenes.sample_layouts(atlas, a.scenes, a.objects, K, a.hw, rng, table=not a.no_table)
+    layout = scenes.sample_layouts(atlas, a.scenes, a.objects, K, a.hw, rng, table=not a.no_table,
+                                   placement="rest" if a.rest else "free")
     sensor = None if a.clean else scenes.sample_sensor(a.scenes, a.hw, rng)
     lights = material = None
     if a.lights:

@@ -4,7 +4,7 @@ scripts/online_learning.py:153-167 starts from (--dtoid_weights_path; :161-162 l
 
     python tools/pretrain_dtoid.py --models MODELS_DIR --steps N --out ckpt.pt \
         [--batch 8] [--scenes 8] [--objects 4] [--views 2] [--jitter 1.0] [--val_every K] [--resume ckpt.pt] [--seed S]
-        [--lights [--shadows]]
+        [--lights [--shadows]] [--rest]
 
 MODELS_DIR holds .ply models, vertex-coloured or texture-mapped, in millimetres as BOP stores them (scenes.read_models_dir).
 Every object's templates are rendered once (TemplateBank.add_mesh, the view grid of subdivision --views: 12, 42, 162 views);
@@ -12,6 +12,7 @@ the scenes are rendered --scenes at a time with --objects objects each, and ever
 (dtoid.pretrain.ScenePretrainSet). Objects are split as the reference splits them (id % 4 == 0 validates); a folder that
 leaves either side empty validates on the training objects, on scenes of another seed. One line per step. --lights
 lights the scenes of both sets (scenes.sample_lights, SPEC.md 13.11-13.12); whether that helps on real frames is untested.
+--rest rests the objects of both sets on a table (SPEC.md 13.16-13.18); the same holds for it.
 """
 import argparse
 import json
@@ -23,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def build_sets(models_dir, batch, n_scenes, n_objects, level, jitter, seed, hw=(480, 640), lights=False, shadows=False):
+def build_sets(models_dir, batch, n_scenes, n_objects, level, jitter, seed, hw=(480, 640), lights=False, shadows=False, rest=False):
     """-> (train set, validation set, the printed line about the split)."""
     from ossid_code_amd import pipeline, render, scenes, synth
     from ossid_code_amd.dtoid import pretrain
@@ -38,9 +39,9 @@ def build_sets(models_dir, batch, n_scenes, n_objects, level, jitter, seed, hw=(
     per_scene = n_objects * len(train_ids) / float(len(meshes))
     n_scenes = min(256, max(n_scenes, int(-(-2 * batch // per_scene))))
     train = pretrain.ScenePretrainSet(atlas, bank, synth.CAM_K, hw, n_objects, n_scenes, batch, seed, obj_ids=train_ids, jitter=jitter,
-                                      lights=lights, shadows=shadows)
+                                      lights=lights, shadows=shadows, rest=rest)
     val = pretrain.ScenePretrainSet(atlas, bank, synth.CAM_K, hw, n_objects, n_scenes, batch, seed + 1000003, obj_ids=val_ids, jitter=None,
-                                    drop_last=False, lights=lights, shadows=shadows)
+                                    drop_last=False, lights=lights, shadows=shadows, rest=rest)
     line = "%d objects, %d views each, %d scenes per refresh: train on %s, validate on %s%s" % (
         len(meshes), int(bank.img[train_ids[0]].shape[0]), n_scenes, train_ids, val_ids,
         " (the split by id %% 4 leaves one side empty: validating on the training objects, scenes of seed %d)" % (seed + 1000003)
@@ -65,6 +66,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--lights", action="store_true", help="light the rendered scenes (default: unlit)")
     ap.add_argument("--shadows", action="store_true", help="let the lights cast shadows (SPEC.md 13.13-13.15); needs --lights")
+    ap.add_argument("--rest", action="store_true", help="rest the objects on a table (SPEC.md 13.16-13.18; default: free poses)")
     ap.add_argument("--curve", default=None, help="also write the losses and validation numbers to this JSON file")
     a = ap.parse_args()
     if a.shadows and not a.lights:
@@ -81,7 +83,7 @@ def main():
         print("resumed %s at iteration %d" % (a.resume, trainer.iteration), flush=True)
     # a resumed run draws new scenes: the sets' seed moves on with the iteration it starts from
     train, val, line = build_sets(a.models, a.batch, a.scenes, a.objects, a.views, a.jitter, a.seed + trainer.iteration,
-                                   lights=a.lights, shadows=a.shadows)
+                                   lights=a.lights, shadows=a.shadows, rest=a.rest)
     print(line, flush=True)
     trainer.train_set, trainer.val_set = train, val if a.val_every > 0 else None
     curve = {"loss": [], "val": [], "first_iteration": trainer.iteration}

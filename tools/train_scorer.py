@@ -3,14 +3,15 @@ ScorerTrainer and prints the loss per step. --out saves {'state_dict': ...}, the
 loads (ckpt = torch.load(path); model.load_state_dict(ckpt['state_dict'])).
 
     python tools/train_scorer.py --steps 20 --hypotheses 64 --out ckpt.pt
-    python tools/train_scorer.py --models MODELS_DIR --scenes 8 --objects 4 --steps 200 --out ckpt.pt [--lights [--shadows]]
+    python tools/train_scorer.py --models MODELS_DIR --scenes 8 --objects 4 --steps 200 --out ckpt.pt [--lights [--shadows]] [--rest]
 
 With --models the frames are rendered scenes (scenes.render_scenes, SPEC.md 13) of the .ply models of MODELS_DIR,
 vertex-coloured or texture-mapped (millimetres, as BOP stores them), with the sampled depth corruption; every step takes the next (scene, object)
 frame whose object is at least --min_visib visible, scores synth.perturb_pose hypotheses around its pose_gt against the
 object's own model cloud (model_cloud.sample_model_cloud), with pp_err from scoring.pose_errors. --lights lights the
 scenes (scenes.sample_lights, SPEC.md 13.11-13.12), so that the true pose no longer has dS = dV = 0; --shadows (with
---lights) lets those lights cast shadows (scenes.Shadows, SPEC.md 13.13-13.15).
+--lights) lets those lights cast shadows (scenes.Shadows, SPEC.md 13.13-13.15). --rest rests the objects on a table
+(scenes.sample_layouts(placement="rest"), SPEC.md 13.16-13.18).
 
 The loss and the recipe are this build's own (zephyr's are in neither tree): unpinned.
 """
@@ -32,7 +33,7 @@ def scene_frames(a):
     atlas = scenes.MeshAtlas(meshes)
     rng = np.random.default_rng(a.seed)
     hw = (480, 640)
-    layout = scenes.sample_layouts(atlas, a.scenes, a.objects, synth.CAM_K, hw, rng)
+    layout = scenes.sample_layouts(atlas, a.scenes, a.objects, synth.CAM_K, hw, rng, placement="rest" if a.rest else "free")
     sensor = scenes.sample_sensor(a.scenes, hw, rng)
     lights = material = None
     if a.lights:                                             # a generator of its own: the layouts and the sensor do not move
@@ -62,6 +63,7 @@ def main():
     ap.add_argument("--min_visib", type=float, default=0.25)
     ap.add_argument("--lights", action="store_true", help="light the rendered scenes (with --models; default: unlit)")
     ap.add_argument("--shadows", action="store_true", help="let the lights cast shadows (with --models; needs --lights)")
+    ap.add_argument("--rest", action="store_true", help="rest the objects on a table (with --models; default: free poses)")
     a = ap.parse_args()
     if a.shadows and not a.lights:
         raise SystemExit("--shadows needs --lights: shadows are cast by lights")
