@@ -54,16 +54,20 @@ def _gpu_step(model, x, keep, dsc, debug=None):
 _CASES = {}
 
 
-def _case(name, hiplib):
+def _case(name, hiplib, shape=None, inputs=None, keep=None, p_drop=P_DROP):
     """Everything the tests of one shape share, computed once: the GPU step with its decisions, the float64 and float32
-    restatements with free decisions and with the GPU's imposed."""
+    restatements with free decisions and with the GPU's imposed. shape (B, M, npoint1, npoint2), default SHAPES[name];
+    inputs(B, M) -> point_x, default rt.make_inputs(B, M, 3); keep(B) -> the keep mask, default drawn with P_DROP; p_drop:
+    the head's dropout probability."""
     if name in _CASES:
         return _CASES[name]
-    B, M, np1, np2 = SHAPES[name]
+    B, M, np1, np2 = shape or SHAPES[name]
     g = torch.Generator().manual_seed(11)
     cpu = _model(np1, np2, 7)
-    x = rt.make_inputs(B, M, 3)
-    keep = (torch.rand(B, 256, generator=g) >= P_DROP).to(torch.uint8)
+    cpu.fc_layer[6].p = p_drop
+    x = inputs(B, M) if inputs else rt.make_inputs(B, M, 3)
+    drawn = (torch.rand(B, 256, generator=g) >= P_DROP).to(torch.uint8)
+    keep = keep(B) if keep else drawn
     dsc = torch.randn(B, 1, generator=g)
     c = {"x": x, "keep": keep, "dsc": dsc, "cpu": cpu, "state0": copy.deepcopy(cpu.state_dict())}
     gpu = copy.deepcopy(cpu).cuda().train()
@@ -75,17 +79,15 @@ def _case(name, hiplib):
     for tag, dtype in (("64", torch.float64), ("32", torch.float32)):
         p = rt.params_of(cpu, dtype)
         with torch.no_grad():
-            _, c["free" + tag] = rt.forward(p, x, idx, keep, P_DROP)
-        s, c["rec" + tag] = rt.forward(p, x, idx, keep, P_DROP, impose=imp)
+            _, c["free" + tag] = rt.forward(p, x, idx, keep, p_drop)
+        s, c["rec" + tag] = rt.forward(p, x, idx, keep, p_drop, impose=imp)
         c["s" + tag], c["g" + tag] = s.detach(), [t.detach() for t in rt.grads(p, s, dsc)]
     c["e_fwd"] = max(float((a.double() - b).abs().max()) for a, b in zip(c["free32"]["y"], c["free64"]["y"]))
     _CASES[name] = c
     return c
 
 
-@pytest.mark.parametrize("name", list(SHAPES))
-def test_decisions_and_scores(hiplib, name):
-    c = _case(name, hiplib)
+def _check_decisions_and_scores(c, name):
     for k in ("fps1", "ball1", "fps2", "ball2"):
         assert torch.equal(c["dbg"][k].cpu().long(), c["idx"][k]), k
     e = c["e_fwd"]
@@ -121,27 +123,43 @@ def test_decisions_and_scores(hiplib, name):
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
-def test_gradients_of_every_parameter(hiplib, name):
-    """12 weights, 11 gamma, 11 beta, the bias: max|err| / max|f64| <= 4 x the float32 restatement's, decisions imposed,
-    dropout on with a fixed mask. Measured on the MI355X: the largest ratio err / e32 over the 35 tensors is 3.21 (S1, beta8:
-    err 2.1e-5 against the restatement's 6.5e-6), then 2.17 (S1, beta2); every other tensor of S1 and all of S2 are under 2."""
-    c = _case(name, hiplib)
-    names = ["w%d" % i for i in range(12)] + ["gamma%d" % i for i in range(11)] + ["beta%d" % i for i in range(11)] + ["bias"]
-    fails = []
-    for n, got, g64, g32 in zip(names, c["grads"], c["g64"], c["g32"]):
+def test_decisions_and_scores(hiplib, name):
+    _check_decisions_and_scores(_case(name, hiplib), name)
+
+
+GRAD_NAMES = ["w%d" % i for i in range(12)] + ["gamma%d" % i for i in range(11)] + ["beta%d" % i for i in range(11)] + ["bias"]
+
+
+def _check_gradients(c, name, kind=""):
+    """max|err| / max|f64| <= 4 x the float32 restatement's for each of the 35 tensors (or those whose name starts with
+    `kind`); returns the largest ratio."""
+    fails, worst = [], (0.0, None)
+    for n, got, g64, g32 in zip(GRAD_NAMES, c["grads"], c["g64"], c["g32"]):
+        if not n.startswith(kind):
+            continue
         ref = float(g64.abs().max())
         e32 = float((g32.double() - g64).abs().max()) / ref
         err = float((got.double().reshape(g64.shape) - g64).abs().max()) / ref
         print("%s %-8s err %.3g  f32 restatement %.3g  ratio %.2f" % (name, n, err, e32, err / max(e32, 1e-30)))
+        if err / max(e32, 1e-30) >= worst[0]:
+            worst = (err / max(e32, 1e-30), n)
         if not err <= 4 * e32:
             fails.append((n, err, e32))
+    print("%s: the largest ratio is %.2f (%s)" % (name, worst[0], worst[1]))
     assert not fails, fails
+    return worst
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
-def test_bit_reproducible(hiplib, name):
-    c = _case(name, hiplib)
-    gpu = c["gpu"]
+def test_gradients_of_every_parameter(hiplib, name):
+    """12 weights, 11 gamma, 11 beta, the bias: max|err| / max|f64| <= 4 x the float32 restatement's, decisions imposed,
+    dropout on with a fixed mask. Measured on the MI355X: the largest ratio err / e32 over the 35 tensors is 3.21 (S1, beta8:
+    err 2.1e-5 against the restatement's 6.5e-6), then 2.17 (S1, beta2); every other tensor of S1 and all of S2 are under 2."""
+    _check_gradients(_case(name, hiplib), name)
+
+
+def _check_bit_reproducible(c):
+    gpu = c["gpu"].train()
     runs = []
     for _ in range(2):
         gpu.load_state_dict(c["state0"])
@@ -152,18 +170,26 @@ def test_bit_reproducible(hiplib, name):
     assert all(torch.equal(a, b) for a, b in zip(st0, st1)) and all(torch.equal(a, b) for a, b in zip(st0, c["stats1"]))
 
 
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_bit_reproducible(hiplib, name):
+    _check_bit_reproducible(_case(name, hiplib))
+
+
 # ---- stage kernels ----------------------------------------------------------------------------------------------------------
 def _dev(t):
     return t.contiguous().cuda()
 
 
-def _bounded(got, want64, ref32, what):
-    """max|got - f64| / max|f64| <= 4 x the same for a float32 torch computation of the same quantity."""
+def _bounded(got, want64, ref32, what, floor=0.0):
+    """max|got - f64| / max|f64| <= 4 x the same for a float32 torch computation of the same quantity (or `floor`, where
+    the caller gives one: at a reduction of one or two terms the float32 yardstick can be exactly right). Returns the ratio."""
     ref = float(want64.abs().max())
     e32 = float((ref32.double() - want64).abs().max()) / ref
     err = float((got.double().cpu() - want64).abs().max()) / ref
-    print("%s: err %.3g, f32 torch %.3g, ratio %.2f" % (what, err, e32, err / max(e32, 1e-30)))
-    assert err <= 4 * e32, what
+    ratio = err / max(e32, floor, 1e-30)
+    print("%s: err %.3g, f32 torch %.3g, ratio %.2f" % (what, err, e32, ratio))
+    assert err <= 4 * max(e32, floor), what
+    return ratio
 
 
 @pytest.mark.parametrize("R,K,C", [(20480, 8, 64), (10240, 136, 128), (160, 264, 256), (5, 1024, 512), (5, 256, 1)])
@@ -263,12 +289,10 @@ def test_batchnorm_statistics_do_not_cancel(hiplib):
 
 
 # ---- module level -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(SHAPES))
-def test_running_statistics_follow_torch(hiplib, name):
+def _check_running_statistics(c, name):
     """After one and two training forwards: running_mean / running_var / num_batches_tracked as torch's BatchNorm1d makes
     them in float64 on the float64 restatement's pre-activations (momentum 0.1, unbiased variance); within 4 x the error of
     the float32 restatement's statistics put through the same update (floor: 4 float32 roundings). Eval writes nothing."""
-    c = _case(name, hiplib)
     gpu = c["gpu"]
     gpu.load_state_dict(c["state0"])
     _, bns0 = c["cpu"].train_layers()
@@ -300,6 +324,11 @@ def test_running_statistics_follow_torch(hiplib, name):
     key = gpu._version_key(gpu.device)
     gpu({"point_x": c["x"].cuda()})
     assert gpu._version_key(gpu.device) == key and all(torch.equal(a, b) for a, b in zip(before, _stats(gpu)))
+
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_running_statistics_follow_torch(hiplib, name):
+    _check_running_statistics(_case(name, hiplib), name)
 
 
 def test_update_rule_above_is_torchs(hiplib):

@@ -10,6 +10,7 @@ import math
 import numpy as np
 import torch
 
+import pn2_train_cases
 from guarded import EINVAL, Contract
 
 SUFFIXES = ("_workspace_bytes", "_workspace_floats", "_partials", "_grid_bytes", "_pyramid_bytes")
@@ -1085,8 +1086,9 @@ def pn2t_build(lib, s):
 
 
 # ---- Z3t ossid_pn2_train_linear_wgrad ----------------------------------------------------------------------------------------------
-# shape (R, K, C) of tests/test_pn2_train_gpu.py::test_linear_kernels_alone: K the padded width, the weight has the real one
-PN2W_SHAPES = [(160, 264, 256), (5, 256, 1)]
+# shape (R, K, C) of tests/test_pn2_train_gpu.py::test_linear_kernels_alone: K the padded width, the weight has the real one;
+# then two row counts of tests/pn2_train_cases.py: a second split of one row, and a chunk grown past 512 with a ragged tail
+PN2W_SHAPES = [(160, 264, 256), (5, 256, 1), (513, 8, 64), (131073, 8, 64)]
 
 
 def _kr(K):
@@ -1100,8 +1102,12 @@ def pn2w_need(lib, s):
 
 def pn2w_pred(lib, s):
     R, K, C = s
-    assert (s == PN2W_SHAPES[0] and _kr(K) != K and R % 64) or (s == PN2W_SHAPES[1] and C == 1 and R < 8)
-    assert pn2w_need(lib, s)["ossid_pn2_train_wgrad_workspace_bytes"] > 0
+    chunk, splits, tail = pn2_train_cases.wgrad_split(R)
+    assert (s == PN2W_SHAPES[0] and _kr(K) != K and R % 64) or (s == PN2W_SHAPES[1] and C == 1 and R < 8) or \
+        (s == PN2W_SHAPES[2] and (chunk, splits, tail) == (512, 2, 1)) or \
+        (s == PN2W_SHAPES[3] and chunk > 512 and splits > 2 and tail % 16 != 0)
+    need = pn2w_need(lib, s)["ossid_pn2_train_wgrad_workspace_bytes"]
+    assert need == (splits * C * _kr(K) * 4 if splits > 1 else 0) + 256
 
 
 def pn2w_build(lib, s):
@@ -1652,6 +1658,6 @@ POSE_CASES = [
 #   conv1x1_c1_bwd 144+ / 5160+   focal_smoothl1_loss 72+   wino 524288, pair 1048576   topk 28744+ / 29256+ / 36936+
 #   nms 264+ / 1296+ / 139656+   detect_post 29192+ / 30736+ / 176776+   chan_op 192+ / 2304+   dense_fwd1_stats rows 7680,
 #   counts 20+   dense_dgrad1_acc 5376+   dense_dgrad3_mask 12288   dw_add_stats 4224+   stem_pool_bwd 1152+
-#   pn2_score 4171520+ / 10844928+   pn2_train 50977792 / 39291136+   pn2_train_linear_wgrad 256+ / 256+
+#   pn2_score 4171520+ / 10844928+   pn2_train 50977792 / 39291136+   pn2_train_linear_wgrad 256+ / 256+ / 4352+ / 510208+
 #   ppf_refine grid 1025312+, workspace 2576+   raster 7776+ / 384+, colour 61536+ / 54144+   scene 62240+
 #   cloud_weights 8208+ / 10760+   det_match 13544+ / 61696+   feat pyramid 217380+ / 21880+, detect 16958+ / 1688+, match 320+
