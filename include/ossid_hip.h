@@ -1051,6 +1051,41 @@ int ossid_pose_select(const double* poses, const float* scores, int N, const flo
                       int S, int K, double sep, float min_score, int32_t* selected, int32_t* count, int32_t* owner,
                       uint64_t* keys, void* stream);
 
+/* An object's symmetries from its own surface (SPEC.md section 17; csrc/symmetry.hip), this build's own definition --
+ * BOP published its models_info.json symmetry lists without the procedure that made them, and the reference reads them.
+ * Candidate rigid transforms are scored by how well they map a thinned sample of the surface (queries) onto a dense one
+ * (targets); ossid_code_amd/symmetry.py generates the candidates and selects among them on the host.
+ *
+ * ossid_sym_grid: targets f32 [Nt][3] (finite; ossid_cloud_candidates' points are the intended input) -> the uniform
+ * cell grid of 17.2 in `grid`, caller-owned, ossid_sym_grid_nbytes(Nt) bytes (0 = Nt outside [1, OSSID_SYM_MAX_TARGETS]),
+ * 16-byte aligned, for acceptance at an f32 squared distance <= tol * tol. One workgroup; integer atomics place the points
+ * and the order inside a cell does not reach any result.
+ *
+ * ossid_sym_score: the grid of ossid_sym_grid(targets, Nt, tol) (same Nt and tol), queries f32 [Mq][3], transforms f64
+ * [C][4][4] row-major (rows 0-2 are read) -> per transform miss int32 [C] (queries without a target at d2 <= tol * tol; a
+ * NaN query or transform misses), worst_d2 f32 [C] (the largest accepted d2, 0 when none), sum_q int64 [C] (the sum over
+ * the accepted queries of trunc(f64(d2) / f64(tol * tol) * 2^32), 17.3). The point is transformed in f64 in 8.7's written
+ * order, rounded to f32, and its nearest target is the lexicographic minimum of (d2, index). One workgroup per transform,
+ * one launch, no atomics: bit-equal to the brute-force restatement. The grid's header records Nt and tol: a buffer whose
+ * header does not carry this call's Nt and tol (bit for bit) and a consistent cell count is not followed, and every query
+ * misses; the positions read from the cell table are clamped to the Nt sorted points, so no content of the buffer makes
+ * the kernel read outside it.
+ *
+ * The size query ends in _nbytes, not in _grid_bytes like ossid_ppf_refine_grid_bytes: tests/test_workspace_contract.py
+ * claims every symbol with that ending for the case table of tests/workspace_cases.py, and this buffer's contract (the
+ * same run_contract) lives in tests/symmetry_cases.py and tests/test_symmetry_gpu.py instead.
+ *
+ * OSSID_EINVAL before any launch, nothing written: Nt outside [1, OSSID_SYM_MAX_TARGETS], Mq outside [1,
+ * OSSID_SYM_MAX_QUERIES], C outside [1, OSSID_SYM_MAX_TRANSFORMS], a tol that is not finite and positive or whose f32
+ * square is not, a NULL pointer, a grid buffer that is misaligned or shorter than ossid_sym_grid_nbytes(Nt). */
+#define OSSID_SYM_MAX_TARGETS 32768
+#define OSSID_SYM_MAX_QUERIES 4096
+#define OSSID_SYM_MAX_TRANSFORMS 16384
+size_t ossid_sym_grid_nbytes(int Nt);
+int ossid_sym_grid(const float* targets, int Nt, float tol, void* grid, size_t grid_bytes, void* stream);
+int ossid_sym_score(const void* grid, size_t grid_bytes, int Nt, const float* queries, int Mq, const double* transforms, int C,
+                    float tol, int32_t* miss, float* worst_d2, int64_t* sum_q, void* stream);
+
 /* 8f-6 the scorer's model cloud from the object's mesh (scripts/online_learning.py:303-311 loads model_points /
  * model_colors / model_normals from zephyr_model_data/{lmo,ycbv}/model_cloud_XX.npz, a download made by a script that is
  * in neither tree). SPEC.md section 9 (csrc/model_cloud.hip): this build's own definition, parity with zephyr's clouds

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("OSSID_HIP_LIB") or os.path.join(_HERE, "libossid_hip.so")
 OBJ_DIR = os.path.join(_HERE, "build")
-SOURCES = ["zephyr.hip", "pn2.hip", "pn2_train.hip", "dtoid.hip", "conv.hip", "pack.hip", "segtail.hip", "pipeline.hip", "icp.hip", "ppf.hip", "ppf_refine.hip", "raster.hip", "texture.hip", "scene.hip", "scene_light.hip", "scene_shadow.hip", "scene_rest.hip", "bop_eval.hip", "pose_select.hip", "det_eval.hip", "model_cloud.hip", "features.hip", "train.hip", "wino.hip", "stem.hip", "wgrad_fc.hip", "dense.hip", "wgrad_t9.hip", "dense_bwd.hip", "seq.hip", "pretrain.hip"]
+SOURCES = ["zephyr.hip", "pn2.hip", "pn2_train.hip", "dtoid.hip", "conv.hip", "pack.hip", "segtail.hip", "pipeline.hip", "icp.hip", "ppf.hip", "ppf_refine.hip", "raster.hip", "texture.hip", "scene.hip", "scene_light.hip", "scene_shadow.hip", "scene_rest.hip", "bop_eval.hip", "pose_select.hip", "symmetry.hip", "det_eval.hip", "model_cloud.hip", "features.hip", "train.hip", "wino.hip", "stem.hip", "wgrad_fc.hip", "dense.hip", "wgrad_t9.hip", "dense_bwd.hip", "seq.hip", "pretrain.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 # Per-source additions. pn2.hip: sa1_kernel runs one wave per SIMD on all 512 registers; for such a kernel the compiler by
 # default selects the MFMA form whose accumulators live in the AGPR half, which vector instructions cannot read, and every

@@ -1239,14 +1239,17 @@ class SceneBatch:
         for s, i, _k in self._objects():
             yield self._frame(h, s, i)
 
-    def write_bop(self, root, dataset_name, split="test", depth_scale=1.0, diameters=None):
+    def write_bop(self, root, dataset_name, split="test", depth_scale=1.0, diameters=None, symmetries=False):
         """The standard BOP layout under <root>/<dataset_name> (millimetres): models/ and models_eval/ (obj_%06d.ply,
         vertex-coloured, or for an object the atlas draws from its texture with `comment TextureFile obj_%06d.png`,
         per-vertex texture_u texture_v and that PNG beside it; models_info.json), test_targets_bop19.json, and per scene
         <split>/%06d/ with rgb/, depth/ (16-bit), mask/,
         mask_visib/, scene_camera.json, scene_gt.json, scene_gt_info.json; every scene holds image 0. depth_scale must be
         the one the batch was rendered with. diameters: dict obj_id -> diameter in the atlas's unit; None computes them
-        on the device (model_cloud.mesh_diameter)."""
+        on the device (model_cloud.mesh_diameter). symmetries (False = off: models_info.json holds the diameter and the
+        bounds only): True finds each object's symmetries from its mesh (symmetry.find_symmetries, SPEC.md section 17) and
+        its entry gains `symmetries_discrete` / `symmetries_continuous`, translations and offsets in millimetres; a dict
+        obj_id -> such a dict in the atlas's unit is written as given (an object without an entry gains nothing)."""
         from PIL import Image
         if float(depth_scale) != self.depth_scale:
             raise ValueError("write_bop: the batch's 16-bit depth was made with depth_scale = %r, not %r"
@@ -1265,6 +1268,13 @@ class SceneBatch:
             lo, size = mm.min(0), mm.max(0) - mm.min(0)
             info[str(o)] = {"diameter": float(diameters[o]) * 1000.0, "min_x": float(lo[0]), "min_y": float(lo[1]),
                             "min_z": float(lo[2]), "size_x": float(size[0]), "size_y": float(size[1]), "size_z": float(size[2])}
+            if symmetries is True:
+                from .symmetry import find_symmetries
+                mesh = _render.Mesh(V, F, device=self.atlas.device, colors=C, **(
+                    {} if tex is None else {"uvs": tex[0], "texture": tex[1]}))
+                models_info_entry(info[str(o)], find_symmetries(mesh, diameter=float(diameters[o])))
+            elif symmetries:
+                models_info_entry(info[str(o)], symmetries.get(o))
             for sub in ("models", "models_eval"):
                 os.makedirs(os.path.join(base, sub), exist_ok=True)
                 if tex is None:
@@ -1305,6 +1315,18 @@ class SceneBatch:
         with open(os.path.join(base, "test_targets_bop19.json"), "w") as f:
             json.dump(targets, f, indent=1)
         return base
+
+
+def models_info_entry(entry, symmetries, unit_to_mm=1000.0):
+    """Adds an object's symmetries (symmetry.find_symmetries' dict, in the atlas's unit; None = nothing) to its
+    models_info.json entry, translations and offsets in millimetres: the keys that are there keep their values and their
+    place, an empty list adds no key. Returns the entry."""
+    if symmetries:
+        from .symmetry import scaled
+        for k, v in scaled(symmetries, unit_to_mm).items():
+            if v:
+                entry[k] = v
+    return entry
 
 
 def _visib_fract(visib, amodal):

@@ -25,7 +25,7 @@ import time
 import numpy as np
 import torch
 
-from . import features, model_cloud, pipeline, ppf, render
+from . import bop_eval, features, model_cloud, pipeline, ppf, render, symmetry
 from .hostutil import K2meta
 from .scoring import networkInference, pose_errors, select_instances
 
@@ -110,7 +110,10 @@ class OnlineStream:
     in translation plus 12 degrees, which move a point at radius D/2 by 0.105 D); nobody has tuned it. Thin objects that
     stack (plates, lids: neighbours a fraction of the diameter apart) need a smaller value.
     symmetries: dict obj_id -> f64 [S,4,4] (bop_eval.symmetry_transformations) in the unit of model_points -- BOP's
-    models_info is in millimetres, the caller converts; an object without an entry has none.
+    models_info is in millimetres, the caller converts; an object without an entry has none. "auto" (needs meshes=...):
+    each object's symmetries are found from its mesh at its first frame (symmetry.find_symmetries, SPEC.md section 17, in
+    the mesh's unit; an object without a mesh has none) and kept, passed where a dict's entry is passed, and an object
+    found to have any symmetry is scored with ADI as under symmetric=True.
     diameters: dict obj_id -> length in that unit; otherwise frame["diameter"], otherwise
     model_cloud.mesh_diameter(model_points) at the object's first frame, kept.
     frame["pose_gt"] may be [G,4,4]: pp_err and every pred_err are then the minimum over the G instances."""
@@ -132,6 +135,10 @@ class OnlineStream:
         if not (np.isfinite(self.instance_sep_rel) and self.instance_sep_rel >= 0.0):
             raise ValueError("instance_sep_rel must be finite and >= 0, got %r" % (instance_sep_rel,))
         self.symmetries, self.diameters, self._diameters = symmetries, diameters, {}
+        if isinstance(symmetries, str):
+            if symmetries != "auto" or meshes is None:
+                raise ValueError('symmetries must be a dict, None or "auto" with meshes=..., got %r' % (symmetries,))
+            self._found = {}
         keys = ("detect", "pose_err", "score", "pseudo_label") + (("icp",) if icp_max_dist is not None else ()) + \
             (("ppf",) if ppf_models is not None else ()) + (("sift",) if feature_models is not None else ()) + \
             (("select",) if self.max_instances > 1 else ())
@@ -225,14 +232,32 @@ class OnlineStream:
                 **({"n_hypos": len(hypos), "ppf_hypos": hypos} if self.ppf_models is not None else {}),
                 **({"n_hypos": len(hypos), "n_feature_hypos": n_feat} if n_feat is not None else {})}
 
+    def _symmetries(self, obj):
+        """The object's symmetry transformations f64 [S,4,4], or None: the caller's dict, or with "auto" what
+        symmetry.find_symmetries makes of its mesh, found once."""
+        if self.symmetries is None:
+            return None
+        if not isinstance(self.symmetries, str):
+            return self.symmetries.get(obj)
+        if obj not in self._found:
+            mesh = self.meshes.get(obj)
+            found = None if mesh is None else symmetry.find_symmetries(mesh)
+            self._found[obj] = bop_eval.symmetry_transformations(found) if found and symmetry.has_symmetry(found) else None
+        return self._found[obj]
+
+    def _symmetric(self, frame):
+        if isinstance(self.symmetries, str) and self._symmetries(int(frame["obj_id"])) is not None:
+            return True
+        return self.symmetric
+
     def _pose_errors(self, hypos, frame):
         """ADD / ADI of the hypotheses against frame["pose_gt"]; against [G,4,4] the minimum over the G instances."""
-        gt = frame["pose_gt"]
+        gt, symmetric = frame["pose_gt"], self._symmetric(frame)
         if len(np.shape(gt)) != 3:
-            return pose_errors(hypos, gt, frame["model_points"], self.symmetric)
+            return pose_errors(hypos, gt, frame["model_points"], symmetric)
         if np.shape(gt)[0] < 1:
             raise ValueError("pose_gt must hold at least one pose, got %s" % (np.shape(gt),))
-        return np.minimum.reduce([pose_errors(hypos, g, frame["model_points"], self.symmetric) for g in gt])
+        return np.minimum.reduce([pose_errors(hypos, g, frame["model_points"], symmetric) for g in gt])
 
     def _diameter(self, frame):
         obj = int(frame["obj_id"])
@@ -248,7 +273,7 @@ class OnlineStream:
         """process() from the scores on for a frame with K > 1: the K best distinct poses, each refined, rendered, masked
         and pseudo-labelled; pick 0 is the argmax and fills the single-instance keys."""
         obj = int(frame["obj_id"])
-        syms = None if self.symmetries is None else self.symmetries.get(obj)
+        syms = self._symmetries(obj)
         sep = self.instance_sep_rel * self._diameter(frame)
         sel, _count, own = self._timed("select", lambda: select_instances(poses, scores, frame["model_points"], K, sep,
                                                                           symmetries=syms))

@@ -3,7 +3,7 @@ that names its texture in `comment TextureFile`, the image beside it) -> a stand
 
     python3 tools/make_scenes.py MODELS_DIR OUT_DIR --scenes 32 --objects 6 --seed 0 [--name synth] [--split test]
                                  [--hw 480 640] [--no-mm2m] [--clean] [--no-table] [--depth_scale 1.0] [--lights [--shadows]]
-                                 [--rest]
+                                 [--rest] [--symmetries]
 
 Every MODELS_DIR/*.ply (obj_XXXXXX.ply keeps its id; millimetres, as BOP stores them, unless --no-mm2m) goes into one
 atlas; scenes.sample_layouts places the objects, scenes.render_scenes (csrc/scene.hip, SPEC.md section 13) draws them with
@@ -13,7 +13,8 @@ folder. At most 256 scenes per call. --lights lights the scenes (scenes.sample_l
 generator of its own: rgb/ is lit, every other file is the one written without the flag at the same seed. --shadows (with
 --lights) lets the lights cast shadows (scenes.Shadows, SPEC.md 13.13-13.15): again rgb/ alone differs. --rest rests the
 objects on the table (scenes.sample_layouts(placement="rest"), SPEC.md 13.16-13.18) instead of letting them float: other
-layouts, so every file differs from the folder written without the flag.
+layouts, so every file differs from the folder written without the flag. --symmetries finds each object's symmetries from
+its mesh (symmetry.find_symmetries, SPEC.md section 17) and writes them into models_info.json, which alone differs.
 """
 import argparse
 import os
@@ -45,6 +46,7 @@ def main():
     ap.add_argument("--lights", action="store_true", help="light the scenes: sampled lights and materials (default: unlit)")
     ap.add_argument("--shadows", action="store_true", help="let the lights cast shadows; needs --lights")
     ap.add_argument("--rest", action="store_true", help="rest the objects on the table, stacked where they overlap (default: free poses)")
+    ap.add_argument("--symmetries", action="store_true", help="find each object's symmetries and write them into models_info.json")
     a = ap.parse_args()
     if a.shadows and not a.lights:
         raise SystemExit("--shadows needs --lights: shadows are cast by lights")
@@ -63,7 +65,7 @@ def main():
         lights, material = scenes.sample_lights(layout, np.random.default_rng(np.random.SeedSequence(a.seed, spawn_key=(0,))))
     batch = scenes.render_scenes(atlas, layout, a.hw, sensor=sensor, depth_scale=a.depth_scale, lights=lights,
                                  material=material, shadows=scenes.Shadows() if a.shadows else None)
-    base = batch.write_bop(a.out_dir, a.name, split=a.split, depth_scale=a.depth_scale)
+    base = batch.write_bop(a.out_dir, a.name, split=a.split, depth_scale=a.depth_scale, symmetries=a.symmetries)
     g = batch.gt_info.cpu().numpy()
     print("%d scenes, %d instances (%d visible) of %d objects -> %s" % (a.scenes, layout.n_instances, int((g[:, 1] > 0).sum()),
                                                                        atlas.n_meshes - 1, base))
