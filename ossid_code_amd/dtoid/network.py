@@ -840,33 +840,18 @@ class Network(nn.Module):
         for t in outputs:
             t.record_stream(main)
 
-    def _forward_train_hip(self, image, g, local, lazy_g=None, lazy_local=None):
-        """Training-mode forward of everything behind the two template encoders on csrc/conv.hip + csrc/train.hip,
-        channels-last end to end (same arithmetic as the module path below; BatchNorm batch statistics folded into the
-        next convolution's input staging). Returns (classifications, regression, anchors, heat_map, segmentation)."""
+    def _backbone_train_hip(self, image, g, lazy_g=None, lazy_local=None, pack_events=(None, None)):
+        """The image backbone's share of _forward_train_hip: stem convolution, template modulation + norm0 + pool0, the four
+        dense blocks with their transitions, norm5 - c1 - ELU - n1. Returns (feat [B,640,h,w], local, join_local): the local
+        template features and the side stream they were computed on when `lazy_local` was given (the caller joins it), else
+        (feat, None, None). pack_events: the events of the step's first two weight-packing launches (the global template
+        encoder's part, the backbone's and encoders' part) when they run on a side stream; without a packing plan every
+        layer packs its own weights."""
         from . import train_ops as T
         from .backbones import DenseBlock, Transition
         ife = self.image_feature_extractor
-        # every conv weight -> MFMA layouts, one launch (0.64 ms: 136 MB read, 272 MB written). Nothing needs it before the
-        # first dense block and the template encoders, so with side streams on it runs on the weight-gradient stream (idle
-        # at the start of a step: the previous step's weight gradients were joined before its optimizer ran) beside the stem
-        # In two launches: the backbone's and the encoders' weights (7 of the 34 M) first, with an event of their own -- the stem
-        # on this repo's kernels takes 0.5 ms, not the 1.5 ms that used to cover the whole packing -- then the head's.
-        # (round 4: three launches -- the GLOBAL template encoder's weights first, in a launch of a few microseconds: that encoder
-        # is the head of the step's critical path (stem modulation needs its output) and used to wait ~1 ms for the whole
-        # first part; tools/step_gaps.py)
-        pack_event = pack_event_all = pack_event_g = None
-        if self._branches_on(image.device):
-            main = torch.cuda.current_stream(image.device)
-            ps = T.side_streams(image.device)["wgrad"]
-            ps.wait_stream(main)                                 # behind the optimizer step that wrote the weights
-            with torch.cuda.stream(ps):
-                evs = self._train_pack_plan().run(want_events=True)
-            pack_event_all = evs[-1]
-            pack_event = evs[-2] if len(evs) >= 2 else pack_event_all
-            pack_event_g = evs[0] if len(evs) >= 3 else pack_event
-        else:
-            self._train_pack_plan().run()
+        pack_event_g, pack_event = pack_events
+        local = None
         self.__dict__["_pack_event"] = pack_event_g              # what a fork waits for: the global encoder only its own part
         seq = list(ife.backdense_1) + list(ife.backdense_2)      # norm0 relu0 pool0 block1 | trans1 block2 ... norm5
         if self.use_hip_stem_training:
@@ -913,20 +898,57 @@ class Network(nn.Module):
         u, sums = T.bn_relu_conv(x, norm5, ife.c1, relu=False, act_elu=True, want_stats=True)
         s, t = T.bn_fold(sums, n_px, ife.n1)
         feat = T.AffineAct.apply(u, s, t, False)                             # n1(elu(c1(norm5(.)))), [B,640,29,39]: one pass
+        return feat, local, join_local
+
+    def _forward_train_hip(self, image, g, local, lazy_g=None, lazy_local=None):
+        """Training-mode forward of everything behind the two template encoders on csrc/conv.hip + csrc/train.hip,
+        channels-last end to end (same arithmetic as the module path below; BatchNorm batch statistics folded into the
+        next convolution's input staging). Returns (classifications, regression, anchors, heat_map, segmentation)."""
+        from . import train_ops as T
+        ife = self.image_feature_extractor
+        # every conv weight -> MFMA layouts, one launch (0.64 ms: 136 MB read, 272 MB written). Nothing needs it before the
+        # first dense block and the template encoders, so with side streams on it runs on the weight-gradient stream (idle
+        # at the start of a step: the previous step's weight gradients were joined before its optimizer ran) beside the stem
+        # In two launches: the backbone's and the encoders' weights (7 of the 34 M) first, with an event of their own -- the stem
+        # on this repo's kernels takes 0.5 ms, not the 1.5 ms that used to cover the whole packing -- then the head's.
+        # (round 4: three launches -- the GLOBAL template encoder's weights first, in a launch of a few microseconds: that encoder
+        # is the head of the step's critical path (stem modulation needs its output) and used to wait ~1 ms for the whole
+        # first part; tools/step_gaps.py)
+        pack_event = pack_event_all = pack_event_g = None
+        if self._branches_on(image.device):
+            main = torch.cuda.current_stream(image.device)
+            ps = T.side_streams(image.device)["wgrad"]
+            ps.wait_stream(main)                                 # behind the optimizer step that wrote the weights
+            with torch.cuda.stream(ps):
+                evs = self._train_pack_plan().run(want_events=True)
+            pack_event_all = evs[-1]
+            pack_event = evs[-2] if len(evs) >= 2 else pack_event_all
+            pack_event_g = evs[0] if len(evs) >= 3 else pack_event
+        else:
+            self._train_pack_plan().run()
+        feat, lazy, join_local = self._backbone_train_hip(image, g, lazy_g, lazy_local, pack_events=(pack_event_g, pack_event))
+        if lazy is not None:
+            local = lazy
         if join_local is not None:
             self._join(join_local, [local])
         if pack_event_all is not None:                           # the head's weights: packed long since
             torch.cuda.current_stream(image.device).wait_event(pack_event_all)
             self.__dict__["_pack_event"] = pack_event_all
         out = self._head_train_hip(feat, local)
-        # the folded BatchNorms update running_mean / running_var in their kernel; the counters in one launch
+        self._bump_folded_bn_counters()
+        return out
+
+    def _bump_folded_bn_counters(self):
+        """num_batches_tracked += 1 for the image backbone's BatchNorms, in one launch: the folded BatchNorms update
+        running_mean / running_var in their kernel, but not the counter."""
         ts = self.__dict__.get("_folded_bn_counters")
         if ts is None:
+            ife = self.image_feature_extractor
+            seq = list(ife.backdense_1) + list(ife.backdense_2)
             folded = seq[3:] + [ife.n1] + ([seq[0]] if self.use_hip_stem_training else [])
             ts = [b.num_batches_tracked for m in folded for b in m.modules() if isinstance(b, nn.BatchNorm2d)]
             self.__dict__["_folded_bn_counters"] = ts
         torch._foreach_add_(ts, 1)
-        return out
 
     def _train_pack_convs(self):
         """(convolutions in packing order, end of the first launch's part, end of the second's): the module structure is fixed,
