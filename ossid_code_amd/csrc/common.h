@@ -85,6 +85,25 @@ static inline int ossid_ensure_dyn_lds(const void* fn, size_t bytes, OssidLdsAtt
         if (rc_ != OSSID_OK) return rc_;                                          \
     } while (0)
 
+// Persistent grids: as many workgroups of 256 as are resident at once -- workgroups per CU x CUs, asked of the runtime once
+// per kernel and kept in *cache (0 = not asked yet) -- each looping over its share of the tiles. dyn_lds: the kernel's dynamic
+// LDS bytes (0: none, and no attribute call); cap_per_cu: at most so many workgroups per CU (0: no cap); fallback: the answer
+// while the runtime cannot be asked (nothing is cached then). Workspace sizes follow from these grids.
+template <typename K>
+int persistent_grid(K kern, int dyn_lds, int cap_per_cu, int fallback, int* cache) {
+    if (!*cache) {
+        int dev = 0, per_cu = 0;
+        hipDeviceProp_t p;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
+            (dyn_lds && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, dyn_lds) != hipSuccess) ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, dyn_lds) != hipSuccess || per_cu <= 0)
+            return fallback;
+        if (cap_per_cu && per_cu > cap_per_cu) per_cu = cap_per_cu;
+        *cache = per_cu * p.multiProcessorCount;
+    }
+    return *cache;
+}
+
 // the direct convolutions' default arithmetic: 1 = split-bf16 operands, 0 = the exact-f32 instruction (formats: csrc/pack.hip)
 #ifdef OSSID_CONV_F32
 #define OSSID_CONV_SB 0

@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "mfma.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -186,9 +187,8 @@ __device__ __forceinline__ void conv_nhwc_body(const ConvArgs& A) {
             const int yy = y_first - 1 + pr, xx = x_first - 1 + pc;
             const bool ok = pos < npos && yy >= 0 && yy < H && xx >= 0 && xx < W;
             // fused nearest-neighbour upsample (F.interpolate(mode="nearest") in front of the conv): the conv reads
-            // its [H][W] input straight from the [Hs][Ws] source, index = min(floor(dst * in/out), in-1)
-            const int sy = (A.Hs == H) ? yy : min((int)floorf((float)yy * A.scale_h), A.Hs - 1);
-            const int sx = (A.Ws == W) ? xx : min((int)floorf((float)xx * A.scale_w), A.Ws - 1);
+            // its [H][W] input straight from the [Hs][Ws] source, by the index map the weight gradients share (wgrad_common.h)
+            const int sy = nearest_src(yy, A.Hs, H, A.scale_h), sx = nearest_src(xx, A.Ws, W, A.scale_w);
             goff[e] = ok ? ((sy * A.Ws + sx) * A.in_cs + 4 * j) : -1;
         }
         // LDS slot of the staged quad. f32: float4 j of the position. Split form: per position and 16-channel unit 64
@@ -269,10 +269,7 @@ __device__ __forceinline__ void conv_nhwc_body(const ConvArgs& A) {
 #pragma unroll
             for (int e = 0; e < NLD; ++e) {
                 if (goff[e] < 0) continue;
-                float4 v = st[e];
-                v.x = v.x * ps.x + pt.x, v.y = v.y * ps.y + pt.y, v.z = v.z * ps.z + pt.z, v.w = v.w * ps.w + pt.w;
-                if (A.pre_relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                st[e] = v;
+                st[e] = prologue4(st[e], ps, pt, true, A.pre_relu != 0);      // (shared with the weight gradients: wgrad_common.h)
             }
         }
         if constexpr (SB) {

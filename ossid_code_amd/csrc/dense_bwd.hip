@@ -356,18 +356,7 @@ __global__ __launch_bounds__(256) void bn_fold_fwd_rows_kernel(const float* __re
 }
 
 int g_df_grid = 0;
-int df_grid() {
-    if (!g_df_grid) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dense_fwd1_stats_kernel<2>, 256, 0) != hipSuccess || per_cu <= 0)
-            return 512;
-        if (per_cu > 2) per_cu = 2;
-        g_df_grid = per_cu * p.multiProcessorCount;
-    }
-    return g_df_grid;
-}
+int df_grid() { return persistent_grid(dense_fwd1_stats_kernel<2>, 0, 2, 512, &g_df_grid); }      // persistent (common.h), at most two workgroups per CU
 // pixels per stage for n_rows: 64, or 32 where 64-pixel stages would leave the chip under ~1.5 workgroups per CU
 int df_pxs(long long n_rows) { return (n_rows + 63) / 64 >= 384 ? 64 : 32; }
 
@@ -494,32 +483,10 @@ __global__ __launch_bounds__(256, 2) void dense_dgrad3_mask_kernel(const DenseBw
 }
 
 int g_d3_grid = 0;
-int d3_grid() {
-    if (!g_d3_grid) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dense_dgrad3_mask_kernel, 256, 0) != hipSuccess || per_cu <= 0)
-            return 512;
-        if (per_cu > 2) per_cu = 2;
-        g_d3_grid = per_cu * p.multiProcessorCount;
-    }
-    return g_d3_grid;
-}
+int d3_grid() { return persistent_grid(dense_dgrad3_mask_kernel, 0, 2, 512, &g_d3_grid); }      // persistent (common.h), at most two workgroups per CU
 
 int g_db_grid = 0;
-int db_grid() {
-    if (!g_db_grid) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dense_dgrad1_acc_kernel, 256, 0) != hipSuccess || per_cu <= 0)
-            return 512;
-        if (per_cu > 2) per_cu = 2;
-        g_db_grid = per_cu * p.multiProcessorCount;
-    }
-    return g_db_grid;
-}
+int db_grid() { return persistent_grid(dense_dgrad1_acc_kernel, 0, 2, 512, &g_db_grid); }      // persistent (common.h), at most two workgroups per CU
 
 }  // namespace
 

@@ -16,6 +16,7 @@
 #include <float.h>
 #include <math.h>
 
+#include "mfma.h"
 #include "workgroup.h"
 
 namespace {
@@ -517,11 +518,11 @@ __global__ __launch_bounds__(256) void feat_match_kernel(const uint8_t* __restri
                 const v4i a = *(const v4i*)(rows + (t * 32 + col) * MT_STRIDE + kk * 32 + half * 16);
                 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[kk], acc, 0, 0, 0);
             }
-            // C / D: column = lane & 31 (scene), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (model): ascending in r, so a
+            // C / D: column = lane & 31 (scene), row = acc_row(r, lane >> 5) (model; csrc/mfma.h): ascending in r, so a
             // strict < keeps the lowest j among equal d2 within the lane
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int row = t * 32 + acc_row(r, half);
                 const int d2 = (norms[row] + nb) - 2 * acc[r];
                 if (d2 < best_d2) best_d2 = d2, best_j = m0 + row;
             }

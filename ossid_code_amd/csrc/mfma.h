@@ -1,5 +1,6 @@
-// Matrix-core primitives shared by the convolution kernels (gfx950): operand vector types, the f32 and split-bf16 MFMA
-// steps, and the split of f32 values into bf16 pieces.
+// Matrix-core primitives shared by the convolution and weight-gradient kernels (gfx950): operand vector types, the f32 and
+// split-bf16 MFMA steps, the row map of a 32x32 accumulator, the split of f32 values into bf16 pieces and, for kernels that
+// keep their operands in LDS as [pixel][channel] bf16 images, the store into such images and the transposed operand read.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,8 @@ typedef short v4i16 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v16f mfma(float a, float b, v16f c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
+// row of register r (0..15) of a 32x32 accumulator in the lanes of wave half `half` (lane >> 5); the column is lane & 31
+__device__ __forceinline__ constexpr int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // Split-bf16 arithmetic (csrc/conv.hip: kernel template argument FORM = 1; chosen per launch, see ossid_conv_desc::exact): every f32 operand is a pair
 // of bf16 values, x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16 significant bits together), and a 16-channel slice
@@ -63,4 +66,31 @@ __device__ __forceinline__ void split_bf16(const float (&v)[4], uint2 (&pc)[N]) 
     }
 #pragma unroll
     for (int k = 0; k < N; ++k) pc[k] = q[k].u;
+}
+
+// ---- split-bf16 operands kept in LDS as [pixel][channel] bf16 images, one image per part (hi, lo), `part_stride` bytes apart
+// a thread's four channels of one pixel -> the hi quad at hi_at, the lo quad one part further
+__device__ __forceinline__ void split_store(const float4& f, char* hi_at, int part_stride) {
+    uint2 pc[2];
+    split_bf16({f.x, f.y, f.z, f.w}, pc);
+    *(uint2*)hi_at = pc[0];
+    *(uint2*)(hi_at + part_stride) = pc[1];
+}
+// The matrix cores want the REDUCTION index (pixels) contiguous per lane, the images have the channels contiguous:
+// ds_read_b64_tr_b16 (cdna_hip_programming.md T10) reads a block of 4 pixels x 16 channels and hands lane i the 4 pixels of
+// channel i. Within its group of 16 lanes, lane 4q+p supplies the address of block row q (a pixel), channels 4p..4p+3 of the
+// block's 16; groups 0 / 1 take channels 0-15 / 16-31 of a 32-channel tile, the wave's halves the pixels 8h..8h+7 of a 16-pixel
+// k-step. tr_lane_offset: this lane's byte offset into an image of `pitch` bytes per pixel whose 32-channel tile starts at
+// channel `ch0`; a tap's column shift or a later k-step is just more pixels added to it.
+__device__ __forceinline__ size_t tr_lane_offset(int lane, int pitch, int ch0) {
+    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = (lane >> 4) & 1, h = lane >> 5;
+    return (size_t)(8 * h + tq) * pitch + (ch0 + 16 * tg + 4 * tp) * 2;
+}
+// two blocks of 4 pixels joined: the 8-pixel operand of v_mfma_f32_32x32x16_bf16
+__device__ __forceinline__ v8bf tr8(const char* at, int pitch) {
+    const v4i16 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)at);
+    const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(at + 4 * pitch));
+    typedef short v8i16 __attribute__((ext_vector_type(8)));
+    const v8i16 v = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(v8bf, v);
 }

@@ -25,6 +25,7 @@
 //   workgroups write partial [64][147] slabs that a second kernel adds in a fixed order (bit-reproducible, no float atomics).
 #include "common.h"
 #include "mfma.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -263,49 +264,20 @@ __global__ __launch_bounds__(256, 2) void stem_conv_wgrad_kernel(StemArgs a) {
     for (int e = threadIdx.x; e < CO * NTAP; e += 256) slab[e] = red[(e / NTAP) * G_RED_STRIDE + e % NTAP];
 }
 
-// out[i] (+)= sum over slabs g of slabs[g][i], fixed order: 32 outputs x 8 slab ranges per workgroup, each range summed
-// with 8 independent loads in flight (one thread walking hundreds of slabs is a chain of L2 round trips), ranges then added
-// in order.
+// out[i] (+)= sum over slabs g of slabs[g][i], fixed order: 32 outputs x 8 slab ranges per workgroup (slab_sum_ranges,
+// csrc/wgrad_common.h)
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slabs, int nslabs, int n, float* __restrict__ out,
                                                           int accumulate) {
-    __shared__ float red[8][32];
-    const int col = threadIdx.x & 31, part = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + col;
-    const int per = (nslabs + 7) / 8, g0 = part * per, g1 = min(nslabs, g0 + per);
-    float s = 0.0f;
-    if (i < n) {
-        int g = g0;
-        for (; g + 8 <= g1; g += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = slabs[(size_t)(g + u) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; g < g1; ++g) s += slabs[(size_t)g * n + i];
-    }
-    red[part][col] = s;
-    __syncthreads();
-    if (part == 0 && i < n) {
-        float t = red[0][col];
-#pragma unroll
-        for (int u = 1; u < 8; ++u) t += red[u][col];
-        out[i] = accumulate ? out[i] + t : t;
-    }
+    const int i = blockIdx.x * 32 + (threadIdx.x & 31);
+    const float t = slab_sum_ranges(slabs + i, (size_t)n, nslabs, i < n);
+    if (threadIdx.x < 32 && i < n) out[i] = accumulate ? out[i] + t : t;
 }
 
-// Persistent grids: as many workgroups as are resident at once (asked of the runtime once per kernel), each looping over tiles.
+// persistent grid (common.h), no larger than the problem's tiles
 template <typename K>
 int stem_grid(K kern, int ntiles, int* cache) {
-    if (!*cache) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu <= 0)
-            return ntiles < 512 ? ntiles : 512;
-        *cache = per_cu * p.multiProcessorCount;
-    }
-    return ntiles < *cache ? ntiles : *cache;
+    const int g = persistent_grid(kern, 0, 0, 512, cache);
+    return ntiles < g ? ntiles : g;
 }
 int g_fwd_grid = 0, g_wgrad_grid = 0;
 

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "mfma.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -378,7 +379,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float4* __restr
 
 // =====================================================================================================================
 // weight gradient: dW[co][ci][tap] = sum_px dY[px][co] * P(X)[px + tap][ci],  P = the forward's input prologue
-// (per-channel affine (+ReLU) on real pixels, zero outside the image). GEMM with the PIXELS on K:
+// (per-channel affine (+ReLU) on real pixels, zero outside the image). GEMM with the PIXELS on K; in the exact form
 // v_mfma_f32_32x32x2_f32, A = dY (rows = output channels, k = two consecutive pixels, one per lane half), B = P(X)
 // shifted by the tap (columns = input channels). A workgroup owns a (WM*TM*32) x (WN*TN*32) tile of (co, ci) for one
 // kernel row and a share of the row-chunks (split-K); a chunk = KT consecutive pixels
@@ -394,24 +395,46 @@ struct WgradArgs {
     long long n_chunks;     // B * H * chunks_per_row
 };
 
-template <int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
+// ---------------------------------------------------------------------------------------------------------------------
+// The same weight gradient on split-bf16 products (SB: the default for the tilings without a wave split of the k-steps;
+// -DOSSID_WGRAD_F32 keeps every launch on the exact form). Both operands are split when they are staged
+// (x = hi + lo, bf16 each) and kept in LDS as [pixel][channel] bf16 images, one per part -- the natural order of the
+// channels-last tensors, so a thread's float4 becomes two 8-byte writes (split_store, csrc/mfma.h). The operands come out of
+// the images by the transposed read tr8 (csrc/mfma.h: 8 pixels of one channel per lane, the operand of
+// v_mfma_f32_32x32x16_bf16); the 3x3 taps' column shift is just a different first row of the block. Per 16 pixels and pair
+// of 32x32 tiles three MFMAs (dy_lo*x_hi + dy_hi*x_lo + dy_hi*x_hi) instead of eight f32 ones. Row pitch of an image:
+// channels * 2 bytes padded so that (pitch mod 256) is 64 or 192 -- the four rows of a block then sit on four different
+// quarter-sets of the 64 banks. One LDS buffer (the images of one chunk), the next chunk's global loads in flight in
+// registers under the MFMAs.
+__host__ __device__ constexpr int wgrad_sb_pitch(int channels) {      // bytes
+    return channels == 128 ? 320 : (channels == 64 ? 192 : (channels == 32 ? 64 : channels * 2 + 64));
+}
+
+// One body for both forms: the tile decode, the staging maps, the chunk walk, the loads (bounds, halo, up-sampling, prologue)
+// and the slab write are the same code; SB selects the chunk size the staging registers are sized by, the LDS layout with its
+// stage_write, the k-step loop, and where the write and the barriers sit around it.
+template <bool SB, int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
 __device__ __forceinline__ void wgrad_body(const WgradArgs& A, const int L) {
     constexpr int CO_T = WM * TM * 32, CI_T = WN * TN * 32;
     constexpr int KX = TAPS == 9 ? 3 : 1;
     constexpr int NT = TM * TN * KX * KYB;                   // accumulator tiles per wave
     constexpr int HALO = TAPS == 9 ? 2 : 0;
-    constexpr int KTMAX = 48;
+    constexpr int KTMAX = (SB && WK == 4) ? 64 : 48;         // pixels per chunk at most (the staging registers are sized by it)
     constexpr int DY4 = CO_T / 4, X4 = CI_T / 4;              // float4 per staged pixel
     constexpr int NLD_DY = (KTMAX * DY4 + 255) / 256, NLD_X = (KYB * (KTMAX + HALO) * X4 + 255) / 256;
+    constexpr int PD = wgrad_sb_pitch(CO_T), PX = wgrad_sb_pitch(CI_T);      // (split form)
     static_assert(WM * WN * WK == 4 && 256 % DY4 == 0 && 256 % X4 == 0, "bad tiling");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int KT = A.KT;
-    const int dy_buf = KT * CO_T, x_buf = KYB * (KT + HALO) * CI_T;      // floats per buffer
-    float* dyl = lds;                                // [2][KT][CO_T]
-    float* xl = lds + 2 * dy_buf;                    // [2][KYB][KT + HALO][CI_T]
+    const int KT = A.KT;                                     // split form: a multiple of 16
+    // LDS: [2][dy_img] then [2][x_img] bytes. Exact form: the two are double buffers of f32, dY [KT][CO_T] and
+    // X [KYB][KT + HALO][CI_T]; split form: the two are the hi and lo parts of ONE buffer of bf16 images [KT][PD], [KYB][KT + HALO][PX]
+    const int dy_img = SB ? KT * PD : KT * CO_T * 4, x_img = SB ? KYB * (KT + HALO) * PX : KYB * (KT + HALO) * CI_T * 4;
+    char* dyl = (char*)lds;
+    char* xl = dyl + 2 * dy_img;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c = lane & 31;
-    // WK > 1 (layers with few channels): the waves of a workgroup share ONE (co, ci) tile and take every WK-th k-step of
-    // a chunk; each writes its own slab (slab index split * WK + wk), so there is no cross-wave reduction in the kernel
+    // WK > 1 (layers with few channels: one or two 32 x 32 tiles of (co, ci) per kernel row): the waves of a workgroup share
+    // ONE (co, ci) tile and take every WK-th k-step of a chunk; each writes its own slab (slab index split * WK + wk), so
+    // there is no cross-wave reduction in the kernel
     const int wm = wave % WM, wn = (wave / WM) % WN, wk = wave / (WM * WN);
 
     // ---- which tile / split: consecutive workgroup ids walk the tiles of ONE split (they read the same dY / X rows,
@@ -480,30 +503,42 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& A, const int L) {
             const int yy = y + (TAPS == 9 ? ky0 + kr - 1 : 0), xx = x0 + p - (TAPS == 9 ? 1 : 0);
             const bool ok = kr < KYB && yy >= 0 && yy < H && xx >= 0 && xx < W && xq_ok;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok) {
-                // same index formula as the forward's fused up-sampling (csrc/conv.hip stage map)
-                const int sy = (A.Hs == H) ? yy : min((int)floorf((float)yy * A.scale_h), A.Hs - 1);
-                const int sxx = (A.Ws == W) ? xx : min((int)floorf((float)xx * A.scale_w), A.Ws - 1);
+            if (ok) {           // the forward's own index map and prologue (csrc/wgrad_common.h)
+                const int sy = nearest_src(yy, A.Hs, H, A.scale_h), sxx = nearest_src(xx, A.Ws, W, A.scale_w);
                 v = *(const float4*)(A.x + ((size_t)(b * A.Hs + sy) * A.Ws + sxx) * A.in_cs + ci0 + 4 * xq);
-                if (A.pre_scale) {
-                    v.x = v.x * ps.x + pt.x, v.y = v.y * ps.y + pt.y, v.z = v.z * ps.z + pt.z, v.w = v.w * ps.w + pt.w;
-                    if (A.pre_relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                }
+                v = prologue4(v, ps, pt, A.pre_scale != nullptr, A.pre_relu != 0);
             }
             sx[e] = v;
         }
     };
-    auto stage_write = [&](int buf) {
+    auto stage_write = [&](int buf) {                         // (split form: one buffer, buf is not used)
 #pragma unroll
         for (int e = 0; e < NLD_DY; ++e) {
             const int idx = tid + e * 256;
-            if (idx < KT * DY4) *(float4*)(dyl + (size_t)buf * dy_buf + (size_t)idx * 4) = sdy[e];
+            if (idx >= KT * DY4) continue;
+            if constexpr (SB) split_store(sdy[e], dyl + (size_t)(idx / DY4) * PD + 8 * dyq, dy_img);
+            else *(float4*)(dyl + (size_t)buf * dy_img + (size_t)idx * 16) = sdy[e];
         }
 #pragma unroll
         for (int e = 0; e < NLD_X; ++e) {
             const int idx = tid + e * 256;
-            if (idx < KYB * (KT + HALO) * X4) *(float4*)(xl + (size_t)buf * x_buf + (size_t)idx * 4) = sx[e];
+            if (idx >= KYB * (KT + HALO) * X4) continue;
+            if constexpr (SB) split_store(sx[e], xl + (size_t)(idx / X4) * PX + 8 * xq, x_img);
+            else *(float4*)(xl + (size_t)buf * x_img + (size_t)idx * 16) = sx[e];
         }
+    };
+    auto run = [&](auto&& product) {                          // acc[t] = product(kr, m, n, kx, acc[t]) over the wave's tiles
+#pragma unroll
+        for (int kr = 0; kr < KYB; ++kr)
+#pragma unroll
+            for (int m = 0; m < TM; ++m)
+#pragma unroll
+                for (int n = 0; n < TN; ++n)
+#pragma unroll
+                    for (int kx = 0; kx < KX; ++kx) {
+                        const int t = ((kr * TM + m) * TN + n) * KX + kx;
+                        acc[t] = product(kr, m, n, kx, acc[t]);
+                    }
     };
 
     long long ch = split;
@@ -515,61 +550,84 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& A, const int L) {
     }
     if (ch < A.n_chunks) {
         stage_load(gb, gy, gcr);
-        stage_write(0);
+        if constexpr (!SB) stage_write(0);
     }
-    __syncthreads();
-    int buf = 0;
-    const int ksteps = KT / 2;
+    if constexpr (!SB) __syncthreads();
+    int buf = 0;                                              // (exact form)
 #pragma unroll 1
     for (; ch < A.n_chunks; ch += A.nsplit) {
+        if constexpr (SB) {
+            stage_write(0);
+            __syncthreads();
+        }
         const long long nxt = ch + A.nsplit;
         advance(gb, gy, gcr);
-        if (nxt < A.n_chunks) stage_load(gb, gy, gcr);
-        const float* da = dyl + (size_t)buf * dy_buf + (size_t)h * CO_T + wm * TM * 32 + c;
-        const float* xb = xl + (size_t)buf * x_buf + (size_t)h * CI_T + wn * TN * 32 + c;
-        float a[2][TM], bv[2][KYB][TN][KX];
-        auto fetch = [&](int k, float(&aa)[TM], float(&bb)[KYB][TN][KX]) {
-#pragma unroll
-            for (int m = 0; m < TM; ++m) aa[m] = da[(size_t)(2 * k) * CO_T + 32 * m];
-#pragma unroll
-            for (int kr = 0; kr < KYB; ++kr)
-#pragma unroll
-                for (int n = 0; n < TN; ++n)
-#pragma unroll
-                    for (int kx = 0; kx < KX; ++kx)
-                        bb[kr][n][kx] = xb[((size_t)kr * (KT + HALO) + 2 * k + kx) * CI_T + 32 * n];
-        };
-        auto run = [&](const float(&aa)[TM], const float(&bb)[KYB][TN][KX]) {
-#pragma unroll
-            for (int kr = 0; kr < KYB; ++kr)
+        if (nxt < A.n_chunks) stage_load(gb, gy, gcr);       // in flight under this chunk's MFMAs
+        if constexpr (SB) {
+            // k-steps of 16 pixels: this lane's transposed-read offsets into the hi images, then parts, pixels and tiles
+            const char* a_base = dyl + tr_lane_offset(lane, PD, wm * TM * 32);
+            const char* b_base = xl + tr_lane_offset(lane, PX, wn * TN * 32);
+#pragma unroll 1
+            for (int k = wk; k < KT / 16; k += WK) {
+                v8bf a[TM][2], bv[KYB][TN][KX][2];
 #pragma unroll
                 for (int m = 0; m < TM; ++m)
 #pragma unroll
+                    for (int part = 0; part < 2; ++part)
+                        a[m][part] = tr8(a_base + (size_t)part * dy_img + (size_t)(16 * k) * PD + m * 64, PD);
+#pragma unroll
+                for (int kr = 0; kr < KYB; ++kr)
+#pragma unroll
                     for (int n = 0; n < TN; ++n)
 #pragma unroll
-                        for (int kx = 0; kx < KX; ++kx) {
-                            const int t = ((kr * TM + m) * TN + n) * KX + kx;
-                            acc[t] = mfma(aa[m], bb[kr][n][kx], acc[t]);
-                        }
-        };
-        // operands of this wave's next k-step are read from LDS while the MFMAs of the current one run (two per trip)
-        if (wk < ksteps) fetch(wk, a[0], bv[0]);
-#pragma unroll 1
-        for (int k = wk; k < ksteps; k += 2 * WK) {
-            if (k + WK < ksteps) fetch(k + WK, a[1], bv[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            run(a[0], bv[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k + WK < ksteps) {
-                if (k + 2 * WK < ksteps) fetch(k + 2 * WK, a[0], bv[0]);
-                __builtin_amdgcn_sched_barrier(0);
-                run(a[1], bv[1]);
-                __builtin_amdgcn_sched_barrier(0);
+                        for (int kx = 0; kx < KX; ++kx)
+#pragma unroll
+                            for (int part = 0; part < 2; ++part)
+                                bv[kr][n][kx][part] = tr8(b_base + (size_t)part * x_img +
+                                                          (size_t)(kr * (KT + HALO) + 16 * k + kx) * PX + n * 64, PX);
+                run([&](int kr, int m, int n, int kx, v16f cc) {
+                    return mfma3(a[m][0], a[m][1], bv[kr][n][kx][0], bv[kr][n][kx][1], cc);
+                });
             }
+        } else {
+            // k-steps of 2 pixels (one per lane half): an operand read is one conflict-free ds_read_b32 per lane
+            const int ksteps = KT / 2;
+            const float* da = (const float*)(dyl + (size_t)buf * dy_img) + (size_t)h * CO_T + wm * TM * 32 + c;
+            const float* xb = (const float*)(xl + (size_t)buf * x_img) + (size_t)h * CI_T + wn * TN * 32 + c;
+            float a[2][TM], bv[2][KYB][TN][KX];
+            auto fetch = [&](int k, float(&aa)[TM], float(&bb)[KYB][TN][KX]) {
+#pragma unroll
+                for (int m = 0; m < TM; ++m) aa[m] = da[(size_t)(2 * k) * CO_T + 32 * m];
+#pragma unroll
+                for (int kr = 0; kr < KYB; ++kr)
+#pragma unroll
+                    for (int n = 0; n < TN; ++n)
+#pragma unroll
+                        for (int kx = 0; kx < KX; ++kx)
+                            bb[kr][n][kx] = xb[((size_t)kr * (KT + HALO) + 2 * k + kx) * CI_T + 32 * n];
+            };
+            auto run1 = [&](const float(&aa)[TM], const float(&bb)[KYB][TN][KX]) {
+                run([&](int kr, int m, int n, int kx, v16f cc) { return mfma(aa[m], bb[kr][n][kx], cc); });
+            };
+            // operands of this wave's next k-step are read from LDS while the MFMAs of the current one run (two per trip)
+            if (wk < ksteps) fetch(wk, a[0], bv[0]);
+#pragma unroll 1
+            for (int k = wk; k < ksteps; k += 2 * WK) {
+                if (k + WK < ksteps) fetch(k + WK, a[1], bv[1]);
+                __builtin_amdgcn_sched_barrier(0);
+                run1(a[0], bv[0]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (k + WK < ksteps) {
+                    if (k + 2 * WK < ksteps) fetch(k + 2 * WK, a[0], bv[0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    run1(a[1], bv[1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (nxt < A.n_chunks) stage_write(buf ^ 1);
+            buf ^= 1;
         }
-        if (nxt < A.n_chunks) stage_write(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
+        __syncthreads();                                      // every wave has read this chunk's buffer
     }
 
     // ---- slab [split][tap][Cout][Cin]: rows of an accumulator tile = output channels (registers), columns = input
@@ -589,235 +647,16 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& A, const int L) {
                     const int tap = TAPS == 9 ? (ky0 + kr) * 3 + kx : 0;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int co = co0 + (wm * TM + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int co = co0 + (wm * TM + m) * 32 + acc_row(r, h);
                         if (co < A.Cout) slab[((size_t)tap * A.Cout + co) * A.Cin + ci] = acc[t][r];
                     }
                 }
             }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The same weight gradient on split-bf16 products (the default for the tilings without a wave split of the k-steps;
-// -DOSSID_WGRAD_F32 keeps every launch on the exact kernel above). Both operands are split when they are staged
-// (x = hi + lo, bf16 each) and kept in LDS as [pixel][channel] bf16 images, one per part -- the natural order of the
-// channels-last tensors, so a thread's float4 becomes two 8-byte writes. The matrix cores want the REDUCTION index (pixels)
-// contiguous per lane: ds_read_b64_tr_b16 (cdna_hip_programming.md T10) reads a block of 4 pixels x 16 channels and hands
-// lane i the 4 pixels of channel i, two of them make the 8-pixel operand of v_mfma_f32_32x32x16_bf16; the 3x3 taps'
-// column shift is just a different first row of the block. Per 16 pixels and pair of 32x32 tiles three MFMAs
-// (dy_lo*x_hi + dy_hi*x_lo + dy_hi*x_hi) instead of eight f32 ones. Row pitch of an image: channels * 2 bytes padded so that
-// (pitch mod 256) is 64 or 192 -- the four rows of a block then sit on four different quarter-sets of the 64 banks.
-// One LDS buffer (the images of one chunk), the next chunk's global loads in flight in registers under the MFMAs.
-
-__host__ __device__ constexpr int wgrad_sb_pitch(int channels) {      // bytes
-    return channels == 128 ? 320 : (channels == 64 ? 192 : (channels == 32 ? 64 : channels * 2 + 64));
-}
-
-template <int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
-__device__ __forceinline__ void wgrad_sb_body(const WgradArgs& A, const int L) {
-    constexpr int CO_T = WM * TM * 32, CI_T = WN * TN * 32;
-    constexpr int KX = TAPS == 9 ? 3 : 1;
-    constexpr int NT = TM * TN * KX * KYB;
-    constexpr int HALO = TAPS == 9 ? 2 : 0;
-    constexpr int KTMAX = WK == 4 ? 64 : 48;                 // pixels per chunk at most (the staging registers are sized by it)
-    constexpr int DY4 = CO_T / 4, X4 = CI_T / 4;
-    constexpr int NLD_DY = (KTMAX * DY4 + 255) / 256, NLD_X = (KYB * (KTMAX + HALO) * X4 + 255) / 256;
-    constexpr int PD = wgrad_sb_pitch(CO_T), PX = wgrad_sb_pitch(CI_T);
-    static_assert(WM * WN * WK == 4 && 256 % DY4 == 0 && 256 % X4 == 0, "bad tiling");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int KT = A.KT;                                     // a multiple of 16 here
-    const int dy_img = KT * PD, x_img = KYB * (KT + HALO) * PX;          // bytes per part
-    char* dyl = (char*)lds;                                  // [2 parts][KT][PD]
-    char* xl = dyl + 2 * dy_img;                             // [2 parts][KYB][KT + HALO][PX]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, c = lane & 31;
-    // WK > 1 (few-channel layers: one or two 32 x 32 tiles of (co, ci) per kernel row): the waves share the tiles and take
-    // every WK-th 16-pixel k-step of a chunk, each writes its own slab (index split * WK + wk)
-    const int wm = wave % WM, wn = (wave / WM) % WN, wk = wave / (WM * WN);
-
-    const int split = L / A.ntiles;
-    int tile = L - split * A.ntiles;
-    int ky0 = 0;
-    if (TAPS == 9 && KYB == 1) {
-        ky0 = tile % 3;
-        tile /= 3;
-    }
-    const int cib = tile % A.ci_blocks, cob = tile / A.ci_blocks;
-    const int co0 = cob * CO_T, ci0 = cib * CI_T;
-
-    v16f acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-
-    const int dyq = tid % DY4, xq = tid % X4;
-    const bool dyq_ok = co0 + 4 * dyq < A.Cout, xq_ok = ci0 + 4 * xq < A.Cin;
-    float4 ps = make_float4(1.f, 1.f, 1.f, 1.f), pt = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (A.pre_scale && xq_ok) {
-        ps = *(const float4*)(A.pre_scale + ci0 + 4 * xq);
-        pt = *(const float4*)(A.pre_shift + ci0 + 4 * xq);
-    }
-    float4 sdy[NLD_DY], sx[NLD_X];
-
-    const int H = A.H, W = A.W;
-    const int cpr = A.chunks_per_row;
-    const int d_cr = A.nsplit % cpr, d_row = A.nsplit / cpr, d_y = d_row % H, d_b = d_row / H;
-    auto advance = [&](int& b, int& y, int& cr) {
-        cr += d_cr;
-        int carry = cr >= cpr ? 1 : 0;
-        cr -= carry * cpr;
-        y += d_y + carry;
-        carry = y >= H ? 1 : 0;
-        y -= carry * H;
-        b += d_b + carry;
-    };
-    int xkr[NLD_X], xp[NLD_X];
-#pragma unroll
-    for (int e = 0; e < NLD_X; ++e) {
-        const int idx = (tid + e * 256) / X4;
-        xkr[e] = idx / (KT + HALO);
-        xp[e] = idx - xkr[e] * (KT + HALO);
-    }
-    auto stage_load = [&](int b, int y, int cr) {
-        const int x0 = cr * KT;
-        const float* dyr = A.dy + ((size_t)(b * H + y) * W) * A.dy_cs + co0 + 4 * dyq;
-#pragma unroll
-        for (int e = 0; e < NLD_DY; ++e) {
-            const int p = (tid + e * 256) / DY4;
-            const bool ok = p < KT && x0 + p < W && dyq_ok;
-            sdy[e] = ok ? *(const float4*)(dyr + (size_t)(x0 + p) * A.dy_cs) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int e = 0; e < NLD_X; ++e) {
-            const int kr = xkr[e], p = xp[e];
-            const int yy = y + (TAPS == 9 ? ky0 + kr - 1 : 0), xx = x0 + p - (TAPS == 9 ? 1 : 0);
-            const bool ok = kr < KYB && yy >= 0 && yy < H && xx >= 0 && xx < W && xq_ok;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok) {
-                const int sy = (A.Hs == H) ? yy : min((int)floorf((float)yy * A.scale_h), A.Hs - 1);
-                const int sxx = (A.Ws == W) ? xx : min((int)floorf((float)xx * A.scale_w), A.Ws - 1);
-                v = *(const float4*)(A.x + ((size_t)(b * A.Hs + sy) * A.Ws + sxx) * A.in_cs + ci0 + 4 * xq);
-                if (A.pre_scale) {
-                    v.x = v.x * ps.x + pt.x, v.y = v.y * ps.y + pt.y, v.z = v.z * ps.z + pt.z, v.w = v.w * ps.w + pt.w;
-                    if (A.pre_relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                }
-            }
-            sx[e] = v;
-        }
-    };
-    auto split_store = [&](const float4& f, char* hi_at, int part_stride) {
-        uint2 pc[2];
-        split_bf16({f.x, f.y, f.z, f.w}, pc);
-        *(uint2*)hi_at = pc[0];
-        *(uint2*)(hi_at + part_stride) = pc[1];
-    };
-    auto stage_write = [&]() {
-#pragma unroll
-        for (int e = 0; e < NLD_DY; ++e) {
-            const int idx = tid + e * 256;
-            if (idx < KT * DY4) split_store(sdy[e], dyl + (size_t)(idx / DY4) * PD + 8 * dyq, dy_img);
-        }
-#pragma unroll
-        for (int e = 0; e < NLD_X; ++e) {
-            const int idx = tid + e * 256;
-            if (idx < KYB * (KT + HALO) * X4) split_store(sx[e], xl + (size_t)(idx / X4) * PX + 8 * xq, x_img);
-        }
-    };
-
-    // transposed-read addresses (T10): within its group of 16 lanes, lane 4q+p supplies the address of block row q (a pixel),
-    // channels 4p..4p+3 of the block's 16; groups 0/1 take channels 0-15 / 16-31 of a 32-channel tile, the wave's halves the
-    // pixels 8h..8h+7 of the k-step (two blocks of 4 pixels each)
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = (lane >> 4) & 1;
-    const char* a_base = dyl + (size_t)(8 * h + tq) * PD + ((wm * TM) * 32 + 16 * tg + 4 * tp) * 2;
-    const char* b_base = xl + (size_t)(8 * h + tq) * PX + ((wn * TN) * 32 + 16 * tg + 4 * tp) * 2;
-    auto tr8 = [&](const char* at, int pitch) {
-        const v4i16 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)at);
-        const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(at + 4 * pitch));
-        typedef short v8i16 __attribute__((ext_vector_type(8)));
-        const v8i16 v = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(v8bf, v);
-    };
-
-    long long ch = split;
-    int gb, gy, gcr;
-    {
-        gcr = split % cpr;
-        const int row = split / cpr;
-        gy = row % H, gb = row / H;
-    }
-    if (ch < A.n_chunks) stage_load(gb, gy, gcr);
-    const int ksteps = KT / 16;
-#pragma unroll 1
-    for (; ch < A.n_chunks; ch += A.nsplit) {
-        stage_write();
-        __syncthreads();
-        const long long nxt = ch + A.nsplit;
-        advance(gb, gy, gcr);
-        if (nxt < A.n_chunks) stage_load(gb, gy, gcr);       // in flight under this chunk's MFMAs
-#pragma unroll 1
-        for (int k = wk; k < ksteps; k += WK) {
-            v8bf a[TM][2], bv[KYB][TN][KX][2];
-#pragma unroll
-            for (int m = 0; m < TM; ++m)
-#pragma unroll
-                for (int part = 0; part < 2; ++part)
-                    a[m][part] = tr8(a_base + (size_t)part * dy_img + (size_t)(16 * k) * PD + m * 64, PD);
-#pragma unroll
-            for (int kr = 0; kr < KYB; ++kr)
-#pragma unroll
-                for (int n = 0; n < TN; ++n)
-#pragma unroll
-                    for (int kx = 0; kx < KX; ++kx)
-#pragma unroll
-                        for (int part = 0; part < 2; ++part)
-                            bv[kr][n][kx][part] = tr8(b_base + (size_t)part * x_img +
-                                                      (size_t)(kr * (KT + HALO) + 16 * k + kx) * PX + n * 64, PX);
-#pragma unroll
-            for (int kr = 0; kr < KYB; ++kr)
-#pragma unroll
-                for (int m = 0; m < TM; ++m)
-#pragma unroll
-                    for (int n = 0; n < TN; ++n)
-#pragma unroll
-                        for (int kx = 0; kx < KX; ++kx) {
-                            const int t = ((kr * TM + m) * TN + n) * KX + kx;
-                            acc[t] = mfma3(a[m][0], a[m][1], bv[kr][n][kx][0], bv[kr][n][kx][1], acc[t]);
-                        }
-        }
-        __syncthreads();                                      // every wave has read this chunk's images
-    }
-
-    float* slab = A.slabs + ((size_t)split * WK + wk) * TAPS * A.Cout * A.Cin;
-#pragma unroll
-    for (int kr = 0; kr < KYB; ++kr)
-#pragma unroll
-        for (int m = 0; m < TM; ++m)
-#pragma unroll
-            for (int n = 0; n < TN; ++n) {
-                const int ci = ci0 + (wn * TN + n) * 32 + c;
-                if (ci >= A.Cin) continue;
-#pragma unroll
-                for (int kx = 0; kx < KX; ++kx) {
-                    const int t = ((kr * TM + m) * TN + n) * KX + kx;
-                    const int tap = TAPS == 9 ? (ky0 + kr) * 3 + kx : 0;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int co = co0 + (wm * TM + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                        if (co < A.Cout) slab[((size_t)tap * A.Cout + co) * A.Cin + ci] = acc[t][r];
-                    }
-                }
-            }
-}
-
-template <bool SB, int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
-__device__ __forceinline__ void wgrad_any_body(const WgradArgs& A, const int L) {
-    if constexpr (SB) wgrad_sb_body<TAPS, KYB, TM, TN, WM, WN, WK>(A, L);
-    else wgrad_body<TAPS, KYB, TM, TN, WM, WN, WK>(A, L);
 }
 
 template <bool SB, int TAPS, int KYB, int TM, int TN, int WM, int WN, int WK>
 __global__ __launch_bounds__(256, (SB && WK == 1) ? 2 : 1) void wgrad_kernel(const WgradArgs A) {
-    wgrad_any_body<SB, TAPS, KYB, TM, TN, WM, WN, WK>(A, blockIdx.x);
+    wgrad_body<SB, TAPS, KYB, TM, TN, WM, WN, WK>(A, blockIdx.x);
 }
 
 // Several independent weight gradients of ONE tiling variant in one launch (the 2 x L small problems of a dense block,
@@ -834,7 +673,7 @@ __global__ __launch_bounds__(256, (SB && WK == 1) ? 2 : 1) void wgrad_group_kern
     int i = 0;
     const int b = blockIdx.x;
     while (i + 1 < G.n && G.first_block[i + 1] <= b) ++i;
-    wgrad_any_body<SB, TAPS, KYB, TM, TN, WM, WN, WK>(G.a[i], b - G.first_block[i]);
+    wgrad_body<SB, TAPS, KYB, TM, TN, WM, WN, WK>(G.a[i], b - G.first_block[i]);
 }
 
 struct ReduceRow {
@@ -847,7 +686,9 @@ struct ReduceGroup {
     int n;
 };
 
-// grouped form of wgrad_reduce2_kernel<4>: 64 elements x 4 partial sums per block
+// grouped form of wgrad_reduce2_kernel<4>: 64 elements x 4 partial sums per block, the same strided walk of the slabs
+// (slab_sum_strided, csrc/wgrad_common.h). The final combine is NOT the same: here (r0 + r1) + (r2 + r3), there
+// ((r0 + r1) + r2) + r3 -- different floating-point sums, each part of the results its route has always given.
 __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const ReduceGroup R) {
     __shared__ float red[4][64];
     int g = 0;
@@ -857,18 +698,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const ReduceGro
     const size_t n = (size_t)row.taps * row.Cout * row.Cin;
     const int e = threadIdx.x & 63, part = threadIdx.x >> 6;
     const size_t i = (size_t)(b - row.first_block) * 64 + e;
-    float s = 0.0f;
-    if (i < n) {
-        int k = part;
-        for (; k + 28 < row.nslabs; k += 32) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = row.slabs[(size_t)(k + 4 * u) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; k < row.nslabs; k += 4) s += row.slabs[(size_t)k * n + i];
-    }
+    float s = i < n ? slab_sum_strided<4>(row.slabs + i, n, row.nslabs, part) : 0.0f;
     red[part][e] = s;
     __syncthreads();
     if (part != 0 || i >= n) return;
@@ -892,24 +722,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce2_kernel(const float* __restr
     const size_t n = (size_t)taps * Cout * Cin;
     const int e = threadIdx.x % EPB, part = threadIdx.x / EPB;
     const size_t i = (size_t)blockIdx.x * EPB + e;                      // index in [tap][co][ci] order: coalesced reads
-    float s = 0.0f;
-    if (i < n) {
-        int k = part;
-        for (; k + 7 * PARTS < nsplit; k += 8 * PARTS) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = slabs[(size_t)(k + u * PARTS) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; k < nsplit; k += PARTS) s += slabs[(size_t)k * n + i];
-    }
+    float s = i < n ? slab_sum_strided<PARTS>(slabs + i, n, nsplit, part) : 0.0f;
     if (PARTS > 1) {
         red[part][e] = s;
         __syncthreads();
         if (part != 0) return;
 #pragma unroll
-        for (int p = 1; p < PARTS; ++p) s += red[p][e];
+        for (int p = 1; p < PARTS; ++p) s += red[p][e];      // in ascending order: ((r0 + r1) + r2) + ...
     }
     if (i >= n) return;
     const int ci = (int)(i % Cin);
@@ -956,7 +775,7 @@ static int wgrad_reduce_parts(int slabs) { return slabs <= 16 ? 1 : slabs <= 128
 struct WgradPlan {
     int variant, co_t, ci_t, kyb, wk, tiles_per_wave;
     int KT, chunks_per_row, nsplit, co_blocks, ci_blocks, ntiles, B, H, W;
-    int sb;                 // 1: the split-bf16 kernel (wgrad_sb_body: KT a multiple of 16, one LDS buffer of bf16 images)
+    int sb;                 // 1: the split-bf16 form (wgrad_body<true>: KT a multiple of 16, one LDS buffer of bf16 images)
     long long n_chunks;
     size_t lds;
 };

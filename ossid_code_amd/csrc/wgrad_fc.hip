@@ -20,6 +20,7 @@
 // channels that kernel's staging is amortised over four column tiles per tap and the 3-product arithmetic wins.)
 #include "common.h"
 #include "mfma.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -89,13 +90,9 @@ __device__ __forceinline__ void fewch_body(const FcArgs& a, const int wg, const 
             const int yy = oy0 - 1 + py, xx = ox0 - 1 + px;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (e < NX && idx < FC_PH * FC_PW && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) {
-                const int sy = (a.Hs == a.H) ? yy : min((int)floorf((float)yy * a.scale_h), a.Hs - 1);
-                const int sxx = (a.Ws == a.W) ? xx : min((int)floorf((float)xx * a.scale_w), a.Ws - 1);
+                const int sy = nearest_src(yy, a.Hs, a.H, a.scale_h), sxx = nearest_src(xx, a.Ws, a.W, a.scale_w);
                 v = *(const float4*)(a.x + ((size_t)(b * a.Hs + sy) * a.Ws + sxx) * a.in_cs + 4 * xq);
-                if (a.pre_scale) {
-                    v.x = v.x * ps.x + pt.x, v.y = v.y * ps.y + pt.y, v.z = v.z * ps.z + pt.z, v.w = v.w * ps.w + pt.w;
-                    if (a.pre_relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                }
+                v = prologue4(v, ps, pt, a.pre_scale != nullptr, a.pre_relu != 0);
             }
             sx[ee] = v;
         }
@@ -162,7 +159,7 @@ __device__ __forceinline__ void fewch_body(const FcArgs& a, const int wg, const 
             for (int r = 0; r < 4; ++r) slab[((size_t)(4 * kk + r) * CIN + ci) * 9 + tap] = acc16[i][r];
         } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) slab[((size_t)((r & 3) + 8 * (r >> 2) + 4 * kk) * CIN + ci) * 9 + tap] = acc32[i][r];
+            for (int r = 0; r < 16; ++r) slab[((size_t)acc_row(r, kk) * CIN + ci) * 9 + tap] = acc32[i][r];
         }
     }
 }
@@ -172,46 +169,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_fewch_kernel(FcArgs a) {
     fewch_body<COUT, CIN>(a, blockIdx.x, gridDim.x);
 }
 
-// dw[i] (+)= sum over slabs, fixed order: 32 outputs x 8 slab ranges per workgroup, 8 independent loads in flight per thread
+// dw[i] (+)= sum over slabs, fixed order: 32 outputs x 8 slab ranges per workgroup (slab_sum_ranges, csrc/wgrad_common.h)
 __global__ __launch_bounds__(256) void fc_slab_reduce_kernel(const float* __restrict__ slabs, int nslabs, int n, float* __restrict__ out,
                                                              int accumulate) {
-    __shared__ float red[8][32];
-    const int col = threadIdx.x & 31, part = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + col;
-    const int per = (nslabs + 7) / 8, g0 = part * per, g1 = min(nslabs, g0 + per);
-    float s = 0.0f;
-    if (i < n) {
-        int g = g0;
-        for (; g + 8 <= g1; g += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = slabs[(size_t)(g + u) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; g < g1; ++g) s += slabs[(size_t)g * n + i];
-    }
-    red[part][col] = s;
-    __syncthreads();
-    if (part == 0 && i < n) {
-        float t = red[0][col];
-#pragma unroll
-        for (int u = 1; u < 8; ++u) t += red[u][col];
-        out[i] = accumulate ? out[i] + t : t;
-    }
+    const int i = blockIdx.x * 32 + (threadIdx.x & 31);
+    const float t = slab_sum_ranges(slabs + i, (size_t)n, nslabs, i < n);
+    if (threadIdx.x < 32 && i < n) out[i] = accumulate ? out[i] + t : t;
 }
 
+// persistent grid (common.h), no larger than the problem's tiles
 template <typename K>
 int fc_grid(K kern, int ntiles, int* cache) {
-    if (!*cache) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu <= 0)
-            return ntiles < 512 ? ntiles : 512;
-        *cache = per_cu * p.multiProcessorCount;
-    }
-    return ntiles < *cache ? ntiles : *cache;
+    const int g = persistent_grid(kern, 0, 0, 512, cache);
+    return ntiles < g ? ntiles : g;
 }
 int g_grid_16_32 = 0, g_grid_32_64 = 0;
 

@@ -9,9 +9,9 @@
 // chunk. The 58 layers of this shape are 1.65 ms of the finetune step's weight-gradient stream at 57-79 TFLOP/s; their operands
 // (100 MB per layer at 120 x 160 x 8) would pass in 20 us, and the 3 x 36 tile products in 15 us of matrix pipe.
 // Here a workgroup owns a 4 x 16 pixel tile: the 6 x 18 input pixels under it are staged ONCE (prologue, split into hi / lo
-// bf16 images [pixel][channel], the layout of train.hip's kernel: operands by ds_read_b64_tr_b16 with the pixels on the MFMA's
-// K axis), wave w owns input channels 32w .. 32w+31 and walks the nine taps of the tile's four 16-pixel rows: 108 MFMAs per
-// tile and wave between two barriers (four times the old ratio), nine accumulator tiles (144 registers) live across all the
+// bf16 images [pixel][channel], the layout of train.hip's split form: split_store and the transposed operand read tr8 of
+// csrc/mfma.h, with the pixels on the MFMA's K axis), wave w owns input channels 32w .. 32w+31 and walks the nine taps of
+// the tile's four 16-pixel rows: 108 MFMAs per tile and wave between two barriers (four times the old ratio), nine accumulator tiles (144 registers) live across all the
 // tiles of the workgroup. Workgroups are persistent (one per CU: 330 registers), each belongs to ONE job of the launch (the L
 // layers of a block are one launch), prefetches its next tile's loads under the current tile's MFMAs, and writes one partial slab
 // [tap][co][ci]; a second kernel adds a problem's slabs in a fixed order: bit-reproducible, no float atomics.
@@ -19,6 +19,7 @@
 // -DOSSID_WGRAD_F32 build does not use this file (ossid_wgrad_t9_takes returns false).
 #include "common.h"
 #include "mfma.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -98,12 +99,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
                                      (dq_ok ? 4 * dq : 0));
         }
     };
-    auto split_store = [&](const float4& fv, char* hi_at, int part_stride) {
-        uint2 pc[2];
-        split_bf16({fv.x, fv.y, fv.z, fv.w}, pc);
-        *(uint2*)hi_at = pc[0];
-        *(uint2*)(hi_at + part_stride) = pc[1];
-    };
     auto commit = [&](int tile) {
         const int tx = tile % A.tiles_x, r1 = tile / A.tiles_x;
         const int oy0 = (r1 % A.tiles_y) * T9_TH, ox0 = tx * T9_TW;
@@ -113,11 +108,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
             if (idx >= T9_PH * T9_PW) continue;
             const int py = idx / T9_PW, px = idx - py * T9_PW;
             const int yy = oy0 - 1 + py, xx = ox0 - 1 + px;
-            float4 v = sx[e];
-            if (has_pre) {
-                v.x = v.x * ps.x + pt.x, v.y = v.y * ps.y + pt.y, v.z = v.z * ps.z + pt.z, v.w = v.w * ps.w + pt.w;
-                if (relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-            }
+            const float4 v = prologue4(sx[e], ps, pt, has_pre, relu);
             const float f = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? 1.0f : 0.0f;      // zero padding (finite clamped values)
             split_store(make_float4(f * v.x, f * v.y, f * v.z, f * v.w), xl + (size_t)idx * T9_PX + 8 * xq, T9_XIMG);
         }
@@ -130,19 +121,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
             split_store(make_float4(f * v.x, f * v.y, f * v.z, f * v.w), dyl + (size_t)idx * PD + 8 * dq, DIMG);
         }
     };
-    // transposed-read addresses (as csrc/train.hip): within its group of 16 lanes, lane 4q+p supplies the address of block row q
-    // (a pixel), channels 4p..4p+3 of the block's 16; groups 0 / 1 take channels 0-15 / 16-31 of a 32-channel tile, the wave's
-    // halves the pixels 8h..8h+7 of a 16-pixel row (two blocks of 4 pixels each)
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = (lane >> 4) & 1;
-    const char* a_base = dyl + (size_t)(8 * h + tq) * PD + (16 * tg + 4 * tp) * 2;
-    const char* b_base = xl + (size_t)(8 * h + tq) * T9_PX + (wave * 32 + 16 * tg + 4 * tp) * 2;
-    auto tr8 = [&](const char* at, int pitch) {
-        const v4i16 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)at);
-        const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(at + 4 * pitch));
-        typedef short v8i16 __attribute__((ext_vector_type(8)));
-        const v8i16 v = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(v8bf, v);
-    };
+    // this lane's transposed-read offsets (csrc/mfma.h); a k-step is one 16-pixel row of the tile
+    const char* a_base = dyl + tr_lane_offset(lane, PD, 0);
+    const char* b_base = xl + tr_lane_offset(lane, T9_PX, wave * 32);
 
     if (wg < A.ntiles) fetch(wg);
     for (int tile = wg; tile < A.ntiles; tile += A.nwg) {
@@ -180,15 +161,15 @@ __global__ __launch_bounds__(256, 1) void wgrad_t9_kernel(const T9Args A) {
         for (int t = 0; t < 9; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int co = m * 32 + acc_row(r, h);
                 slab[((size_t)t * (TM * 32) + co) * T9_CIN + ci] = acc[m][t][r];
             }
 }
 
 // dw[co][ci][tap] (+)= sum over a job's slabs [tap][co][ci], fixed order; 8 slab ranges x 32 outputs per workgroup
+// (slab_sum_ranges, csrc/wgrad_common.h)
 template <int TM>
 __global__ __launch_bounds__(256) void wgrad_t9_reduce_kernel(const T9Args A) {
-    __shared__ float red[8][32];
     constexpr int SLAB = t9_slab(TM), per_job = SLAB / 32;
     const int ji = blockIdx.x / per_job, blk = blockIdx.x - ji * per_job;
     const T9Job P = A.j[ji];
@@ -197,24 +178,8 @@ __global__ __launch_bounds__(256) void wgrad_t9_reduce_kernel(const T9Args A) {
     const int tap = i / (TM * 32 * T9_CIN), rem = i - tap * (TM * 32 * T9_CIN);
     const int co = rem / T9_CIN, ci = rem - co * T9_CIN;
     if (co >= P.cout_w) return;                            // (uniform per block)
-    const float* base = A.slabs + (size_t)ji * A.nwg * SLAB + i;
-    const int per = (A.nwg + 7) / 8, g0 = part * per, g1 = min(A.nwg, g0 + per);
-    float s = 0.0f;
-    int g = g0;
-    for (; g + 8 <= g1; g += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = base[(size_t)(g + u) * SLAB];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; g < g1; ++g) s += base[(size_t)g * SLAB];
-    red[part][col] = s;
-    __syncthreads();
+    const float t = slab_sum_ranges(A.slabs + (size_t)ji * A.nwg * SLAB + i, SLAB, A.nwg, true);
     if (part == 0) {
-        float t = red[0][col];
-#pragma unroll
-        for (int u = 1; u < 8; ++u) t += red[u][col];
         float* o = P.dw + ((size_t)co * P.cin_total + ci) * 9 + tap;
         *o = P.accumulate ? *o + t : t;
     }
@@ -292,23 +257,13 @@ __global__ __launch_bounds__(256, 1) void wgrad_t1_kernel(const T1Args A) {
             if (has_add) sa[e] = *(const float4*)(J.dy_add + (size_t)p * J.dy_cs + 4 * dq);
         }
     };
-    auto split_store = [&](const float4& fv, char* hi_at, int part_stride) {
-        uint2 pc[2];
-        split_bf16({fv.x, fv.y, fv.z, fv.w}, pc);
-        *(uint2*)hi_at = pc[0];
-        *(uint2*)(hi_at + part_stride) = pc[1];
-    };
     auto commit = [&](int stage) {
         const long long p0 = (long long)stage * T1_PXS;
         if (xq_ok) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int px = (tid >> 6) + 4 * e;
-                float4 v = sx[e];
-                if (has_pre) {
-                    v.x = v.x * ps.x + pt.x, v.y = v.y * ps.y + pt.y, v.z = v.z * ps.z + pt.z, v.w = v.w * ps.w + pt.w;
-                    if (relu) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-                }
+                const float4 v = prologue4(sx[e], ps, pt, has_pre, relu);
                 split_store(v, xl + (size_t)px * T1_PXB + 8 * xq, T1_XIMG);      // (pixels past the end pair with zero dZ rows)
             }
         }
@@ -323,16 +278,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_t1_kernel(const T1Args A) {
             split_store(make_float4(f * v.x, f * v.y, f * v.z, f * v.w), dyl + (size_t)px * T1_PD + 8 * dq, T1_DIMG);
         }
     };
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = (lane >> 4) & 1;
-    const char* a_base = dyl + (size_t)(8 * h + tq) * T1_PD + (wave * 32 + 16 * tg + 4 * tp) * 2;
-    const char* b_base = xl + (size_t)(8 * h + tq) * T1_PXB + (16 * tg + 4 * tp) * 2;
-    auto tr8 = [&](const char* at, int pitch) {
-        const v4i16 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)at);
-        const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(at + 4 * pitch));
-        typedef short v8i16 __attribute__((ext_vector_type(8)));
-        const v8i16 v = __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(v8bf, v);
-    };
+    const char* a_base = dyl + tr_lane_offset(lane, T1_PD, wave * 32);
+    const char* b_base = xl + tr_lane_offset(lane, T1_PXB, 0);
 
     if (wg < A.nstages) fetch(wg);
     for (int stage = wg; stage < A.nstages; stage += A.nwg) {
@@ -360,7 +307,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_t1_kernel(const T1Args A) {
         if (n >= ntn) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int co = wave * 32 + acc_row(r, h);
             slab[(size_t)co * T1_CIB + n * 32 + c] = acc[n][r];
         }
     }
@@ -368,7 +315,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_t1_kernel(const T1Args A) {
 
 // dw[co][ci] (+)= sum over a job's slabs [co][256], fixed order
 __global__ __launch_bounds__(256) void wgrad_t1_reduce_kernel(const T1Args A) {
-    __shared__ float red[8][32];
     constexpr int per_job = T1_SLAB / 32;
     const int ji = blockIdx.x / per_job, blk = blockIdx.x - ji * per_job;
     const T1Job J = A.j[ji];
@@ -376,57 +322,20 @@ __global__ __launch_bounds__(256) void wgrad_t1_reduce_kernel(const T1Args A) {
     const int i = blk * 32 + col;                          // slab element (co, ci)
     const int co = i / T1_CIB, ci = i - co * T1_CIB;
     if (blk * 32 % T1_CIB >= J.cw) return;                 // (whole block outside the job's channels: uniform)
-    const float* base = A.slabs + (size_t)ji * A.nwg * T1_SLAB + i;
-    const int per = (A.nwg + 7) / 8, g0 = part * per, g1 = min(A.nwg, g0 + per);
-    float s = 0.0f;
-    int g = g0;
-    for (; g + 8 <= g1; g += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = base[(size_t)(g + u) * T1_SLAB];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; g < g1; ++g) s += base[(size_t)g * T1_SLAB];
-    red[part][col] = s;
-    __syncthreads();
+    const float t = slab_sum_ranges(A.slabs + (size_t)ji * A.nwg * T1_SLAB + i, T1_SLAB, A.nwg, true);
     if (part == 0 && ci < J.cw) {
-        float t = red[0][col];
-#pragma unroll
-        for (int u = 1; u < 8; ++u) t += red[u][col];
         float* o = J.dw + (size_t)co * J.cin_total + ci;
         *o = J.accumulate ? *o + t : t;
     }
 }
 
+// persistent grids (common.h); the query also raises the kernel's dynamic-LDS limit, so every launch path asks first
 int g_t1_grid = 0;
-int t1_grid() {
-    if (!g_t1_grid) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_t1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T1_LDS) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wgrad_t1_kernel, 256, T1_LDS) != hipSuccess || per_cu <= 0)
-            return 256;
-        g_t1_grid = per_cu * p.multiProcessorCount;
-    }
-    return g_t1_grid;
-}
+int t1_grid() { return persistent_grid(wgrad_t1_kernel, T1_LDS, 0, 256, &g_t1_grid); }
 
 int g_t9_grid[3] = {0, 0, 0};
 template <int TM>
-int t9_grid() {
-    if (!g_t9_grid[TM]) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_t9_kernel<TM>, hipFuncAttributeMaxDynamicSharedMemorySize, t9_lds(TM)) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wgrad_t9_kernel<TM>, 256, t9_lds(TM)) != hipSuccess || per_cu <= 0)
-            return 256;
-        g_t9_grid[TM] = per_cu * p.multiProcessorCount;
-    }
-    return g_t9_grid[TM];
-}
+int t9_grid() { return persistent_grid(wgrad_t9_kernel<TM>, t9_lds(TM), 0, 256, &g_t9_grid[TM]); }
 
 }  // namespace
 
